@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the sig_mp per-frame path on MI355X: body-frames/s at batch 256 (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--conf mixed|high|occ]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--conf mixed|high|occ] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,13 +15,24 @@ Scaling: ``weak`` (default) = 256 bodies on EVERY rank; ``strong`` = 256 bodies 
 dist.shard_range. For N > 1 the outputs are gathered to rank 0 (RCCL) inside the timed region, in four asynchronous
 chunks that overlap the remaining frames.
 
-Rank 0 prints ONE JSON line (metric, value, ..., roofline, cpu_baseline). The K-step call is timed ``--reps`` times
-(default 5; every repetition = reset + W warm-up frames + K timed frames between barrier + synchronize) and ``value`` /
-``ms_per_step`` are those of the MEDIAN repetition (``timing`` carries min / max). ``variants`` carries the other
-configurations of BASELINE.json on the same box: ``high`` (all-visible, same K), ``fp32_mfma``, ``mixed_long`` /
+Rank 0 prints ONE JSON line (metric, value, ..., roofline, cpu_baseline). Every repetition of the K-step call = reset + W
+warm-up frames + K timed frames between barrier + synchronize; ``value`` / ``ms_per_step`` are those of the MEDIAN of
+``--reps`` repetitions (``timing`` carries min / max).
+
+A plain run does only what the headline figure needs: untimed repetitions of the same shape (first launches, lazy device
+buffers and plan tables, the allocator's blocks for the outputs, the clocks; at least 3 of them and 256 frames in all, at
+most 4,096 frames each), then ``--reps`` (default 1) timed repetitions, so that exactly K steps are timed. ``roofline``,
+``cpu_baseline`` and ``variants`` are null.
+
+``--full`` adds everything else, as before: ``--reps`` defaults to 5 (no untimed repetition), the roofline pass,
+``cpu_baseline`` and ``variants``, the other configurations of BASELINE.json on the same box: ``high`` (all-visible, same K), ``fp32_mfma``, ``mixed_long`` /
 ``high_long`` (512 frames per call whatever --steps is: configs[1]'s own T, the wavefront engine's steady state), ``occ1024`` (config 4) and
 ``live_b1`` (config 5: p50 / p99 of the captured batch-1 frame; ``graph_replay`` = the same capture through hipGraphLaunch). The roofline pass and the side legs are guarded: a
 failure there is recorded as {"error": ...} and the line is still printed.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step returned to its caller: ``DIR/pose.npy``
+[rows, 24, 3, 3] and ``DIR/tran.npy`` [rows, 3], float32, rows = every body of the run (gathered on rank 0 for N > 1;
+a fixed seeded sample of rows if they would exceed 64 MB). Inputs are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -50,6 +61,10 @@ PACED_FRAMES = 1000                    # live_b1.paced_60fps: frames at 60 fps (
 CPU_FRAMES_BATCHED = 8                 # cpu_baseline: 5 samples of B x 8 frames batched (median; round-4 review: three samples spread by
 CPU_FRAMES_SINGLE = 48                 # 20 %) + 48 frames batch-1 (~20-30 s of CPU work)
 CPU_SAMPLES = 5
+DUMP_MAX_BYTES = 64 * 1000 * 1000      # --dump-outputs: at most 64 MB in all
+PRIME_FRAMES = 4096                    # plain run: frames of an untimed call at most (rc_sequence plans at most 4,096 frames at a time)
+PRIME_CALLS, PRIME_MIN_FRAMES = 3, 256 # plain run: untimed calls at least, and at least this many frames (warm-up + call) in all (the
+                                       # first two 20-frame calls of a process run 5-10 % slower than later ones; 200-frame calls are warm at once)
 
 
 def pmc_traffic(batch, conf, steps):
@@ -153,6 +168,24 @@ def cpu_baseline(sd, body, m, frames_batched=CPU_FRAMES_BATCHED, frames_single=C
                       f"({frames_single} frames = {dt_1:.1f}s), on one thread {n_1t / dt_1t:.1f} ({n_1t} frames = {dt_1t:.1f}s); nproc={os.cpu_count()}"}
 
 
+def dump_outputs(outdir, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """{name: [rows, ...] tensor or array} -> ``outdir/<name>.npy`` in float32. Above ``max_bytes`` in all, every array keeps the same
+    fixed seeded sample of its rows (in row order)."""
+    host = {k: np.ascontiguousarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=np.float32) for k, v in arrays.items()}
+    n = {a.shape[0] for a in host.values()}
+    if len(n) != 1:
+        raise ValueError(f"dump_outputs: the arrays disagree on their row count ({sorted(n)})")
+    n = n.pop()
+    row_bytes = sum(a.nbytes for a in host.values()) // max(1, n)
+    keep = (max_bytes - 4096 * len(host)) // max(1, row_bytes)         # (4 KiB per file for the .npy header)
+    if keep < n:
+        rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        host = {k: a[rows] for k, a in host.items()}
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+
+
 def guarded(fn, *a, **k):
     """fn(*a, **k), or {"error": ...} -- the bench line must be printed whatever the side legs do."""
     try:
@@ -231,6 +264,9 @@ class Workload:
             torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
             dt = float(tmax.item())
         assert torch.isfinite(pose).all() and torch.isfinite(tran).all()
+        # what the last timed step returned (rank 0 holds the gathered rows for N > 1); copies, so that the next repetition's
+        # outputs do not need fresh blocks from the allocator inside its timed region
+        self.last = (pose.reshape(pose.shape[0], -1, 24, 3, 3)[:, -1].clone(), tran.reshape(tran.shape[0], -1, 3)[:, -1].clone())
         return dt
 
     def timed_reps(self, K, reps, gather_rows_total=None):
@@ -299,9 +335,11 @@ class Workload:
 
 def self_launch(n):
     """`python bench.py --gpus N ...` without a launcher (WORLD_SIZE unset): one process per GPU via torch.distributed.run on a
-    free local port -- the same command line the driver uses for N > 1. Fails loudly when fewer than N devices are visible
+    free local port -- the same command line the driver uses for N > 1 -- started as a child process (this one has already
+    asked the runtime for its devices); its exit status is this process's. Fails loudly when fewer than N devices are visible
     (RC_DIST_SHARE_DEVICE=1, dry runs on a 1-GPU box, lets the ranks share device 0)."""
     import socket
+    import subprocess
     have = torch.cuda.device_count()
     if have < n and os.environ.get("RC_DIST_SHARE_DEVICE") != "1":
         raise SystemExit(f"bench.py: --gpus {n} but only {have} GPU(s) are visible to this process")
@@ -312,7 +350,7 @@ def self_launch(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(sys.executable, cmd, env)
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def rate(dts, K, bodies_total, what):
@@ -438,20 +476,24 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=16)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed K-step call (value = median)")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed K-step call (value = median; default 1, with --full 5)")
     ap.add_argument("--batch", type=int, default=256, help="bodies per GPU (weak) or in total (strong)")
     ap.add_argument("--conf", default="mixed", choices=["mixed", "high", "occ"])
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--gemm-mode", default="auto", choices=["auto", "split", "fp32"],
                     help="product arithmetic of the GEMMs (auto: split-bf16 products from 48 bodies in total)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the variants (other schedules / configs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="(with --full) skip the variants (other schedules / configs)")
+    ap.add_argument("--full", action="store_true", help="also the roofline pass, the CPU baseline and the variants")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
     if args.steps < 1 or args.warmup < 0 or args.batch < 1 or args.reps < 1:
         ap.error("--steps >= 1, --warmup >= 0, --batch >= 1, --reps >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args.gpus)              # does not return: re-executes this command line under torch.distributed.run
+        self_launch(args.gpus)              # does not return: runs this command line under torch.distributed.run in a child process
     rank, world, local = rdist.init_from_env()
     if world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher's WORLD_SIZE is {world}")
@@ -476,15 +518,22 @@ def main():
     # The product arithmetic follows the TOTAL workload, not this rank's shard: the same rows give the same bits on 1 or N GPUs.
     from robustcap_amd.net.sig_mp import Net
     split_total = Net.default_gemm_mode(bodies_total) if args.gemm_mode == "auto" else args.gemm_mode == "split"
-    long_frames = LONG_FRAMES if (not args.no_variants and K < LONG_FRAMES) else 0
+    long_frames = LONG_FRAMES if (args.full and not args.no_variants and K < LONG_FRAMES) else 0
 
     main_w = Workload(sd, body, args.conf, B, W, max(K, long_frames), rank, world, split=split_total)
+    if not args.full:                        # untimed: the same call (at most PRIME_FRAMES frames) until the timed one finds everything warm
+        for _ in range(max(PRIME_CALLS, -(-PRIME_MIN_FRAMES // (W + min(K, PRIME_FRAMES))))):
+            main_w.timed(min(K, PRIME_FRAMES), strong_total)
+        if K > PRIME_FRAMES:                 # the timed call's outputs are larger: their blocks, freed at once, wait in the allocator's cache
+            torch.empty(B, K, 24, 3, 3, device=main_w.dev), torch.empty(B, K, 3, device=main_w.dev)
     dts = main_w.timed_reps(K, args.reps, strong_total)
     dt = dts[len(dts) // 2]
-    roof = guarded(main_w.roofline, K, dt, bodies_total) if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pose": main_w.last[0], "tran": main_w.last[1]})
+    roof = guarded(main_w.roofline, K, dt, bodies_total) if (args.full and rank == 0) else None
 
     variants = None
-    if not args.no_variants:
+    if args.full and not args.no_variants:
         v = {}
 
         def variant(w, k, what, reps=3):
@@ -540,7 +589,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             m_cpu = make_inputs(body, B, 1 + max(CPU_SAMPLES * CPU_FRAMES_BATCHED, CPU_FRAMES_SINGLE), args.conf, seed=2)
             cpu = guarded(cpu_baseline, sd, body, m_cpu)
         value = bodies_total * K / dt

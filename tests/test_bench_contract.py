@@ -1,5 +1,6 @@
 """bench.py's contract with the driver: the JSON line must come out for the driver's own arguments
-(`--gpus 1 --steps 20 --warmup 5` killed round 1's run inside cpu_baseline), whatever the side legs do."""
+(`--gpus 1 --steps 20 --warmup 5` killed round 1's run inside cpu_baseline), whatever the side legs do (`--full`); a plain run
+times exactly --steps steps and leaves the side legs out; `--dump-outputs` writes what the last timed step returned."""
 import json
 import os
 import subprocess
@@ -33,6 +34,29 @@ def test_guarded_records_the_error_instead_of_raising():
     assert bench.guarded(lambda: 7) == 7
 
 
+def test_dump_outputs_writes_float32_within_the_budget(tmp_path):
+    """--dump-outputs: DIR/<name>.npy in float32, every row while they fit, else the same fixed seeded sample of rows in each."""
+    import bench
+    import torch
+    rng = np.random.default_rng(3)
+    pose, tran = rng.standard_normal((40, 24, 3, 3)), rng.standard_normal((40, 3))
+    bench.dump_outputs(str(tmp_path / "all"), {"pose": torch.from_numpy(pose), "tran": tran})
+    p, t = np.load(tmp_path / "all" / "pose.npy"), np.load(tmp_path / "all" / "tran.npy")
+    assert p.dtype == np.float32 and t.dtype == np.float32 and p.shape == (40, 24, 3, 3) and t.shape == (40, 3)
+    assert np.array_equal(p, pose.astype(np.float32)) and np.array_equal(t, tran.astype(np.float32))
+    budget = 2 * 4096 + 10 * (216 + 3) * 4                                   # headers + 10 rows
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"pose": pose, "tran": tran}, max_bytes=budget)
+    p1, t1 = np.load(tmp_path / "s1" / "pose.npy"), np.load(tmp_path / "s1" / "tran.npy")
+    assert p1.shape == (10, 24, 3, 3) and t1.shape == (10, 3)
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in ("pose.npy", "tran.npy")) <= budget
+    rows = [int(np.flatnonzero((tran.astype(np.float32) == r).all(1))[0]) for r in t1]
+    assert rows == sorted(rows) and np.array_equal(p1, pose[rows].astype(np.float32))        # the same rows in both, in row order
+    assert np.array_equal(p1, np.load(tmp_path / "s2" / "pose.npy"))                            # fixed sample
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "bad"), {"pose": pose, "tran": tran[:5]})
+
+
 def test_pmc_traffic_is_keyed_by_batch_and_schedule():
     import bench
     v, src = bench.pmc_traffic(12345, "mixed", 128)            # no PMC pass of such a batch is committed
@@ -49,8 +73,8 @@ def test_pmc_traffic_is_keyed_by_batch_and_schedule():
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra", [[], ["--scaling", "strong"]])
 def test_bench_runs_with_the_drivers_arguments(extra):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` -> rc 0 and one JSON line with roofline + cpu_baseline."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"] + extra
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` -> rc 0 and one JSON line with roofline + cpu_baseline."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"] + extra
     if extra:
         cmd.append("--no-cpu-baseline")                         # the CPU leg is covered by the first run
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
@@ -90,3 +114,31 @@ def test_bench_runs_with_the_drivers_arguments(extra):
     if not extra:
         cpu = d["cpu_baseline"]
         assert "error" not in cpu and cpu["value"] > 0 and cpu["kind"] == "port"
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path, synth_assets):
+    """A plain run: one JSON line with the headline keys, exactly --steps timed steps in one repetition, no side legs; --dump-outputs
+    holds pose / tran of the last timed frame for every body -- what the same call returns when it is made here again."""
+    import torch
+    import bench
+    K, W = 24, 5
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "body-frames/sec (sig_mp fwd + FK) at batch 256" and d["unit"] == "body-frames/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == K and d["warmup"] == W and d["timing"]["reps"] == 1
+    assert d["value"] > 0 and abs(d["value"] - 256 * 1e3 / d["ms_per_step"]) < 0.01 * d["value"]
+    assert abs(d["timing"]["call_ms"] - d["ms_per_step"] * K) < 0.01 * d["timing"]["call_ms"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["variants"] is None
+    pose, tran = np.load(tmp_path / "pose.npy"), np.load(tmp_path / "tran.npy")
+    assert pose.dtype == np.float32 and pose.shape == (256, 24, 3, 3) and tran.dtype == np.float32 and tran.shape == (256, 3)
+    w = bench.Workload(synth_assets["state_dict"], synth_assets["body"], "mixed", 256, W, K, 0, 1)
+    w.net.reset_states()
+    w.run(0, W, True)
+    p, tr = w.run(W, W + K, False)
+    torch.cuda.synchronize()
+    assert float(np.abs(p[:, -1].cpu().numpy() - pose).max()) <= 1e-6 and float(np.abs(tr[:, -1].cpu().numpy() - tran).max()) <= 1e-6

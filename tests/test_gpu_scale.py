@@ -196,8 +196,8 @@ def test_strong_split_over_two_ranks_equals_one_rank():
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["bodies_total"] == 37 and d["config"]["batch_per_gpu"] == 19
     assert d["value"] > 0 and d["cpu_baseline"] is None
     # weak scaling with the variants, as the driver launches it for N > 1 (here 2 ranks x 48 bodies on the one GPU)
-    r = subprocess.run(base + ["--master-port", port(), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4", "--batch", "48"],
-                       capture_output=True, text=True, timeout=900, cwd=root, env=env)
+    r = subprocess.run(base + ["--master-port", port(), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4", "--batch", "48",
+                               "--full"], capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["bodies_total"] == 96 and d["variants"]["high"]["value"] > 0
@@ -205,7 +205,7 @@ def test_strong_split_over_two_ranks_equals_one_rank():
     # `python bench.py --gpus 2` with NO launcher: the bench starts its own ranks (torch.distributed.run on a free port), the line
     # says n_gpus 2, every rank answered the collective, and the strong split of the headline batch sits beside the weak figure
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "4", "--batch", "48",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root,
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root,
                        env={k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -25,7 +25,7 @@ for rnd in range(int(opt["--rounds"])):
         if lib:
             env["RC_LIB_PATH"] = os.path.join(ROOT, lib)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", opt["--batch"], "--steps", opt["--steps"], "--warmup", opt["--warmup"],
-                            "--reps", opt["--reps"], "--conf", opt["--conf"], "--no-cpu-baseline", "--no-variants"], capture_output=True, text=True, cwd=ROOT, env=env)
+                            "--reps", opt["--reps"], "--conf", opt["--conf"], "--full", "--no-cpu-baseline", "--no-variants"], capture_output=True, text=True, cwd=ROOT, env=env)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         if not line:
             print(f"{label}: ERROR {r.stderr[-400:]}", flush=True)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of environment switches on the bench's long variants: tools/ab_env.sh "NAME=VAL ..." "NAME=VAL ..." ...   (one bench run per argument)
 for cfg in "$@"; do
-  env $cfg python bench.py --steps 20 --warmup 5 --no-cpu-baseline > /tmp/ab.json 2>/dev/null
+  env $cfg python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > /tmp/ab.json 2>/dev/null
   python - "$cfg" <<'PY'
 import json, sys
 d = json.loads(open('/tmp/ab.json').read().strip().split('\n')[-1])

@@ -5,9 +5,9 @@ out=$PWD/gpurun_out/pmc_stall
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_VMEM_TA_ADDR_FIFO_FULL \
-  --kernel-trace -d $out/a -o pmc -- python $OLDPWD/bench.py --steps 32 --warmup 8 --no-cpu-baseline > $out/a.log 2>&1 || echo "pass a failed"
+  --kernel-trace -d $out/a -o pmc -- python $OLDPWD/bench.py --full --steps 32 --warmup 8 --no-cpu-baseline > $out/a.log 2>&1 || echo "pass a failed"
 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_IFETCH \
-  --kernel-trace -d $out/b -o pmc -- python $OLDPWD/bench.py --steps 32 --warmup 8 --no-cpu-baseline > $out/b.log 2>&1 || echo "pass b failed"
+  --kernel-trace -d $out/b -o pmc -- python $OLDPWD/bench.py --full --steps 32 --warmup 8 --no-cpu-baseline > $out/b.log 2>&1 || echo "pass b failed"
 cd $OLDPWD
 python - <<'PY'
 import sqlite3, glob, collections, json
