@@ -249,6 +249,11 @@ int rc_normalize_rows(const float* x, float* out, float* norm, int64_t rows, int
 /* Keypoint normalisation of forward_online (net/sig_mp.py:150-152 with get_bbox_scale L277-284): kp[n,33,3] -> out[n,33,3]
  * (xy / max(bbox width, height), rows != 23 relative to row 23, confidence copied). */
 int rc_bbox_normalise(const float* kp, float* out, int64_t n, void* stream);
+/* The confidence mean that picks a frame's regime (net/sig_mp.py:138): j2dc[n,33,3] -> mean[n] = the float32 mean of the 33
+ * confidences summed in the reference's order (torch's CPU reduction of the strided row `j2dc[:, -1]`), code[n] = 2 if
+ * (double)mean >= hi, 1 if > lo, else 0. The kernel that plans rc_sequence, on the helper the per-frame prep uses. Either
+ * output may be NULL, not both; n < 2^31. */
+int rc_conf_mean(const float* j2dc, int64_t n, double lo, double hi, float* mean, int8_t* code, void* stream);
 /* Shape blendshapes of ParametricModel.get_zero_pose_joint_and_vertex(shape) (articulate/model.py:88-91), before its root
  * alignment: verts_out[V,3] = tensordot(beta, shapedirs) + v_template, joints_out[24,3] = J_regressor . verts_out. All
  * pointers HOST (v_template[V,3], shapedirs[V,3,10], J_regressor[24,V] dense, beta[10]); computed on the device,

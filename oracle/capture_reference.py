@@ -8,7 +8,8 @@ imu-orientation terms, never the 'reprojection' output captured here). A synthet
 written to a temp cwd because net/sig_mp.py:19-20 loads ``models/SMPL_male.pkl`` at import.
 
 What is stored: numbers only -- seeded inputs, the reference's outputs, a per-frame branch trace and the
-per-frame outputs of each sub-net's ``linear2`` (forward hooks). Weights / body are NOT stored: fixtures hold
+per-frame outputs of each sub-net's ``linear2`` (forward hooks); the threshold scenarios (EDGE_PLANS) also store the reference's
+own float32 confidence mean of every frame (``conf_ref``, sig_mp.py:138). Weights / body are NOT stored: fixtures hold
 the generator seed + checksums (robustcap_amd.synth regenerates them bit-identically).
 
 Usage:  python oracle/capture_reference.py            (writes tests/golden/: ops.npz, seq_*.npz, meta.json with sha256)
@@ -205,7 +206,62 @@ SCENARIOS = {
     # skewed stage pipeline) accelerates; mid stretches inside exercise the lerp there
     "allvis_long": dict(T=512, conf="allvis", first_tran=True),
     "allvis_ff": dict(T=160, conf="allvis", first_frame=True),
+    # frames whose confidence mean sits on a regime threshold, where the last bit of the float32 mean picks the branch (see
+    # EDGE_PLANS): thresholds (0.7, 0.8) on the sequence engines, (0.85, 0.9) on a context built live
+    "threshold_edges": dict(T=160, conf="mixed", first_tran=True, edges="plain"),
+    "live_pre_edges": dict(T=144, conf="livepre", first_frame=True, live="pre", edges="live"),
 }
+
+# Per-keypoint confidences written over chosen frames after make_motion: (first frame, last frame + 1, kind). Kinds: "lo+" / "lo-"
+# a frame whose reference mean is just above / at-or-below conf_lo while a 64-lane xor butterfly sum falls on the other side;
+# "hi+" / "hi-" the same at conf_hi (>= there); "lo~" / "hi~" alternate + and - frame by frame; "low" an occluded frame; "high"
+# a plainly high frame; "eq_lo" / "eq_hi" all 33 confidences equal to the float32 threshold. The edge frames come early, so a
+# branch taken differently there changes the LSTM states of every later frame: low -> mid and an occluded stretch ending on an
+# edge, mid stretches with k = (c - lo) / (hi - lo) of a few 1e-7, the first high frame (init_net) on an edge.
+EDGE_PLANS = {
+    "plain": [(0, 10, "low"), (10, 11, "lo+"), (11, 14, "low"), (14, 15, "lo-"), (15, 16, "lo+"), (16, 24, "lo~"),
+              (24, 25, "hi+"), (25, 32, "hi~"), (32, 40, "high"), (40, 48, "low"), (48, 64, "lo~"), (64, 72, "lo+"),
+              (72, 88, "hi~"), (100, 108, "lo~"), (120, 128, "hi~"), (140, 141, "eq_lo"), (150, 151, "eq_hi")],
+    "live": [(0, 1, "lo+"), (1, 8, "low"), (8, 9, "lo+"), (9, 12, "low"), (12, 13, "lo-"), (13, 21, "lo~"), (21, 22, "hi+"),
+             (22, 30, "hi~"), (30, 38, "high"), (38, 46, "low"), (46, 62, "lo~"), (62, 78, "hi~"), (100, 108, "lo~"),
+             (110, 118, "hi~"), (130, 131, "eq_lo"), (131, 132, "eq_hi")],
+}
+
+
+def _straddle(seed, stream, thr, at_hi, above):
+    """33 confidences whose reference-order mean is above thr (> for conf_lo, >= for conf_hi) iff ``above``, while the
+    butterfly-order mean is not: the first of a batch of seeded candidates spread +-0.1 around thr that does this."""
+    from oracle.sig_mp_oracle import conf_mean_butterfly_np, conf_mean_ref_np
+    for q in range(64):
+        u = synth.uniform01(seed, stream * 64 + q, 256 * 33).reshape(256, 33).astype(np.float64)
+        v = thr + 0.2 * (u - 0.5)
+        v[:, 32] = 33.0 * thr - v[:, :32].sum(axis=1)
+        v = np.clip(v, 0.0, 1.0).astype(np.float32)
+        r, b = conf_mean_ref_np(v).astype(np.float64), conf_mean_butterfly_np(v).astype(np.float64)
+        ra, ba = (r >= thr, b >= thr) if at_hi else (r > thr, b > thr)
+        ok = np.nonzero((ra == above) & (ba != above))[0]
+        if ok.size:
+            return v[ok[0]]
+    raise RuntimeError(f"no straddling frame at {thr}")
+
+
+def _edge_conf(ck, plan, lo, hi, seed):
+    """ck [T, 33] per-keypoint confidences of one body, overwritten by EDGE_PLANS[plan] (thresholds lo, hi)."""
+    ck = ck.copy()
+    T = ck.shape[0]
+    u = synth.uniform01(seed, 90, T * 33).reshape(T, 33)
+    for a, b, kind in EDGE_PLANS[plan]:
+        for t in range(a, min(b, T)):
+            if kind == "low":
+                ck[t] = (lo - 0.35) + 0.2 * u[t]
+            elif kind == "high":
+                ck[t] = np.minimum(hi + 0.03 + 0.1 * u[t], 1.0)
+            elif kind in ("eq_lo", "eq_hi"):
+                ck[t] = np.float32(lo if kind == "eq_lo" else hi)
+            else:
+                sign = kind[2] if kind[2] != "~" else ("+" if (t - a) % 2 == 0 else "-")
+                ck[t] = _straddle(seed, t, hi if kind[:2] == "hi" else lo, kind[:2] == "hi", sign == "+")
+    return ck
 
 
 def _conf(kind, T, seed):
@@ -262,7 +318,7 @@ def run_reference(sig_mp, sd, inputs, sc):
     hooks = [getattr(net, n).linear2.register_forward_hook(
         lambda mod, inp, out, n=n: calls.append((n, out.detach().numpy().reshape(-1).copy())))
         for n, *_ in C.NETS]
-    poses, trans, trace, outs = [], [], [], []
+    poses, trans, trace, outs, conf = [], [], [], [], []
     for t in range(T):
         calls.clear()
         j2 = torch.from_numpy(inputs["j2dc"][t].copy())
@@ -282,13 +338,14 @@ def run_reference(sig_mp, sd, inputs, sc):
             k = C.NET_INDEX[n]
             rec[k * 144:k * 144 + o.size] = o
         outs.append(rec)
+        conf.append(j2[:, -1].mean().item())                 # sig_mp.py:138, the value its thresholds compare
         trace.append([float(inputs["j2dc"][t, :, 2].mean()), order.count("rnn4"), order.count("rnn6"),
                       len(net.floor_y) - n_floor0, len(net.floor_y), int(reach0 and not net.first_reach),
                       int(net.update_vision_count) if live else 0])
     for h in hooks:
         h.remove()
     res = dict(pose=np.stack(poses), tran=np.stack(trans), trace=np.asarray(trace, np.float64), net_out=np.stack(outs),
-               last_pfoot=net.last_pfoot.numpy())
+               last_pfoot=net.last_pfoot.numpy(), conf_ref=np.asarray(conf, np.float32))
     for n, *_ in C.NETS:
         slot = int(n[3:]) - 1
         hc = net.hidden[slot]
@@ -336,12 +393,17 @@ def capture_sequences(art, sig_mp, body):
         mseed = 100 + si
         conf = _conf(sc["conf"], T, mseed * 7919)
         m = synth.make_motion(mseed, 1, T, body, conf=conf)
+        if sc.get("edges"):
+            lo, hi = (0.85, 0.9) if sc.get("live") == "pre" else (0.7, 0.8)
+            m["j2dc"][0, :, :, 2] = _edge_conf(m["j2dc"][0, :, :, 2], sc["edges"], lo, hi, mseed)
         ft = sc.get("first_tran")
         if ft is True:
             ft = m["first_tran"][0]
         ft = np.zeros(0, np.float32) if ft is None else np.asarray(ft, np.float32)
         inputs = dict(j2dc=m["j2dc"][0], accc=m["accc"][0], oric=m["oric"][0], gravityc=m["gravityc"][0], first_tran=ft)
         res = run_reference(sig_mp, sd, inputs, sc)
+        if not sc.get("edges"):
+            del res["conf_ref"]                              # the fixtures captured before it keep their bytes
         _npz.save(
             os.path.join(OUT, f"seq_{name}.npz"), **inputs, first_frame=np.int32(bool(sc.get("first_frame", False))),
             live=np.str_(sc.get("live") or ""), use_flat_floor=np.int32(sc.get("use_flat_floor", True)),
@@ -371,6 +433,8 @@ def check_sequences(sig_mp):
         z = np.load(os.path.join(OUT, name))
         inputs = {k: z[k] for k in ("j2dc", "accc", "oric", "gravityc", "first_tran")}
         res = run_reference(sig_mp, sd, inputs, _scenario_of(z))
+        if "conf_ref" not in z:
+            del res["conf_ref"]
         diffs = {k: (float(np.abs(v.astype(np.float64) - z[k].astype(np.float64)).max()) if v.size else 0.0) for k, v in res.items()}
         ok = all(np.array_equal(v, z[k]) for k, v in res.items())
         bad += 0 if ok else 1

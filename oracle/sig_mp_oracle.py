@@ -31,6 +31,87 @@ from robustcap_amd import config as C
 F32 = torch.float32
 
 
+# ------------------------------------------------------------------------------------- confidence mean (L138)
+def conf_mean_ref_np(c):
+    """float32 mean of the 33 keypoint confidences of each frame ([..., 33] -> [...]) summed in the reference's order.
+
+    ``j2dc[:, -1].mean()`` on a [33, 3] tensor is torch's CPU scalar reduction of a strided 33-element row: four
+    accumulators acc[k] = ((v[k] + v[4+k]) + ...) + v[28+k], then acc[0] += v[32], then acc[0] += acc[1], += acc[2],
+    += acc[3], each in float32, then one float32 division by 33. (torch's vectorised mean of a CONTIGUOUS 33-vector sums
+    in yet another order.) The regime thresholds compare this rounded value, so its last bit picks the branch."""
+    v = np.asarray(c, np.float32)
+    acc = [v[..., k].copy() for k in range(4)]
+    for j in range(1, 8):
+        for k in range(4):
+            acc[k] = acc[k] + v[..., 4 * j + k]
+    a = acc[0] + v[..., 32]
+    for k in (1, 2, 3):
+        a = a + acc[k]
+    return np.asarray(a / np.float32(33.0), np.float32)
+
+
+def conf_mean_butterfly_np(c):
+    """The same mean summed as a 64-lane xor butterfly (lanes 0..32 hold the confidences, the rest 0): the device's order
+    before it adopted the reference's. Kept to show that the fixtures and tests tell the two orders apart."""
+    v = np.zeros(np.shape(c)[:-1] + (64,), np.float32)
+    v[..., :33] = np.asarray(c, np.float32)
+    lanes = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        v = v + v[..., lanes ^ off]
+    return np.asarray(v[..., 0] / np.float32(33.0), np.float32)
+
+
+CONF_THRESHOLDS = (0.7, 0.8, 0.85, 0.9)     # conf_range (0.7, 0.8), and (0.85, 0.9) for a context built live (sig_mp.py:28, 91-93)
+
+
+def conf_edge_frames(seed, n_random, n_edge, thresholds=CONF_THRESHOLDS, extremes=True):
+    """float32 [N, 33] confidence rows where the summation order of the mean matters: ``n_random`` uniform rows, ``n_edge``
+    rows per threshold whose reference mean lands within +-2 float32 ulp of it, rows of 33 equal values at every threshold
+    and its +-1..4-ulp neighbours, and (``extremes``) an all-zero and an all-one row."""
+    from robustcap_amd import synth
+    rows = [synth.uniform01(seed, 0, n_random * 33).reshape(n_random, 33)]
+    for thr in thresholds:
+        i = CONF_THRESHOLDS.index(thr)
+        t32 = np.float32(thr)
+        ulp = np.spacing(t32)
+        got, q = [], 0
+        while sum(len(g) for g in got) < n_edge:
+            m = 4 * n_edge
+            u = synth.uniform01(seed, 10 + 100 * i + q, m * 33).reshape(m, 33).astype(np.float64)
+            v = thr + 0.2 * (u - 0.5)
+            v[:, 32] = 33.0 * thr - v[:, :32].sum(axis=1)     # exact mean thr in float64; float32 rounding leaves a few ulp
+            v = np.clip(v, 0.0, 1.0).astype(np.float32)
+            d = (conf_mean_ref_np(v).astype(np.float64) - float(t32)) / float(ulp)
+            got.append(v[np.abs(d) <= 2])
+            q += 1
+        rows.append(np.concatenate(got)[:n_edge])
+        for k in range(-4, 5):
+            rows.append(np.full((1, 33), t32 + np.float32(k) * ulp, np.float32))
+    if extremes:
+        rows += [np.zeros((1, 33), np.float32), np.ones((1, 33), np.float32)]
+    return np.ascontiguousarray(np.concatenate(rows), np.float32)
+
+
+def conf_regimes(c, lo, hi):
+    """regime codes of float32 means c: 2 if c >= hi, 1 if c > lo, else 0, compared as Python doubles like the reference."""
+    c = np.asarray(c, np.float32).astype(np.float64)
+    return np.where(c >= hi, 2, np.where(c > lo, 1, 0))
+
+
+def fixture_regimes(s):
+    """per-frame regime of a captured sequence fixture: from the reference's stored means (conf_ref) where it has them, else
+    from its stored keypoints in the reference's order; thresholds (0.85, 0.9) for a context built live."""
+    lo, hi = (0.85, 0.9) if str(s["live"]) == "pre" else (0.7, 0.8)
+    c = s["conf_ref"] if "conf_ref" in s.files else conf_mean_ref_np(s["j2dc"][:, :, 2])
+    return conf_regimes(c, lo, hi)
+
+
+def conf_mean(j2dc):
+    """[B, 33, 3] -> float32 [B]: the reference's ``j2dc[:, -1].mean()`` per row. The strided batched form sums in the
+    same order (tests/test_conf_order.py pins it); tests replace this function to show that a different order is caught."""
+    return j2dc[:, :, 2].mean(dim=1)
+
+
 # ------------------------------------------------------------------------------------------------ math (L0)
 def normalize(x):
     return x / x.norm(dim=-1, keepdim=True)
@@ -321,7 +402,7 @@ class OracleNet(torch.nn.Module):
         j2dc, accc, oric = j2dc.reshape(B, 33, 3).float(), accc.reshape(B, 6, 3).float(), oric.reshape(B, 6, 3, 3).float()
         flat = lambda *xs: torch.cat([x.reshape(B, -1) for x in xs], dim=1)
 
-        c64 = j2dc[:, :, 2].mean(dim=1).double()                              # L138 (python double compares)
+        c64 = conf_mean(j2dc).double()                                        # L138 (python double compares)
         is_hi, is_mid = c64 >= hi, (c64 > lo) & (c64 < hi)
         vis = (c64 > lo) | first_frame                                        # L149
         Rcr = oric[:, 5]                                                      # L139

@@ -80,6 +80,7 @@ SIGNATURES = {
     "rc_lerp": (_I32, [_P, _P, C.c_double, _P, _I64, _P]),
     "rc_normalize_rows": (_I32, [_P, _P, _P, _I64, _I32, _P]),
     "rc_bbox_normalise": (_I32, [_P, _P, _I64, _P]),
+    "rc_conf_mean": (_I32, [_P, _I64, C.c_double, C.c_double, _P, _P, _P]),
     "rc_shape_body": (_I32, [_P, _P, _P, _P, _P, _I32, _P, _P]),
     "rc_fk_r": (_I32, [_P, _P, _P, _I64, _P]),
     "rc_bone_to_joint": (_I32, [_P, _P, _P, _I64, _P]),

@@ -2418,8 +2418,9 @@ int rc_live_step(rc_ctx* ctx, const float* j2dc, const float* accc, const float*
     std::memcpy(ctx->live_in_h + B * 117, oric, B * 54 * sizeof(float));
     // Host-side, CONSERVATIVE mirror of two device flags (rc_prep_kernel): a row needs a transition step iff it carries
     // a deferred updater step (previous frame had c <= lo) and steps on camera data now (c > lo or first frame). The
-    // margin covers the summation-order difference between this double mean and the device's float butterfly; any
-    // doubt, or an unknown previous frame, selects the full graph, where unneeded transition tiles simply exit.
+    // margin covers the difference between this double mean and the device's float32 mean in the reference's order
+    // (rc_conf_mean33); any doubt, or an unknown previous frame, selects the full graph, where unneeded transition tiles
+    // simply exit.
     bool need_tr = !ctx->live_prev_known;
     bool maybe_reach = false;        // some row may trigger init_net in this frame (c >= hi on a row that has not yet, L178-183)
     {
@@ -2685,6 +2686,12 @@ int rc_bbox_normalise(const float* kp, float* out, int64_t n, void* stream) {
     if (n == 0) return RC_OK;
     if (!kp || !out || n < 0) return RC_ERR_INVALID;
     rc_launch_bbox_normalise(kp, out, n, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RC_OK : RC_ERR_HIP;
+}
+int rc_conf_mean(const float* j2dc, int64_t n, double lo, double hi, float* mean, int8_t* code, void* stream) {
+    if (n == 0) return RC_OK;
+    if (!j2dc || (!mean && !code) || n < 0 || n > INT32_MAX) return RC_ERR_INVALID;
+    rc_launch_scan_conf(j2dc, 99, (int)n, 1, lo, hi, (signed char*)code, (hipStream_t)stream, mean);    // the planner's kernel
     return hipGetLastError() == hipSuccess ? RC_OK : RC_ERR_HIP;
 }
 int rc_fk_r(rc_ctx* ctx, const float* Rl, float* Rg, int64_t n, void* stream) {

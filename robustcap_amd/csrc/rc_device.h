@@ -10,6 +10,25 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 // value of lane `l` (a compile-time constant) on every lane: v_readlane_b32
 __device__ __forceinline__ float lane_bcast(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+// The float32 mean of the 33 keypoint confidences of a frame in the reference's order (net/sig_mp.py:138, `j2dc[:, -1].mean()` of
+// a [33, 3] tensor: torch's CPU reduction of a strided 33-element row): four accumulators acc[k] = ((v[k] + v[4+k]) + ...) + v[28+k],
+// then acc[0] += v[32], += acc[1], += acc[2], += acc[3], then / 33. Lanes 0..32 hold v; the result is wave-uniform. The regime
+// thresholds compare this rounded value, so its last bit picks a frame's branch: an xor butterfly (wave_sum) rounds differently on
+// about a third of all frames. Whole-wave call sites only (readlane). The Makefile builds without fast-math: no reassociation.
+__device__ __forceinline__ float rc_conf_mean33(float v) {
+    float acc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] = lane_bcast(v, k);
+#pragma unroll
+    for (int j = 1; j < 8; ++j)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] += lane_bcast(v, 4 * j + k);
+    float a = acc[0] + lane_bcast(v, 32);
+    a += acc[1];
+    a += acc[2];
+    a += acc[3];
+    return a / 33.0f;
+}
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off));

@@ -69,7 +69,7 @@ struct PrepVals {
 __device__ __forceinline__ PrepVals prep_values(const PrepIn& in, const rc_params_dev& prm, const int lane, const int first_frame,
                                                 const int pend_in, const int uv_count, const unsigned flags2_extra = 0u) {
     PrepVals v;
-    const float c = wave_sum(in.cf) / 33.0f;                              // L138
+    const float c = rc_conf_mean33(in.cf);                                // L138, the reference's order
     const double c64 = (double)c;                                         // python-double compares
     const bool gt_lo = c64 > prm.conf_lo, is_hi = c64 >= prm.conf_hi;
     const bool refresh = !prm.live || uv_count == 0;

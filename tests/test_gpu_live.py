@@ -53,12 +53,14 @@ def test_live_capture_vs_reference_sequences(path, synth_assets):
     net.use_graph = True
     ft = t(s["first_tran"]) if s["first_tran"].size else None
     T = s["pose"].shape[0]
+    regime = O.fixture_regimes(s)
     poses, trans = [], []
     for i in range(T):
         p, tr = net.forward_online(t(s["j2dc"][i]), t(s["accc"][i]), t(s["oric"][i]), ft if i == 0 else None,
                                    bool(s["first_frame"]) and i == 0)
         tc = net.get_trace()[0].tolist()
         exp = s["trace"][i]
+        assert tc[0] == int(regime[i]), f"frame {i}: regime {tc[0]}, the reference's {regime[i]}"
         assert tc[1] == int(exp[1]) and tc[2] == int(exp[2]), f"frame {i}: rnn4/rnn6 step counts {tc} vs {exp}"
         assert tc[3] == int(exp[4]) and tc[4] == int(exp[5]), f"frame {i}: floor/reach {tc} vs {exp}"
         poses.append(p.clone()), trans.append(tr.clone())

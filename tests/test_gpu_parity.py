@@ -257,12 +257,14 @@ def test_sequence_vs_reference_capture(path, split, synth_assets):
     net.gravityc = t(s["gravityc"])
     ft = t(s["first_tran"]) if s["first_tran"].size else None
     T = s["pose"].shape[0]
+    regime = O.fixture_regimes(s)                              # the reference's float32 mean, its double compares
     poses, trans = [], []
     for i in range(T):
         p, tr = net.forward_online(t(s["j2dc"][i]), t(s["accc"][i]), t(s["oric"][i]), ft if i == 0 else None,
                                    bool(s["first_frame"]) and i == 0)
         tc = net.get_trace()[0].tolist()
         exp = s["trace"][i]
+        assert tc[0] == int(regime[i]), f"frame {i}: regime {tc[0]}, the reference's {regime[i]}"
         assert tc[1] == int(exp[1]) and tc[2] == int(exp[2]), f"frame {i}: rnn4/rnn6 step counts {tc} vs {exp}"
         assert tc[3] == int(exp[4]) and tc[4] == int(exp[5]), f"frame {i}: floor/reach {tc} vs {exp}"
         poses.append(p), trans.append(tr)
@@ -382,11 +384,18 @@ def test_live_graph_step_equals_eager(synth_assets, monkeypatch):
     a, b = make_net(synth_assets, 1), make_net(synth_assets, 1)
     a.gravityc = b.gravityc = t(m["gravityc"])
     b.use_graph = True
+    from oracle import sig_mp_oracle as O
+    ora = make_oracle(synth_assets, 1)                           # ... and both right: the oracle sums the means in the reference's order
+    ora.gravityc = t(m["gravityc"])
     for i in range(T):
         args = (t(m["j2dc"][0, i]), t(m["accc"][0, i]), t(m["oric"][0, i]))
         pa, ta = a.forward_online(*args, first_frame=(i == 0))
         pb, tb = b.forward_online(*args, first_frame=(i == 0))
         assert torch.equal(pa, pb) and torch.equal(ta, tb), i
+        po, to = ora.forward_online(*args, first_frame=(i == 0))
+        assert a.get_trace()[0].tolist()[:3] == [int(O.conf_regimes(ora.trace["c"].numpy(), 0.7, 0.8)[0]), int(ora.trace["n4"][0]),
+                                                  int(ora.trace["n6"][0])], i
+        assert maxdiff(ta, to) <= 1e-4 and float(O.rotation_angle_deg(pa.cpu(), po).max()) <= 0.1, i
     b.use_flat_floor = False                                     # attribute poke re-captures the graph
     a.use_flat_floor = False
     for i in range(T - 5, T):
