@@ -280,7 +280,8 @@ int rc_fk_bone(rc_ctx* ctx, const float* Rglobal, float* joints, int64_t n, void
 int rc_body_fk(rc_ctx* ctx, const float* pose, const float* tran, float* grot, float* joint, float* j33,
                int64_t n, void* stream);
 /* One step of sub-net `net` ("rnn2".."rnn8") = f(i, x) of forward_online (net/sig_mp.py:126-129) on its
- * recurrent state: x[batch, in] -> y[batch, out]. row_mask DEVICE uint8[batch] or NULL (all rows). */
+ * recurrent state: x[batch, in] -> y[batch, out]. row_mask DEVICE uint8[batch] or NULL (all rows): rows it does not select keep
+ * h and c, their x is never read (NaN / inf there change nothing) and their y elements are left untouched (not zeroed). */
 int rc_lstm_step(rc_ctx* ctx, const char* net, const float* x, const uint8_t* row_mask, float* y, void* stream);
 /* Full-mesh skinning for the metrics of evaluate.py:120-133 (cal_mpjpe: PVE and regressor joints need every vertex).
  * rc_set_mesh uploads v_template[V,3] and weights[V,24] (HOST pointers, same J / parent as rc_set_body);

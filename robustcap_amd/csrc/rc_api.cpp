@@ -1770,6 +1770,16 @@ int rc_create(int32_t batch, int32_t live, rc_ctx** out) {
     tile_env("RC_TILE_S2H512", &ctx->tile378[0], &ctx->tile378[1]);
     tile_env("RC_TILE_RNN2", &ctx->tile2[0], &ctx->tile2[1]);
     tile_env("RC_TILE_RNN4", &ctx->tile4[0], &ctx->tile4[1]);
+    // lstm_problem runs H / (4 nc) column tiles: a width that does not divide H (4x5 / 2x10 on H = 512 or 1024) would leave the
+    // last units of every layer step uncomputed -- rejected here rather than run
+    const struct { const char* knob; int nc, H; } tiles[4] = {{"RC_TILE_RNN6", ctx->tile6[1], 1024}, {"RC_TILE_S2H512", ctx->tile378[1], 512},
+                                                              {"RC_TILE_RNN2", ctx->tile2[1], 512}, {"RC_TILE_RNN4", ctx->tile4[1], 1280}};
+    for (const auto& t : tiles)
+        if (t.nc > 0 && t.H % (4 * t.nc) != 0) {
+            rc_destroy(ctx);
+            return fail(nullptr, RC_ERR_INVALID, std::string("rc_create: ") + t.knob + " tile width of " + std::to_string(4 * t.nc) +
+                                                 " units does not divide H = " + std::to_string(t.H));
+        }
     const size_t B = (size_t)batch, Bp = (size_t)ctx->Bp;
     int rc = RC_OK;
     FrameBuffers& fb = ctx->fb;
