@@ -283,6 +283,29 @@ int rc_body_fk(rc_ctx* ctx, const float* pose, const float* tran, float* grot, f
  * recurrent state: x[batch, in] -> y[batch, out]. row_mask DEVICE uint8[batch] or NULL (all rows): rows it does not select keep
  * h and c, their x is never read (NaN / inf there change nothing) and their y elements are left untouched (not zeroed). */
 int rc_lstm_step(rc_ctx* ctx, const char* net, const float* x, const uint8_t* row_mask, float* y, void* stream);
+/* Sub-net forward over a list of variable-length sequences: RNN.forward(x, init) in eval mode (articulate/utils/torch/rnn.py:121-133:
+ * linear1 -> ReLU -> two-layer LSTM over a packed sequence -> linear2) for sub-net `net` ("rnn2".."rnn8"), time-hoisted: per time
+ * chunk, linear1, the input half x . W_ih of each layer and linear2 run as tall GEMMs over every frame, only h . W_hh in the time loop.
+ * n sequences of lengths_host[i] >= 1 frames (HOST int32[n]); x DEVICE [sum T_i, in] row-major with sequence i at row sum_{j<i} T_j,
+ * y DEVICE [sum T_i, out] packed the same way. init_h / init_c DEVICE [2, n, H] or NULL (zeros); final_h / final_c DEVICE [2, n, H]
+ * or NULL: every sequence's state after its last frame. Every output has the bits of rc_lstm_step run frame by frame on the same
+ * rows in the context's gemm mode (rc_set_gemm_mode). Stateless with respect to the context's own recurrent state, counters, pending
+ * updater steps and live capture: the call reads the packed weights and writes only its own scratch and the caller's buffers.
+ * Scratch (grow-only, released by rc_destroy): the per-chunk buffers -- packed input, relu(linear1), the hoisted x halves and both
+ * layers' h -- stay within RC_SUBNET_SCRATCH_BYTES whatever the lengths; beside them 24 * H bytes of state per sequence of a group
+ * (a group: as many sequences as one time step's rows fit in that budget) and the plan, 4 bytes per frame of the call plus 8 per
+ * sequence, in device and pinned host memory. Enqueued on `stream` with no device read-back; the host waits only for the previous
+ * call's plan upload to leave the pinned buffer, and growing the scratch (hipFree / hipMalloc) synchronises the device. Calls on
+ * different streams are ordered: a call waits for the previous call's work, whose scratch it reuses. RC_ERR_INVALID on n < 1, a
+ * length < 1 or a null x / y (nothing enqueued). */
+#define RC_SUBNET_SCRATCH_BYTES (256ll << 20)
+int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
+                      const float* init_h, const float* init_c, float* final_h, float* final_c, void* stream);
+/* RNNWithInit.init_net (articulate/utils/torch/rnn.py:195-201, used at :207-219): Linear(69,512) ReLU Linear(512,1024) ReLU
+ * Linear(1024,2048) on v DEVICE [n, 69] -> out DEVICE [n, 2048], on the packed weights of rnn2.init_net in the context's gemm mode. */
+int rc_init_net_forward(rc_ctx* ctx, int32_t n, const float* v, float* out, void* stream);
+/* rc_subnet_forward / rc_init_net_forward calls, frames run, time chunks launched, and device bytes of scratch held (any may be NULL). */
+int rc_get_subnet_stats(rc_ctx* ctx, int64_t* calls, int64_t* frames, int64_t* chunks, int64_t* scratch_bytes);
 /* Full-mesh skinning for the metrics of evaluate.py:120-133 (cal_mpjpe: PVE and regressor joints need every vertex).
  * rc_set_mesh uploads v_template[V,3] and weights[V,24] (HOST pointers, same J / parent as rc_set_body);
  * rc_body_mesh = ParametricModel.forward_kinematics(pose, tran, calc_mesh=True)[2] (articulate/model.py:229-241):

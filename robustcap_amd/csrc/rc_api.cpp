@@ -207,6 +207,7 @@ struct rc_ctx {
     double cost_tick_us = 1.0, cost_tick_small_us = 13.0, cost_frame_us = 285.0, cost_tr_us = 55.0;   // engine choice (plan_wave): scale of the
                                                          // per-layer tick estimate, hand-over per tick, frame-stepped frame, its transition launches
     SmplifyState* smplify = nullptr;     // optimiser work space (rc_smplify_api.cpp)
+    SubnetState* subnet = nullptr;       // scratch of rc_subnet_forward (rc_subnet_api.cpp)
     int trace_next = 0;                  // tile-trace slot counter (tools/tile_trace.py)
     long long stat_wide_launches = 0;    // launches of the wide-tile kernels (rc_get_launch_stats)
     // shared-weight gate GEMM (rc_gemm_lds.hip): LSTM layer steps of >= lds_min_rows rows in split-product mode
@@ -1638,6 +1639,23 @@ int check_ready(rc_ctx* ctx) {
 // =============================================================================================== C ABI
 const BodyConst* rc_ctx_body(rc_ctx* ctx) { return ctx->have_body ? ctx->body : nullptr; }
 int rc_ctx_fail(rc_ctx* ctx, int code, const char* msg) { return fail(ctx, code, msg); }
+static SubnetDense subnet_dense(const Dense& d) { return SubnetDense{d.W, d.Ws, d.b, d.K, d.N, d.Kp, d.Np}; }
+int rc_ctx_subnet_net(rc_ctx* ctx, int ni, SubnetNet* o) {
+    if (!ctx->have_weights) return RC_ERR_STATE;
+    const NetDev& n = ctx->net[ni];
+    o->lin1 = subnet_dense(n.lin1); o->lin2 = subnet_dense(n.lin2);
+    for (int l = 0; l < 2; ++l) { o->Wl[l] = n.Wl[l]; o->Wls[l] = n.Wls[l]; o->bl[l] = n.bl[l]; }
+    o->in = n.in; o->H = n.H; o->out = n.out;
+    return RC_OK;
+}
+int rc_ctx_init_net(rc_ctx* ctx, SubnetDense out[3]) {
+    if (!ctx->have_weights) return RC_ERR_STATE;
+    for (int q = 0; q < 3; ++q) out[q] = subnet_dense(ctx->init[q]);
+    return RC_OK;
+}
+int rc_ctx_net_index(const char* name) { return net_index(name); }
+int rc_ctx_gemm_split(rc_ctx* ctx) { return ctx->gemm_split ? 1 : 0; }
+SubnetState*& rc_ctx_subnet(rc_ctx* ctx) { return ctx->subnet; }
 SmplifyState*& rc_ctx_smplify(rc_ctx* ctx) { return ctx->smplify; }
 unsigned long long rc_ctx_ign_mask(rc_ctx* ctx) { return ctx->ign_mask; }
 
@@ -1822,6 +1840,7 @@ int rc_destroy(rc_ctx* ctx) {
     if (!ctx) return RC_OK;
     rc_live_end(ctx);
     rc_smplify_free(ctx->smplify);
+    rc_subnet_free(ctx->subnet);
     for (void* p : ctx->allocs) (void)hipFree(p);
     for (void* p : ctx->weight_allocs) (void)hipFree(p);
     if (ctx->eager_ev) (void)hipEventDestroy(ctx->eager_ev);

@@ -444,3 +444,50 @@ int rc_ctx_fail(rc_ctx* ctx, int code, const char* msg);   // records the messag
 SmplifyState*& rc_ctx_smplify(rc_ctx* ctx);
 unsigned long long rc_ctx_ign_mask(rc_ctx* ctx);
 void rc_smplify_free(SmplifyState* s);
+
+// ---- sub-net forward over ragged sequences (rc_subnet.hip, rc_subnet_api.cpp; articulate/utils/torch/rnn.py:121-133) ----------------
+// One tall GEMM: rows = frames of a time chunk (or the active prefix of one time step), workgroups of 64 * mr rows x 16 * nc columns,
+// the weight k-blocks of a column tile staged once per workgroup in LDS and applied to all its rows. It forms the K quarters
+// [c0, c1) of the packed weights (the per-wave chains of gemm_tile: quarter q = packed k [q Kp / 4, (q + 1) Kp / 4)) with the chains'
+// instructions (rc_mma.h) and sums them in gemm_tile's order, so every output has the bits of the stepped launches.
+enum { RC_SG_DENSE = 0, RC_SG_RELU = 1, RC_SG_HALF = 2, RC_SG_LSTM = 3 };
+struct SubGemm {
+    const float* A;          // rc_pk order, [rows, lda]; the chains read A column k - a_koff for packed k
+    int lda, a_koff, M;
+    const float* W;          // pack_weights (mode 0)
+    const void* Ws;          // pack_weights_split (mode 1)
+    int Kp, ncb;             // packed K (all four quarters), 16-column blocks of the packing
+    int c0, c1;              // quarters formed here
+    int N;                   // valid output columns
+    int epi;                 // RC_SG_*
+    const float* bias;       // packed column order (DENSE / RELU / LSTM)
+    float* out;              // DENSE / RELU: rc_pk(row', col, ldo) if out_packed else row' * ldo + col, row' = out_map ? out_map[row] : row
+    int ldo, out_packed;     // HALF: out[row * ldo + col] = q0 + q1 (the x half of a layer step, no bias)
+    const int* out_map;
+    // LSTM (a layer step over rows 0 .. M - 1 = the active prefix): gates = (pre[row * ldp + col] + (q2 + q3)) + bias
+    const float* pre;
+    int ldp, H;
+    float* cst;              // [rows, H] in place
+    float* hout;             // h(t): rc_pk(row, unit, H)
+    float* hseq;             // ... and the chunk's sequence buffer rc_pk(hseq_row0 + row, unit, H)
+    long long hseq_row0;
+};
+void rc_launch_subnet_gemm(const SubGemm& G, int split, int tall, hipStream_t s);   // tall: 256-row tiles whatever M
+// dst[rc_pk(j, k, ld)] = k < cols ? src[map[j] * cols + k] : 0 for j < rows, k < ld (user rows -> zero-padded A operand)
+void rc_launch_subnet_pack(const float* src, int cols, const int* map, float* dst, int ld, int rows, hipStream_t s);
+// state of sequence perm[r] <-> row r < nr (n: sequences in h, c). hp: per layer (hp + l * hl) two copies of h in rc_pk order, ps floats apart; cp: per layer
+// (cp + l * cl) c [rows, H]; h, c: [2, n, H] in the caller's order. in = 1: copy 1 of hp and cp from h, c (zeros where null);
+// in = 0: h, c (either may be null) from copy par[r] of hp and from cp
+void rc_launch_subnet_state(float* hp, long long hl, long long ps, const int* par, float* cp, long long cl, float* h, float* c,
+                            const int* perm, int nr, int n, int H, int in, hipStream_t s);
+
+// narrow view of the context for rc_subnet_api.cpp
+struct SubnetState;
+struct SubnetDense { const float* W; const void* Ws; const float* b; int K, N, Kp, Np; };
+struct SubnetNet { SubnetDense lin1, lin2; const float* Wl[2]; const void* Wls[2]; const float* bl[2]; int in, H, out; };
+int rc_ctx_subnet_net(rc_ctx* ctx, int net, SubnetNet* out);     // net: kNets index (rnn2 .. rnn8); RC_ERR_STATE before weights
+int rc_ctx_init_net(rc_ctx* ctx, SubnetDense out[3]);
+int rc_ctx_net_index(const char* name);
+int rc_ctx_gemm_split(rc_ctx* ctx);
+SubnetState*& rc_ctx_subnet(rc_ctx* ctx);
+void rc_subnet_free(SubnetState* s);

@@ -1,0 +1,181 @@
+// Sub-net forward over ragged sequences (articulate/utils/torch/rnn.py:121-133, RNN.forward on a packed sequence), time-hoisted:
+// per time chunk, relu(linear1), the input half x . W_ih of each LSTM layer and linear2 are tall GEMMs over every frame of the chunk;
+// only h(t - 1) . W_hh stays in the time loop. Host side: rc_subnet_api.cpp.
+//
+// One kernel carries all of them (rc_subnet_gemm_kernel): a workgroup of four waves owns 64 * MR rows (16 * MR per wave) x 16 * NC
+// columns; the weight k-blocks of its column tile are staged in LDS once and applied to every row of the tile. The packed K of a
+// layer is formed as the four quarters the four waves of a stepped tile form (gemm_tile in rc_gemm.hip: wave w chains the k-blocks
+// of [w Kp / 4, (w + 1) Kp / 4)), each quarter with the same instructions in the same order (rc_mma.h: mma_chunk / mma_kblock), and
+// the quarters are summed in the stepped epilogues' order:
+//   linear1 / linear2 / init_net: ((q0 + q1) + q2) + q3 + bias
+//   LSTM layer step:              (q0 + q1) + (q2 + q3) + bias -- q0 + q1 is the hoisted x half, stored in fp32 between the launches
+// so every output carries the bits of the stepped launches (rc_lstm_step) in each gemm mode.
+#include "rc_internal.h"
+#include "rc_gates.h"
+#include "rc_mma.h"
+
+#define RC_SG_STAGE 4         // k-blocks of weights staged in LDS per round
+
+template <int MR, int NC, bool SPLIT>
+__global__ __launch_bounds__(256) void rc_subnet_gemm_kernel(const SubGemm G) {
+    constexpr int U = SPLIT ? 192 : 128;                 // uint4 per (16-column block, 32-k block): three bf16 planes, or two fp32 chunks
+    constexpr int ROWS = 64 * MR, COLS = 16 * NC, LD = COLS + 4;
+    __shared__ __attribute__((aligned(16))) u32x4 s_w[RC_SG_STAGE * NC * U];
+    __shared__ __attribute__((aligned(16))) float s_o[ROWS * LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, kq = lane >> 4;
+    const int m0 = blockIdx.x * ROWS, cb0 = blockIdx.y * NC;
+    const float* pa[MR];
+#pragma unroll
+    for (int r = 0; r < MR; ++r) {
+        const int row = min(m0 + wave * 16 * MR + 16 * r + i, G.M - 1);    // rows past the end load a valid row and are not stored
+        pa[r] = G.A + rc_pk(row, 4 * kq, G.lda);
+    }
+    const int Qs = G.Kp / 32, nkb = Qs / 4;                               // k-blocks per quarter (Kp % 128 == 0)
+    const u32x4* Wv = reinterpret_cast<const u32x4*>(SPLIT ? G.Ws : (const void*)G.W);
+    f32x4 sum[MR][NC], acc[MR][NC];
+    for (int c = G.c0; c < G.c1; ++c) {
+#pragma unroll
+        for (int r = 0; r < MR; ++r)
+#pragma unroll
+            for (int j = 0; j < NC; ++j) acc[r][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int kb0 = c * nkb; kb0 < (c + 1) * nkb; kb0 += RC_SG_STAGE) {
+            const int ng = min(RC_SG_STAGE, (c + 1) * nkb - kb0);
+            __syncthreads();                                              // the previous round's weights are consumed
+            for (int idx = tid; idx < ng * NC * U; idx += 256) {
+                const int g = idx / (NC * U), rem = idx - g * NC * U, j = rem / U, e = rem - j * U;
+                const int cb = min(cb0 + j, G.ncb - 1);                   // column blocks past the packing: a valid block, not stored
+                s_w[idx] = Wv[((long long)cb * Qs + kb0 + g) * U + e];
+            }
+            __syncthreads();
+            for (int g = 0; g < ng; ++g) {
+                const long long aoff = (long long)((kb0 + g) * 32 - G.a_koff) * 16;
+                if constexpr (SPLIT) {
+                    FragS<MR, NC, false> f;
+#pragma unroll
+                    for (int r = 0; r < MR; ++r) {
+                        f.a0[r] = *reinterpret_cast<const f32x4*>(pa[r] + aoff);
+                        f.a1[r] = *reinterpret_cast<const f32x4*>(pa[r] + aoff + 256);
+                    }
+#pragma unroll
+                    for (int j = 0; j < NC; ++j)
+#pragma unroll
+                        for (int p = 0; p < 3; ++p) f.b[j][p] = s_w[(g * NC + j) * U + p * 64 + lane];
+                    mma_kblock(f, acc);
+                } else {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {                         // the k-block's two 16-k chunks, in k order
+                        Frag<MR, NC> f;
+#pragma unroll
+                        for (int r = 0; r < MR; ++r) f.a[r] = *reinterpret_cast<const f32x4*>(pa[r] + aoff + 256 * h);
+#pragma unroll
+                        for (int j = 0; j < NC; ++j) f.b[j] = __builtin_bit_cast(f32x4, s_w[(g * NC + j) * U + h * 64 + lane]);
+                        mma_chunk<MR, NC>(f, acc);
+                    }
+                }
+            }
+        }
+        // quarters summed left to right: ((q0 + q1) + q2) + q3 for dense layers, q0 + q1 (x half), q2 + q3 (recurrent half)
+#pragma unroll
+        for (int r = 0; r < MR; ++r)
+#pragma unroll
+            for (int j = 0; j < NC; ++j) sum[r][j] = c == G.c0 ? acc[r][j] : sum[r][j] + acc[r][j];
+    }
+    // C layout of 16x16: column lane & 15, row (lane >> 4) * 4 + element
+#pragma unroll
+    for (int r = 0; r < MR; ++r)
+#pragma unroll
+        for (int j = 0; j < NC; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s_o[(wave * 16 * MR + 16 * r + 4 * kq + e) * LD + 16 * j + i] = sum[r][j][e];
+    __syncthreads();
+    constexpr int C4 = COLS / 4;
+    for (int item = tid; item < ROWS * C4; item += 256) {
+        const int rl = item / C4, q4 = item - rl * C4;
+        const int row = m0 + rl, col = cb0 * 16 + 4 * q4;
+        if (row >= G.M || col >= G.ncb * 16 || col >= G.N) continue;
+        f32x4 v = *reinterpret_cast<const f32x4*>(&s_o[rl * LD + 4 * q4]);
+        if (G.epi == RC_SG_HALF) {
+            *reinterpret_cast<f32x4*>(&G.out[(long long)row * G.ldo + col]) = v;
+            continue;
+        }
+        const f32x4 b = *reinterpret_cast<const f32x4*>(&G.bias[col]);
+        if (G.epi == RC_SG_LSTM) {                                        // four consecutive columns = the i, f, g, o gates of one unit
+            f32x4 g4 = *reinterpret_cast<const f32x4*>(&G.pre[(long long)row * G.ldp + col]) + v;
+            g4 += b;
+            const int unit = col >> 2;
+            const long long ci = (long long)row * G.H + unit;
+            float cn, hn;
+            rc_lstm_cell(g4[0], g4[1], g4[2], g4[3], G.cst[ci], cn, hn);
+            G.cst[ci] = cn;
+            G.hout[rc_pk(row, unit, G.H)] = hn;
+            G.hseq[rc_pk(G.hseq_row0 + row, unit, G.H)] = hn;
+            continue;
+        }
+        v += b;
+        if (G.epi == RC_SG_RELU) { v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f); }
+        const long long orow = G.out_map ? G.out_map[row] : row;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (col + q < G.N) G.out[G.out_packed ? rc_pk(orow, col + q, G.ldo) : orow * G.ldo + col + q] = v[q];
+    }
+}
+
+void rc_launch_subnet_gemm(const SubGemm& G, int split, int tall, hipStream_t s) {
+    if (G.M <= 0) return;
+    // tall launches (every frame of a chunk; init_net): 256-row tiles whatever M, so each staged weight k-block serves 256 A rows. A time
+    // step's active rows: 256-row tiles above 512 rows, else 64-row tiles, 16 columns wide at most 64 rows (more workgroups streaming
+    // slices of W_hh). Below 513 rows the step launches never run the 256-row instantiation: its kernel-trace entries are the tall GEMMs.
+    const int mr = (tall || G.M > 512) ? 4 : 1, nc = (tall || G.M > 64) ? 4 : 1;
+    const int cbs = (min(G.N, G.ncb * 16) + 15) / 16;
+    const dim3 grid((G.M + 64 * mr - 1) / (64 * mr), (cbs + nc - 1) / nc), block(256);
+#define RC_SG_GO(MR, NC)                                                                                   \
+    do {                                                                                                   \
+        if (split) hipLaunchKernelGGL((rc_subnet_gemm_kernel<MR, NC, true>), grid, block, 0, s, G);       \
+        else hipLaunchKernelGGL((rc_subnet_gemm_kernel<MR, NC, false>), grid, block, 0, s, G);            \
+    } while (0)
+    if (mr == 4) RC_SG_GO(4, 4);
+    else if (nc == 4) RC_SG_GO(1, 4);
+    else RC_SG_GO(1, 1);
+#undef RC_SG_GO
+}
+
+__global__ void rc_subnet_pack_kernel(const float* src, int cols, const int* map, float* dst, int ld, int rows) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)rows * ld) return;
+    const int j = (int)(idx / ld), k = (int)(idx - (long long)j * ld);
+    const long long sr = map ? map[j] : j;
+    dst[rc_pk(j, k, ld)] = k < cols ? src[sr * cols + k] : 0.0f;
+}
+
+void rc_launch_subnet_pack(const float* src, int cols, const int* map, float* dst, int ld, int rows, hipStream_t s) {
+    const long long n = (long long)rows * ld;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(rc_subnet_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, cols, map, dst, ld, rows);
+}
+
+// hp: per layer (+ l * hl) two copies of h [rows, H] in rc_pk order, ps floats apart (step t writes copy t & 1); cp: per layer (+ l * cl) c
+__global__ void rc_subnet_state_kernel(float* hp, long long hl, long long ps, const int* par, float* cp, long long cl, float* h, float* c,
+                                       const int* perm, int nr, int n, int H, int in) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= 2ll * nr * H) return;
+    const int l = (int)(idx / ((long long)nr * H));
+    const long long rem = idx - (long long)l * nr * H;
+    const int r = (int)(rem / H), e = (int)(rem - (long long)r * H);
+    const long long user = ((long long)l * n + perm[r]) * H + e;
+    float* hr = hp + l * hl + (in ? 1 : par[r]) * ps + rc_pk(r, e, H);     // (the first step, t = 0, reads copy 1)
+    float* cr = cp + l * cl + (long long)r * H + e;
+    if (in) {
+        *hr = h ? h[user] : 0.0f;
+        *cr = c ? c[user] : 0.0f;
+    } else {
+        if (h) h[user] = *hr;
+        if (c) c[user] = *cr;
+    }
+}
+
+void rc_launch_subnet_state(float* hp, long long hl, long long ps, const int* par, float* cp, long long cl, float* h, float* c,
+                            const int* perm, int nr, int n, int H, int in, hipStream_t s) {
+    const long long tot = 2ll * nr * H;
+    hipLaunchKernelGGL(rc_subnet_state_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, hp, hl, ps, par, cp, cl, h, c, perm,
+                       nr, n, H, in);
+}

@@ -68,6 +68,28 @@ class _ModuleView:
     def __repr__(self):
         return f"<view of {self._prefix}: {len(self._keys())} tensors>"
 
+    # The sub-nets run like the reference's modules (articulate/utils/torch/rnn.py): net.rnn4(x, init) is RNN.forward, net.rnn2(x) is
+    # RNNWithInit.forward and net.rnn2.init_net(v) the Sequential -- on the context's packed weights (rc_subnet_forward, rc_init_net_forward).
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+    def forward(self, x, init=None, return_state=False):
+        """RNN.forward (rnn.py:121-133) for ``net.rnn3`` .. ``net.rnn8``: x a list of N tensors [T_i, in], init None or (h0, c0) each
+        [2, N, H]; returns the list of N device tensors [T_i, out] (views of one packed buffer), and with ``return_state=True`` also
+        (h_n, c_n), each [2, N, H] at every sequence's last frame. ``net.rnn2``: RNNWithInit.forward (rnn.py:207-219), x a list of
+        (x_i [T_i, 72], x_init_i [69]); its second argument is ignored like the reference's. ``net.rnn2.init_net``: v [n, 69] -> [n, 2048]."""
+        p = self._prefix
+        if p == "rnn2.init_net":
+            return self._net._init_net_forward(x)
+        if p == "rnn2":
+            return self._net._rnn_with_init_forward(x, return_state)
+        if p in _SUBNETS:
+            return self._net._subnet_forward(p, x, init, return_state)
+        raise TypeError(f"{p} is not a module that runs on its own")
+
+
+_SUBNETS = {n: (i, h, o) for n, i, h, o in cfg.NETS}
+
 
 class Net:
     # class attributes callers read or poke on the reference (net/sig_mp.py:27-45)
@@ -227,6 +249,72 @@ class Net:
         if sd is not None and name.startswith("rnn") and any(k.startswith(name + ".") for k, _ in cfg.state_dict_spec()):
             return _ModuleView(self, name)
         raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    # ---------------------------------------------------------------------------------- sub-nets over ragged sequences
+    def _subnet_forward(self, name, x, init=None, return_state=False):
+        """net.rnnK(x, init): rc_subnet_forward on the current stream. Bad input raises ValueError before anything is enqueued."""
+        nin, H, nout = _SUBNETS[name]
+        if isinstance(x, torch.Tensor) or not isinstance(x, (list, tuple)) or len(x) == 0:
+            raise ValueError(f"{name}: x must be a non-empty list of [T_i, {nin}] tensors")
+        xs = [torch.as_tensor(t) for t in x]
+        for i, t in enumerate(xs):
+            if t.dim() != 2 or t.shape[1] != nin or t.shape[0] < 1:
+                raise ValueError(f"{name}: sequence {i} has shape {tuple(t.shape)}, expected [T >= 1, {nin}]")
+        N = len(xs)
+        h0 = c0 = None
+        if init is not None:
+            if not isinstance(init, (list, tuple)) or len(init) != 2:
+                raise ValueError(f"{name}: init must be (h0, c0)")
+            h0, c0 = (torch.as_tensor(t) for t in init)
+            if tuple(h0.shape) != (2, N, H) or tuple(c0.shape) != (2, N, H):
+                raise ValueError(f"{name}: init shapes {tuple(h0.shape)}, {tuple(c0.shape)}, expected [2, {N}, {H}] each")
+            h0, c0 = self._prep(h0, (2, N, H)), self._prep(c0, (2, N, H))
+        lengths = [int(t.shape[0]) for t in xs]
+        xcat = torch.cat([t.to(device=self.device, dtype=torch.float32) for t in xs]).contiguous()
+        y = torch.empty(sum(lengths), nout, device=self.device)
+        fh = torch.empty(2, N, H, device=self.device) if return_state else None
+        fc = torch.empty(2, N, H, device=self.device) if return_state else None
+        lens = (C.c_int32 * N)(*lengths)
+        rc = self._lib.rc_subnet_forward(self._ctx, name.encode(), N, lens, _lib.ptr(xcat), _lib.ptr(y), _lib.ptr(h0), _lib.ptr(c0),
+                                         _lib.ptr(fh), _lib.ptr(fc), _lib.stream_ptr())
+        _lib.check(self._ctx, rc, "rc_subnet_forward")
+        self.__dict__["_keep_subnet"] = (xcat, h0, c0)                     # inputs must outlive the async launches
+        outs = list(torch.split(y, lengths))
+        return (outs, (fh, fc)) if return_state else outs
+
+    def _init_net_forward(self, v):
+        v = torch.as_tensor(v)
+        if v.dim() != 2 or v.shape[1] != 69 or v.shape[0] < 1:
+            raise ValueError(f"rnn2.init_net: v has shape {tuple(v.shape)}, expected [n >= 1, 69]")
+        v = self._prep(v, tuple(v.shape))
+        out = torch.empty(v.shape[0], 2048, device=self.device)
+        _lib.check(self._ctx, self._lib.rc_init_net_forward(self._ctx, int(v.shape[0]), _lib.ptr(v), _lib.ptr(out), _lib.stream_ptr()),
+                   "rc_init_net_forward")
+        self.__dict__["_keep_init_net"] = v
+        return out
+
+    def _rnn_with_init_forward(self, x, return_state=False):
+        """RNNWithInit.forward (rnn.py:207-219): the initial state regressed by init_net from every sequence's x_init."""
+        if isinstance(x, torch.Tensor) or not isinstance(x, (list, tuple)) or len(x) == 0:
+            raise ValueError("rnn2: x must be a non-empty list of (x_i [T_i, 72], x_init_i [69])")
+        if not all(isinstance(e, (list, tuple)) and len(e) == 2 for e in x):
+            raise ValueError("rnn2: every element of x must be a pair (x_i, x_init_i)")
+        xs = [e[0] for e in x]
+        v = [torch.as_tensor(e[1]).to(device=self.device, dtype=torch.float32).reshape(-1) for e in x]
+        if any(t.numel() != 69 for t in v):
+            raise ValueError("rnn2: every x_init_i must hold 69 values")
+        for i, t in enumerate(xs):                                       # (checked before init_net runs: a bad call enqueues nothing)
+            t = torch.as_tensor(t)
+            if t.dim() != 2 or t.shape[1] != 72 or t.shape[0] < 1:
+                raise ValueError(f"rnn2: sequence {i} has shape {tuple(t.shape)}, expected [T >= 1, 72]")
+        s = self._init_net_forward(torch.stack(v)).view(-1, 2, 2, 512).permute(1, 2, 0, 3)
+        return self._subnet_forward("rnn2", xs, (s[0].contiguous(), s[1].contiguous()), return_state)
+
+    def subnet_stats(self):
+        """(sub-net and init_net calls, frames run, time chunks launched, device bytes of scratch held) since construction."""
+        a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(self._ctx, self._lib.rc_get_subnet_stats(self._ctx, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "rc_get_subnet_stats")
+        return a.value, b.value, c.value, d.value
 
     def reset_states(self, rows=None):
         """net/sig_mp.py:95-104. rows: optional bool/uint8 mask [batch] (batched API)."""
