@@ -98,38 +98,38 @@ struct rc_ctx {
     std::vector<float> mesh_vt_h, mesh_w_h, mesh_Jr_h; // host copies: the fold is recomputed when mesh, regressor or root change
     float jroot_h[3] = {0.f, 0.f, 0.f};
     bool fold_dirty = false;
-    float* sweep_scratch = nullptr;                   // per-frame transforms + slab partial sums of the mesh sweeps (grow-only)
+    DevBuf<float> sweep_scratch;                      // per-frame transforms + slab partial sums of the mesh sweeps (grow-only)
     size_t sweep_scratch_cap = 0;
     unsigned long long ign_mask = RC_IGN_DEFAULT;     // smplify: landmarks with zeroed confidence
     bool have_body = false, have_weights = false;
     std::map<std::string, std::vector<float>> staged;    // host copy of the tensors loaded since the last rc_finalize_weights
                                                          // (released there: a context does not hold 254 MB of host memory)
-    std::vector<void*> allocs;
+    std::vector<DevBuf<char>> allocs;
     std::vector<std::pair<void*, size_t>> alloc_bytes;   // (pointer, bytes) of every dev_alloc that is not a weight: state + scratch
-    std::vector<void*> weight_allocs;    // packed weights of the current rc_finalize_weights (freed by the next one)
+    std::vector<DevBuf<char>> weight_allocs;   // packed weights of the current rc_finalize_weights (freed by the next one)
     bool alloc_weights = false;          // dev_alloc books into weight_allocs
     // ordering between the eager entry points (caller's stream) and the live graph (private stream)
-    hipEvent_t eager_ev = nullptr;
+    HipEvent eager_ev;
     bool eager_dirty = false;
     std::string err;
     // live mode: one captured frame on a private stream, pinned host staging
-    hipStream_t live_stream = nullptr;
-    hipGraph_t live_graph = nullptr;
-    hipGraphExec_t live_exec = nullptr;
-    float *live_in_h = nullptr, *live_out_h = nullptr;      // pinned: [B,171] and [B,219]
-    float *live_in_d = nullptr, *live_out_d = nullptr, *live_ft_d = nullptr;
+    HipStream live_stream;
+    HipGraph live_graph;
+    HipGraphExec live_exec;
+    PinBuf<float> live_in_h, live_out_h;                    // pinned: [B,171] and [B,219]
+    DevBuf<float> live_in_d, live_out_d, live_ft_d;
     float *live_in_io = nullptr, *live_out_io = nullptr;    // what the frame kernels read / write (device copy or mapped host memory)
     bool live_zero_copy = false;
     bool live_eager = false;
-    hipGraph_t live_graph_notr = nullptr;                   // the same frame without the transition launches
-    hipGraphExec_t live_exec_notr = nullptr;
+    HipGraph live_graph_notr;                               // the same frame without the transition launches
+    HipGraphExec live_exec_notr;
     std::vector<unsigned char> live_maybe_pend;             // host-side, conservative: row may carry a deferred updater step
     bool live_prev_known = false;
     // the lean live frame (rc_live.hip): seven launches for the steady-state frame of a small batch
     int live_lean = 1;                                      // RC_LIVE_LEAN: 0 = the frame-stepped plan for every live frame
     int live_lean_nc = 1;                                   // RC_LIVE_LEAN_NC: 16-column blocks per LSTM tile (1 or 2)
-    hipGraph_t live_graph_lean = nullptr;
-    hipGraphExec_t live_exec_lean = nullptr;
+    HipGraph live_graph_lean;
+    HipGraphExec live_exec_lean;
     LiveFrame live_frame{};
     int live_aql_on = 1;                                    // RC_LIVE_AQL: 0 = lean frames by hipGraphLaunch only
     AqlChain* live_aql = nullptr;                           // the lean frame as pre-built AQL packets on a queue of its own (rc_aql.cpp)
@@ -142,7 +142,7 @@ struct rc_ctx {
                                                             // fine on a dedicated box, hostile on a shared one): 1 behind frames of a paced caller, 2 behind every lean frame
     volatile unsigned* spin_mb = nullptr;                   // mailbox, host-writable device memory: [0] command, [16] decision
     float* spin_in = nullptr;                               // the frame's inputs, same allocation
-    unsigned* spin_state_h = nullptr;                       // pinned: 3 = the waiting kernel gave up
+    PinBuf<unsigned> spin_state_h;                          // pinned: 3 = the waiting kernel gave up
     int aql_prog_spin[2] = {-1, -1}, aql_prog_spin_pre[2] = {-1, -1};   // by mailbox (frames queued ahead alternate between two)
     int spin_pending = -1;                                  // program whose first kernel is waiting
     int spin_pending_par = 0, spin_next_par = 0;            // its mailbox / the next one's
@@ -152,17 +152,17 @@ struct rc_ctx {
     long long stat_live_spin = 0, stat_live_spin_lost = 0;  // frames that started from a waiting K1 / waiting K1s sent away or timed out
     bool live_arm = true;                                   // RC_LIVE_ARM=0 switches it off: a paced caller leaves a barrier packet waiting at the head of the queue
     double live_prestep_idle_us = 500.0;                    // RC_LIVE_PRESTEP_IDLE_US: idle time in front of a frame from which the next pre-step is enqueued
-    float* live_pre_buf = nullptr;                          // [tiles of the twelve layer steps][2 waves][64 lanes][4]
+    DevBuf<float> live_pre_buf;                             // [tiles of the twelve layer steps][2 waves][64 lanes][4]
     int aql_prog_lean = -1, aql_prog_lean_pre = -1, aql_prog_pre = -1;     // programs of the AQL chain
     bool live_pre_valid = false;                            // a pre-step of the CURRENT state is in the queue (or done)
     bool live_have_return = false;
     std::chrono::steady_clock::time_point live_last_return{};
     long long stat_live_pre = 0;
-    int* live_status_h = nullptr;                           // pinned + mapped: set by a lean frame that met an init_net trigger
+    PinBuf<int> live_status_h;                              // pinned + mapped: set by a lean frame that met an init_net trigger
     std::vector<unsigned char> live_may_reach;              // host-side, conservative: the row may still trigger init_net (L178-183)
     long long stat_live_lean = 0, stat_live_full = 0;
     long long stat_live_replayed = 0;                       // lean frames whose own check (K1) found them off the lean plan: replayed on the full capture
-    int* live_abort_d = nullptr;                            // LiveFrame.abort
+    DevBuf<int> live_abort_d;                               // LiveFrame.abort
     bool live_blind = false;                                // RC_LIVE_MIRROR_BLIND=1 (tests): no host-side mirror of the transition / init_net flags
     double live_prof_us[4] = {0.0, 0.0, 0.0, 0.0};          // host time of rc_live_step: staging + choice | enqueue | wait | copy out (sums, lean frames)
     long long live_prof_n = 0;
@@ -170,7 +170,7 @@ struct rc_ctx {
     // timing of the gate GEMM launches
     bool timing = false;
     int timing_mode = 1;                 // 1: every gate-GEMM launch, 2: only the wide-tile kernels, 3: only the shared-weight kernel (rc_gemm_lds_kernel)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    std::vector<std::pair<HipEvent, HipEvent>> ev_pool;
     size_t ev_used = 0;
     double timed_ms = 0.0;
     double timed_busy_ms = 0.0;          // time with at least one timed launch running (launches on two streams overlap)
@@ -185,15 +185,15 @@ struct rc_ctx {
     int tile6[2] = {0, 0}, tile378[2] = {0, 0}, tile2[2] = {0, 0}, tile4[2] = {0, 0};   // LSTM tile shapes of full-batch stages (0 = pick_tile)
     bool ring2_failed = false;           // ensure_wave2_buffers failed once: not retried
     bool seq_two_streams = true;         // tuning: per-row kernels + linear2 on the second stream (else everything on the caller's)
-    hipStream_t aux_stream = nullptr;    // per-row kernels of a tick run beside the tick's GEMM launch
-    hipStream_t h512_stream = nullptr;   // the tick's {H = 512 nets, linear1} launch, beside the {rnn6, rnn4} launch on the caller's stream
-    hipEvent_t ev_main[8] = {}, ev_aux[8] = {}, ev_h512[4] = {};
-    hipStream_t lin1_stream = nullptr;   // round 6 (regrouped ticks): the tick's {linear1, init_net} launch on a stream of its own
-    hipEvent_t ev_lin1[4] = {}, ev_h5[4] = {};
+    HipStream aux_stream;                // per-row kernels of a tick run beside the tick's GEMM launch
+    HipStream h512_stream;               // the tick's {H = 512 nets, linear1} launch, beside the {rnn6, rnn4} launch on the caller's stream
+    HipEvent ev_main[8], ev_aux[8], ev_h512[4];
+    HipStream lin1_stream;               // round 6 (regrouped ticks): the tick's {linear1, init_net} launch on a stream of its own
+    HipEvent ev_lin1[4], ev_h5[4];
     float* x1_alt2[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // third relu(linear1) buffer per net (h512_stream runs a tick ahead)
-    signed char* scan_codes_d = nullptr; // [cap] regime code per (frame, row)
-    signed char* scan_codes_h = nullptr; // pinned
-    int* scan_state_h = nullptr;         // pinned: first_reach[B] then pend[B] (as ints)
+    DevBuf<signed char> scan_codes_d;    // [cap] regime code per (frame, row)
+    PinBuf<signed char> scan_codes_h;    // pinned
+    PinBuf<int> scan_state_h;            // pinned: first_reach[B] then pend[B] (as ints)
     size_t scan_cap = 0;
     long long stat_wave_frames = 0, stat_stepped_frames = 0, stat_ticks = 0;
     // per-row-cursor wavefront engine (run_wave2_segment)
@@ -201,13 +201,13 @@ struct rc_ctx {
     FrameBuffers ring2[16];              // ring slots: inter-stage buffers, updater inputs, frame index and step numbers per row
     std::vector<GemmProblem> wave2_prob; // [16 slots][W2_PROB]
     bool wave2_valid = false;
-    int* frame_at_d = nullptr;           // [cap] host plan: frame every row starts at every tick
-    int* frame_at_h = nullptr;           // pinned
+    DevBuf<int> frame_at_d;              // [cap] host plan: frame every row starts at every tick
+    PinBuf<int> frame_at_h;              // pinned
     size_t frame_at_cap = 0;
     double cost_tick_us = 1.0, cost_tick_small_us = 13.0, cost_frame_us = 285.0, cost_tr_us = 55.0;   // engine choice (plan_wave): scale of the
                                                          // per-layer tick estimate, hand-over per tick, frame-stepped frame, its transition launches
-    SmplifyState* smplify = nullptr;     // optimiser work space (rc_smplify_api.cpp)
-    SubnetState* subnet = nullptr;       // scratch of rc_subnet_forward (rc_subnet_api.cpp)
+    SmplifyOwner smplify;                // optimiser work space (rc_smplify_api.cpp)
+    SubnetOwner subnet;                  // scratch of rc_subnet_forward (rc_subnet_api.cpp)
     int trace_next = 0;                  // tile-trace slot counter (tools/tile_trace.py)
     long long stat_wide_launches = 0;    // launches of the wide-tile kernels (rc_get_launch_stats)
     // shared-weight gate GEMM (rc_gemm_lds.hip): LSTM layer steps of >= lds_min_rows rows in split-product mode
@@ -220,16 +220,16 @@ struct rc_ctx {
                                          // 64 rows and fewer keep the one-reader 64-row launches (688k against 576k)
     int lds_ksplit[3] = {1, 2, 2};       // RC_LDS_KSPLIT_512 / _1024 / _1280: workgroups per tile (1: both K halves in one workgroup; the H = 512
                                          // nets' items are short -- 2 x 16 k-blocks -- and a hand-over per tile costs more than it levels: +1 %)
-    float* lds_slab = nullptr;           // [kLdsRegions][lds_region_tiles][RC_LDS_SLAB_FLOATS]: half sums in flight, one region per launch
-    int* lds_tickets = nullptr;          // [kLdsRegions][lds_region_tiles]
+    DevBuf<float> lds_slab;              // [kLdsRegions][lds_region_tiles][RC_LDS_SLAB_FLOATS]: half sums in flight, one region per launch
+    DevBuf<int> lds_tickets;             // [kLdsRegions][lds_region_tiles]
     size_t lds_region_tiles = 0;
     unsigned lds_rot = 0;
     // resident layer-step kernel of the wavefront engine (run_wave2_segment: `resident`)
-    ResidentTick* res_ticks_d = nullptr;     // [res_cap]
-    ResidentTick* res_ticks_h = nullptr;     // pinned
-    int* res_ints_d = nullptr;               // item_base [res_cap + 1] | done [res_cap][RC_RES_MAXP] | tick_done [res_cap] | head, flag_l1, flag_tail, abort
-    int* res_base_h = nullptr;               // pinned: item_base
-    int* res_abort_h = nullptr;              // pinned: the abort word of the last segment
+    DevBuf<ResidentTick> res_ticks_d;        // [res_cap]
+    PinBuf<ResidentTick> res_ticks_h;        // pinned
+    DevBuf<int> res_ints_d;                  // item_base [res_cap + 1] | done [res_cap][RC_RES_MAXP] | tick_done [res_cap] | head, flag_l1, flag_tail, abort
+    PinBuf<int> res_base_h;                  // pinned: item_base
+    PinBuf<int> res_abort_h;                 // pinned: the abort word of the last segment (allocated with the first resident segment)
     size_t res_cap = 0;
     long long stat_resident_segments = 0, stat_resident_aborts = 0;
     bool live_selfcheck_ran = false;         // rc_live_begin compared the packet chain with the graph replay (live_selfcheck)
@@ -245,21 +245,15 @@ int fail(rc_ctx* ctx, int code, const std::string& msg) {
     if (ctx) ctx->err = msg; else g_create_error = msg;
     return code;
 }
-#define HIP_TRY(ctx, expr)                                                                        \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return fail(ctx, RC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-    } while (0)
 
 template <typename T>
 int dev_alloc(rc_ctx* ctx, T** p, size_t count, bool zero = true) {
-    void* q = nullptr;
-    HIP_TRY(ctx, hipMalloc(&q, count * sizeof(T)));
-    if (zero) HIP_TRY(ctx, hipMemset(q, 0, count * sizeof(T)));
-    (ctx->alloc_weights ? ctx->weight_allocs : ctx->allocs).push_back(q);
-    if (!ctx->alloc_weights) ctx->alloc_bytes.emplace_back(q, count * sizeof(T));      // (what live_selfcheck saves and puts back: state + scratch)
-    *p = static_cast<T*>(q);
+    DevBuf<char> q;
+    HIP_TRY(ctx, rc_alloc(q, count * sizeof(T)));
+    if (zero) HIP_TRY(ctx, hipMemset(q.get(), 0, count * sizeof(T)));
+    *p = reinterpret_cast<T*>(q.get());
+    if (!ctx->alloc_weights) ctx->alloc_bytes.emplace_back(q.get(), count * sizeof(T));      // (what live_selfcheck saves and puts back: state + scratch)
+    (ctx->alloc_weights ? ctx->weight_allocs : ctx->allocs).push_back(std::move(q));
     return RC_OK;
 }
 
@@ -285,7 +279,7 @@ int mark_eager(rc_ctx* ctx, hipStream_t st) {
     ctx->spin_valid = false;
     if (int rc = dismiss_queued_frame(ctx)) return rc;
     if (!ctx->eager_ev) return RC_OK;
-    HIP_TRY(ctx, hipEventRecord(ctx->eager_ev, st));
+    HIP_TRY(ctx, hipEventRecord(ctx->eager_ev.get(), st));
     ctx->eager_dirty = true;
     return RC_OK;
 }
@@ -512,23 +506,21 @@ int ensure_lds_pool(rc_ctx* ctx) {
     if (ctx->lds_slab) return RC_OK;
     const size_t m_tiles = ((size_t)ctx->B + 255) / 256;
     const size_t tiles = 320 * m_tiles;    // all twelve layer steps in one launch: 2 x (40 + 32 + 4 x 16) column tiles per row tile; + 34 of linear1 (resident kernel)
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->lds_slab, (size_t)kLdsRegions * tiles * RC_LDS_SLAB_FLOATS * sizeof(float)));
-    ctx->allocs.push_back(ctx->lds_slab);
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->lds_tickets, (size_t)kLdsRegions * tiles * sizeof(int)));
-    ctx->allocs.push_back(ctx->lds_tickets);
-    HIP_TRY(ctx, hipMemset(ctx->lds_tickets, 0, (size_t)kLdsRegions * tiles * sizeof(int)));   // (the kernel leaves every ticket at zero)
+    HIP_TRY(ctx, rc_alloc(ctx->lds_slab, (size_t)kLdsRegions * tiles * RC_LDS_SLAB_FLOATS));
+    HIP_TRY(ctx, rc_alloc(ctx->lds_tickets, (size_t)kLdsRegions * tiles));
+    HIP_TRY(ctx, hipMemset(ctx->lds_tickets.get(), 0, (size_t)kLdsRegions * tiles * sizeof(int)));   // (the kernel leaves every ticket at zero)
     ctx->lds_region_tiles = tiles;
     return RC_OK;
 }
 
-bool timing_pair(rc_ctx* ctx, hipEvent_t** a, hipEvent_t** b) {
+bool timing_pair(rc_ctx* ctx, hipEvent_t* a, hipEvent_t* b) {
     if (ctx->ev_used == ctx->ev_pool.size()) {
-        hipEvent_t x, y;
-        if (hipEventCreate(&x) != hipSuccess || hipEventCreate(&y) != hipSuccess) return false;
-        ctx->ev_pool.emplace_back(x, y);
+        std::pair<HipEvent, HipEvent> ev;
+        if (hipEventCreate(rc_out(ev.first)) != hipSuccess || hipEventCreate(rc_out(ev.second)) != hipSuccess) return false;
+        ctx->ev_pool.push_back(std::move(ev));
     }
-    auto& ev = ctx->ev_pool[ctx->ev_used++];
-    *a = &ev.first; *b = &ev.second;
+    const auto& ev = ctx->ev_pool[ctx->ev_used++];
+    *a = ev.first.get(); *b = ev.second.get();
     return true;
 }
 
@@ -595,20 +587,20 @@ int launch_lds(rc_ctx* ctx, const std::vector<GemmProblem>& ps_in, const unsigne
     for (int r = 1; r < replicate && (int)ps.size() + (int)ps_in.size() <= RC_LDS_MAXP; ++r) ps.insert(ps.end(), ps_in.begin(), ps_in.end());
     LdsLaunch L{};
     const size_t region = ctx->lds_rot++ % kLdsRegions;
-    float* slab = ctx->lds_slab + region * ctx->lds_region_tiles * RC_LDS_SLAB_FLOATS;
-    int* tickets = ctx->lds_tickets + region * ctx->lds_region_tiles;
+    float* slab = ctx->lds_slab.get() + region * ctx->lds_region_tiles * RC_LDS_SLAB_FLOATS;
+    int* tickets = ctx->lds_tickets.get() + region * ctx->lds_region_tiles;
     int base = 0;
     size_t tiles = 0;
     build_lds_launch(ctx, ps, flags_override, slab, tickets, L, &base, &tiles);
     if (tiles > ctx->lds_region_tiles) return fail(ctx, RC_ERR_INVALID, "shared-weight launch: more tiles than its slab region holds");
     ctx->stat_lds_launches += 1;
     if (ctx->timing) {
-        hipEvent_t *a, *b;
+        hipEvent_t a, b;
         if (!timing_pair(ctx, &a, &b)) return fail(ctx, RC_ERR_HIP, "hipEventCreate");
-        HIP_TRY(ctx, hipEventRecord(*a, st));
+        HIP_TRY(ctx, hipEventRecord(a, st));
         rc_launch_gemm_lds(L, base, st, stop);      // (the hand-over event rides on the dispatch as in an untimed run: the instrumented pass issues the same tick)
         if (launched && stop) *launched = true;
-        HIP_TRY(ctx, hipEventRecord(*b, st));
+        HIP_TRY(ctx, hipEventRecord(b, st));
     } else {
         rc_launch_gemm_lds(L, base, st, stop);
         if (launched && stop) *launched = true;
@@ -622,34 +614,34 @@ int launch_lds(rc_ctx* ctx, const std::vector<GemmProblem>& ps_in, const unsigne
 // must agree bit for bit wherever the launch wrote (stderr: one line per problem).
 bool dense_items_selftest_wanted(rc_ctx* ctx, const std::vector<GemmProblem>& ps, hipStream_t st, bool fp32) {
     static const int on = std::getenv("RC_DBG_DENSE_ITEMS") ? std::atoi(std::getenv("RC_DBG_DENSE_ITEMS")) : 0;
-    if (!on || !ctx->gemm_split || fp32 || ctx->B > 256 || st == ctx->aux_stream || (int)ps.size() > RC_RES_MAXP) return false;
+    if (!on || !ctx->gemm_split || fp32 || ctx->B > 256 || st == ctx->aux_stream.get() || (int)ps.size() > RC_RES_MAXP) return false;
     for (const GemmProblem& p : ps)
         if (!(p.epi == RC_EPI_RELU && p.out_packed && p.N % 128 == 0 && p.Kp % 128 == 0 && p.out_bit == 0 && p.out_col0 == 0 && p.seg[0].par_mode == 0)) return false;
     return true;
 }
 int dense_items_selftest(rc_ctx* ctx, const std::vector<GemmProblem>& ps, const unsigned char* flags_override, hipStream_t st) {
     if (int rc = ensure_lds_pool(ctx)) return rc;
-    static ResidentTick* tk_d = nullptr;
-    static int* ints_d = nullptr;
     const int n_ints = 2 + RC_RES_MAXP + 1 + 4;
-    if (!tk_d) { HIP_TRY(ctx, hipMalloc((void**)&tk_d, sizeof(ResidentTick))); HIP_TRY(ctx, hipMalloc((void**)&ints_d, n_ints * sizeof(int))); }
+    DevBuf<ResidentTick> tk_d;                                               // (a debugging path: its tables live for this call)
+    DevBuf<int> ints_d;
+    HIP_TRY(ctx, rc_alloc_all(tk_d, 1, ints_d, n_ints));
     ResidentTick T{};
     std::vector<GemmProblem> q(ps);
     for (GemmProblem& p : q) p.m_tiles = 1;
     size_t tiles = 0;
     T.B = ctx->B;
-    T.n = build_lds_problems(ctx, q, flags_override, ctx->lds_slab, ctx->lds_tickets, T.p, RC_RES_MAXP, &T.n_items, &tiles, true);
+    T.n = build_lds_problems(ctx, q, flags_override, ctx->lds_slab.get(), ctx->lds_tickets.get(), T.p, RC_RES_MAXP, &T.n_items, &tiles, true);
     for (int i = 0; i < RC_RES_MAXP; ++i) T.dep[i][0] = T.dep[i][1] = -1;
     const int base[2] = {0, T.n_items};
     const size_t Bp = (size_t)ctx->Bp;
     HIP_TRY(ctx, hipStreamSynchronize(st));
     for (const GemmProblem& p : ps) HIP_TRY(ctx, hipMemset(p.out, 0xff, Bp * p.N * sizeof(float)));
-    HIP_TRY(ctx, hipMemcpy(tk_d, &T, sizeof(T), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemset(ints_d, 0, n_ints * sizeof(int)));
-    HIP_TRY(ctx, hipMemcpy(ints_d, base, sizeof(base), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(tk_d.get(), &T, sizeof(T), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemset(ints_d.get(), 0, n_ints * sizeof(int)));
+    HIP_TRY(ctx, hipMemcpy(ints_d.get(), base, sizeof(base), hipMemcpyHostToDevice));
     ResidentArgs R{};
-    R.ticks = tk_d; R.item_base = ints_d; R.n_ticks = 1;
-    R.done = ints_d + 2; R.tick_done = ints_d + 2 + RC_RES_MAXP; R.head = ints_d + 3 + RC_RES_MAXP; R.flag_tail = R.head + 1; R.abort = R.head + 2;
+    R.ticks = tk_d.get(); R.item_base = ints_d.get(); R.n_ticks = 1;
+    R.done = ints_d.get() + 2; R.tick_done = ints_d.get() + 2 + RC_RES_MAXP; R.head = ints_d.get() + 3 + RC_RES_MAXP; R.flag_tail = R.head + 1; R.abort = R.head + 2;
     R.spin_bound = 100000ull * 100;
     rc_launch_gemm_resident(R, 64, st);
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -743,12 +735,12 @@ int launch_problems(rc_ctx* ctx, std::vector<GemmProblem> ps, const unsigned cha
     if (!rc_gemm_is_small(L)) ctx->stat_wide_launches += 1;
     if (rc_gemm_is_w32(L)) ctx->stat_w32_launches += 1;
     if (ctx->timing && ctx->timing_mode != 3 && !(ctx->timing_mode == 2 && rc_gemm_is_small(L))) {
-        hipEvent_t *a, *b;
+        hipEvent_t a, b;
         if (!timing_pair(ctx, &a, &b)) return fail(ctx, RC_ERR_HIP, "hipEventCreate");
-        HIP_TRY(ctx, hipEventRecord(*a, st));
+        HIP_TRY(ctx, hipEventRecord(a, st));
         rc_launch_gemm(L, base, st, stop);
         if (launched && stop) *launched = true;
-        HIP_TRY(ctx, hipEventRecord(*b, st));
+        HIP_TRY(ctx, hipEventRecord(b, st));
     } else {
         rc_launch_gemm(L, base, st, stop);
         if (launched && stop) *launched = true;
@@ -1027,9 +1019,9 @@ static int ensure_wave2_buffers_once(rc_ctx* ctx) {
         const int want = tune_env("RC_SEQ_H512_PRIO", 0);
         int lo = 0, hi = 0;
         if (want != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
-            HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->h512_stream, hipStreamNonBlocking, want < 0 ? lo : hi));
+            HIP_TRY(ctx, hipStreamCreateWithPriority(rc_out(ctx->h512_stream), hipStreamNonBlocking, want < 0 ? lo : hi));
         else
-            HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->h512_stream, hipStreamNonBlocking));
+            HIP_TRY(ctx, hipStreamCreateWithFlags(rc_out(ctx->h512_stream), hipStreamNonBlocking));
     }
     {
         // RC_SEQ_AUX_PRIO: -1 lowest / +1 highest queue priority for the second stream (0: default) -- its short kernels share the
@@ -1037,19 +1029,19 @@ static int ensure_wave2_buffers_once(rc_ctx* ctx) {
         const int want = tune_env("RC_SEQ_AUX_PRIO", 0);
         int lo = 0, hi = 0;
         if (want != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
-            HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->aux_stream, hipStreamNonBlocking, want < 0 ? lo : hi));
+            HIP_TRY(ctx, hipStreamCreateWithPriority(rc_out(ctx->aux_stream), hipStreamNonBlocking, want < 0 ? lo : hi));
         else
-            HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
+            HIP_TRY(ctx, hipStreamCreateWithFlags(rc_out(ctx->aux_stream), hipStreamNonBlocking));
     }
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->lin1_stream, hipStreamNonBlocking));
+    HIP_TRY(ctx, hipStreamCreateWithFlags(rc_out(ctx->lin1_stream), hipStreamNonBlocking));
     for (int i = 0; i < 8; ++i) {
         // device-scope release: the hand-over is between two streams of this GPU
         const unsigned evf = hipEventDisableTiming | hipEventReleaseToDevice;
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_main[i], evf));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_aux[i], evf));
-        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_h512[i], evf));
-        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_lin1[i], evf));
-        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_h5[i], evf));
+        HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_main[i]), evf));
+        HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_aux[i]), evf));
+        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_h512[i]), evf));
+        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_lin1[i]), evf));
+        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_h5[i]), evf));
     }
     ctx->ring2_ready = true;
     ctx->wave2_valid = false;
@@ -1125,32 +1117,27 @@ inline int w2_group(int q, bool merge_h512, bool merge_big, bool regroup = false
     return g;
 }
 
+// the plan's table frame_at [ticks][B], device + pinned (grow-only: the caller makes sure nothing in flight reads it)
+int reserve_frame_at(rc_ctx* ctx, size_t need, size_t want) {
+    HIP_TRY(ctx, rc_grow(ctx->frame_at_cap, need, want, ctx->frame_at_d, want, ctx->frame_at_h, want));
+    return RC_OK;
+}
+
 int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0, int t_last, hipStream_t st) {
     if (int rc = ensure_wave2_buffers(ctx)) return rc;
     if (!ctx->wave2_valid) if (int rc = build_wave2_problems(ctx)) return rc;
     const int B = ctx->B;
     const rc_params_dev prm = dev_params(ctx->prm);
     const bool two = ctx->seq_two_streams;
-    hipStream_t aux = two ? ctx->aux_stream : st;
+    hipStream_t aux = two ? ctx->aux_stream.get() : st;
     // the plan's table: frame every row starts at every tick
     const size_t need = (size_t)P.n_prep * B;
     if (need > ctx->frame_at_cap) {
         HIP_TRY(ctx, hipDeviceSynchronize());                               // nothing in flight (on any of the engine's streams) may still read the old table
-        if (ctx->frame_at_d) (void)hipFree(ctx->frame_at_d);
-        if (ctx->frame_at_h) (void)hipHostFree(ctx->frame_at_h);
-    if (ctx->res_ticks_d) (void)hipFree(ctx->res_ticks_d);
-    if (ctx->res_ticks_h) (void)hipHostFree(ctx->res_ticks_h);
-    if (ctx->res_ints_d) (void)hipFree(ctx->res_ints_d);
-    if (ctx->res_base_h) (void)hipHostFree(ctx->res_base_h);
-    if (ctx->res_abort_h) (void)hipHostFree(ctx->res_abort_h);
-        ctx->frame_at_d = nullptr; ctx->frame_at_h = nullptr; ctx->frame_at_cap = 0;
-        const size_t cap = need + need / 4 + 4096;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->frame_at_d, cap * sizeof(int)));
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->frame_at_h, cap * sizeof(int), hipHostMallocDefault));
-        ctx->frame_at_cap = cap;
+        if (int rc = reserve_frame_at(ctx, need, need + need / 4 + 4096)) return rc;
     }
-    std::memcpy(ctx->frame_at_h, P.frame_at.data(), need * sizeof(int));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->frame_at_d, ctx->frame_at_h, need * sizeof(int), hipMemcpyHostToDevice, st));
+    std::memcpy(ctx->frame_at_h.get(), P.frame_at.data(), need * sizeof(int));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->frame_at_d.get(), ctx->frame_at_h.get(), need * sizeof(int), hipMemcpyHostToDevice, st));
 
     static const bool narrow_fill = tune_env("RC_SEQ_NARROW_FILL", 1) != 0;
     static const bool lin1_wide = tune_env("RC_SEQ_LIN1_WIDE", 1) != 0;
@@ -1170,7 +1157,7 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
     static const int split_main_env = tune_env("RC_SEQ_SPLIT_MAIN", -1);      // 0 / 1 force, default: by batch
     const bool split_main = (split_main_env < 0 ? B >= RC_SPLIT_MAIN_MIN_BATCH : split_main_env != 0) && two && merge_h512 &&
                             merge_big && !merge_fill && ext_events;
-    hipStream_t s2 = ctx->h512_stream, s4 = ctx->lin1_stream;
+    hipStream_t s2 = ctx->h512_stream.get(), s4 = ctx->lin1_stream.get();
     static const int regroup_env = tune_env("RC_SEQ_REGROUP", 1);
     static const int lin1_env = tune_env("RC_SEQ_LIN1_STREAM", 1);
     const bool regroup = split_main && regroup_env != 0 && ctx->gemm_split && ctx->lds_min_rows > 0 && B >= ctx->lds_min_batch;   // (with the shared-weight kernel only)
@@ -1262,10 +1249,10 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
     wt.on = 1; wt.t_last = t_last;
     wt.steps4 = ctx->net[N4].steps; wt.steps6 = ctx->net[N6].steps;
     wt.cx4l = ctx->fb.x4l; wt.cx6l = ctx->fb.x6l;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_main[7], st));                    // the second stream joins (also: the table upload)
-    if (two) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_main[7], 0));
-    if (split_main) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_main[7], 0));
-    if (lin1_own) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_main[7], 0));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_main[7].get(), st));                    // the second stream joins (also: the table upload)
+    if (two) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_main[7].get(), 0));
+    if (split_main) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_main[7].get(), 0));
+    if (lin1_own) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_main[7].get(), 0));
     // ---- resident layer-step kernel ------------------------------------------------------------------------------------------------
     // On streams, a tick's layer steps are launches: every launch ends in a drain of the CUs it held, starts behind an event, and its
     // workgroups queue for CUs against the other streams' (one shared-weight workgroup holds a CU): the CUs hold an item 70-76 % of the
@@ -1279,27 +1266,19 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
     const bool resident = tri && ctx->resident_on && B <= 256 && P.n_ticks > 0 && !(ctx->timing && ctx->timing_mode != 3);
     if (resident) {
         if (int rc = ensure_lds_pool(ctx)) return rc;
+        if (!ctx->res_abort_h) {                                              // (read by the next rc_sequence call: kept until rc_destroy)
+            HIP_TRY(ctx, rc_alloc(ctx->res_abort_h, 1));
+            ctx->res_abort_h[0] = 0;
+        }
         const size_t nt = (size_t)P.n_ticks;
         if (nt > ctx->res_cap) {
             HIP_TRY(ctx, hipDeviceSynchronize());
-            if (ctx->res_ticks_d) (void)hipFree(ctx->res_ticks_d);
-            if (ctx->res_ticks_h) (void)hipHostFree(ctx->res_ticks_h);
-            if (ctx->res_ints_d) (void)hipFree(ctx->res_ints_d);
-            if (ctx->res_base_h) (void)hipHostFree(ctx->res_base_h);
-            ctx->res_ticks_d = nullptr; ctx->res_ticks_h = nullptr; ctx->res_ints_d = nullptr; ctx->res_base_h = nullptr; ctx->res_cap = 0;
             const size_t cap = nt + nt / 4 + 64;
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->res_ticks_d, cap * sizeof(ResidentTick)));
-            HIP_TRY(ctx, hipHostMalloc((void**)&ctx->res_ticks_h, cap * sizeof(ResidentTick), hipHostMallocDefault));
-            HIP_TRY(ctx, hipMalloc((void**)&ctx->res_ints_d, (cap * (RC_RES_MAXP + 2) + 1 + 4 + 16) * sizeof(int)));   // (+ 16: the sums of a -DRC_RES_PROF build)
-            HIP_TRY(ctx, hipHostMalloc((void**)&ctx->res_base_h, (cap + 1) * sizeof(int), hipHostMallocDefault));
-            if (!ctx->res_abort_h) {
-                HIP_TRY(ctx, hipHostMalloc((void**)&ctx->res_abort_h, sizeof(int), hipHostMallocDefault));
-                *ctx->res_abort_h = 0;
-            }
-            ctx->res_cap = cap;
+            HIP_TRY(ctx, rc_grow(ctx->res_cap, nt, cap, ctx->res_ticks_d, cap, ctx->res_ticks_h, cap,
+                                 ctx->res_ints_d, cap * (RC_RES_MAXP + 2) + 1 + 4 + 16, ctx->res_base_h, cap + 1));   // (+ 16: the sums of a -DRC_RES_PROF build)
         }
         const size_t cap = ctx->res_cap;
-        int* item_base_d = ctx->res_ints_d;
+        int* item_base_d = ctx->res_ints_d.get();
         int* done_d = item_base_d + cap + 1;
         int* tick_done_d = done_d + cap * RC_RES_MAXP;
         int* words_d = tick_done_d + cap;                                    // head, (unused), flag_tail, abort
@@ -1324,8 +1303,8 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
             const size_t region = (size_t)(k & 3);
             size_t tiles = 0;
             T.B = B;
-            T.n = build_lds_problems(ctx, ls, nullptr, ctx->lds_slab + region * ctx->lds_region_tiles * RC_LDS_SLAB_FLOATS,
-                                     ctx->lds_tickets + region * ctx->lds_region_tiles, T.p, RC_RES_MAXP, &T.n_items, &tiles, true);
+            T.n = build_lds_problems(ctx, ls, nullptr, ctx->lds_slab.get() + region * ctx->lds_region_tiles * RC_LDS_SLAB_FLOATS,
+                                     ctx->lds_tickets.get() + region * ctx->lds_region_tiles, T.p, RC_RES_MAXP, &T.n_items, &tiles, true);
             if (T.n != (int)ls.size()) return fail(ctx, RC_ERR_INVALID, "resident engine: more problems in a tick than its table holds");
             if (tiles > ctx->lds_region_tiles) return fail(ctx, RC_ERR_INVALID, "resident engine: more tiles in a tick than a slab region holds");
             const bool tail_wrote = cnt(P.n_reach, k - 1 - kTailStage) > 0;
@@ -1348,29 +1327,29 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
             run += T.n_items;
         }
         ctx->res_base_h[nt] = run;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->res_ticks_d, ctx->res_ticks_h, nt * sizeof(ResidentTick), hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(item_base_d, ctx->res_base_h, (nt + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->res_ticks_d.get(), ctx->res_ticks_h.get(), nt * sizeof(ResidentTick), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(item_base_d, ctx->res_base_h.get(), (nt + 1) * sizeof(int), hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemsetAsync(done_d, 0, (cap * (RC_RES_MAXP + 1) + 4 + 16) * sizeof(int), st));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_main[6], st));
-        HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_main[6], 0));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_main[6].get(), st));
+        HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_main[6].get(), 0));
         ResidentArgs R{};
-        R.ticks = ctx->res_ticks_d; R.item_base = item_base_d; R.n_ticks = P.n_ticks;
+        R.ticks = ctx->res_ticks_d.get(); R.item_base = item_base_d; R.n_ticks = P.n_ticks;
         R.head = words_d; R.done = done_d; R.tick_done = tick_done_d;
         R.flag_tail = words_d + 2; R.abort = words_d + 3;
         R.spin_bound = (unsigned long long)std::max(1, tune_env("RC_SEQ_RESIDENT_BOUND_MS", 2000)) * 100000ull;   // wall_clock64: 100 MHz
         {
-            hipEvent_t *ta = nullptr, *tb = nullptr;
+            hipEvent_t ta = nullptr, tb = nullptr;
             if (ctx->timing && !timing_pair(ctx, &ta, &tb)) return fail(ctx, RC_ERR_HIP, "hipEventCreate");
-            if (ta) HIP_TRY(ctx, hipEventRecord(*ta, st));
+            if (ta) HIP_TRY(ctx, hipEventRecord(ta, st));
             rc_launch_gemm_resident(R, res_wgs, st);
-            if (tb) HIP_TRY(ctx, hipEventRecord(*tb, st));
+            if (tb) HIP_TRY(ctx, hipEventRecord(tb, st));
         }
         ctx->stat_lds_launches += 1;
         // second stream, tick k: [init_net] -> prep -> [every item of tick k - 1] -> linear2 -> fuse -> tail -> flag_tail = k + 1
         for (int k = 0; k < P.n_ticks; ++k) {
             if (int rc = launch_problems(ctx, init_l[k], nullptr, aux, false)) return rc;
             if (k < P.n_prep) {
-                wp.frame_at = ctx->frame_at_d + (size_t)k * B;
+                wp.frame_at = ctx->frame_at_d.get() + (size_t)k * B;
                 wp.first_tick = k == 0 ? 1 : 0;
                 rc_launch_prep_wave(ctx->ring2[k % kRing], io0, prm, B, wp, aux);
             }
@@ -1385,9 +1364,9 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
             rc_launch_flag_set(words_d + 2, k + 1, aux);
             ctx->stat_ticks += 1;
         }
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[0], aux));
-        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[0], 0));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->res_abort_h, words_d + 3, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[0].get(), aux));
+        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[0].get(), 0));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->res_abort_h.get(), words_d + 3, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipGetLastError());
 #ifdef RC_RES_PROF
         {   // profiling builds (tools/probe_resprof.so): where the resident workgroups' time went, per item
@@ -1412,22 +1391,22 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
             // second-stream work, in front of its waits for the layer steps of tick k - 1
             for (const GemmProblem& p : collect(k, last_group)) (p.epi != RC_EPI_LSTM ? tri_l1 : (p.H == 1024 ? tri_ls6 : tri_ls5)).push_back(p);
             bool sigl = false;
-            if (int rc = launch_problems(ctx, tri_l1, nullptr, aux, false, ctx->ev_lin1[e], &sigl)) return rc;
-            if (!sigl) HIP_TRY(ctx, hipEventRecord(ctx->ev_lin1[e], aux));
+            if (int rc = launch_problems(ctx, tri_l1, nullptr, aux, false, ctx->ev_lin1[e].get(), &sigl)) return rc;
+            if (!sigl) HIP_TRY(ctx, hipEventRecord(ctx->ev_lin1[e].get(), aux));
         }
         // ---- per-row kernels and linear2 of tick k (second stream: after the previous tick's wide launches)
         const bool prep_first = tri && prep_early != 0 && k < P.n_prep;
         if (prep_first) {
-            wp.frame_at = ctx->frame_at_d + (size_t)k * B;
+            wp.frame_at = ctx->frame_at_d.get() + (size_t)k * B;
             wp.first_tick = k == 0 ? 1 : 0;
             rc_launch_prep_wave(ctx->ring2[k % kRing], io0, prm, B, wp, aux);
         }
-        if (tri && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_h5[ep], 0));
-        if (two && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_main[ep], 0));
-        if (split_main && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_h512[ep], 0));
-        if (lin1_own && !tri && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_lin1[ep], 0));   // (init_net's last layer -> the tail)
+        if (tri && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_h5[ep].get(), 0));
+        if (two && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_main[ep].get(), 0));
+        if (split_main && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_h512[ep].get(), 0));
+        if (lin1_own && !tri && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_lin1[ep].get(), 0));   // (init_net's last layer -> the tail)
         if (k < P.n_prep && !prep_first) {
-            wp.frame_at = ctx->frame_at_d + (size_t)k * B;
+            wp.frame_at = ctx->frame_at_d.get() + (size_t)k * B;
             wp.first_tick = k == 0 ? 1 : 0;
             rc_launch_prep_wave(ctx->ring2[k % kRing], io0, prm, B, wp, aux);   // (before the tail: it initialises the tail's target slot)
         }
@@ -1440,7 +1419,7 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
             wt.x4l = tgt.x4l; wt.x6l = tgt.x6l; wt.flags2 = tgt.flags2; wt.wsteps = tgt.wsteps;
             aux_signalled = two && ext_events;
             merged = rc_launch_fuse_tail(ctx->ring2[(k - kTailStage) % kRing], ctx->ring2[(k - kFuseStage) % kRing], io0, prm, ctx->body, B, wt, aux,
-                                         aux_signalled ? ctx->ev_aux[e] : nullptr);
+                                         aux_signalled ? ctx->ev_aux[e].get() : nullptr);
             if (!merged) aux_signalled = false;
         }
         if (!merged && cnt(P.n_valid, k - kFuseStage) > 0) rc_launch_fuse(ctx->ring2[(k - kFuseStage) % kRing], io0, prm, B, aux);
@@ -1448,9 +1427,9 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
             const FrameBuffers& tgt = ctx->ring2[k % kRing];
             wt.x4l = tgt.x4l; wt.x6l = tgt.x6l; wt.flags2 = tgt.flags2; wt.wsteps = tgt.wsteps;
             aux_signalled = two && ext_events;
-            rc_launch_tail(ctx->ring2[(k - kTailStage) % kRing], io0, prm, ctx->body, B, 0, aux, nullptr, &wt, aux_signalled ? ctx->ev_aux[e] : nullptr);
+            rc_launch_tail(ctx->ring2[(k - kTailStage) % kRing], io0, prm, ctx->body, B, 0, aux, nullptr, &wt, aux_signalled ? ctx->ev_aux[e].get() : nullptr);
         }
-        if (two && !aux_signalled) HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[e], aux));
+        if (two && !aux_signalled) HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[e].get(), aux));
         // ---- the GEMM stages of tick k (caller's stream: after the previous tick's second-stream work)
         // Of the caller's-stream launches only linear1 (and init_net) READ what the second stream wrote in the previous tick, and
         // with the groups merged they sit in the LAST launch: the wait goes in front of that one (late_wait), and the first launch
@@ -1468,33 +1447,33 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
             for (const GemmProblem& p : gp[g]) n_tiles += (long long)p.n_tiles * p.m_tiles;
         }
         bool main_signalled = false;
-        hipEvent_t stop_ev = (two && ext_events) ? ctx->ev_main[e] : nullptr;
+        hipEvent_t stop_ev = (two && ext_events) ? ctx->ev_main[e].get() : nullptr;
         if (tri) {
             bool sig6 = false, sig5 = false, sig0 = false;
             // (tri_swap: rnn4 -- the longest chain of a tick -- on the context's own stream, which may carry a queue priority
             // (RC_SEQ_H512_PRIO), rnn6 on the caller's)
             hipStream_t s_r6 = tri_swap ? st : s2, s_r4 = tri_swap ? s2 : st;
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s_r6, ctx->ev_lin1[ep], 0));
-            if (int rc = launch_problems(ctx, tri_ls6, nullptr, s_r6, false, ctx->ev_h512[e], &sig6)) return rc;
-            if (!sig6) HIP_TRY(ctx, hipEventRecord(ctx->ev_h512[e], s_r6));
+            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s_r6, ctx->ev_lin1[ep].get(), 0));
+            if (int rc = launch_problems(ctx, tri_ls6, nullptr, s_r6, false, ctx->ev_h512[e].get(), &sig6)) return rc;
+            if (!sig6) HIP_TRY(ctx, hipEventRecord(ctx->ev_h512[e].get(), s_r6));
             // The H = 512 nets' stream waits for the END of the second stream's previous tick. It NEEDS only linear1(k - 1) -- the head of
             // that tick, behind that stream's tick k - 2, which covers every buffer the layer steps rewrite -- and the end only behind an
             // init_net state write of its tail (rnn2 l0). RC_SEQ_H5_EARLY=1 issues exactly that (race free on the stream model), and is
             // SLOWER: all-visible 1,458k -> 1,405k, mixed 1,211k -> 1,182k body-frames/s -- the three layer-step launches of a tick do
             // better in step with each other than spread over the tick (profiles/r06_resident_notes.txt).
             static const int h5_early = tune_env("RC_SEQ_H5_EARLY", 0);
-            if (k > 0 && h5_early && cnt(P.n_reach, k - 1 - kTailStage) == 0) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_lin1[ep], 0));
-            else if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_aux[ep], 0));
-            if (int rc = launch_problems(ctx, tri_ls5, nullptr, s4, false, ctx->ev_h5[e], &sig5)) return rc;
-            if (!sig5) HIP_TRY(ctx, hipEventRecord(ctx->ev_h5[e], s4));
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s_r4, ctx->ev_lin1[ep], 0));
+            if (k > 0 && h5_early && cnt(P.n_reach, k - 1 - kTailStage) == 0) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_lin1[ep].get(), 0));
+            else if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_aux[ep].get(), 0));
+            if (int rc = launch_problems(ctx, tri_ls5, nullptr, s4, false, ctx->ev_h5[e].get(), &sig5)) return rc;
+            if (!sig5) HIP_TRY(ctx, hipEventRecord(ctx->ev_h5[e].get(), s4));
+            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s_r4, ctx->ev_lin1[ep].get(), 0));
             for (int g = 0; g < last_group; ++g)
                 if (!gp[g].empty()) {
                     bool sig = false;
-                    if (int rc = launch_problems(ctx, gp[g], nullptr, s_r4, false, sig0 ? nullptr : ctx->ev_main[e], &sig)) return rc;
+                    if (int rc = launch_problems(ctx, gp[g], nullptr, s_r4, false, sig0 ? nullptr : ctx->ev_main[e].get(), &sig)) return rc;
                     sig0 = sig0 || sig;
                 }
-            if (!sig0) HIP_TRY(ctx, hipEventRecord(ctx->ev_main[e], s_r4));
+            if (!sig0) HIP_TRY(ctx, hipEventRecord(ctx->ev_main[e].get(), s_r4));
             main_signalled = true;
         } else if (lin1_own) {
             // Regrouped tick with {linear1, init_net} on a stream of its own: linear1(k) needs only the second stream's work of tick k - 1,
@@ -1504,60 +1483,60 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
             std::vector<GemmProblem> l1, ls;
             for (const GemmProblem& p : gp[last_group]) (p.epi == RC_EPI_LSTM ? ls : l1).push_back(p);
             bool sigl = false, sig2 = false, sig0 = false;
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_aux[ep], 0));
-            if (int rc = launch_problems(ctx, l1, nullptr, s4, false, ctx->ev_lin1[e], &sigl)) return rc;
-            if (!sigl) HIP_TRY(ctx, hipEventRecord(ctx->ev_lin1[e], s4));
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_aux[ep], 0));      // (rnn2 l0 behind the tail's init_net state write)
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_lin1[ep], 0));
-            if (int rc = launch_problems(ctx, ls, nullptr, s2, false, ctx->ev_h512[e], &sig2)) return rc;
-            if (!sig2) HIP_TRY(ctx, hipEventRecord(ctx->ev_h512[e], s2));
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_lin1[ep], 0));
+            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_aux[ep].get(), 0));
+            if (int rc = launch_problems(ctx, l1, nullptr, s4, false, ctx->ev_lin1[e].get(), &sigl)) return rc;
+            if (!sigl) HIP_TRY(ctx, hipEventRecord(ctx->ev_lin1[e].get(), s4));
+            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_aux[ep].get(), 0));      // (rnn2 l0 behind the tail's init_net state write)
+            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_lin1[ep].get(), 0));
+            if (int rc = launch_problems(ctx, ls, nullptr, s2, false, ctx->ev_h512[e].get(), &sig2)) return rc;
+            if (!sig2) HIP_TRY(ctx, hipEventRecord(ctx->ev_h512[e].get(), s2));
+            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_lin1[ep].get(), 0));
             for (int g = 0; g < last_group; ++g)
                 if (!gp[g].empty()) {
                     bool sig = false;
-                    if (int rc = launch_problems(ctx, gp[g], nullptr, st, false, sig0 ? nullptr : ctx->ev_main[e], &sig)) return rc;
+                    if (int rc = launch_problems(ctx, gp[g], nullptr, st, false, sig0 ? nullptr : ctx->ev_main[e].get(), &sig)) return rc;
                     sig0 = sig0 || sig;
                 }
             main_signalled = sig0;
         } else if (split_main) {
             // {H = 512 nets, linear1} (reads what the second stream wrote in tick k - 1) on its own stream ...
             bool sig2 = false, sig0 = false;
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_aux[ep], 0));
-            if (int rc = launch_problems(ctx, gp[last_group], nullptr, s2, false, ctx->ev_h512[e], &sig2)) return rc;
-            if (!sig2) HIP_TRY(ctx, hipEventRecord(ctx->ev_h512[e], s2));
+            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_aux[ep].get(), 0));
+            if (int rc = launch_problems(ctx, gp[last_group], nullptr, s2, false, ctx->ev_h512[e].get(), &sig2)) return rc;
+            if (!sig2) HIP_TRY(ctx, hipEventRecord(ctx->ev_h512[e].get(), s2));
             // ... {rnn6, rnn4 (+ init_net)} behind the previous tick's linear1 (init_net also reads the previous tick's fuse)
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_h512[ep], 0));
-            if (k > 0 && init_now && !regroup) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep], 0));
+            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_h512[ep].get(), 0));
+            if (k > 0 && init_now && !regroup) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep].get(), 0));
             for (int g = 0; g < last_group; ++g)
                 if (!gp[g].empty()) {
                     bool sig = false;
-                    if (int rc = launch_problems(ctx, gp[g], nullptr, st, false, sig0 ? nullptr : ctx->ev_main[e], &sig)) return rc;
+                    if (int rc = launch_problems(ctx, gp[g], nullptr, st, false, sig0 ? nullptr : ctx->ev_main[e].get(), &sig)) return rc;
                     sig0 = sig0 || sig;
                 }
             main_signalled = sig0;
         } else if (merge_fill && n_prob > 0 && n_prob <= RC_MAX_PROB && n_tiles <= 512) {
             // a filling / draining tick (or one of lagging rows): everything fits two rounds of one launch -- no boundary at all, but
             // the stream wait is back in front of the tick's first launch: a wash (off by default)
-            if (two && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep], 0));
+            if (two && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep].get(), 0));
             std::vector<GemmProblem> all;
             for (int g = 0; g <= last_group; ++g) all.insert(all.end(), gp[g].begin(), gp[g].end());
             if (int rc = launch_problems(ctx, all, nullptr, st, false, stop_ev, &main_signalled)) return rc;
         } else {
             const bool late = late_wait && merge_h512 && !init_now;
-            if (two && k > 0 && !late) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep], 0));
+            if (two && k > 0 && !late) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep].get(), 0));
             for (int g = 0; g <= last_group; ++g) {
-                if (two && k > 0 && late && g == last_group) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep], 0));
+                if (two && k > 0 && late && g == last_group) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep].get(), 0));
                 if (int rc = launch_problems(ctx, gp[g], nullptr, st, false, g == last_group ? stop_ev : nullptr, g == last_group ? &main_signalled : nullptr)) return rc;
             }
         }
-        if (two && !main_signalled) HIP_TRY(ctx, hipEventRecord(ctx->ev_main[e], st));
+        if (two && !main_signalled) HIP_TRY(ctx, hipEventRecord(ctx->ev_main[e].get(), st));
         ctx->stat_ticks += 1;
     }
-    if (two && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[(P.n_ticks - 1) & 3], 0));
-    if (split_main && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_h512[(P.n_ticks - 1) & 3], 0));
-    if (lin1_own && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_lin1[(P.n_ticks - 1) & 3], 0));
-    if (tri && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_h5[(P.n_ticks - 1) & 3], 0));
-    if (tri && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_main[(P.n_ticks - 1) & 3], 0));
+    if (two && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[(P.n_ticks - 1) & 3].get(), 0));
+    if (split_main && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_h512[(P.n_ticks - 1) & 3].get(), 0));
+    if (lin1_own && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_lin1[(P.n_ticks - 1) & 3].get(), 0));
+    if (tri && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_h5[(P.n_ticks - 1) & 3].get(), 0));
+    if (tri && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_main[(P.n_ticks - 1) & 3].get(), 0));
     HIP_TRY(ctx, hipGetLastError());
     ctx->stat_wave_frames += t_last - t0 + 1;
     return RC_OK;
@@ -1568,10 +1547,7 @@ int sweep_scratch(rc_ctx* ctx, size_t floats, hipStream_t st) {
     if (floats <= ctx->sweep_scratch_cap) return RC_OK;
     (void)st;
     HIP_TRY(ctx, hipDeviceSynchronize());          // the scratch is shared by entry points that take independent stream arguments
-    if (ctx->sweep_scratch) (void)hipFree(ctx->sweep_scratch);
-    ctx->sweep_scratch = nullptr; ctx->sweep_scratch_cap = 0;
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->sweep_scratch, floats * sizeof(float)));
-    ctx->sweep_scratch_cap = floats;
+    HIP_TRY(ctx, rc_grow(ctx->sweep_scratch_cap, floats, floats, ctx->sweep_scratch, floats));
     return RC_OK;
 }
 
@@ -1605,28 +1581,12 @@ int fold_regressor(rc_ctx* ctx) {
 int reserve_plan_tables(rc_ctx* ctx, int T) {
     const size_t B = (size_t)ctx->B;
     const size_t need = B * (size_t)T;
-    if (need > ctx->scan_cap) {
-        if (ctx->scan_codes_d) (void)hipFree(ctx->scan_codes_d);
-        if (ctx->scan_codes_h) (void)hipHostFree(ctx->scan_codes_h);
-        ctx->scan_codes_d = nullptr; ctx->scan_codes_h = nullptr; ctx->scan_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->scan_codes_d, need));
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->scan_codes_h, need, hipHostMallocDefault));
-        ctx->scan_cap = need;
-    }
-    if (!ctx->scan_state_h) HIP_TRY(ctx, hipHostMalloc((void**)&ctx->scan_state_h, B * 3 * sizeof(int), hipHostMallocDefault));
+    HIP_TRY(ctx, rc_grow(ctx->scan_cap, need, need, ctx->scan_codes_d, need, ctx->scan_codes_h, need));
+    if (!ctx->scan_state_h) HIP_TRY(ctx, rc_alloc(ctx->scan_state_h, B * 3));
     const size_t fneed = B * ((size_t)T + 64);                                  // ticks of a T-frame plan: T + pipeline depth + lag
-    if (fneed > ctx->frame_at_cap) {
-        if (ctx->frame_at_d) (void)hipFree(ctx->frame_at_d);
-        if (ctx->frame_at_h) (void)hipHostFree(ctx->frame_at_h);
-        ctx->frame_at_d = nullptr; ctx->frame_at_h = nullptr; ctx->frame_at_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->frame_at_d, fneed * sizeof(int)));
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->frame_at_h, fneed * sizeof(int), hipHostMallocDefault));
-        ctx->frame_at_cap = fneed;
-    }
-    return RC_OK;
+    return reserve_frame_at(ctx, fneed, fneed);
 }
 
-// tables of the one-launch-per-tick path for a call of n_ticks ticks (grow-only; the caller makes sure nothing in flight reads them)
 int check_ready(rc_ctx* ctx) {
     if (!ctx) return RC_ERR_INVALID;
     if (!ctx->have_weights) return fail(ctx, RC_ERR_STATE, "weights not finalized (rc_finalize_weights)");
@@ -1655,8 +1615,8 @@ int rc_ctx_init_net(rc_ctx* ctx, SubnetDense out[3]) {
 }
 int rc_ctx_net_index(const char* name) { return net_index(name); }
 int rc_ctx_gemm_split(rc_ctx* ctx) { return ctx->gemm_split ? 1 : 0; }
-SubnetState*& rc_ctx_subnet(rc_ctx* ctx) { return ctx->subnet; }
-SmplifyState*& rc_ctx_smplify(rc_ctx* ctx) { return ctx->smplify; }
+SubnetOwner& rc_ctx_subnet(rc_ctx* ctx) { return ctx->subnet; }
+SmplifyOwner& rc_ctx_smplify(rc_ctx* ctx) { return ctx->smplify; }
 unsigned long long rc_ctx_ign_mask(rc_ctx* ctx) { return ctx->ign_mask; }
 
 // Begin-time self-check of the AQL packet chain (round-4/5 review): ONE lean frame on a fixed synthetic input, once as the graph replay
@@ -1669,7 +1629,7 @@ std::string live_selfcheck(rc_ctx* ctx) {
     static const int mode = std::getenv("RC_LIVE_AQL_SELFCHECK") ? std::atoi(std::getenv("RC_LIVE_AQL_SELFCHECK")) : 1;
     if (mode == 0 || !ctx->live_aql || ctx->aql_prog_lean < 0 || !ctx->live_exec_lean || !ctx->live_zero_copy) return std::string();
     const size_t B = ctx->B;
-    hipStream_t st = ctx->live_stream;
+    hipStream_t st = ctx->live_stream.get();
     if (hipDeviceSynchronize() != hipSuccess) return "self-check: device synchronisation failed";
     // save
     const size_t kMaxBytes = 8u << 20;
@@ -1682,37 +1642,37 @@ std::string live_selfcheck(rc_ctx* ctx) {
     auto restore = [&]() -> bool {
         size_t o = 0;
         for (const auto& r : regs) { if (hipMemcpy(r.first, save.data() + o, r.second, hipMemcpyHostToDevice) != hipSuccess) return false; o += r.second; }
-        *ctx->live_status_h = 0;
+        ctx->live_status_h[0] = 0;
         return hipDeviceSynchronize() == hipSuccess;
     };
     // a mid-confidence frame (no init_net trigger, no deferred updater step): identity orientations, small accelerations, a plausible skeleton
-    std::vector<float> in_keep(ctx->live_in_h, ctx->live_in_h + B * 171), out_keep(ctx->live_out_h, ctx->live_out_h + B * 219);
+    std::vector<float> in_keep(ctx->live_in_h.get(), ctx->live_in_h.get() + B * 171), out_keep(ctx->live_out_h.get(), ctx->live_out_h.get() + B * 219);
     for (size_t b = 0; b < B; ++b) {
-        float* j = ctx->live_in_h + b * 99;
+        float* j = ctx->live_in_h.get() + b * 99;
         for (int k = 0; k < 33; ++k) { j[3 * k] = 0.05f * (float)((k * 7) % 11 - 5) / 5.0f; j[3 * k + 1] = 0.08f * (float)((k * 5) % 13 - 6) / 6.0f; j[3 * k + 2] = 0.75f; }
-        float* a = ctx->live_in_h + B * 99 + b * 18;
+        float* a = ctx->live_in_h.get() + B * 99 + b * 18;
         for (int k = 0; k < 18; ++k) a[k] = 0.01f * (float)(k % 5 - 2);
-        float* o = ctx->live_in_h + B * 117 + b * 54;
+        float* o = ctx->live_in_h.get() + B * 117 + b * 54;
         for (int k = 0; k < 54; ++k) o[k] = (k % 9 == 0 || k % 9 == 4 || k % 9 == 8) ? 1.0f : 0.0f;
     }
     std::string verdict;
     std::vector<float> out_graph(B * 219), out_aql(B * 219);
     int status_graph = 0, status_aql = 0;
     for (size_t q = 0; q < B * 219; ++q) ctx->live_out_h[q] = -7.0f;
-    if (hipGraphLaunch(ctx->live_exec_lean, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) verdict = "self-check: graph replay of the lean frame failed";
-    status_graph = *ctx->live_status_h;
-    std::copy(ctx->live_out_h, ctx->live_out_h + B * 219, out_graph.begin());
+    if (hipGraphLaunch(ctx->live_exec_lean.get(), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) verdict = "self-check: graph replay of the lean frame failed";
+    status_graph = ctx->live_status_h[0];
+    std::copy(ctx->live_out_h.get(), ctx->live_out_h.get() + B * 219, out_graph.begin());
     if (!restore() && verdict.empty()) verdict = "self-check: state restore failed";
     if (verdict.empty()) {
         for (size_t q = 0; q < B * 219; ++q) ctx->live_out_h[q] = -7.0f;
         if (rc_aql_run(ctx->live_aql, ctx->aql_prog_lean) != 0) verdict = "self-check: the packet chain did not retire";
-        status_aql = *ctx->live_status_h;
-        std::copy(ctx->live_out_h, ctx->live_out_h + B * 219, out_aql.begin());
+        status_aql = ctx->live_status_h[0];
+        std::copy(ctx->live_out_h.get(), ctx->live_out_h.get() + B * 219, out_aql.begin());
         if (mode == 2) { uint32_t u; std::memcpy(&u, &out_aql[0], 4); u ^= 1u; std::memcpy(&out_aql[0], &u, 4); }      // forced mismatch (test hook)
         if (!restore() && verdict.empty()) verdict = "self-check: state restore failed";
     }
-    std::copy(in_keep.begin(), in_keep.end(), ctx->live_in_h);
-    std::copy(out_keep.begin(), out_keep.end(), ctx->live_out_h);
+    std::copy(in_keep.begin(), in_keep.end(), ctx->live_in_h.get());
+    std::copy(out_keep.begin(), out_keep.end(), ctx->live_out_h.get());
     if (verdict.empty() && (status_graph != status_aql || std::memcmp(out_graph.data(), out_aql.data(), B * 219 * sizeof(float)) != 0)) {
         verdict = "self-check: packet chain and graph replay disagree on the probe frame";
     }
@@ -1747,7 +1707,7 @@ int rc_create(int32_t batch, int32_t live, rc_ctx** out) {
     ctx->B = batch;
     ctx->Bp = round_up(batch, RC_MT);
     (void)hipGetDevice(&ctx->dev);
-    if (hipEventCreateWithFlags(&ctx->eager_ev, hipEventDisableTiming) != hipSuccess) ctx->eager_ev = nullptr;
+    (void)hipEventCreateWithFlags(rc_out(ctx->eager_ev), hipEventDisableTiming);      // (without it the live graph does not wait for eager work)
     rc_default_params(live, &ctx->prm);
     ctx->gemm_split = tune_env("RC_GEMM_SPLIT", batch >= RC_SPLIT_MIN_BATCH ? 1 : 0) != 0;
     ctx->live_eager = tune_env("RC_LIVE_EAGER", 0) != 0;
@@ -1839,28 +1799,7 @@ int rc_create(int32_t batch, int32_t live, rc_ctx** out) {
 int rc_destroy(rc_ctx* ctx) {
     if (!ctx) return RC_OK;
     rc_live_end(ctx);
-    rc_smplify_free(ctx->smplify);
-    rc_subnet_free(ctx->subnet);
-    for (void* p : ctx->allocs) (void)hipFree(p);
-    for (void* p : ctx->weight_allocs) (void)hipFree(p);
-    if (ctx->eager_ev) (void)hipEventDestroy(ctx->eager_ev);
-    if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
-    if (ctx->h512_stream) (void)hipStreamDestroy(ctx->h512_stream);
-    for (hipEvent_t e : ctx->ev_h512) if (e) (void)hipEventDestroy(e);
-    if (ctx->lin1_stream) (void)hipStreamDestroy(ctx->lin1_stream);
-    for (hipEvent_t e : ctx->ev_lin1) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_h5) if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < 8; ++i) {
-        if (ctx->ev_main[i]) (void)hipEventDestroy(ctx->ev_main[i]);
-        if (ctx->ev_aux[i]) (void)hipEventDestroy(ctx->ev_aux[i]);
-    }
-    if (ctx->scan_codes_d) (void)hipFree(ctx->scan_codes_d);
-    if (ctx->scan_codes_h) (void)hipHostFree(ctx->scan_codes_h);
-    if (ctx->scan_state_h) (void)hipHostFree(ctx->scan_state_h);
-    if (ctx->sweep_scratch) (void)hipFree(ctx->sweep_scratch);
-    if (ctx->frame_at_d) (void)hipFree(ctx->frame_at_d);
-    if (ctx->frame_at_h) (void)hipHostFree(ctx->frame_at_h);
-    for (auto& e : ctx->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    (void)hipDeviceSynchronize();        // every buffer, stream and event of the context is released by its owner in ~rc_ctx
     delete ctx;
     return RC_OK;
 }
@@ -1919,7 +1858,6 @@ int rc_finalize_weights(rc_ctx* ctx) {
     // leak a 242 MB copy per call.
     rc_live_end(ctx);
     HIP_TRY(ctx, hipDeviceSynchronize());
-    for (void* p : ctx->weight_allocs) (void)hipFree(p);
     ctx->weight_allocs.clear();
     ctx->have_weights = false;
     ctx->wave2_valid = false;            // the sequence-mode launch tables hold weight pointers
@@ -2094,10 +2032,10 @@ int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const
             HIP_TRY(ctx, hipStreamSynchronize(st));                             // nothing in flight may still read the old tables
             if (int rc = reserve_plan_tables(ctx, T)) return rc;
         }
-        rc_launch_scan_conf(j2dc, rs_j2d, B, T, ctx->prm.conf_lo, ctx->prm.conf_hi, ctx->scan_codes_d, st);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->scan_codes_h, ctx->scan_codes_d, need, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->scan_state_h, ctx->fb.first_reach, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-        unsigned char* pend_b = reinterpret_cast<unsigned char*>(ctx->scan_state_h + 2 * B);     // pinned, like the other two
+        rc_launch_scan_conf(j2dc, rs_j2d, B, T, ctx->prm.conf_lo, ctx->prm.conf_hi, ctx->scan_codes_d.get(), st);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->scan_codes_h.get(), ctx->scan_codes_d.get(), need, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->scan_state_h.get(), ctx->fb.first_reach, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+        unsigned char* pend_b = reinterpret_cast<unsigned char*>(ctx->scan_state_h.get() + 2 * B);     // pinned, like the other two
         HIP_TRY(ctx, hipMemcpyAsync(pend_b, ctx->fb.pend, (size_t)B, hipMemcpyDeviceToHost, st));
         {   // a blocking wait wakes up tens of microseconds late: poll for a bounded while first (the stream may still hold
             // milliseconds of earlier frames, which a sleeping wait serves better)
@@ -2107,9 +2045,9 @@ int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const
                    std::chrono::steady_clock::now() - t_spin < std::chrono::microseconds(300)) { }
         }
         HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (ctx->res_abort_h && *ctx->res_abort_h) {                           // (the copy sits behind the segment on this stream)
+        if (ctx->res_abort_h && ctx->res_abort_h[0]) {                           // (the copy sits behind the segment on this stream)
             ctx->stat_resident_aborts += 1;
-            *ctx->res_abort_h = 0;
+            ctx->res_abort_h[0] = 0;
             return fail(ctx, RC_ERR_STATE, "resident layer-step kernel: a wait ran out in the previous call (its outputs and the recurrent state are invalid); "
                                            "RC_SEQ_RESIDENT=0 selects the stream engine");
         }
@@ -2118,7 +2056,7 @@ int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const
         const bool imu = ctx->prm.use_imu_updater != 0, vup = ctx->prm.use_vision_updater != 0;
         {
             // per-row-cursor engine on frames [w0, T): the rows' state in front of frame w0
-            std::vector<int> fr(ctx->scan_state_h, ctx->scan_state_h + B), pd(ctx->scan_state_h + B, ctx->scan_state_h + 2 * B);
+            std::vector<int> fr(ctx->scan_state_h.get(), ctx->scan_state_h.get() + B), pd(ctx->scan_state_h.get() + B, ctx->scan_state_h.get() + 2 * B);
             if (w0) {
                 for (int b = 0; b < B; ++b) {
                     const int c = ctx->scan_codes_h[b];
@@ -2127,13 +2065,13 @@ int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const
                 }
             }
             const double cost[4] = {ctx->cost_tick_us, ctx->cost_tick_small_us, ctx->cost_frame_us, ctx->cost_tr_us};
-            plan_wave(ctx->scan_codes_h, B, T, w0, fr.data(), pd.data(), imu, vup, cost, wplan);
+            plan_wave(ctx->scan_codes_h.get(), B, T, w0, fr.data(), pd.data(), imu, vup, cost, wplan);
             if (ctx->seq_mode == 2 || wplan.est_wave_us < wplan.est_stepped_us) wave2_from = w0;
             static const bool dbg = tune_env("RC_SEQ_DEBUG", 0) != 0;
             if (dbg) std::fprintf(stderr, "rc_sequence plan: T=%d ticks=%d lag_max=%d est_wave=%.0f us est_stepped=%.0f us -> %s\n", T, wplan.n_ticks,
                                   wplan.lag_max, wplan.est_wave_us, wplan.est_stepped_us, wave2_from >= 0 ? "wavefront" : "frame-stepped");
         }
-        plan_sequence(ctx->scan_codes_h, B, T, ctx->scan_state_h + B, ff, vup, mode.data());    // transition-launch marks of stepped frames
+        plan_sequence(ctx->scan_codes_h.get(), B, T, ctx->scan_state_h.get() + B, ff, vup, mode.data());    // transition-launch marks of stepped frames
     }
     bool prep_done = false;                 // the previous frame's tail kernel already ran this frame's prep
     for (int t = 0; t < T;) {
@@ -2238,27 +2176,17 @@ int rc_plan_wave(const int8_t* codes, int32_t B, int32_t T, int32_t t0, const in
 
 int rc_live_end(rc_ctx* ctx) {
     if (!ctx) return RC_ERR_INVALID;
-    if (ctx->live_exec) { (void)hipGraphExecDestroy(ctx->live_exec); ctx->live_exec = nullptr; }
-    if (ctx->live_graph) { (void)hipGraphDestroy(ctx->live_graph); ctx->live_graph = nullptr; }
-    if (ctx->live_exec_notr) { (void)hipGraphExecDestroy(ctx->live_exec_notr); ctx->live_exec_notr = nullptr; }
+    // (order: the packet chain goes before the buffers its packets read, every graph exec before its graph)
+    ctx->live_exec.reset(); ctx->live_graph.reset(); ctx->live_exec_notr.reset();
     if (ctx->live_aql) { rc_aql_destroy(ctx->live_aql); ctx->live_aql = nullptr; }     // (waits for a pre-step still in flight; tells a waiting K1 to leave)
     ctx->spin_mb = nullptr; ctx->spin_in = nullptr; ctx->spin_pending = -1; ctx->spin_valid = false;
     for (int q = 0; q < 2; ++q) ctx->aql_prog_spin[q] = ctx->aql_prog_spin_pre[q] = -1;
-    if (ctx->spin_state_h) { (void)hipHostFree(ctx->spin_state_h); ctx->spin_state_h = nullptr; }
-    if (ctx->live_pre_buf) { (void)hipFree(ctx->live_pre_buf); ctx->live_pre_buf = nullptr; }
+    ctx->spin_state_h.reset(); ctx->live_pre_buf.reset();
     ctx->aql_prog_lean = ctx->aql_prog_lean_pre = ctx->aql_prog_pre = -1;
     ctx->live_pre_valid = false; ctx->live_have_return = false;
-    if (ctx->live_exec_lean) { (void)hipGraphExecDestroy(ctx->live_exec_lean); ctx->live_exec_lean = nullptr; }
-    if (ctx->live_graph_lean) { (void)hipGraphDestroy(ctx->live_graph_lean); ctx->live_graph_lean = nullptr; }
-    if (ctx->live_status_h) { (void)hipHostFree(ctx->live_status_h); ctx->live_status_h = nullptr; }
-    if (ctx->live_abort_d) { (void)hipFree(ctx->live_abort_d); ctx->live_abort_d = nullptr; }
-    if (ctx->live_graph_notr) { (void)hipGraphDestroy(ctx->live_graph_notr); ctx->live_graph_notr = nullptr; }
-    if (ctx->live_stream) { (void)hipStreamDestroy(ctx->live_stream); ctx->live_stream = nullptr; }
-    if (ctx->live_in_h) { (void)hipHostFree(ctx->live_in_h); ctx->live_in_h = nullptr; }
-    if (ctx->live_out_h) { (void)hipHostFree(ctx->live_out_h); ctx->live_out_h = nullptr; }
-    if (ctx->live_in_d) { (void)hipFree(ctx->live_in_d); ctx->live_in_d = nullptr; }
-    if (ctx->live_out_d) { (void)hipFree(ctx->live_out_d); ctx->live_out_d = nullptr; }
-    if (ctx->live_ft_d) { (void)hipFree(ctx->live_ft_d); ctx->live_ft_d = nullptr; }
+    ctx->live_exec_lean.reset(); ctx->live_graph_lean.reset(); ctx->live_status_h.reset(); ctx->live_abort_d.reset();
+    ctx->live_graph_notr.reset(); ctx->live_stream.reset();
+    ctx->live_in_h.reset(); ctx->live_out_h.reset(); ctx->live_in_d.reset(); ctx->live_out_d.reset(); ctx->live_ft_d.reset();
     return RC_OK;
 }
 
@@ -2266,23 +2194,21 @@ int rc_live_begin(rc_ctx* ctx) {
     if (int rc = check_ready(ctx)) return rc;
     rc_live_end(ctx);
     const size_t B = ctx->B;
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->live_stream, hipStreamNonBlocking));
-    HIP_TRY(ctx, hipHostMalloc((void**)&ctx->live_in_h, B * 171 * sizeof(float), hipHostMallocMapped));
-    HIP_TRY(ctx, hipHostMalloc((void**)&ctx->live_out_h, B * 219 * sizeof(float), hipHostMallocMapped));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->live_in_d, B * 171 * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->live_out_d, B * 219 * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->live_ft_d, B * 3 * sizeof(float)));
+    HIP_TRY(ctx, hipStreamCreateWithFlags(rc_out(ctx->live_stream), hipStreamNonBlocking));
+    HIP_TRY(ctx, rc_alloc(ctx->live_in_h, B * 171, hipHostMallocMapped));
+    HIP_TRY(ctx, rc_alloc(ctx->live_out_h, B * 219, hipHostMallocMapped));
+    HIP_TRY(ctx, rc_alloc_all(ctx->live_in_d, B * 171, ctx->live_out_d, B * 219, ctx->live_ft_d, B * 3));
     // Small batches: the frame kernels read the 684 B / body of inputs and write the 876 B of outputs straight from / to
     // the pinned host buffers (two copy nodes and their barriers cost more than the PCIe reads). Larger batches keep
     // H2D -> frame -> D2H. Layout: inputs [j2dc B*99 | accc B*18 | oric B*54], outputs [pose B*216 | tran B*3].
     ctx->live_zero_copy = B <= 16;
-    ctx->live_in_io = ctx->live_in_d;
-    ctx->live_out_io = ctx->live_out_d;
+    ctx->live_in_io = ctx->live_in_d.get();
+    ctx->live_out_io = ctx->live_out_d.get();
     if (ctx->live_zero_copy) {
-        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->live_in_io, ctx->live_in_h, 0));
-        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->live_out_io, ctx->live_out_h, 0));
+        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->live_in_io, ctx->live_in_h.get(), 0));
+        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->live_out_io, ctx->live_out_h.get(), 0));
     }
-    hipStream_t st = ctx->live_stream;
+    hipStream_t st = ctx->live_stream.get();
     const bool timing = ctx->timing;
     struct TimingGuard { rc_ctx* c; bool v; ~TimingGuard() { c->timing = v; } } timing_guard{ctx, timing};   // restored on every exit path
     ctx->timing = false;
@@ -2293,15 +2219,15 @@ int rc_live_begin(rc_ctx* ctx) {
     int rc = RC_OK;
     for (int v = 0; v < 2 && !rc; ++v) {
         HIP_TRY(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_in_d, ctx->live_in_h, B * 171 * sizeof(float), hipMemcpyHostToDevice, st);
+        if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_in_d.get(), ctx->live_in_h.get(), B * 171 * sizeof(float), hipMemcpyHostToDevice, st);
         ctx->live_launch = true;
         rc = step_impl(ctx, io, 0u, st, v == 0);
         ctx->live_launch = false;
-        if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_out_h, ctx->live_out_d, B * 219 * sizeof(float), hipMemcpyDeviceToHost, st);
-        hipGraph_t* g = v == 0 ? &ctx->live_graph : &ctx->live_graph_notr;
-        const hipError_t e = hipStreamEndCapture(st, g);
+        if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_out_h.get(), ctx->live_out_d.get(), B * 219 * sizeof(float), hipMemcpyDeviceToHost, st);
+        HipGraph& g = v == 0 ? ctx->live_graph : ctx->live_graph_notr;
+        const hipError_t e = hipStreamEndCapture(st, rc_out(g));
         if (!rc && e != hipSuccess) rc = fail(ctx, RC_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        if (!rc && hipGraphInstantiate(v == 0 ? &ctx->live_exec : &ctx->live_exec_notr, *g, nullptr, nullptr, 0) != hipSuccess)
+        if (!rc && hipGraphInstantiate(rc_out(v == 0 ? ctx->live_exec : ctx->live_exec_notr), g.get(), nullptr, nullptr, 0) != hipSuccess)
             rc = fail(ctx, RC_ERR_HIP, "hipGraphInstantiate");
     }
     // The lean plan of the steady-state frame (rc_live.hip): seven launches. rc_live_step replays it when the frame needs neither a
@@ -2312,9 +2238,9 @@ int rc_live_begin(rc_ctx* ctx) {
     if (!rc && ctx->live_lean && B <= RC_LIVE_MAXB && !ctx->gemm_split) {
         ctx->live_aql_note.clear();
         auto lean_setup = [&]() -> std::string {
-            if (hipHostMalloc((void**)&ctx->live_status_h, sizeof(int), hipHostMallocMapped) != hipSuccess) return "lean frame: status word allocation failed";
-            *ctx->live_status_h = 0;
-            if (hipMalloc((void**)&ctx->live_abort_d, 64) != hipSuccess || hipMemset(ctx->live_abort_d, 0, 64) != hipSuccess) return "lean frame: abort word allocation failed";
+            if (rc_alloc(ctx->live_status_h, 1, hipHostMallocMapped) != hipSuccess) return "lean frame: status word allocation failed";
+            ctx->live_status_h[0] = 0;
+            if (rc_alloc(ctx->live_abort_d, 16) != hipSuccess || hipMemset(ctx->live_abort_d.get(), 0, 64) != hipSuccess) return "lean frame: abort word allocation failed";
             LiveFrame& F = ctx->live_frame;
             F = LiveFrame{};
             for (int i = 0; i < 6; ++i) {
@@ -2328,18 +2254,18 @@ int rc_live_begin(rc_ctx* ctx) {
                 l.BpH = (long long)ctx->Bp * n.H;
             }
             F.fb = ctx->fb; F.io = io; F.prm = dev_params(ctx->prm); F.body = ctx->body; F.B = (int)B; F.nc = ctx->live_lean_nc;
-            if (hipHostGetDevicePointer((void**)&F.status, ctx->live_status_h, 0) != hipSuccess) return "lean frame: status word not mapped";
-            F.abort = ctx->live_abort_d;
+            if (hipHostGetDevicePointer((void**)&F.status, ctx->live_status_h.get(), 0) != hipSuccess) return "lean frame: status word not mapped";
+            F.abort = ctx->live_abort_d.get();
             std::vector<LiveKernel> plan(RC_LIVE_KERNELS);
             const int nk = rc_live_plan(F, plan.data());
             if (nk != RC_LIVE_KERNELS) return "lean frame: sub-net sizes these kernels are not compiled for";
             if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) return "lean frame: hipStreamBeginCapture failed";
-            if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_in_d, ctx->live_in_h, B * 171 * sizeof(float), hipMemcpyHostToDevice, st);
+            if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_in_d.get(), ctx->live_in_h.get(), B * 171 * sizeof(float), hipMemcpyHostToDevice, st);
             rc_launch_live_frame(F, st);
-            if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_out_h, ctx->live_out_d, B * 219 * sizeof(float), hipMemcpyDeviceToHost, st);
-            const hipError_t e = hipStreamEndCapture(st, &ctx->live_graph_lean);      // (always ended: the stream must not stay in capture mode)
+            if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_out_h.get(), ctx->live_out_d.get(), B * 219 * sizeof(float), hipMemcpyDeviceToHost, st);
+            const hipError_t e = hipStreamEndCapture(st, rc_out(ctx->live_graph_lean));      // (always ended: the stream must not stay in capture mode)
             if (e != hipSuccess) return std::string("lean frame: hipStreamEndCapture: ") + hipGetErrorString(e);
-            if (hipGraphInstantiate(&ctx->live_exec_lean, ctx->live_graph_lean, nullptr, nullptr, 0) != hipSuccess) return "lean frame: hipGraphInstantiate failed";
+            if (hipGraphInstantiate(rc_out(ctx->live_exec_lean), ctx->live_graph_lean.get(), nullptr, nullptr, 0) != hipSuccess) return "lean frame: hipGraphInstantiate failed";
             // ... and the same seven dispatches as pre-built AQL packets (rc_aql.cpp); without them the graph above is replayed.
             // Not under a tool that intercepts the HSA queues (rocprofv3's interception crashes on packets written straight into the ring --
             // ROCm 7.2; traces then show the graph replay of the same kernels; a debugger's or tracer's runtime hooks are treated alike).
@@ -2358,14 +2284,14 @@ int rc_live_begin(rc_ctx* ctx) {
                     // the pre-step and the frame that starts from its partial sums: two more programs on the same queue; without them
                     // (an allocation or a symbol failed) the chain simply keeps the one frame program
                     const size_t nf = (size_t)rc_live_pre_floats(F);
-                    if (hipMalloc((void**)&ctx->live_pre_buf, nf * sizeof(float)) == hipSuccess && hipMemset(ctx->live_pre_buf, 0, nf * sizeof(float)) == hipSuccess) {
+                    if (rc_alloc(ctx->live_pre_buf, nf) == hipSuccess && hipMemset(ctx->live_pre_buf.get(), 0, nf * sizeof(float)) == hipSuccess) {
                         std::vector<LiveKernel> plan2(RC_LIVE_KERNELS), plan3(2);
-                        const int n3 = rc_live_pre_plan(F, ctx->live_pre_buf, plan3.data());
-                        if (rc_live_plan(F, plan2.data(), ctx->live_pre_buf) == RC_LIVE_KERNELS && n3 >= 1) {
+                        const int n3 = rc_live_pre_plan(F, ctx->live_pre_buf.get(), plan3.data());
+                        if (rc_live_plan(F, plan2.data(), ctx->live_pre_buf.get()) == RC_LIVE_KERNELS && n3 >= 1) {
                             ctx->aql_prog_lean_pre = rc_aql_add(ctx->live_aql, plan2.data(), RC_LIVE_KERNELS, 1, msg, (int)sizeof(msg));
                             if (ctx->aql_prog_lean_pre >= 0) ctx->aql_prog_pre = rc_aql_add(ctx->live_aql, plan3.data(), n3, 0, msg, (int)sizeof(msg));
                         }
-                    } else { ctx->live_pre_buf = nullptr; (void)hipGetLastError(); }
+                    } else { ctx->live_pre_buf.reset(); (void)hipGetLastError(); }
                     if (ctx->aql_prog_pre < 0) ctx->aql_prog_lean_pre = -1;
                 }
                 // RC_LIVE_SPIN: the same programs once more with the inputs and a mailbox in host-writable device memory; their first
@@ -2374,8 +2300,8 @@ int rc_live_begin(rc_ctx* ctx) {
                     void* shared = nullptr;
                     unsigned* state_d = nullptr;
                     if (rc_aql_alloc_shared(ctx->live_aql, 4096 + B * 171 * sizeof(float), &shared) == 0 &&
-                        hipHostMalloc((void**)&ctx->spin_state_h, 64, hipHostMallocMapped) == hipSuccess &&
-                        hipHostGetDevicePointer((void**)&state_d, ctx->spin_state_h, 0) == hipSuccess) {
+                        rc_alloc(ctx->spin_state_h, 16, hipHostMallocMapped) == hipSuccess &&
+                        hipHostGetDevicePointer((void**)&state_d, ctx->spin_state_h.get(), 0) == hipSuccess) {
                         for (int q = 0; q < 16; ++q) ctx->spin_state_h[q] = 0;
                         ctx->spin_mb = (volatile unsigned*)shared;
                         ctx->spin_in = (float*)((char*)shared + 4096);
@@ -2388,7 +2314,7 @@ int rc_live_begin(rc_ctx* ctx) {
                             Fs.spin_mb = (unsigned*)shared + 32 * par; Fs.spin_state = state_d + 4 * par;
                             if (rc_live_plan(Fs, ps.data()) == RC_LIVE_KERNELS) ctx->aql_prog_spin[par] = rc_aql_add(ctx->live_aql, ps.data(), RC_LIVE_KERNELS, 1, msg, (int)sizeof(msg));
                             ok = ctx->aql_prog_spin[par] >= 0;
-                            if (ok && ctx->aql_prog_lean_pre >= 0 && rc_live_plan(Fs, ps.data(), ctx->live_pre_buf) == RC_LIVE_KERNELS)
+                            if (ok && ctx->aql_prog_lean_pre >= 0 && rc_live_plan(Fs, ps.data(), ctx->live_pre_buf.get()) == RC_LIVE_KERNELS)
                                 ctx->aql_prog_spin_pre[par] = rc_aql_add(ctx->live_aql, ps.data(), RC_LIVE_KERNELS, 1, msg, (int)sizeof(msg));
                         }
                         if (!ok) ctx->aql_prog_spin[0] = ctx->aql_prog_spin[1] = -1;
@@ -2403,10 +2329,9 @@ int rc_live_begin(rc_ctx* ctx) {
         const std::string why = lean_setup();
         if (!why.empty()) {                                                // back to the two full captures
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(st, &g); if (g) (void)hipGraphDestroy(g); }
+            if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) { HipGraph g; (void)hipStreamEndCapture(st, rc_out(g)); }
             (void)hipGetLastError();
-            if (ctx->live_exec_lean) { (void)hipGraphExecDestroy(ctx->live_exec_lean); ctx->live_exec_lean = nullptr; }
-            if (ctx->live_graph_lean) { (void)hipGraphDestroy(ctx->live_graph_lean); ctx->live_graph_lean = nullptr; }
+            ctx->live_exec_lean.reset(); ctx->live_graph_lean.reset();
             ctx->live_aql_note = why;
         } else if (ctx->live_aql) {
             const std::string bad = live_selfcheck(ctx);
@@ -2432,19 +2357,19 @@ int rc_live_step(rc_ctx* ctx, const float* j2dc, const float* accc, const float*
     if (!ctx || !ctx->live_exec) return ctx ? fail(ctx, RC_ERR_STATE, "rc_live_step: call rc_live_begin first") : RC_ERR_INVALID;
     if (!j2dc || !accc || !oric || !pose || !tran) return fail(ctx, RC_ERR_INVALID, "rc_live_step: null buffer");
     const size_t B = ctx->B;
-    hipStream_t st = ctx->live_stream;
+    hipStream_t st = ctx->live_stream.get();
     const auto t_in = std::chrono::steady_clock::now();
     // how long the caller left the device alone since the previous frame returned: a 60 fps stream idles 16.6 ms, a benchmark loop none
     const double idle_us = ctx->live_have_return ? std::chrono::duration<double, std::micro>(t_in - ctx->live_last_return).count() : 0.0;
     bool waited_eager = false;
     if (ctx->eager_dirty) {          // e.g. reset_states() on the caller's stream just before this frame
-        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->eager_ev, 0));
+        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->eager_ev.get(), 0));
         ctx->eager_dirty = false;
         waited_eager = true;
     }
-    std::memcpy(ctx->live_in_h, j2dc, B * 99 * sizeof(float));
-    std::memcpy(ctx->live_in_h + B * 99, accc, B * 18 * sizeof(float));
-    std::memcpy(ctx->live_in_h + B * 117, oric, B * 54 * sizeof(float));
+    std::memcpy(ctx->live_in_h.get(), j2dc, B * 99 * sizeof(float));
+    std::memcpy(ctx->live_in_h.get() + B * 99, accc, B * 18 * sizeof(float));
+    std::memcpy(ctx->live_in_h.get() + B * 117, oric, B * 54 * sizeof(float));
     // Host-side, CONSERVATIVE mirror of two device flags (rc_prep_kernel): a row needs a transition step iff it carries
     // a deferred updater step (previous frame had c <= lo) and steps on camera data now (c > lo or first frame). The
     // margin covers the difference between this double mean and the device's float32 mean in the reference's order
@@ -2481,10 +2406,10 @@ int rc_live_step(rc_ctx* ctx, const float* j2dc, const float* accc, const float*
     if (ctx->spin_pending >= 0 && ctx->live_aql) {
         const int par = ctx->spin_pending_par;
         const int want = use_pre ? ctx->aql_prog_spin_pre[par] : ctx->aql_prog_spin[par];
-        const bool gone = __atomic_load_n(ctx->spin_state_h + 4 * par, __ATOMIC_ACQUIRE) == 3u;
+        const bool gone = __atomic_load_n(ctx->spin_state_h.get() + 4 * par, __ATOMIC_ACQUIRE) == 3u;
         spin_go = lean && !gone && ctx->spin_valid && ctx->spin_pending == want && !waited_eager;
         if (spin_go) {
-            std::memcpy(ctx->spin_in, ctx->live_in_h, B * 171 * sizeof(float));
+            std::memcpy(ctx->spin_in, ctx->live_in_h.get(), B * 171 * sizeof(float));
             RC_STORE_FENCE();
             ctx->spin_mb[32 * par] = 1u;                                    // go: behind the inputs (stores to the device are posted in order; 0.1 us of host time)
             RC_STORE_FENCE();
@@ -2516,12 +2441,12 @@ int rc_live_step(rc_ctx* ctx, const float* j2dc, const float* accc, const float*
         if (rc_aql_wait_background(ctx->live_aql) != 0) return fail(ctx, RC_ERR_HIP, "rc_live_step: the pre-step did not complete");
     }
     if (first_tran || (flags & RC_FLAG_FIRST_FRAME)) {           // sequence start: ordinary enqueue path
-        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_in_d, ctx->live_in_h, B * 171 * sizeof(float), hipMemcpyHostToDevice, st));
-        if (first_tran) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_ft_d, first_tran, B * 3 * sizeof(float), hipMemcpyHostToDevice, st));
-        FrameIO io{ctx->live_in_io, ctx->live_in_io + B * 99, ctx->live_in_io + B * 117, first_tran ? ctx->live_ft_d : nullptr,
+        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_in_d.get(), ctx->live_in_h.get(), B * 171 * sizeof(float), hipMemcpyHostToDevice, st));
+        if (first_tran) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_ft_d.get(), first_tran, B * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+        FrameIO io{ctx->live_in_io, ctx->live_in_io + B * 99, ctx->live_in_io + B * 117, first_tran ? ctx->live_ft_d.get() : nullptr,
                    ctx->live_out_io, ctx->live_out_io + B * 216, 99, 18, 54, 216, 3};
         if (int rc = step_impl(ctx, io, flags, st)) return rc;
-        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_out_h, ctx->live_out_d, B * 219 * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_out_h.get(), ctx->live_out_d.get(), B * 219 * sizeof(float), hipMemcpyDeviceToHost, st));
     } else if (lean) {
         if (ctx->live_aql) {
             if (waited_eager) HIP_TRY(ctx, hipStreamSynchronize(st));        // the AQL queue is not ordered behind the stream: wait here
@@ -2535,7 +2460,7 @@ int rc_live_step(rc_ctx* ctx, const float* j2dc, const float* accc, const float*
             // when the caller comes back that kernel has its arguments and weights and is polling. (A paced caller's is queued behind the pre-step, below.)
             if (arc == 0 && ctx->live_spin_b2b && ctx->aql_prog_spin[0] >= 0 && ctx->spin_pending < 0 && idle_us < ctx->live_prestep_idle_us) queue_ahead(false, true);
             if (arc == 0) arc = rc_aql_wait_seq(ctx->live_aql, my_seq);
-            if (spin_go && arc == 0 && __atomic_load_n(ctx->spin_state_h + 4 * my_par, __ATOMIC_ACQUIRE) == 3u) {
+            if (spin_go && arc == 0 && __atomic_load_n(ctx->spin_state_h.get() + 4 * my_par, __ATOMIC_ACQUIRE) == 3u) {
                 // the waiting kernel gave up in the very moment the frame arrived: the six kernels behind it have changed nothing
                 // (LiveFrame.abort) -- the frame runs on the ordinary program, in front of which nothing may be waiting
                 ctx->spin_state_h[4 * my_par] = 0;
@@ -2558,16 +2483,16 @@ int rc_live_step(rc_ctx* ctx, const float* j2dc, const float* accc, const float*
             }
             aql_done = true;
         } else if (ctx->live_eager) rc_launch_live_frame(ctx->live_frame, st);
-        else HIP_TRY(ctx, hipGraphLaunch(ctx->live_exec_lean, st));
+        else HIP_TRY(ctx, hipGraphLaunch(ctx->live_exec_lean.get(), st));
         ctx->stat_live_lean += 1;
     } else if (ctx->live_eager) {                                // tuning (RC_LIVE_EAGER=1): the 11-14 launches enqueued directly
         FrameIO io{ctx->live_in_io, ctx->live_in_io + B * 99, ctx->live_in_io + B * 117, nullptr,
                    ctx->live_out_io, ctx->live_out_io + B * 216, 99, 18, 54, 216, 3};
-        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_in_d, ctx->live_in_h, B * 171 * sizeof(float), hipMemcpyHostToDevice, st));
+        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_in_d.get(), ctx->live_in_h.get(), B * 171 * sizeof(float), hipMemcpyHostToDevice, st));
         if (int rc = step_impl(ctx, io, 0u, st, need_tr)) return rc;
-        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_out_h, ctx->live_out_d, B * 219 * sizeof(float), hipMemcpyDeviceToHost, st));
+        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_out_h.get(), ctx->live_out_d.get(), B * 219 * sizeof(float), hipMemcpyDeviceToHost, st));
     } else {
-        HIP_TRY(ctx, hipGraphLaunch(need_tr ? ctx->live_exec : ctx->live_exec_notr, st));
+        HIP_TRY(ctx, hipGraphLaunch(need_tr ? ctx->live_exec.get() : ctx->live_exec_notr.get(), st));
     }
     const auto t_enq = std::chrono::steady_clock::now();
     // A frame is ~100 us of GPU work: poll for its completion instead of sleeping on the stream (the blocking wait's wake-up
@@ -2583,20 +2508,20 @@ int rc_live_step(rc_ctx* ctx, const float* j2dc, const float* accc, const float*
         HIP_TRY(ctx, hipStreamSynchronize(st));
     }
     if (!lean) ctx->stat_live_full += 1;
-    if (lean && *ctx->live_status_h != 0) {
+    if (lean && ctx->live_status_h[0] != 0) {
         // The lean plan's own check (rc_live_k1) found the frame off the plan -- a transition step or an init_net trigger the host-side
         // mirror above did not foresee. Its kernels have changed nothing (LiveFrame.abort): the frame runs again on the full capture,
         // from the inputs still staged in the pinned buffer.
-        *ctx->live_status_h = 0;
+        ctx->live_status_h[0] = 0;
         ctx->stat_live_lean -= 1;
         ctx->stat_live_full += 1;
         ctx->stat_live_replayed += 1;
-        HIP_TRY(ctx, hipGraphLaunch(ctx->live_exec, st));
+        HIP_TRY(ctx, hipGraphLaunch(ctx->live_exec.get(), st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
     }
     const auto t_done = std::chrono::steady_clock::now();
-    std::memcpy(pose, ctx->live_out_h, B * 216 * sizeof(float));
-    std::memcpy(tran, ctx->live_out_h + B * 216, B * 3 * sizeof(float));
+    std::memcpy(pose, ctx->live_out_h.get(), B * 216 * sizeof(float));
+    std::memcpy(tran, ctx->live_out_h.get() + B * 216, B * 3 * sizeof(float));
     // The pre-step of the NEXT frame, behind this one in the queue, when the caller paces its frames (the idle time in front of this call
     // says so): it streams half of the weights while the device would otherwise idle, and a caller that comes back at once -- a
     // throughput loop -- would only wait for it.
@@ -2758,22 +2683,21 @@ int rc_shape_body(rc_ctx* ctx, const float* v_template, const float* shapedirs, 
     if (!v_template || !shapedirs || !J_regressor || !beta || !verts_out || !joints_out || V < 1)
         return fail(ctx, RC_ERR_INVALID, "rc_shape_body: bad argument");
     const size_t n = (size_t)V;
-    float *vt = nullptr, *sd = nullptr, *jr = nullptr, *bt = nullptr, *v = nullptr, *j = nullptr;
+    DevBuf<float> vt, sd, jr, bt, v, j;
     int rc = RC_OK;
-    auto up = [&](float** d, const float* h, size_t count) {
+    auto up = [&](DevBuf<float>& d, const float* h, size_t count) {
         if (rc) return;
-        if (hipMalloc((void**)d, count * sizeof(float)) != hipSuccess || (h && hipMemcpy(*d, h, count * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))
+        if (rc_alloc(d, count) != hipSuccess || (h && hipMemcpy(d.get(), h, count * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))
             rc = fail(ctx, RC_ERR_HIP, "rc_shape_body: device buffer");
     };
-    up(&vt, v_template, n * 3); up(&sd, shapedirs, n * 30); up(&jr, J_regressor, n * 24); up(&bt, beta, 10);
-    up(&v, nullptr, n * 3); up(&j, nullptr, 72);
+    up(vt, v_template, n * 3); up(sd, shapedirs, n * 30); up(jr, J_regressor, n * 24); up(bt, beta, 10);
+    up(v, nullptr, n * 3); up(j, nullptr, 72);
     if (!rc) {
-        rc_launch_shape_body(vt, sd, bt, jr, V, v, j, nullptr);
-        if (hipMemcpy(verts_out, v, n * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(joints_out, j, 72 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        rc_launch_shape_body(vt.get(), sd.get(), bt.get(), jr.get(), V, v.get(), j.get(), nullptr);
+        if (hipMemcpy(verts_out, v.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(joints_out, j.get(), 72 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(ctx, RC_ERR_HIP, "rc_shape_body: read back");
     }
-    for (float* q : {vt, sd, jr, bt, v, j}) if (q) (void)hipFree(q);
     return rc;
 }
 int rc_ik_r(rc_ctx* ctx, const float* Rg, float* Rl, int64_t n, void* stream) {
@@ -2820,7 +2744,7 @@ int rc_body_mesh(rc_ctx* ctx, const float* pose, const float* tran, float* vert,
     for (int64_t a = 0; a < n; a += chunk) {
         const int64_t m = std::min(chunk, n - a);
         rc_launch_body_mesh(ctx->body, ctx->mesh_vt, ctx->mesh_w, ctx->mesh_V, pose + a * 216, tran + a * 3, vert + a * ctx->mesh_V * 3, m,
-                            ctx->sweep_scratch, (hipStream_t)stream);
+                            ctx->sweep_scratch.get(), (hipStream_t)stream);
     }
     HIP_TRY(ctx, hipGetLastError());
     return RC_OK;
@@ -2845,7 +2769,7 @@ int rc_mesh_metrics(rc_ctx* ctx, const float* pose, const float* gt_pose, int64_
     for (int64_t a = 0; a < n; a += chunk) {
         const int64_t m = std::min(chunk, n - a);
         rc_launch_mesh_metrics(ctx->body, ctx->mesh_vt, ctx->mesh_w, ctx->mesh_V, have_reg ? ctx->mesh_kM : nullptr, have_reg ? ctx->mesh_nk : 24,
-                               pose + a * 216, gt_pose + a * 216, per_frame + a * 3, m, ctx->sweep_scratch, st);
+                               pose + a * 216, gt_pose + a * 216, per_frame + a * 3, m, ctx->sweep_scratch.get(), st);
     }
     HIP_TRY(ctx, hipGetLastError());
     if (mean_host) {                                       // evaluate.py:131-133: the three means over the sequence
@@ -3047,10 +2971,10 @@ int rc_gemm_timing_read(rc_ctx* ctx, double* total_ms, int64_t* launches) {
     std::vector<std::pair<double, double>> iv;
     iv.reserve(ctx->ev_used);
     for (size_t i = 0; i < ctx->ev_used; ++i) {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_pool[i].second));
+        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_pool[i].second.get()));
         float ms = 0.f, t0 = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_pool[i].first, ctx->ev_pool[i].second));
-        if (i > 0) HIP_TRY(ctx, hipEventElapsedTime(&t0, ctx->ev_pool[0].first, ctx->ev_pool[i].first));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_pool[i].first.get(), ctx->ev_pool[i].second.get()));
+        if (i > 0) HIP_TRY(ctx, hipEventElapsedTime(&t0, ctx->ev_pool[0].first.get(), ctx->ev_pool[i].first.get()));
         iv.emplace_back((double)t0, (double)t0 + ms);
         ctx->timed_ms += ms;
         ctx->timed_launches += 1;

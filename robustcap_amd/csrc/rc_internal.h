@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <memory>
+#include <string>
+#include <type_traits>
 
 // ---- GEMM tiling -------------------------------------------------------------------------------------------
 // One workgroup = RC_NW waves = one 32-row x (16*NC)-column output tile; the K range is split across the waves
@@ -436,14 +439,71 @@ void rc_launch_vec_pair(const float* g_new, const float* g_old, const float* d, 
 void rc_launch_vec_comb(const VecComb& c, float* out, long long n, hipStream_t s);
 void rc_launch_vec_dots(const VecJob* jobs_dev, int n_jobs, long long n, double* partial, hipStream_t s);
 
-// narrow view of the context for rc_smplify_api.cpp (the struct itself lives in rc_api.cpp)
+// ---- owners of the host code's HIP resources ----------------------------------------------------------------------------------------
+// Move-only; resetting or destroying the owner releases the resource (return code ignored). Never give an owner static storage duration:
+// its destructor would run after the HIP runtime has been torn down at exit. Kernel arguments take the raw pointer: .get().
+template <auto Release> struct RcRelease { template <class P> void operator()(P p) const { (void)Release(p); } };
+template <class T> using DevBuf = std::unique_ptr<T[], RcRelease<hipFree>>;        // hipMalloc
+template <class T> using PinBuf = std::unique_ptr<T[], RcRelease<hipHostFree>>;    // hipHostMalloc
+using HipStream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, RcRelease<hipStreamDestroy>>;
+using HipEvent = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, RcRelease<hipEventDestroy>>;
+using HipGraph = std::unique_ptr<std::remove_pointer_t<hipGraph_t>, RcRelease<hipGraphDestroy>>;
+using HipGraphExec = std::unique_ptr<std::remove_pointer_t<hipGraphExec_t>, RcRelease<hipGraphExecDestroy>>;
+
+// out-parameter of a create call, e.g. hipEventCreate(rc_out(ev)): the previous handle is released first, the new one is owned from the
+// end of the statement
+template <class Own> struct RcOut {
+    Own& own;
+    typename Own::pointer raw;
+    ~RcOut() { own.reset(raw); }
+    operator typename Own::pointer*() { return &raw; }
+};
+template <class Own> RcOut<Own> rc_out(Own& own) { own.reset(); return {own, nullptr}; }
+
+// the previous buffer is released first; the contents are not kept
+template <class T> hipError_t rc_alloc(DevBuf<T>& p, size_t n) {
+    p.reset();
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, n * sizeof(T));
+    p.reset(static_cast<T*>(q));
+    return e;
+}
+template <class T> hipError_t rc_alloc(PinBuf<T>& p, size_t n, unsigned flags = hipHostMallocDefault) {
+    p.reset();
+    void* q = nullptr;
+    const hipError_t e = hipHostMalloc(&q, n * sizeof(T), flags);
+    p.reset(static_cast<T*>(q));
+    return e;
+}
+inline hipError_t rc_alloc_all() { return hipSuccess; }
+template <class Buf, class... Rest> hipError_t rc_alloc_all(Buf& p, size_t n, Rest&&... rest) {
+    const hipError_t e = rc_alloc(p, n);
+    return e != hipSuccess ? e : rc_alloc_all(rest...);
+}
+// Grow-only buffers that share one capacity (contents not kept): if cap < need, each buffer is allocated anew for the count that follows
+// it, and cap becomes `want`. cap stays 0 until every allocation succeeded, so a failed growth is retried whole.
+template <class Cap, class... BufsAndCounts> hipError_t rc_grow(Cap& cap, size_t need, size_t want, BufsAndCounts&&... bc) {
+    if (need <= (size_t)cap) return hipSuccess;
+    cap = 0;
+    const hipError_t e = rc_alloc_all(bc...);
+    if (e == hipSuccess) cap = (Cap)want;
+    return e;
+}
+
+// narrow view of the context for rc_smplify_api.cpp and rc_subnet_api.cpp (the struct itself lives in rc_api.cpp)
 struct rc_ctx;
 struct SmplifyState;
 const BodyConst* rc_ctx_body(rc_ctx* ctx);                 // nullptr until rc_set_body
 int rc_ctx_fail(rc_ctx* ctx, int code, const char* msg);   // records the message, returns code
-SmplifyState*& rc_ctx_smplify(rc_ctx* ctx);
+#define HIP_TRY(ctx, expr)                                                                                                              \
+    do {                                                                                                                                \
+        const hipError_t e_ = (expr);                                                                                                   \
+        if (e_ != hipSuccess) return rc_ctx_fail(ctx, RC_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str());       \
+    } while (0)
+void rc_smplify_free(SmplifyState* s);                     // delete s (the type is complete in rc_smplify_api.cpp only)
+using SmplifyOwner = std::unique_ptr<SmplifyState, RcRelease<rc_smplify_free>>;
+SmplifyOwner& rc_ctx_smplify(rc_ctx* ctx);
 unsigned long long rc_ctx_ign_mask(rc_ctx* ctx);
-void rc_smplify_free(SmplifyState* s);
 
 // ---- sub-net forward over ragged sequences (rc_subnet.hip, rc_subnet_api.cpp; articulate/utils/torch/rnn.py:121-133) ----------------
 // One tall GEMM: rows = frames of a time chunk (or the active prefix of one time step), workgroups of 64 * mr rows x 16 * nc columns,
@@ -489,5 +549,6 @@ int rc_ctx_subnet_net(rc_ctx* ctx, int net, SubnetNet* out);     // net: kNets i
 int rc_ctx_init_net(rc_ctx* ctx, SubnetDense out[3]);
 int rc_ctx_net_index(const char* name);
 int rc_ctx_gemm_split(rc_ctx* ctx);
-SubnetState*& rc_ctx_subnet(rc_ctx* ctx);
-void rc_subnet_free(SubnetState* s);
+void rc_subnet_free(SubnetState* s);                       // delete s
+using SubnetOwner = std::unique_ptr<SubnetState, RcRelease<rc_subnet_free>>;
+SubnetOwner& rc_ctx_subnet(rc_ctx* ctx);

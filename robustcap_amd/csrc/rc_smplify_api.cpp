@@ -27,28 +27,29 @@
 constexpr size_t kPriorLd = 72, kPriorMat = 8 * 69 * kPriorLd;   // rc_smplify.hip: SM_PLD
 
 struct SmplifyState {
-    float *means = nullptr, *prec = nullptr, *lognll = nullptr;     // device; prec = [2][8][69][72]: P, then P + P^T, rows padded
+    DevBuf<float> means, prec, lognll;                                // device; prec = [2][8][69][72]: P, then P + P^T, rows padded
     bool have_prior = false;
     int64_t cap = 0;                                                  // frames the buffers below hold
-    float *x = nullptr, *grad = nullptr;                              // [cap*75] flat [aa | tran]
-    float *ref3d = nullptr, *imu_aa = nullptr, *mj = nullptr, *proj = nullptr, *joint = nullptr;
-    float *terms = nullptr;                                           // [3*cap] frame | imu | smooth losses
-    int* argmin = nullptr;
-    float *prior_ll = nullptr, *prior_g = nullptr;                    // [cap], [cap*69]: outputs of the prior kernel
-    float* fk = nullptr;                                              // [cap*432]: rotations of the forward kernel's primal
-    float *res0 = nullptr, *res1 = nullptr, *Kd = nullptr;            // residuals [cap,33] before / after, K on the device
-    float *h_x = nullptr, *h_grad = nullptr, *h_terms = nullptr, *h_res = nullptr;   // pinned
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevBuf<float> x, grad;                                            // [cap*75] flat [aa | tran]
+    DevBuf<float> ref3d, imu_aa, mj, proj, joint;
+    DevBuf<float> terms;                                              // [3*cap] frame | imu | smooth losses
+    DevBuf<int> argmin;
+    DevBuf<float> prior_ll, prior_g;                                  // [cap], [cap*69]: outputs of the prior kernel
+    DevBuf<float> fk;                                                 // [cap*432]: rotations of the forward kernel's primal
+    DevBuf<float> res0, res1, Kd;                                     // residuals [cap,33] before / after, K on the device
+    PinBuf<float> h_x, h_grad, h_terms, h_res;                        // pinned
+    HipEvent ev0, ev1;
     double device_ms = 0.0;
     // device-resident L-BFGS (minimize_on_device): vectors of the optimiser, job table and partial sums of the inner products
     int64_t lb_cap = 0;                                               // frames the buffers below hold
     int lb_pairs = 0;                                                 // curvature pairs they hold
-    float *xt = nullptr, *dir = nullptr, *gslot = nullptr, *Sv = nullptr, *Yv = nullptr;   // [n], [n], [6][n], [pairs][n] x 2
-    VecJob *jobs_d = nullptr, *jobs_h = nullptr;                      // device / pinned
-    double *part_d = nullptr, *part_h = nullptr;
+    DevBuf<float> xt, dir, gslot, Sv, Yv;                             // [n], [n], [6][n], [pairs][n] x 2
+    DevBuf<VecJob> jobs_d; PinBuf<VecJob> jobs_h;                     // device / pinned
+    DevBuf<double> part_d; PinBuf<double> part_h;
     const float* ref3d_override = nullptr;                            // rc_smplify_set_ref3d: caller-owned [T,33,3], next run only
     // arenas of rc_smplify_run_batch (grow-only: a second evaluation of the same size allocates nothing)
-    char *batch_dev = nullptr, *batch_pin = nullptr;
+    DevBuf<char> batch_dev;
+    PinBuf<char> batch_pin;
     size_t batch_dev_cap = 0, batch_pin_cap = 0;
 };
 
@@ -56,66 +57,24 @@ namespace {
 
 typedef float (*cubic_fn)(float, float, float, float, float, float, bool, float, float);
 
-#define SM_TRY(ctx, expr)                                                                                   \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return rc_ctx_fail(ctx, RC_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
-void free_work(SmplifyState* s) {
-    for (float** p : {&s->x, &s->grad, &s->ref3d, &s->imu_aa, &s->mj, &s->proj, &s->joint, &s->terms, &s->res0, &s->res1, &s->prior_ll, &s->prior_g, &s->fk})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (s->argmin) { (void)hipFree(s->argmin); s->argmin = nullptr; }
-    for (float** p : {&s->h_x, &s->h_grad, &s->h_terms, &s->h_res})
-        if (*p) { (void)hipHostFree(*p); *p = nullptr; }
-    s->cap = 0;
-    for (float** p : {&s->xt, &s->dir, &s->gslot, &s->Sv, &s->Yv})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (s->jobs_d) { (void)hipFree(s->jobs_d); s->jobs_d = nullptr; }
-    if (s->part_d) { (void)hipFree(s->part_d); s->part_d = nullptr; }
-    if (s->jobs_h) { (void)hipHostFree(s->jobs_h); s->jobs_h = nullptr; }
-    if (s->part_h) { (void)hipHostFree(s->part_h); s->part_h = nullptr; }
-    s->lb_cap = 0; s->lb_pairs = 0;
-}
-
 int state_of(rc_ctx* ctx, SmplifyState** out) {
-    SmplifyState*& s = rc_ctx_smplify(ctx);
-    if (!s) {
-        s = new SmplifyState();
-        SM_TRY(ctx, hipMalloc((void**)&s->means, 8 * 69 * sizeof(float)));
-        SM_TRY(ctx, hipMalloc((void**)&s->prec, 2 * kPriorMat * sizeof(float)));
-        SM_TRY(ctx, hipMalloc((void**)&s->lognll, 8 * sizeof(float)));
-        SM_TRY(ctx, hipMalloc((void**)&s->Kd, 9 * sizeof(float)));
-        SM_TRY(ctx, hipEventCreate(&s->ev0));
-        SM_TRY(ctx, hipEventCreate(&s->ev1));
+    SmplifyOwner& s = rc_ctx_smplify(ctx);
+    if (!s) {                                                         // (kept only once complete)
+        SmplifyOwner f(new SmplifyState());
+        HIP_TRY(ctx, rc_alloc_all(f->means, 8 * 69, f->prec, 2 * kPriorMat, f->lognll, 8, f->Kd, 9));
+        HIP_TRY(ctx, hipEventCreate(rc_out(f->ev0)));
+        HIP_TRY(ctx, hipEventCreate(rc_out(f->ev1)));
+        s = std::move(f);
     }
-    *out = s;
+    *out = s.get();
     return RC_OK;
 }
 
 int reserve(rc_ctx* ctx, SmplifyState* s, int64_t T) {
-    if (T <= s->cap) return RC_OK;
-    free_work(s);
     const size_t n = (size_t)T;
-    SM_TRY(ctx, hipMalloc((void**)&s->x, n * 75 * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->grad, n * 75 * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->ref3d, n * 99 * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->imu_aa, n * 18 * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->mj, n * 99 * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->proj, n * 66 * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->joint, n * 72 * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->terms, n * 3 * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->argmin, n * sizeof(int)));
-    SM_TRY(ctx, hipMalloc((void**)&s->prior_ll, n * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->prior_g, n * 69 * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->fk, n * 432 * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->res0, n * 33 * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->res1, n * 33 * sizeof(float)));
-    SM_TRY(ctx, hipHostMalloc((void**)&s->h_x, n * 75 * sizeof(float)));
-    SM_TRY(ctx, hipHostMalloc((void**)&s->h_grad, n * 75 * sizeof(float)));
-    SM_TRY(ctx, hipHostMalloc((void**)&s->h_terms, n * 3 * sizeof(float)));
-    SM_TRY(ctx, hipHostMalloc((void**)&s->h_res, n * 66 * sizeof(float)));
-    s->cap = T;
+    HIP_TRY(ctx, rc_grow(s->cap, n, n, s->x, n * 75, s->grad, n * 75, s->ref3d, n * 99, s->imu_aa, n * 18, s->mj, n * 99, s->proj, n * 66,
+                         s->joint, n * 72, s->terms, n * 3, s->argmin, n, s->prior_ll, n, s->prior_g, n * 69, s->fk, n * 432, s->res0, n * 33,
+                         s->res1, n * 33, s->h_x, n * 75, s->h_grad, n * 75, s->h_terms, n * 3, s->h_res, n * 66));
     return RC_OK;
 }
 
@@ -124,10 +83,10 @@ SmplifyArgs make_args(SmplifyState* s, const float* x, const float* kp, const fl
     SmplifyArgs A{};
     A.aa = x; A.tran = x + T * 72;
     A.kp = kp; A.ref3d = ref3d; A.imu_aa = imu_aa;
-    A.means = s->means; A.prec = s->prec; A.prec_sym = s->prec + kPriorMat; A.lognll = s->lognll;
-    A.mj = s->mj; A.proj = s->proj;
-    A.frame_loss = s->terms; A.imu_loss = s->terms + T; A.smooth_loss = s->terms + 2 * T;
-    A.argmin = s->argmin; A.prior_ll = s->prior_ll; A.prior_g = s->prior_g; A.fk = s->fk;
+    A.means = s->means.get(); A.prec = s->prec.get(); A.prec_sym = s->prec.get() + kPriorMat; A.lognll = s->lognll.get();
+    A.mj = s->mj.get(); A.proj = s->proj.get();
+    A.frame_loss = s->terms.get(); A.imu_loss = s->terms.get() + T; A.smooth_loss = s->terms.get() + 2 * T;
+    A.argmin = s->argmin.get(); A.prior_ll = s->prior_ll.get(); A.prior_g = s->prior_g.get(); A.fk = s->fk.get();
     A.grad_aa = grad; A.grad_tran = grad + T * 72;
     for (int q = 0; q < 9; ++q) A.K[q] = K[q];
     A.ign_mask = ign_mask;
@@ -162,31 +121,18 @@ int lbfgs_history_env() {
 
 int reserve_lbfgs(rc_ctx* ctx, SmplifyState* s, int64_t T, int pairs) {
     if (T <= s->lb_cap && pairs <= s->lb_pairs) return RC_OK;
-    for (float** p : {&s->xt, &s->dir, &s->gslot, &s->Sv, &s->Yv})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (s->jobs_d) { (void)hipFree(s->jobs_d); s->jobs_d = nullptr; }
-    if (s->part_d) { (void)hipFree(s->part_d); s->part_d = nullptr; }
-    if (s->jobs_h) { (void)hipHostFree(s->jobs_h); s->jobs_h = nullptr; }
-    if (s->part_h) { (void)hipHostFree(s->part_h); s->part_h = nullptr; }
-    s->lb_cap = 0; s->lb_pairs = 0;
+    s->lb_cap = 0; s->lb_pairs = 0;                                   // (capacity in frames AND pairs: either one short grows everything)
     const size_t n = (size_t)T * 75, nb = (n + 4095) / 4096;
     const size_t max_jobs = (size_t)kSlots * kSlotJobs + 6 * (size_t)pairs + 8;
-    SM_TRY(ctx, hipMalloc((void**)&s->xt, n * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->dir, n * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->gslot, kSlots * n * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->Sv, (size_t)pairs * n * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->Yv, (size_t)pairs * n * sizeof(float)));
-    SM_TRY(ctx, hipMalloc((void**)&s->jobs_d, max_jobs * sizeof(VecJob)));
-    SM_TRY(ctx, hipMalloc((void**)&s->part_d, max_jobs * nb * sizeof(double)));
-    SM_TRY(ctx, hipHostMalloc((void**)&s->jobs_h, max_jobs * sizeof(VecJob)));
-    SM_TRY(ctx, hipHostMalloc((void**)&s->part_h, max_jobs * nb * sizeof(double)));
-    s->lb_cap = T; s->lb_pairs = pairs;
+    HIP_TRY(ctx, rc_grow(s->lb_cap, (size_t)T, (size_t)T, s->xt, n, s->dir, n, s->gslot, kSlots * n, s->Sv, (size_t)pairs * n, s->Yv, (size_t)pairs * n,
+                         s->jobs_d, max_jobs, s->part_d, max_jobs * nb, s->jobs_h, max_jobs, s->part_h, max_jobs * nb));
+    s->lb_pairs = pairs;
     return RC_OK;
 }
 
 struct DevResult { int n_iter = 0, n_eval = 0; float first_loss = 0, loss = 0; };
 
-// x (device, s->x) is updated in place. kp / K / ref3d / imu_aa as for the closure.
+// x (device, s->x.get()) is updated in place. kp / K / ref3d / imu_aa as for the closure.
 int minimize_on_device(rc_ctx* ctx, SmplifyState* s, const BodyConst* body, const float* kp, const float* K, int64_t T, float lr,
                        int max_iter, hipStream_t st, DevResult& res) {
     const size_t n = (size_t)T * 75;
@@ -200,18 +146,18 @@ int minimize_on_device(rc_ctx* ctx, SmplifyState* s, const BodyConst* body, cons
     const int max_eval = max_iter * 5 / 4;
     const float tolerance_grad = 1e-7f, tolerance_change = 1e-9f;
     const unsigned long long ign = rc_ctx_ign_mask(ctx);
-    auto slot = [&](int k) { return s->gslot + (size_t)k * n; };
+    auto slot = [&](int k) { return s->gslot.get() + (size_t)k * n; };
     // fixed part of the job table: per gradient slot {g.d, max |g|, sum |g|, max |d|}
     for (int k = 0; k < kSlots; ++k) {
-        s->jobs_h[k * kSlotJobs + 0] = VecJob{slot(k), s->dir, 0, 0};
+        s->jobs_h[k * kSlotJobs + 0] = VecJob{slot(k), s->dir.get(), 0, 0};
         s->jobs_h[k * kSlotJobs + 1] = VecJob{slot(k), nullptr, 1, 0};
         s->jobs_h[k * kSlotJobs + 2] = VecJob{slot(k), nullptr, 2, 0};
-        s->jobs_h[k * kSlotJobs + 3] = VecJob{s->dir, nullptr, 1, 0};
+        s->jobs_h[k * kSlotJobs + 3] = VecJob{s->dir.get(), nullptr, 1, 0};
     }
     const int var0 = kSlots * kSlotJobs;                                // first job of the per-iteration (Gram) part
-    SM_TRY(ctx, hipMemcpyAsync(s->jobs_d, s->jobs_h, (size_t)var0 * sizeof(VecJob), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(s->jobs_d.get(), s->jobs_h.get(), (size_t)var0 * sizeof(VecJob), hipMemcpyHostToDevice, st));
     auto job_sum = [&](int job, bool is_max) {
-        const double* p = s->part_h + (size_t)job * nb;
+        const double* p = s->part_h.get() + (size_t)job * nb;
         double r = p[0];
         for (int b = 1; b < nb; ++b) r = is_max ? std::max(r, p[b]) : r + p[b];
         return r;
@@ -220,22 +166,22 @@ int minimize_on_device(rc_ctx* ctx, SmplifyState* s, const BodyConst* body, cons
     hipError_t herr = hipSuccess;
     // closure at x + t d into gradient slot k (t == 0: at x itself; the direction-dependent products are then meaningless)
     auto eval = [&](float t, int k, Eval& e) -> bool {
-        const float* xp = s->x;
-        if (t != 0.0f) { rc_launch_vec_axpy(s->x, s->dir, t, s->xt, (long long)n, st); xp = s->xt; }
-        const SmplifyArgs A = make_args(s, xp, kp, s->ref3d, s->imu_aa, K, slot(k), T, ign);
-        herr = hipEventRecord(s->ev0, st);
+        const float* xp = s->x.get();
+        if (t != 0.0f) { rc_launch_vec_axpy(s->x.get(), s->dir.get(), t, s->xt.get(), (long long)n, st); xp = s->xt.get(); }
+        const SmplifyArgs A = make_args(s, xp, kp, s->ref3d.get(), s->imu_aa.get(), K, slot(k), T, ign);
+        herr = hipEventRecord(s->ev0.get(), st);
         rc_launch_smplify(A, body, st);
-        if (herr == hipSuccess) herr = hipEventRecord(s->ev1, st);
-        rc_launch_vec_dots(s->jobs_d + k * kSlotJobs, kSlotJobs, (long long)n, s->part_d + (size_t)k * kSlotJobs * nb, st);
-        if (herr == hipSuccess) herr = hipMemcpyAsync(s->part_h + (size_t)k * kSlotJobs * nb, s->part_d + (size_t)k * kSlotJobs * nb,
+        if (herr == hipSuccess) herr = hipEventRecord(s->ev1.get(), st);
+        rc_launch_vec_dots(s->jobs_d.get() + k * kSlotJobs, kSlotJobs, (long long)n, s->part_d.get() + (size_t)k * kSlotJobs * nb, st);
+        if (herr == hipSuccess) herr = hipMemcpyAsync(s->part_h.get() + (size_t)k * kSlotJobs * nb, s->part_d.get() + (size_t)k * kSlotJobs * nb,
                                                       (size_t)kSlotJobs * nb * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (herr == hipSuccess) herr = hipMemcpyAsync(s->h_terms, s->terms, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (herr == hipSuccess) herr = hipMemcpyAsync(s->h_terms.get(), s->terms.get(), (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
         if (herr == hipSuccess) herr = hipStreamSynchronize(st);
         if (herr == hipSuccess) herr = hipGetLastError();
         if (herr != hipSuccess) return false;
         float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, s->ev0, s->ev1) == hipSuccess) s->device_ms += ms;
-        e.f = (float)total_loss(s->h_terms, T);
+        if (hipEventElapsedTime(&ms, s->ev0.get(), s->ev1.get()) == hipSuccess) s->device_ms += ms;
+        e.f = (float)total_loss(s->h_terms.get(), T);
         e.gtd = (float)job_sum(k * kSlotJobs + 0, false);
         e.gmax = (float)job_sum(k * kSlotJobs + 1, true);
         e.gsum = (float)job_sum(k * kSlotJobs + 2, false);
@@ -271,7 +217,7 @@ int minimize_on_device(rc_ctx* ctx, SmplifyState* s, const BodyConst* body, cons
         } else {
             // candidate pair (slot `spare`): y = g - prev_g, s = t d
             const int c = spare;
-            rc_launch_vec_pair(slot(base), slot(prev_base), s->dir, t, s->Yv + (size_t)c * n, s->Sv + (size_t)c * n, (long long)n, st);
+            rc_launch_vec_pair(slot(base), slot(prev_base), s->dir.get(), t, s->Yv.get() + (size_t)c * n, s->Sv.get() + (size_t)c * n, (long long)n, st);
             // inner products: the candidate against the pairs kept (and itself), the gradient against all of them
             struct Want { int a, b; };
             std::vector<Want> want;
@@ -282,12 +228,12 @@ int minimize_on_device(rc_ctx* ctx, SmplifyState* s, const BodyConst* body, cons
             for (int j : with_c) { want.push_back({IG, j}); want.push_back({IG, P + j}); }
             want.push_back({IG, IG});
             auto vec_of = [&](int idx) -> const float* {
-                return idx == IG ? slot(base) : (idx >= P ? s->Yv + (size_t)(idx - P) * n : s->Sv + (size_t)idx * n);
+                return idx == IG ? slot(base) : (idx >= P ? s->Yv.get() + (size_t)(idx - P) * n : s->Sv.get() + (size_t)idx * n);
             };
             for (size_t q = 0; q < want.size(); ++q) s->jobs_h[var0 + q] = VecJob{vec_of(want[q].a), vec_of(want[q].b), 0, 0};
-            herr = hipMemcpyAsync(s->jobs_d + var0, s->jobs_h + var0, want.size() * sizeof(VecJob), hipMemcpyHostToDevice, st);
-            rc_launch_vec_dots(s->jobs_d + var0, (int)want.size(), (long long)n, s->part_d + (size_t)var0 * nb, st);
-            if (herr == hipSuccess) herr = hipMemcpyAsync(s->part_h + (size_t)var0 * nb, s->part_d + (size_t)var0 * nb,
+            herr = hipMemcpyAsync(s->jobs_d.get() + var0, s->jobs_h.get() + var0, want.size() * sizeof(VecJob), hipMemcpyHostToDevice, st);
+            rc_launch_vec_dots(s->jobs_d.get() + var0, (int)want.size(), (long long)n, s->part_d.get() + (size_t)var0 * nb, st);
+            if (herr == hipSuccess) herr = hipMemcpyAsync(s->part_h.get() + (size_t)var0 * nb, s->part_d.get() + (size_t)var0 * nb,
                                                           want.size() * nb * sizeof(double), hipMemcpyDeviceToHost, st);
             if (herr == hipSuccess) herr = hipStreamSynchronize(st);
             if (herr != hipSuccess) LB_FAIL();
@@ -324,20 +270,20 @@ int minimize_on_device(rc_ctx* ctx, SmplifyState* s, const BodyConst* body, cons
             for (int i = 0; i < m; ++i) { const int j = order[i]; const double be = dot_q(P + j) * ro[j]; delta[j] += al[j] - be; }
             comb.n_vec = 0;
             for (int j : order) {
-                comb.v[comb.n_vec] = s->Sv + (size_t)j * n; comb.c[comb.n_vec++] = (float)delta[j];
-                comb.v[comb.n_vec] = s->Yv + (size_t)j * n; comb.c[comb.n_vec++] = (float)delta[P + j];
+                comb.v[comb.n_vec] = s->Sv.get() + (size_t)j * n; comb.c[comb.n_vec++] = (float)delta[j];
+                comb.v[comb.n_vec] = s->Yv.get() + (size_t)j * n; comb.c[comb.n_vec++] = (float)delta[P + j];
             }
             comb.v[comb.n_vec] = slot(base); comb.c[comb.n_vec++] = (float)delta[IG];
             gtd = (float)dot_q(IG);
         }
-        rc_launch_vec_comb(comb, s->dir, (long long)n, st);
+        rc_launch_vec_comb(comb, s->dir.get(), (long long)n, st);
         prev_base = base;
         prev_loss = loss;
         if (n_iter == 1) {
             t = std::min(1.0f, 1.0f / gsum) * lr;
             // g.d of d = -g: the base slot's table entry pairs it with d (one more small readback, once per run)
-            rc_launch_vec_dots(s->jobs_d + base * kSlotJobs, 1, (long long)n, s->part_d + (size_t)base * kSlotJobs * nb, st);
-            herr = hipMemcpyAsync(s->part_h + (size_t)base * kSlotJobs * nb, s->part_d + (size_t)base * kSlotJobs * nb, (size_t)nb * sizeof(double),
+            rc_launch_vec_dots(s->jobs_d.get() + base * kSlotJobs, 1, (long long)n, s->part_d.get() + (size_t)base * kSlotJobs * nb, st);
+            herr = hipMemcpyAsync(s->part_h.get() + (size_t)base * kSlotJobs * nb, s->part_d.get() + (size_t)base * kSlotJobs * nb, (size_t)nb * sizeof(double),
                                   hipMemcpyDeviceToHost, st);
             if (herr == hipSuccess) herr = hipStreamSynchronize(st);
             if (herr != hipSuccess) LB_FAIL();
@@ -410,7 +356,7 @@ int minimize_on_device(rc_ctx* ctx, SmplifyState* s, const BodyConst* body, cons
         t = br[lo].t;
         loss = br[lo].f;
         base = br[lo].k;                                                  // gradient at the accepted point
-        rc_launch_vec_axpy(s->x, s->dir, t, s->x, (long long)n, st);      // x += t d (element-wise, in place)
+        rc_launch_vec_axpy(s->x.get(), s->dir.get(), t, s->x.get(), (long long)n, st);      // x += t d (element-wise, in place)
         // |g|_inf of the accepted point: its slot's partial sums are still in the pinned table unless the slot is the old base
         gmax = base == prev_base ? gmax : (float)job_sum(base * kSlotJobs + 1, true);
         const bool opt_cond = gmax <= tolerance_grad;
@@ -491,7 +437,7 @@ class RowBatch {
     float *terms_d = nullptr, *terms_h = nullptr;
     double *total_d = nullptr, *total_h = nullptr;                       // total loss per closure-table entry of the round
     bool device_totals = true;                                           // RC_SMPLIFY_DEVICE_TOTALS=0: read the per-frame terms back and add them on the host (A/B)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    HipEvent ev0, ev1;                                                    // (the arenas belong to the context's SmplifyState)
     double device_ms = 0.0, round_ms = 0.0;                              // closure kernels (events) / wall time inside run_round
     int rounds = 0;
     // rendezvous
@@ -508,10 +454,6 @@ class RowBatch {
     ucontext_t sched{};
     std::vector<ucontext_t> fctx;
 
-    ~RowBatch() {                                                         // (the arenas belong to the context's SmplifyState)
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
     double job_sum(const RowReq& q, int j, int nb, bool is_max) const {
         const double* p = part_h + (size_t)(q.job0 + j) * nb_max;
         double r = p[0];
@@ -556,7 +498,7 @@ class RowBatch {
                 SmplifyArgs A{};
                 A.aa = xp; A.tran = xp + b.T * 72;
                 A.kp = b.kp; A.ref3d = b.ref3d; A.imu_aa = b.imu_aa;
-                A.means = prior->means; A.prec = prior->prec; A.prec_sym = prior->prec + kPriorMat; A.lognll = prior->lognll;
+                A.means = prior->means.get(); A.prec = prior->prec.get(); A.prec_sym = prior->prec.get() + kPriorMat; A.lognll = prior->lognll.get();
                 A.mj = b.mj; A.proj = b.proj;
                 A.frame_loss = b.terms; A.imu_loss = b.terms + b.T; A.smooth_loss = b.terms + 2 * b.T;
                 A.argmin = b.argmin; A.prior_ll = b.prior_ll; A.prior_g = b.prior_g; A.fk = b.fk;
@@ -597,9 +539,9 @@ class RowBatch {
             } else rc_launch_vec_ops(ops_d, n_ops, (long long)n_max, st);
         }
         if (n_args > 0) {
-            if (herr == hipSuccess) herr = hipEventRecord(ev0, st);
+            if (herr == hipSuccess) herr = hipEventRecord(ev0.get(), st);
             rc_launch_smplify_rows(args_d, n_args, T_max, body, st);
-            if (herr == hipSuccess) herr = hipEventRecord(ev1, st);
+            if (herr == hipSuccess) herr = hipEventRecord(ev1.get(), st);
             if (device_totals) rc_launch_smplify_totals(args_d, n_args, total_d, st);
         }
         rc_launch_vec_dots_rows(jobs_d, n_jobs, nb_max, part_d, st);
@@ -612,7 +554,7 @@ class RowBatch {
         if (herr == hipSuccess) herr = hipGetLastError();
         if (n_args > 0 && herr == hipSuccess) {
             float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) device_ms += ms;
+            if (hipEventElapsedTime(&ms, ev0.get(), ev1.get()) == hipSuccess) device_ms += ms;
         }
         ++rounds;
         round_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_round).count();
@@ -843,17 +785,7 @@ void lbfgs_row(RowBatch& B, const int r, const float lr, const int max_iter, Dev
 
 }  // namespace
 
-void rc_smplify_free(SmplifyState* s) {
-    if (!s) return;
-    free_work(s);
-    if (s->batch_dev) (void)hipFree(s->batch_dev);
-    if (s->batch_pin) (void)hipHostFree(s->batch_pin);
-    for (float** p : {&s->means, &s->prec, &s->lognll, &s->Kd})
-        if (*p) (void)hipFree(*p);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    delete s;
-}
+void rc_smplify_free(SmplifyState* s) { delete s; }
 
 extern "C" {
 
@@ -867,7 +799,7 @@ int rc_smplify_set_prior(rc_ctx* ctx, const float* means, const float* prec, con
         if (!(nllw[m] > 0.0f)) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_set_prior: nll_weights must be positive");
         lg[m] = logf(nllw[m]);
     }
-    SM_TRY(ctx, hipMemcpy(s->means, means, 8 * 69 * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(s->means.get(), means, 8 * 69 * sizeof(float), hipMemcpyHostToDevice));
     // rows padded to 72 floats (32-byte aligned for the prior kernel's scalar loads); the second half is P + P^T, the matrix of the
     // gradient of d^T P d (the fp32 sum the gradient kernel used to form per element)
     std::vector<float> pad(2 * kPriorMat, 0.0f);
@@ -878,8 +810,8 @@ int rc_smplify_set_prior(rc_ctx* ctx, const float* means, const float* prec, con
                 pad[((size_t)m * 69 + i) * kPriorLd + j] = a;
                 pad[kPriorMat + ((size_t)m * 69 + i) * kPriorLd + j] = a + b;
             }
-    SM_TRY(ctx, hipMemcpy(s->prec, pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
-    SM_TRY(ctx, hipMemcpy(s->lognll, lg, sizeof(lg), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(s->prec.get(), pad.data(), pad.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(s->lognll.get(), lg, sizeof(lg), hipMemcpyHostToDevice));
     s->have_prior = true;
     return RC_OK;
 }
@@ -906,10 +838,10 @@ int rc_smplify_loss_grad(rc_ctx* ctx, const float* x, const float* kp, const flo
     if (int rc = reserve(ctx, s, T)) return rc;
     hipStream_t st = (hipStream_t)stream;
     rc_launch_smplify(make_args(s, x, kp, ref3d, imu_aa, K, grad, T, rc_ctx_ign_mask(ctx)), body, st);
-    SM_TRY(ctx, hipGetLastError());
-    SM_TRY(ctx, hipMemcpyAsync(s->h_terms, s->terms, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-    SM_TRY(ctx, hipStreamSynchronize(st));
-    *loss = total_loss(s->h_terms, T);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_terms.get(), s->terms.get(), (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    *loss = total_loss(s->h_terms.get(), T);
     return RC_OK;
 }
 
@@ -934,52 +866,52 @@ int rc_smplify_run(rc_ctx* ctx, const float* pose, const float* tran, const floa
     s->device_ms = 0.0;
 
     // pre-check (run.py:24-29): mean residual of the FIRST frame against the threshold
-    SM_TRY(ctx, hipMemcpyAsync(s->Kd, K, 9 * sizeof(float), hipMemcpyHostToDevice, st));
-    rc_launch_residual(body, pose, tran, kp, s->Kd, 100.0f, rc_ctx_ign_mask(ctx), s->res0, T, st);
-    SM_TRY(ctx, hipMemcpyAsync(s->h_res, s->res0, (size_t)T * 33 * sizeof(float), hipMemcpyDeviceToHost, st));
-    SM_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipMemcpyAsync(s->Kd.get(), K, 9 * sizeof(float), hipMemcpyHostToDevice, st));
+    rc_launch_residual(body, pose, tran, kp, s->Kd.get(), 100.0f, rc_ctx_ign_mask(ctx), s->res0.get(), T, st);
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_res.get(), s->res0.get(), (size_t)T * 33 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
     auto frame_mean = [](const float* r) {                  // torch mean(dim=-1) of 33 fp32 values
         float acc = 0.0f;
         for (int v = 0; v < 33; ++v) acc += r[v];
         return acc / 33.0f;
     };
-    if (frame_mean(s->h_res) > loss_threshold) {
-        if (pose_out != pose) SM_TRY(ctx, hipMemcpyAsync(pose_out, pose, (size_t)T * 216 * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (tran_out != tran) SM_TRY(ctx, hipMemcpyAsync(tran_out, tran, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-        SM_TRY(ctx, hipStreamSynchronize(st));
+    if (frame_mean(s->h_res.get()) > loss_threshold) {
+        if (pose_out != pose) HIP_TRY(ctx, hipMemcpyAsync(pose_out, pose, (size_t)T * 216 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (tran_out != tran) HIP_TRY(ctx, hipMemcpyAsync(tran_out, tran, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
         info->status = 0;
         info->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
         return RC_OK;
     }
 
     // parameters and constants of the closure (temporal_smplify.py:111-139)
-    rc_launch_R2aa(pose, s->x, T * 24, st);                                            // body_pose = axis-angle of the prediction
-    SM_TRY(ctx, hipMemcpyAsync(s->x + T * 72, tran, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    rc_launch_R2aa(imu_ori, s->imu_aa, T * 6, st);
+    rc_launch_R2aa(pose, s->x.get(), T * 24, st);                                            // body_pose = axis-angle of the prediction
+    HIP_TRY(ctx, hipMemcpyAsync(s->x.get() + T * 72, tran, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    rc_launch_R2aa(imu_ori, s->imu_aa.get(), T * 6, st);
     if (s->ref3d_override) {                                                           // see rc_smplify_set_ref3d
-        SM_TRY(ctx, hipMemcpyAsync(s->ref3d, s->ref3d_override, (size_t)T * 99 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(s->ref3d.get(), s->ref3d_override, (size_t)T * 99 * sizeof(float), hipMemcpyDeviceToDevice, st));
         s->ref3d_override = nullptr;
     } else {
-        rc_launch_body_fk(body, pose, tran, nullptr, s->joint, s->ref3d, T, st);      // preserved 3D landmarks
+        rc_launch_body_fk(body, pose, tran, nullptr, s->joint.get(), s->ref3d.get(), T, st);      // preserved 3D landmarks
     }
-    SM_TRY(ctx, hipMemcpyAsync(s->h_x, s->x, (size_t)T * 75 * sizeof(float), hipMemcpyDeviceToHost, st));
-    SM_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_x.get(), s->x.get(), (size_t)T * 75 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
 
     using L = rc::Lbfgs<float>;
     const size_t n = (size_t)T * 75;
     const char* hv = std::getenv("RC_SMPLIFY_HOST_LBFGS");            // read per call: tests flip it
     const bool host_vectors = hv && std::atoi(hv) != 0;
     if (!host_vectors) {
-        // the optimiser's vectors stay on the device (minimize_on_device); s->x is updated in place
+        // the optimiser's vectors stay on the device (minimize_on_device); s->x.get() is updated in place
         DevResult dr;
         if (int rc = minimize_on_device(ctx, s, body, kp, K, T, lr, max_iter, st, dr)) return rc;
-        rc_launch_aa2R(s->x, pose_out, T * 24, st);
-        SM_TRY(ctx, hipMemcpyAsync(tran_out, s->x + T * 72, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-        rc_launch_residual(body, pose_out, tran_out, kp, s->Kd, 100.0f, rc_ctx_ign_mask(ctx), s->res1, T, st);
-        SM_TRY(ctx, hipMemcpyAsync(s->h_res + T * 33, s->res1, (size_t)T * 33 * sizeof(float), hipMemcpyDeviceToHost, st));
-        SM_TRY(ctx, hipStreamSynchronize(st));
-        SM_TRY(ctx, hipGetLastError());
-        for (int64_t t = 0; t < T; ++t) update[t] = frame_mean(s->h_res + (T + t) * 33) < frame_mean(s->h_res + t * 33) ? 1 : 0;
+        rc_launch_aa2R(s->x.get(), pose_out, T * 24, st);
+        HIP_TRY(ctx, hipMemcpyAsync(tran_out, s->x.get() + T * 72, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        rc_launch_residual(body, pose_out, tran_out, kp, s->Kd.get(), 100.0f, rc_ctx_ign_mask(ctx), s->res1.get(), T, st);
+        HIP_TRY(ctx, hipMemcpyAsync(s->h_res.get() + T * 33, s->res1.get(), (size_t)T * 33 * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, hipGetLastError());
+        for (int64_t t = 0; t < T; ++t) update[t] = frame_mean(s->h_res.get() + (T + t) * 33) < frame_mean(s->h_res.get() + t * 33) ? 1 : 0;
         info->status = 1;
         info->n_iter = dr.n_iter;
         info->n_eval = dr.n_eval;
@@ -990,17 +922,17 @@ int rc_smplify_run(rc_ctx* ctx, const float* pose, const float* tran, const floa
         return RC_OK;
     }
     // RC_SMPLIFY_HOST_LBFGS=1: round 2's formulation (vectors on the host, rc_lbfgs.h run as is) for A/B runs
-    L::Vec x(s->h_x, s->h_x + n);
+    L::Vec x(s->h_x.get(), s->h_x.get() + n);
     int hip_rc = RC_OK;
-    const SmplifyArgs A = make_args(s, s->x, kp, s->ref3d, s->imu_aa, K, s->grad, T, rc_ctx_ign_mask(ctx));
+    const SmplifyArgs A = make_args(s, s->x.get(), kp, s->ref3d.get(), s->imu_aa.get(), K, s->grad.get(), T, rc_ctx_ign_mask(ctx));
     L::Objective closure = [&](const L::Vec& xv, L::Vec& g) -> float {
-        std::memcpy(s->h_x, xv.data(), n * sizeof(float));
-        hipError_t e = hipMemcpyAsync(s->x, s->h_x, n * sizeof(float), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipEventRecord(s->ev0, st);
+        std::memcpy(s->h_x.get(), xv.data(), n * sizeof(float));
+        hipError_t e = hipMemcpyAsync(s->x.get(), s->h_x.get(), n * sizeof(float), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipEventRecord(s->ev0.get(), st);
         rc_launch_smplify(A, body, st);
-        if (e == hipSuccess) e = hipEventRecord(s->ev1, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->h_grad, s->grad, n * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->h_terms, s->terms, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipEventRecord(s->ev1.get(), st);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->h_grad.get(), s->grad.get(), n * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->h_terms.get(), s->terms.get(), (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e == hipSuccess) e = hipGetLastError();
         if (e != hipSuccess) {
@@ -1009,9 +941,9 @@ int rc_smplify_run(rc_ctx* ctx, const float* pose, const float* tran, const floa
             return 0.0f;
         }
         float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, s->ev0, s->ev1) == hipSuccess) s->device_ms += ms;
-        std::memcpy(g.data(), s->h_grad, n * sizeof(float));
-        return (float)total_loss(s->h_terms, T);
+        if (hipEventElapsedTime(&ms, s->ev0.get(), s->ev1.get()) == hipSuccess) s->device_ms += ms;
+        std::memcpy(g.data(), s->h_grad.get(), n * sizeof(float));
+        return (float)total_loss(s->h_terms.get(), T);
     };
     L::Options opt;
     opt.lr = lr;
@@ -1022,15 +954,15 @@ int rc_smplify_run(rc_ctx* ctx, const float* pose, const float* tran, const floa
     if (hip_rc != RC_OK) return hip_rc;
 
     // results (temporal_smplify.py:188-196, run.py:31-34): rotation matrices, new residual, per-frame update mask
-    std::memcpy(s->h_x, x.data(), n * sizeof(float));
-    SM_TRY(ctx, hipMemcpyAsync(s->x, s->h_x, n * sizeof(float), hipMemcpyHostToDevice, st));
-    rc_launch_aa2R(s->x, pose_out, T * 24, st);
-    SM_TRY(ctx, hipMemcpyAsync(tran_out, s->x + T * 72, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    rc_launch_residual(body, pose_out, tran_out, kp, s->Kd, 100.0f, rc_ctx_ign_mask(ctx), s->res1, T, st);
-    SM_TRY(ctx, hipMemcpyAsync(s->h_res + T * 33, s->res1, (size_t)T * 33 * sizeof(float), hipMemcpyDeviceToHost, st));
-    SM_TRY(ctx, hipStreamSynchronize(st));
-    SM_TRY(ctx, hipGetLastError());
-    for (int64_t t = 0; t < T; ++t) update[t] = frame_mean(s->h_res + (T + t) * 33) < frame_mean(s->h_res + t * 33) ? 1 : 0;
+    std::memcpy(s->h_x.get(), x.data(), n * sizeof(float));
+    HIP_TRY(ctx, hipMemcpyAsync(s->x.get(), s->h_x.get(), n * sizeof(float), hipMemcpyHostToDevice, st));
+    rc_launch_aa2R(s->x.get(), pose_out, T * 24, st);
+    HIP_TRY(ctx, hipMemcpyAsync(tran_out, s->x.get() + T * 72, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    rc_launch_residual(body, pose_out, tran_out, kp, s->Kd.get(), 100.0f, rc_ctx_ign_mask(ctx), s->res1.get(), T, st);
+    HIP_TRY(ctx, hipMemcpyAsync(s->h_res.get() + T * 33, s->res1.get(), (size_t)T * 33 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipGetLastError());
+    for (int64_t t = 0; t < T; ++t) update[t] = frame_mean(s->h_res.get() + (T + t) * 33) < frame_mean(s->h_res.get() + t * 33) ? 1 : 0;
     info->status = 1;
     info->n_iter = r.n_iter;
     info->n_eval = r.n_eval;
@@ -1121,22 +1053,12 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
     const size_t p_args = ptake(nr * sizeof(SmplifyArgs)), p_ops = ptake(3 * nr * sizeof(VecOp)), p_comb = ptake(nr * sizeof(VecCombRow));
     const size_t p_jobs = ptake(nr * B.max_jobs * sizeof(VecJobN)), p_part = ptake(nr * B.max_jobs * (size_t)B.nb_max * sizeof(double));
     const size_t p_terms = ptake(nr * 3 * (size_t)B.T_max * 4);
-    if (dev_need > s0->batch_dev_cap) {
-        if (s0->batch_dev) (void)hipFree(s0->batch_dev);
-        s0->batch_dev = nullptr; s0->batch_dev_cap = 0;
-        SM_TRY(ctx, hipMalloc((void**)&s0->batch_dev, dev_need));
-        s0->batch_dev_cap = dev_need;
-    }
-    if (pin_need > s0->batch_pin_cap) {
-        if (s0->batch_pin) (void)hipHostFree(s0->batch_pin);
-        s0->batch_pin = nullptr; s0->batch_pin_cap = 0;
-        SM_TRY(ctx, hipHostMalloc((void**)&s0->batch_pin, pin_need, hipHostMallocDefault));
-        s0->batch_pin_cap = pin_need;
-    }
-    B.dev = s0->batch_dev; B.pin = s0->batch_pin;
+    HIP_TRY(ctx, rc_grow(s0->batch_dev_cap, dev_need, dev_need, s0->batch_dev, dev_need));
+    HIP_TRY(ctx, rc_grow(s0->batch_pin_cap, pin_need, pin_need, s0->batch_pin, pin_need));
+    B.dev = s0->batch_dev.get(); B.pin = s0->batch_pin.get();
     B.dev_bytes = dev_need; B.pin_bytes = pin_need;
-    SM_TRY(ctx, hipEventCreate(&B.ev0));
-    SM_TRY(ctx, hipEventCreate(&B.ev1));
+    HIP_TRY(ctx, hipEventCreate(rc_out(B.ev0)));
+    HIP_TRY(ctx, hipEventCreate(rc_out(B.ev1)));
     B.args_d = (SmplifyArgs*)(B.dev + o_args); B.ops_d = (VecOp*)(B.dev + o_ops); B.comb_d = (VecCombRow*)(B.dev + o_comb);
     B.jobs_d = (VecJobN*)(B.dev + o_jobs); B.part_d = (double*)(B.dev + o_part); B.terms_d = (float*)(B.dev + o_terms);
     B.args_h = (SmplifyArgs*)(B.pin + p_args); B.ops_h = (VecOp*)(B.pin + p_ops); B.comb_h = (VecCombRow*)(B.pin + p_comb);
@@ -1170,10 +1092,10 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
         for (int e = 0; e < 9; ++e) io.K[e] = b.K[e];
         io.T = (int)b.T; io.live = 0;
     }
-    SM_TRY(ctx, hipMemcpyAsync(io_d, io_h, nr * sizeof(SmplifyRowIO), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(io_d, io_h, nr * sizeof(SmplifyRowIO), hipMemcpyHostToDevice, st));
     rc_launch_smplify_begin_rows(io_d, n_rows, B.T_max, body, 100.0f, B.ign, st);
-    SM_TRY(ctx, hipMemcpyAsync(B.pin + p_r0, B.dev + r0_begin, r_bytes, hipMemcpyDeviceToHost, st));
-    SM_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipMemcpyAsync(B.pin + p_r0, B.dev + r0_begin, r_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
     auto frame_mean = [](const float* v) {
         float acc = 0.0f;
         for (int q = 0; q < 33; ++q) acc += v[q];
@@ -1183,16 +1105,16 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
     for (int r = 0; r < n_rows; ++r) {
         RowBuf& b = B.row[r];
         if (frame_mean(b.h_res0) > loss_threshold) {
-            if (pose_out[r] != pose[r]) SM_TRY(ctx, hipMemcpyAsync(pose_out[r], pose[r], (size_t)b.T * 216 * sizeof(float), hipMemcpyDeviceToDevice, st));
-            if (tran_out[r] != tran[r]) SM_TRY(ctx, hipMemcpyAsync(tran_out[r], tran[r], (size_t)b.T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if (pose_out[r] != pose[r]) HIP_TRY(ctx, hipMemcpyAsync(pose_out[r], pose[r], (size_t)b.T * 216 * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if (tran_out[r] != tran[r]) HIP_TRY(ctx, hipMemcpyAsync(tran_out[r], tran[r], (size_t)b.T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
             infos[r].status = 0;
             continue;
         }
         live.push_back(r);
         io_h[r].live = 1;
     }
-    SM_TRY(ctx, hipStreamSynchronize(st));
-    SM_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipGetLastError());
     const auto t_opt = std::chrono::steady_clock::now();
     // ---- the optimisers: a fiber (or, RC_SMPLIFY_THREADS=1, a host thread) per row, the device work in lock-step rounds
     std::vector<DevResult> res((size_t)n_rows);
@@ -1246,12 +1168,12 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
     const auto t_res = std::chrono::steady_clock::now();
     // ---- results in ONE launch: rotations, translation, residual after; then the per-frame update mask (run.py:31-34)
     if (!live.empty()) {
-        SM_TRY(ctx, hipMemcpyAsync(io_d, io_h, nr * sizeof(SmplifyRowIO), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(io_d, io_h, nr * sizeof(SmplifyRowIO), hipMemcpyHostToDevice, st));
         rc_launch_smplify_end_rows(io_d, n_rows, B.T_max, body, 100.0f, B.ign, st);
-        SM_TRY(ctx, hipMemcpyAsync(B.pin + p_r1, B.dev + r1_begin, r_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(B.pin + p_r1, B.dev + r1_begin, r_bytes, hipMemcpyDeviceToHost, st));
     }
-    SM_TRY(ctx, hipStreamSynchronize(st));
-    SM_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipGetLastError());
     const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     if (const char* e = std::getenv("RC_SMPLIFY_TRACE"); e && *e == '1') {
         auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };

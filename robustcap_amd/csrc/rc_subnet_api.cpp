@@ -17,58 +17,30 @@
 #include "rc_internal.h"
 #include "../../include/robustcap_hip.h"
 
-struct SubnetState {
-    float* buf = nullptr;            // per-chunk buffers (X | relu(linear1) = h of layer 1 | x halves | h of layer 0)
+struct SubnetState {                 // (grow-only buffers; the context's destruction waits for the device before releasing them)
+    DevBuf<float> buf;               // per-chunk buffers (X | relu(linear1) = h of layer 1 | x halves | h of layer 0)
     size_t buf_floats = 0;
-    float* st = nullptr;             // recurrent state of a group: per layer two copies of h [npad, H] and c [npad, H]
+    DevBuf<float> st;                // recurrent state of a group: per layer two copies of h [npad, H] and c [npad, H]
     size_t st_floats = 0;
-    int* ibuf = nullptr;             // rank -> sequence, final copy per rank, row maps of every frame of the call
+    DevBuf<int> ibuf;                // rank -> sequence, final copy per rank, row maps of every frame of the call
     size_t ibuf_ints = 0;
-    int* ihost = nullptr;            // pinned staging of ibuf
+    PinBuf<int> ihost;               // pinned staging of ibuf
     size_t ihost_ints = 0;
-    hipEvent_t ev = nullptr;         // the last upload from ihost
-    hipEvent_t done = nullptr;       // the end of the last call's work (a call on another stream waits for it: the scratch is shared)
+    HipEvent ev;                     // the last upload from ihost
+    HipEvent done;                   // the end of the last call's work (a call on another stream waits for it: the scratch is shared)
     long long calls = 0, frames = 0, chunks = 0;
 };
 
-void rc_subnet_free(SubnetState* s) {
-    if (!s) return;
-    if (s->ev) (void)hipEventSynchronize(s->ev);
-    if (s->buf) (void)hipFree(s->buf);
-    if (s->st) (void)hipFree(s->st);
-    if (s->ibuf) (void)hipFree(s->ibuf);
-    if (s->ihost) (void)hipHostFree(s->ihost);
-    if (s->ev) (void)hipEventDestroy(s->ev);
-    if (s->done) (void)hipEventDestroy(s->done);
-    delete s;
-}
+void rc_subnet_free(SubnetState* s) { delete s; }
 
 namespace {
 
 inline long long r16(long long x) { return (x + 15) / 16 * 16; }
 
-#define SUB_TRY(ctx, expr)                                                                               \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return rc_ctx_fail(ctx, RC_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
 SubnetState* state(rc_ctx* ctx) {
-    SubnetState*& s = rc_ctx_subnet(ctx);
-    if (!s) s = new SubnetState();
-    return s;
-}
-
-// grow-only device buffer (its previous contents are not kept; hipFree waits for the work that still reads it)
-template <typename T>
-int grow(rc_ctx* ctx, T** p, size_t* cap, size_t want) {
-    if (want <= *cap) return RC_OK;
-    if (*p) SUB_TRY(ctx, hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    SUB_TRY(ctx, hipMalloc((void**)p, want * sizeof(T)));
-    *cap = want;
-    return RC_OK;
+    SubnetOwner& s = rc_ctx_subnet(ctx);
+    if (!s) s.reset(new SubnetState());
+    return s.get();
 }
 
 SubGemm dense(const SubnetDense& d, const float* A, int M, float* out, int ldo, bool packed, bool relu, const int* out_map) {
@@ -145,45 +117,41 @@ int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* le
 
     // ---- scratch (grow-only) and the upload of the plan -----------------------------------------------------------------------------
     // The scratch is shared by every call of the context: a call on another stream than the previous one waits for that call's work.
-    if (S->done) SUB_TRY(ctx, hipStreamWaitEvent(st, S->done, 0));
-    else SUB_TRY(ctx, hipEventCreateWithFlags(&S->done, hipEventDisableTiming));
+    if (S->done) HIP_TRY(ctx, hipStreamWaitEvent(st, S->done.get(), 0));
+    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->done), hipEventDisableTiming));
+    // (grow-only scratch, contents not kept; releasing the old buffer waits for the work that still reads it)
     const long long R = r16(max_rows), G = r16(max_group);
-    if (int rc = grow(ctx, &S->buf, &S->buf_floats, (size_t)(R * (Kp1 + 6ll * H)))) return rc;
-    if (int rc = grow(ctx, &S->st, &S->st_floats, (size_t)(6 * G * H))) return rc;
-    if (int rc = grow(ctx, &S->ibuf, &S->ibuf_ints, ih.size())) return rc;
-    if (S->ev) SUB_TRY(ctx, hipEventSynchronize(S->ev));                  // the previous call's upload has left the staging buffer
-    else SUB_TRY(ctx, hipEventCreateWithFlags(&S->ev, hipEventDisableTiming));
-    if (ih.size() > S->ihost_ints) {
-        if (S->ihost) SUB_TRY(ctx, hipHostFree(S->ihost));
-        S->ihost = nullptr;
-        S->ihost_ints = 0;
-        SUB_TRY(ctx, hipHostMalloc((void**)&S->ihost, ih.size() * sizeof(int), hipHostMallocDefault));
-        S->ihost_ints = ih.size();
-    }
-    std::copy(ih.begin(), ih.end(), S->ihost);
-    SUB_TRY(ctx, hipMemcpyAsync(S->ibuf, S->ihost, ih.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    SUB_TRY(ctx, hipEventRecord(S->ev, st));
+    const size_t n_buf = (size_t)(R * (Kp1 + 6ll * H)), n_st = (size_t)(6 * G * H);
+    HIP_TRY(ctx, rc_grow(S->buf_floats, n_buf, n_buf, S->buf, n_buf));
+    HIP_TRY(ctx, rc_grow(S->st_floats, n_st, n_st, S->st, n_st));
+    HIP_TRY(ctx, rc_grow(S->ibuf_ints, ih.size(), ih.size(), S->ibuf, ih.size()));
+    if (S->ev) HIP_TRY(ctx, hipEventSynchronize(S->ev.get()));            // the previous call's upload has left the staging buffer
+    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->ev), hipEventDisableTiming));
+    HIP_TRY(ctx, rc_grow(S->ihost_ints, ih.size(), ih.size(), S->ihost, ih.size()));
+    std::copy(ih.begin(), ih.end(), S->ihost.get());
+    HIP_TRY(ctx, hipMemcpyAsync(S->ibuf.get(), S->ihost.get(), ih.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(S->ev.get(), st));
 
-    float* X = S->buf;                       // [R, Kp1]  packed input
+    float* X = S->buf.get();                       // [R, Kp1]  packed input
     float* A1 = X + R * Kp1;                 // [R, H]    relu(linear1); then h of layer 1 (A1 is dead once layer 0's x half is formed)
     float* PRE = A1 + R * H;                 // [R, 4H]   x half of the layer being stepped
     float* H0 = PRE + R * 4 * H;             // [R, H]    h of layer 0
     const long long ps = G * H, hl = 3 * G * H;   // state: per layer [copy 0 | copy 1 | c]
-    float* hst = S->st;
-    float* cst = S->st + 2 * G * H;
+    float* hst = S->st.get();
+    float* cst = hst + 2 * G * H;
 
     // final_* of the group of ranks [g0, g1): every rank's h from the copy its last step wrote
     auto finish = [&](int g0, int g1) {
-        rc_launch_subnet_state(hst, hl, ps, S->ibuf + n + g0, cst, hl, final_h, final_c, S->ibuf + g0, g1 - g0, n, H, 0, st);
+        rc_launch_subnet_state(hst, hl, ps, S->ibuf.get() + n + g0, cst, hl, final_h, final_c, S->ibuf.get() + g0, g1 - g0, n, H, 0, st);
     };
     int g0 = -1, g1 = -1;
     for (const Chunk& c : chunks) {
         const long long M = c.off.back();
-        const int* map = S->ibuf + 2 * (size_t)n + c.frame0;
+        const int* map = S->ibuf.get() + 2 * (size_t)n + c.frame0;
         if (c.g0 != g0) {                    // a new group: its state from init_* (or zeros)
             if (g0 >= 0) finish(g0, g1);
             g0 = c.g0; g1 = c.g1;
-            rc_launch_subnet_state(hst, hl, ps, nullptr, cst, hl, const_cast<float*>(init_h), const_cast<float*>(init_c), S->ibuf + g0,
+            rc_launch_subnet_state(hst, hl, ps, nullptr, cst, hl, const_cast<float*>(init_h), const_cast<float*>(init_c), S->ibuf.get() + g0,
                                    g1 - g0, n, H, 1, st);
         }
         rc_launch_subnet_pack(x, w.in, map, X, Kp1, (int)M, st);
@@ -210,8 +178,8 @@ int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* le
         S->chunks += 1;
     }
     finish(g0, g1);
-    SUB_TRY(ctx, hipGetLastError());
-    SUB_TRY(ctx, hipEventRecord(S->done, st));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(S->done.get(), st));
     S->calls += 1;
     S->frames += total;
     return RC_OK;
@@ -228,10 +196,11 @@ int rc_init_net_forward(rc_ctx* ctx, int32_t n, const float* v, float* out, void
     const long long per_row = d[0].Kp + d[1].Kp + d[2].Kp;               // packed v | hidden 1 | hidden 2
     const long long rows_max = std::max(16ll, RC_SUBNET_SCRATCH_BYTES / (4 * per_row) / 16 * 16);
     const long long R = r16(std::min<long long>(n, rows_max));
-    if (S->done) SUB_TRY(ctx, hipStreamWaitEvent(st, S->done, 0));
-    else SUB_TRY(ctx, hipEventCreateWithFlags(&S->done, hipEventDisableTiming));
-    if (int rc = grow(ctx, &S->buf, &S->buf_floats, (size_t)(R * per_row))) return rc;
-    float* X = S->buf;
+    if (S->done) HIP_TRY(ctx, hipStreamWaitEvent(st, S->done.get(), 0));
+    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->done), hipEventDisableTiming));
+    const size_t n_buf = (size_t)(R * per_row);
+    HIP_TRY(ctx, rc_grow(S->buf_floats, n_buf, n_buf, S->buf, n_buf));
+    float* X = S->buf.get();
     float* h1 = X + R * d[0].Kp;
     float* h2 = h1 + R * d[1].Kp;
     for (long long r0 = 0; r0 < n; r0 += rows_max) {
@@ -242,8 +211,8 @@ int rc_init_net_forward(rc_ctx* ctx, int32_t n, const float* v, float* out, void
         rc_launch_subnet_gemm(dense(d[2], h2, M, out + r0 * d[2].N, d[2].N, false, false, nullptr), split, 1, st);
         S->chunks += 1;
     }
-    SUB_TRY(ctx, hipGetLastError());
-    SUB_TRY(ctx, hipEventRecord(S->done, st));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(S->done.get(), st));
     S->calls += 1;
     S->frames += n;
     return RC_OK;
@@ -251,7 +220,7 @@ int rc_init_net_forward(rc_ctx* ctx, int32_t n, const float* v, float* out, void
 
 int rc_get_subnet_stats(rc_ctx* ctx, int64_t* calls, int64_t* frames, int64_t* chunks, int64_t* scratch_bytes) {
     if (!ctx) return RC_ERR_INVALID;
-    const SubnetState* s = rc_ctx_subnet(ctx);
+    const SubnetState* s = rc_ctx_subnet(ctx).get();
     if (calls) *calls = s ? s->calls : 0;
     if (frames) *frames = s ? s->frames : 0;
     if (chunks) *chunks = s ? s->chunks : 0;

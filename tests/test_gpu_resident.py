@@ -20,16 +20,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NETS = ("rnn2", "rnn3", "rnn4", "rnn6", "rnn7", "rnn8")
 
 
-def _run(sd, body, m, B, resident, seq=True, cut=None):
+def _run(sd, body, m, B, resident, seq=True, cut=None, late_tables=False):
+    """cut: None, or the first frame of the second call, or a tuple of the first frames of the calls after the first.
+    late_tables: sequence mode is off while the weights load, so the first planned call sizes the plan's tables (not rc_finalize_weights)."""
     t = torch.from_numpy
     net = Net(body=body, batch=B)
+    if late_tables:
+        net.set_sequence_mode(False)
     net.load_state_dict(sd)
     net.gravityc = t(m["gravityc"])
     net.set_sequence_mode(seq, 8, force=True)
     net.set_resident(resident)
     T = m["j2dc"].shape[1]
+    bounds = (0,) + (cut if isinstance(cut, tuple) else (cut or T,)) + (T,)
     P, Tr = [], []
-    for lo, hi in ((0, cut or T), (cut or T, T)):
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
         if hi > lo:
             p, tr = net.forward_sequence(t(m["j2dc"][:, lo:hi]), t(m["accc"][:, lo:hi]), t(m["oric"][:, lo:hi]), first_frame=(lo == 0))
             P.append(p), Tr.append(tr)
@@ -54,17 +59,26 @@ def _schedule(rng, B, T):
     return c
 
 
-@pytest.mark.parametrize("B,T,conf,cut", [(256, 40, "high", None), (256, 48, "switching", 19), (192, 36, "switching", None), (160, 30, "mixed", 11)])
+# "alternating": three calls on one Net, the plan's tables sized by the first (32 frames, all visible). In the second (40 frames) every
+# fourth row alternates occluded / visible frame by frame and lags 9 ticks per occlusion: the plan needs more ticks than rc_sequence
+# reserved for the call (tests/test_wave_plan.py), and run_wave2_segment grows frame_at. The third call reads the resident abort word.
+# "-streams": the same calls on the stream engine (resident kernel off).
+@pytest.mark.parametrize("B,T,conf,cut", [(256, 40, "high", None), (256, 48, "switching", 19), (192, 36, "switching", None), (160, 30, "mixed", 11),
+                                          (160, 80, "alternating", (32, 72)), (160, 80, "alternating-streams", (32, 72))])
 def test_resident_engine_is_bitwise_the_frame_stepped_path(B, T, conf, cut):
     sd, body = synth.make_state_dict(0), synth.make_body(1)
-    m = synth.make_motion(70 + B, 16, T, body, conf="high" if conf == "switching" else conf)
+    m = synth.make_motion(70 + B, 16, T, body, conf=conf if conf == "mixed" else "high")
     rep = (B + 15) // 16
     m = {k: np.concatenate([v] * rep, 0)[:B].copy() for k, v in m.items()}
     if conf == "switching":
         m["j2dc"][..., 2] = _schedule(np.random.default_rng(B + T), B, T)[:, :, None]
-    rp, rt, rs, rtr, rstat, rres = _run(sd, body, m, B, True, cut=cut)
+    alternating = conf.startswith("alternating")
+    if alternating:
+        m["j2dc"][1::4, cut[0]:cut[1], :, 2] = np.where(np.arange(cut[1] - cut[0]) % 2 == 0, 0.5, 0.9)[None, :, None]
+    resident = conf != "alternating-streams"
+    rp, rt, rs, rtr, rstat, rres = _run(sd, body, m, B, resident, cut=cut, late_tables=alternating)
     sp, st_, ss, strc, sstat, _ = _run(sd, body, m, B, False, seq=False, cut=cut)
-    assert rres[0] >= 1 and rres[1] == 0, rres                       # the resident kernel ran, no wait ran out
+    assert (rres[0] >= 1) == resident and rres[1] == 0, rres         # the resident kernel ran (or not: -streams), no wait ran out
     assert rstat[0] > 0 and sstat[0] == 0
     assert torch.equal(rp, sp) and torch.equal(rt, st_) and torch.equal(rtr, strc)
     for (h1, c1), (h2, c2) in zip(rs, ss):

@@ -181,3 +181,15 @@ def test_random_plans_respect_every_hazard(seed):
                     waited_for_rider = codes[f, b] >= 1 and vis and ((i and codes[f - 1, b] == 0) or (not i and pd[b]))
                     assert waited_for_rider or imu
         assert est[0] > 0 and est[1] > 0
+
+
+def test_rows_alternating_occlusion_outgrow_the_reserved_table():
+    """A row occluded on every other frame waits TAIL + 1 ticks after each occluded frame: a 40-frame call plans more ticks than the
+    B x (T + 64) entries of frame_at that rc_sequence reserves for a call of T frames, so run_wave2_segment grows the table. The second
+    call of the "alternating" cases of tests/test_gpu_resident.py has this pattern on every fourth row (all rows visible before)."""
+    T, B = 40, 8
+    codes = np.full((T, B), 2)
+    codes[0::2, 1::4] = 0
+    fa, nt, cnt, _ = plan(codes, first_reach=np.zeros(B), pend=np.zeros(B))
+    assert fa.shape[0] > T + 64
+    replay(codes, fa, nt, cnt, 0, np.zeros(B, int), np.zeros(B, int))
