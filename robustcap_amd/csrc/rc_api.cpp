@@ -10,7 +10,7 @@
 //        -> tail (fusion logic, FK, landmarks; marks the rows whose updater step is now pending)
 // Independent sub-nets share a launch ("problems" of one gate-GEMM grid). 8-14 kernel launches per frame, no host
 // synchronisation. rc_sequence runs whole calls on the per-row-cursor wavefront engine instead (run_wave2_segment below): the
-// same stages skewed over consecutive ticks and a ring of slots, two merged wide launches per tick (on two streams from 48 rows).
+// same stages skewed over consecutive ticks and a ring of slots, two or three wide launches per tick on one to three streams.
 #include "../../include/robustcap_hip.h"
 #include "rc_internal.h"
 
@@ -37,7 +37,7 @@
 // ~80 rows; with 64-row tiles from 33 rows of a problem it wins from 48 (mixed, 128-frame calls, body-frames/s, split vs fp32
 // MFMA: batch 40 329k vs 344k, 48 434k vs 410k, 64 556k vs 417k, 72 486k vs 339k). 64-row tiles for the FRAME-STEPPED full-batch
 // stages stay tied to 192 rows (below that they leave CUs without a tile).
-#define RC_SPLIT_MAIN_MIN_BATCH 48  // wavefront engine: the tick's two wide launches on two streams from this many rows
+#define RC_SPLIT_MAIN_MIN_BATCH 48  // wavefront engine: the tick's wide launches on streams of their own from this many rows (pick_wave_engine)
 #define RC_SPLIT_MIN_BATCH 48
 #define RC_TILE64_MIN_BATCH 192
 
@@ -184,13 +184,14 @@ struct rc_ctx {
     float* x1_alt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // second relu(linear1) buffer per net
     int tile6[2] = {0, 0}, tile378[2] = {0, 0}, tile2[2] = {0, 0}, tile4[2] = {0, 0};   // LSTM tile shapes of full-batch stages (0 = pick_tile)
     bool ring2_failed = false;           // ensure_wave2_buffers failed once: not retried
-    bool seq_two_streams = true;         // tuning: per-row kernels + linear2 on the second stream (else everything on the caller's)
-    HipStream aux_stream;                // per-row kernels of a tick run beside the tick's GEMM launch
-    HipStream h512_stream;               // the tick's {H = 512 nets, linear1} launch, beside the {rnn6, rnn4} launch on the caller's stream
-    HipEvent ev_main[8], ev_aux[8], ev_h512[4];
-    HipStream lin1_stream;               // round 6 (regrouped ticks): the tick's {linear1, init_net} launch on a stream of its own
-    HipEvent ev_lin1[4], ev_h5[4];
-    float* x1_alt2[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // third relu(linear1) buffer per net (h512_stream runs a tick ahead)
+    // streams of a tick beside the caller's (stream_tick; caller's stream: plain both wide launches | split {rnn6, rnn4, init_net} | tri rnn4)
+    HipStream aux_stream;                // the second stream, every engine: prep, linear2, fuse, tail; tri also {linear1, init_net} at the head of its tick
+    HipStream wide2_stream;              // plain: unused | split: {H = 512 nets, linear1} | tri: rnn6
+    HipEvent ev_main[8], ev_aux[8], ev_wide2[4];   // [tick & 3]: the last wide launch of the caller's stream | the end of aux_stream's tick | wide2_stream's
+                                                   // launch is done (ev_main[6], [7]: the engine's streams join the caller's)
+    HipStream wide3_stream;              // tri only: the H = 512 nets
+    HipEvent ev_head[4], ev_wide3[4];    // tri only: {linear1, init_net} at the head of aux_stream's tick | wide3_stream's launch is done
+    float* x1_alt2[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // third relu(linear1) buffer per net (linear1 runs up to a tick ahead of its readers)
     DevBuf<signed char> scan_codes_d;    // [cap] regime code per (frame, row)
     PinBuf<signed char> scan_codes_h;    // pinned
     PinBuf<int> scan_state_h;            // pinned: first_reach[B] then pend[B] (as ints)
@@ -224,7 +225,7 @@ struct rc_ctx {
     DevBuf<int> lds_tickets;             // [kLdsRegions][lds_region_tiles]
     size_t lds_region_tiles = 0;
     unsigned lds_rot = 0;
-    // resident layer-step kernel of the wavefront engine (run_wave2_segment: `resident`)
+    // resident layer-step kernel of the wavefront engine (run_resident_segment)
     DevBuf<ResidentTick> res_ticks_d;        // [res_cap]
     PinBuf<ResidentTick> res_ticks_h;        // pinned
     DevBuf<int> res_ints_d;                  // item_base [res_cap + 1] | done [res_cap][RC_RES_MAXP] | tick_done [res_cap] | head, flag_l1, flag_tail, abort
@@ -448,6 +449,11 @@ void pick_tile(int H, int rows, int* mr, int* nc) {
     *mr = 1; *nc = 1;
 }
 
+// "This problem runs on the shared-weight kernel (rc_gemm_lds.hip)": a CONTEXT takes it (and the tri engine) in split-product mode from
+// lds_min_batch rows, a PROBLEM inside such a context from lds_min_rows rows.
+inline bool lds_context(const rc_ctx* c) { return c->gemm_split && c->lds_min_rows > 0 && c->B >= c->lds_min_batch; }
+inline bool lds_problem(const rc_ctx* c, int rows) { return lds_context(c) && rows >= c->lds_min_rows; }
+
 GemmProblem lin1_problem(const rc_ctx* c, const Stage& s) {
     const NetDev& n = c->net[s.net];
     GemmProblem p = dense_problem(c, n.lin1, seg(s.x, s.ldx, 0), Out{n.x1, n.H, 0, true}, true, s.flag_bit,
@@ -484,7 +490,7 @@ GemmProblem lstm_problem(const rc_ctx* c, const Stage& s, int layer) {
         if (s.net == N4 && c->tile4[0]) { mr = c->tile4[0]; nc = c->tile4[1]; }
     }
     const int rows = s.rows_hint < 0 ? c->B : (s.rows_hint < c->B ? s.rows_hint : c->B);
-    if (c->gemm_split && c->lds_min_rows > 0 && c->B >= c->lds_min_batch && rows >= c->lds_min_rows) { mr = 16; nc = 8; }   // the shared-weight kernel (rc_gemm_lds.hip)
+    if (lds_problem(c, rows)) { mr = 16; nc = 8; }
     p.n_tiles = n.H / (4 * nc); p.m_tiles = (rows + 16 * mr - 1) / (16 * mr); p.Kp = 2 * n.H; p.nc = nc; p.mr = mr;
     p.nt = (c->live_nt_mask >> s.net) & 1u;
     return p;
@@ -526,7 +532,7 @@ bool timing_pair(rc_ctx* ctx, hipEvent_t* a, hipEvent_t* b) {
 
 // The problems `ps` (LSTM layer steps; for the resident kernel also relu(linear1)) as ONE launch of the shared-weight kernel: longest items
 // first, every problem's item range padded to a multiple of 8; *items = work items (workgroups) of the launch, *tiles = slab tiles it uses.
-// resident_order: the linear1 items between the rnn4 / rnn6 items and those of the H = 512 nets (run_wave2_segment).
+// resident_order: the linear1 items between the rnn4 / rnn6 items and those of the H = 512 nets (build_resident_ticks).
 int build_lds_problems(rc_ctx* ctx, const std::vector<GemmProblem>& ps, const unsigned char* flags_override, float* slab, int* tickets,
                        LdsProblem* out, int max_p, int* items, size_t* tiles_out, bool resident_order = false) {
     std::vector<GemmProblem> ord(ps);
@@ -708,7 +714,7 @@ int launch_problems(rc_ctx* ctx, std::vector<GemmProblem> ps, const unsigned cha
             return launch_lds(ctx, lds, flags_override, st, stop, launched);
         }
     }
-    if ((int)ps.size() > RC_MAX_PROB) {        // (a regrouped tick of a mixed batch: linear1 + init_net + the few-row layer steps) two launches
+    if ((int)ps.size() > RC_MAX_PROB) {        // (a tri tick of a mixed batch: linear1 + init_net + the few-row layer steps) two launches
         std::vector<GemmProblem> head(ps.begin(), ps.begin() + RC_MAX_PROB), tail(ps.begin() + RC_MAX_PROB, ps.end());
         if (int rc = launch_problems(ctx, head, flags_override, st, fp32)) return rc;
         return launch_problems(ctx, tail, flags_override, st, fp32, stop, launched);
@@ -841,24 +847,28 @@ int flush_pending(rc_ctx* ctx, hipStream_t st) {
 // Stages of a frame in the wavefront engine below (stage s of the ring slot started at tick e runs at tick e + s):
 //   0 prep | 1 linear1{rnn2,rnn4} | 2,3 LSTM l0,l1 {rnn2,rnn4} | 4 linear2{rnn2,rnn4} then fuse |
 //   5 linear1{rnn6,rnn3,rnn7,rnn8} (+ init_net layer 0) | 6,7 LSTM l0,l1 (+ init_net layers 1, 2) | 8 linear2 then tail
-// linear2, fuse and tail are consecutive kernels of ONE tick on the second stream (a dependent chain of ~150 us beside the
-// ~245 us of wide launches), so a frame is 9 ticks deep, not 11 as in round 2.
-// Launch groups of a tick (kTick.group names round 2's four groups by TILE DURATION; w2_group merges them): G0 = {rnn6 l0, l1,
-// rnn4 l0, l1 + init_net} and G2 = {the H = 512 nets' eight layer steps + the six linear1} -- each a whole number of rounds of
-// equal tiles at batch 256 (rnn4 64 x 80, rnn6 and the H = 512 nets 64 x 128) -- and linear2 (16-row tiles, fp32-input kernel)
-// with the per-row kernels on a context-owned second stream. From RC_SPLIT_MAIN_MIN_BATCH rows G0 runs on the caller's stream and
-// G2 on a third stream, up to a tick ahead (run_wave2_segment); below that both on the caller's stream with the second stream's
-// hand-over in front of the last one. (Weight-streaming launches BESIDE the wide ones stretch those: linear1 rides in G2.)
+// linear2, fuse and tail are consecutive kernels of ONE tick on the second stream, so a frame is 9 ticks deep.
+// Launch groups of a tick: G_BIG = rnn6's and rnn4's layer steps (+ init_net), G_REST = the H = 512 nets' eight layer steps + the six
+// linear1 -- each a whole number of rounds of equal 64-row tiles at batch 256 -- and G_LIN2 = linear2 (16-row tiles, fp32-input kernel),
+// which runs with the per-row kernels prep / fuse / tail on a context-owned second stream. Three engines issue them (pick_wave_engine,
+// stream_tick; docs/DESIGN_HISTORY.md has the measurements behind each):
+//   plain (batch < RC_SPLIT_MAIN_MIN_BATCH: a tick is launch latency, every further stream adds hand-overs): G_BIG then G_REST on the
+//          caller's stream, the second stream's hand-over in front of G_REST (of G_BIG in a tick with init_net problems);
+//   split (from that batch, contexts not on the shared-weight kernel): G_BIG on the caller's stream, G_REST on wide2_stream, up to a tick ahead;
+//   tri   (contexts on the shared-weight kernel, lds_context): rnn4 | rnn6 | the H = 512 nets on the caller's stream | wide2_stream |
+//          wide3_stream, {linear1, init_net} at the head of the second stream's tick; rnn6 and init_net move from G_BIG to G_REST (w2_group).
+// On top of tri, rc_set_resident replaces the three layer-step streams by ONE launch per segment (run_resident_segment).
+// (Weight-streaming launches BESIDE the wide ones stretch those: linear1 rides in a wide launch.)
 enum { SEQ_STEPPED_TR = 0, SEQ_STEPPED = 1 };
 const int kRing = 16;
 
-struct TickStage { int kind; int net; int stage; int group; };   // kind: 0 linear1, 1 LSTM l0, 2 LSTM l1, 3 linear2
-// groups 0-3: wide tiles (linear1 rides in group 3; merged into G0 / G2 by w2_group); 5 (linear2): second stream (16-row tiles)
+enum { G_BIG = 0, G_REST = 1, G_LIN2 = 2 };
+struct TickStage { int kind; int net; int stage; int group; };   // kind: 0 linear1, 1 LSTM l0, 2 LSTM l1, 3 linear2; group: plain / split (tri: w2_group)
 const TickStage kTick[RC_TICK_PROB] = {
-    {1, N4, 2, 0}, {2, N4, 3, 0}, {1, N6, 6, 1}, {2, N6, 7, 1},
-    {1, N2, 2, 2}, {2, N2, 3, 2}, {1, N3, 6, 2}, {2, N3, 7, 2}, {1, N7, 6, 3}, {2, N7, 7, 3}, {1, N8, 6, 3}, {2, N8, 7, 3},
-    {0, N4, 1, 3}, {0, N2, 1, 3}, {0, N6, 5, 3}, {0, N3, 5, 3}, {0, N7, 5, 3}, {0, N8, 5, 3},
-    {3, N4, 4, 5}, {3, N2, 4, 5}, {3, N6, 8, 5}, {3, N3, 8, 5}, {3, N7, 8, 5}, {3, N8, 8, 5}};
+    {1, N4, 2, G_BIG}, {2, N4, 3, G_BIG}, {1, N6, 6, G_BIG}, {2, N6, 7, G_BIG},
+    {1, N2, 2, G_REST}, {2, N2, 3, G_REST}, {1, N3, 6, G_REST}, {2, N3, 7, G_REST}, {1, N7, 6, G_REST}, {2, N7, 7, G_REST}, {1, N8, 6, G_REST}, {2, N8, 7, G_REST},
+    {0, N4, 1, G_REST}, {0, N2, 1, G_REST}, {0, N6, 5, G_REST}, {0, N3, 5, G_REST}, {0, N7, 5, G_REST}, {0, N8, 5, G_REST},
+    {3, N4, 4, G_LIN2}, {3, N2, 4, G_LIN2}, {3, N6, 8, G_LIN2}, {3, N3, 8, G_LIN2}, {3, N7, 8, G_LIN2}, {3, N8, 8, G_LIN2}};
 const int kFuseStage = 4, kTailStage = 8, kInitStage = 5;
 
 int tune_env(const char* name, int dflt) {
@@ -885,11 +895,10 @@ void plan_sequence(const signed char* codes, int B, int T, const int* pend, bool
 }
 
 
-// ============================================================== per-row-cursor wavefront engine (round 3)
-// Round 2's engine skewed the stages only over stretches on which EVERY row saw the camera: the vision updater
-// (net/sig_mp.py:264-271) feeds the END of a frame (landmarks of the tail) back into rnn6 / rnn4, so a row's next camera step
-// has to wait for it -- and one occluded row stopped the batch. But rows are independent, so a row can
-// simply LAG the batch. Here every row has its own frame cursor:
+// ============================================================== per-row-cursor wavefront engine
+// The vision updater (net/sig_mp.py:264-271) feeds the END of a frame (landmarks of the tail) back into rnn6 / rnn4, so a row's next
+// camera step has to wait for it. Rows are independent, so such a row simply LAGS the batch: every row has its own
+// frame cursor.
 //   * tick k initialises ring slot k % 16: row r starts its next frame there, or nothing (a bubble) when that frame has to
 //     wait. The slot carries, per row, the frame index and the step number of every sub-net step the frame takes, so the stages
 //     of a row's frames can be in flight at different step counts while the row's counters move on;
@@ -904,7 +913,7 @@ void plan_sequence(const signed char* codes, int B, int T, const int* pend, bool
 //   * a step left pending by the frames before the segment rides slot 0; the last frame of the segment leaves its updater step
 //     pending in the context's own buffers, as the frame-stepped path does.
 // The host plans all of it from the regime codes of the pre-pass (plan_wave: pure host logic, exposed as rc_plan_wave) and
-// uploads one table, frame_at[tick][row]; per tick it launches only the problems that have rows, with tile shapes picked
+// uploads one table, frame_at[tick][row]; per tick it launches only the problems that have rows (collect), with tile shapes picked
 // from the exact row counts (ticks that only serve lagging rows stream the weights through 16/32-row tiles).
 // Arithmetic per row is that of the frame-stepped plan, operation for operation: outputs and states are bitwise equal.
 enum { W2_INIT0 = RC_TICK_PROB, W2_INIT1, W2_INIT2, W2_PROB };
@@ -1014,14 +1023,14 @@ static int ensure_wave2_buffers_once(rc_ctx* ctx) {
         if (int rc = dev_alloc(ctx, &ctx->x1_alt2[i], Bp * ctx->net[i].H)) return rc;
     }
     {
-        // RC_SEQ_H512_PRIO: queue priority of the third stream (-1 lowest, +1 highest, 0 default). With the shared-weight kernel the caller's
-        // stream carries the longest items of a tick (rnn4: the chain h(t) -> h(t + 1) is one item long); the third stream's are the filler.
+        // RC_SEQ_H512_PRIO: queue priority of wide2_stream (-1 lowest, +1 highest, 0 default). With the shared-weight kernel the caller's
+        // stream carries the longest items of a tick (rnn4: the chain h(t) -> h(t + 1) is one item long); the other streams' are the filler.
         const int want = tune_env("RC_SEQ_H512_PRIO", 0);
         int lo = 0, hi = 0;
         if (want != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
-            HIP_TRY(ctx, hipStreamCreateWithPriority(rc_out(ctx->h512_stream), hipStreamNonBlocking, want < 0 ? lo : hi));
+            HIP_TRY(ctx, hipStreamCreateWithPriority(rc_out(ctx->wide2_stream), hipStreamNonBlocking, want < 0 ? lo : hi));
         else
-            HIP_TRY(ctx, hipStreamCreateWithFlags(rc_out(ctx->h512_stream), hipStreamNonBlocking));
+            HIP_TRY(ctx, hipStreamCreateWithFlags(rc_out(ctx->wide2_stream), hipStreamNonBlocking));
     }
     {
         // RC_SEQ_AUX_PRIO: -1 lowest / +1 highest queue priority for the second stream (0: default) -- its short kernels share the
@@ -1033,15 +1042,15 @@ static int ensure_wave2_buffers_once(rc_ctx* ctx) {
         else
             HIP_TRY(ctx, hipStreamCreateWithFlags(rc_out(ctx->aux_stream), hipStreamNonBlocking));
     }
-    HIP_TRY(ctx, hipStreamCreateWithFlags(rc_out(ctx->lin1_stream), hipStreamNonBlocking));
+    HIP_TRY(ctx, hipStreamCreateWithFlags(rc_out(ctx->wide3_stream), hipStreamNonBlocking));
     for (int i = 0; i < 8; ++i) {
         // device-scope release: the hand-over is between two streams of this GPU
         const unsigned evf = hipEventDisableTiming | hipEventReleaseToDevice;
         HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_main[i]), evf));
         HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_aux[i]), evf));
-        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_h512[i]), evf));
-        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_lin1[i]), evf));
-        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_h5[i]), evf));
+        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_wide2[i]), evf));
+        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_head[i]), evf));
+        if (i < 4) HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->ev_wide3[i]), evf));
     }
     ctx->ring2_ready = true;
     ctx->wave2_valid = false;
@@ -1062,7 +1071,6 @@ int ensure_wave2_buffers(rc_ctx* ctx) {
 // GEMM problems of every ring slot: problem q (kTick order, then the three init_net layers) working on slot sl. Rows come from
 // the slot's flag bytes as in step_impl; tile shapes and row-tile counts are filled in per tick from the plan's row counts.
 int build_wave2_problems(rc_ctx* ctx) {
-    ctx->seq_two_streams = tune_env("RC_SEQ_STREAMS", 2) == 2;
     ctx->wave2_prob.assign((size_t)kRing * W2_PROB, GemmProblem{});
     const int B = ctx->B;
     for (int sl = 0; sl < kRing; ++sl) {
@@ -1098,23 +1106,35 @@ int build_wave2_problems(rc_ctx* ctx) {
     return RC_OK;
 }
 
-// stage and launch group of the problems beyond kTick (init_net layers: beside linear1 / LSTM l0 / l1 of the second half)
+// stage of problem q (beyond kTick the init_net layers: beside linear1 / LSTM l0 / l1 of the second half)
 inline int w2_stage(int q) { return q < RC_TICK_PROB ? kTick[q].stage : kInitStage + (q - W2_INIT0); }
-// merge_h512: the H = 512 nets' eight layer steps and the six linear1 share ONE launch (512 equal 64 x 128 tiles = two rounds, then
-// the linear1 tiles) instead of two launches of one round each; init_net then rides with rnn6
-// merge_big: rnn6's and rnn4's layer steps share one launch as well (rnn6's longer tiles first): two launches per tick.
-// Measured on one box (mixed 512 frames, body-frames/s): 4 launches 1.005 M, H = 512 merged 1.037 M, both merged 1.066 M;
-// 20-frame calls 0.890 -> 0.913 M (every launch boundary of a tick is a drain + ramp of all 256 CUs)
-// regroup (round 6, two-stream ticks): rnn6's two layer steps and the init_net layers ride the {H = 512 nets, linear1} stream, the caller's
-// stream keeps rnn4 alone. With the shared-weight kernel (rc_gemm_lds.hip) the items of a tick are 160 of 40 k-blocks (rnn4, K halved),
-// 128 of 32 (rnn6, K halved) and 128 of 32 (the H = 512 nets): {rnn4} is one round of the CUs on one stream, {rnn6, H = 512} one round
-// of equal items on the other, instead of 288 items (two rounds) behind the init_net launch on the caller's stream and a short launch
-// on the other (profiles/r06_timeline_lds_v1.txt). Race-free on the stream model: tests/test_wave_streams.py.
-inline int w2_group(int q, bool merge_h512, bool merge_big, bool regroup = false) {
-    if (regroup && merge_h512 && (q >= RC_TICK_PROB || (kTick[q].net == N6 && (kTick[q].kind == 1 || kTick[q].kind == 2)))) return 2;
-    int g = q >= RC_TICK_PROB ? (merge_h512 ? 1 : 2) : ((merge_h512 && kTick[q].group == 3) ? 2 : kTick[q].group);
-    if (merge_big && g == 1) g = 0;
-    return g;
+
+// Which engine issues the ticks of a context (the table in front of kTick says what each puts on which stream).
+enum WaveEngine { ENG_PLAIN, ENG_SPLIT, ENG_TRI };
+WaveEngine pick_wave_engine(const rc_ctx* c) {
+    if (c->B < RC_SPLIT_MAIN_MIN_BATCH) return ENG_PLAIN;
+    return lds_context(c) ? ENG_TRI : ENG_SPLIT;
+}
+// ... and whether the layer steps of a whole segment go out as ONE launch of the resident kernel (run_resident_segment)
+bool resident_segment(const rc_ctx* c, WaveEngine eng, const WavePlan& P) {
+    return eng == ENG_TRI && c->resident_on && c->B <= 256 && P.n_ticks > 0 && !(c->timing && c->timing_mode != 3);
+}
+// launch group of problem q: in the tri engine rnn6's layer steps and init_net leave the caller's stream to rnn4
+inline int w2_group(int q, bool tri) {
+    if (q >= RC_TICK_PROB) return tri ? G_REST : G_BIG;
+    return (tri && kTick[q].net == N6 && kTick[q].group == G_BIG) ? G_REST : kTick[q].group;
+}
+
+// 64-row tile shapes (16-row x 16-column blocks) of the wide launches: rnn4 | rnn6 | the H = 512 nets. One stream for both wide launches
+// (plain): rnn4 on 64 x 80 tiles, 256 per layer = whole rounds of the CUs; beside a launch on another stream the 64 x 128 tile's fewer
+// operand bytes per MFMA win.
+struct WaveTiles { int t4[2], t6[2], t5[2]; };
+WaveTiles wave_tiles(WaveEngine eng) {
+    WaveTiles t{{4, eng == ENG_PLAIN ? 5 : 8}, {4, 8}, {4, 8}};
+    tile_env("RC_SEQ_RNN4", &t.t4[0], &t.t4[1]);
+    tile_env("RC_SEQ_RNN6", &t.t6[0], &t.t6[1]);
+    tile_env("RC_SEQ_H512", &t.t5[0], &t.t5[1]);
+    return t;
 }
 
 // the plan's table frame_at [ticks][B], device + pinned (grow-only: the caller makes sure nothing in flight reads it)
@@ -1123,15 +1143,304 @@ int reserve_frame_at(rc_ctx* ctx, size_t need, size_t want) {
     return RC_OK;
 }
 
+// The problems of launch group g that have rows at tick k, with tile shapes picked from the exact row counts.
+std::vector<GemmProblem> collect(const rc_ctx* ctx, const WavePlan& P, WaveEngine eng, const WaveTiles& tiles, int k, int g) {
+    // rows of a problem from which it runs 64-row tiles (split products): a half-filled 64-row tile still halves the weight bytes of two 32-row tiles
+    static const int tile64_rows = tune_env("RC_SEQ_TILE64_ROWS", 33);
+    const int B = ctx->B;
+    std::vector<GemmProblem> ps;
+    for (int qi = 0; qi < W2_PROB; ++qi) {
+        const int q = qi < 4 ? (qi ^ 2) : qi;                                 // rnn6 (kTick 2, 3) in front of rnn4 (0, 1): longest tiles first
+        if (w2_group(q, eng == ENG_TRI) != g) continue;
+        const int e = k - w2_stage(q);
+        if (e < 0 || e >= P.n_prep) continue;
+        const int net = q < RC_TICK_PROB ? kTick[q].net : -1;
+        const int kind = q < RC_TICK_PROB ? kTick[q].kind : 4;                 // 4: init_net layer
+        const int riders = P.n_rider[e];
+        const int rows = kind == 4 ? P.n_reach[e] : ((net == N4 || net == N6) ? P.n_vis[e] + riders : P.n_valid[e]);
+        if (rows <= 0) continue;
+        GemmProblem p = ctx->wave2_prob[(size_t)(e % kRing) * W2_PROB + q];
+        if (kind == 0 || kind == 1) {                                          // relu(linear1) of the frame started at tick e: one of three buffers
+            float* x1 = e % 3 == 0 ? ctx->net[net].x1 : (e % 3 == 1 ? ctx->x1_alt[net] : ctx->x1_alt2[net]);
+            if (kind == 0) p.out = x1; else p.seg[0].base = x1;
+        }
+        if (kind == 1 || kind == 2) {
+            const NetDev& n = ctx->net[net];
+            int mr, nc;
+            if (lds_problem(ctx, rows)) {                                      // the shared-weight kernel (rc_gemm_lds.hip)
+                mr = 16; nc = 8;
+            } else if (ctx->gemm_split && rows >= tile64_rows) {               // (split products: the K loop is operand-bound, 64-row tiles)
+                const int* t = n.H == 512 ? tiles.t5 : (n.H == 1024 ? tiles.t6 : tiles.t4);
+                mr = t[0]; nc = t[1];
+            } else {
+                pick_tile(n.H, rows, &mr, &nc);
+            }
+            p.mr = mr; p.nc = nc; p.n_tiles = n.H / (4 * nc);
+        } else if (kind == 0 || kind == 4) {
+            if (rows <= 16) { p.mr = 1; p.nc = 1; p.n_tiles = (p.N + 15) / 16; }
+            else if (kind == 0 && ctx->gemm_split && rows >= tile64_rows) {
+                // linear1 rides in a wide launch behind its 256 LSTM tiles: as 544 tiles of 32 x 64 (K = 128 / 256: two k-blocks, i.e. all
+                // prologue and epilogue) it added two rounds, ~18 us of a 245 us tick; 136 tiles of 64 x 128 add one
+                const int np = round_up(p.N, 64);
+                if (np % 128 == 0) { p.mr = 4; p.nc = 8; p.n_tiles = np / 128; }
+            }
+        }
+        p.m_tiles = (rows + 16 * p.mr - 1) / (16 * p.mr);
+        if (rows == B && kind != 4) {                                          // every row: no compaction needed
+            p.flags = nullptr; p.flag_bit = 0;
+            if (riders == 0 && (net == N4 || net == N6) && P.n_vis[e] == B) {
+                p.alt_base = nullptr; p.sel_flags = nullptr; p.sel_bit = 0; p.out_flags = nullptr; p.out_bit = 0;
+            }
+        }
+        ps.push_back(p);
+    }
+    // Filling and draining ticks (and ticks of lagging rows) carry fewer problems per launch: when the launch would leave
+    // half of the CUs without a tile, the 64 x 128 tiles are cut to 64 x 64 (twice the tiles, half as long each).
+    if (g != G_LIN2) {
+        int total = 0;
+        for (const GemmProblem& p : ps) total += p.n_tiles * p.m_tiles;
+        if (total > 0 && total <= 128)
+            for (GemmProblem& p : ps)
+                if (p.epi == RC_EPI_LSTM && p.mr == 4 && p.nc == 8) { p.nc = 4; p.n_tiles *= 2; }
+    }
+    return ps;
+}
+
+struct WaveSeg {                               // one segment on the wavefront engine: what its ticks share
+    rc_ctx* ctx; const WavePlan& P; const FrameIO& io0; hipStream_t st, aux;          // caller's stream, second stream
+    WaveEngine eng; WaveTiles tiles; rc_params_dev prm; WavePrep wp; WaveTail wt;
+    int rows(const std::vector<int>& v, int tick) const { return tick >= 0 && tick < P.n_prep ? v[tick] : 0; }   // of the slot initialised at `tick`
+    std::vector<GemmProblem> group(int k, int g) const { return collect(ctx, P, eng, tiles, k, g); }
+};
+
+// prep of tick k on the second stream: initialises ring slot k % 16 (before the tick's tail, whose target slot it is)
+void wave_prep(WaveSeg& S, int k) {
+    if (k >= S.P.n_prep) return;
+    S.wp.frame_at = S.ctx->frame_at_d.get() + (size_t)k * S.ctx->B;
+    S.wp.first_tick = k == 0 ? 1 : 0;
+    rc_launch_prep_wave(S.ctx->ring2[k % kRing], S.io0, S.prm, S.ctx->B, S.wp, S.aux);
+}
+
+// linear2 of stages 4 and 8 on the second stream (fp32-input kernel, as in run_stage), then their consumers fuse and tail -- ONE launch where
+// `merge` allows and both have rows. `signal` (may be null) rides on the last kernel where there is a tail and is recorded behind the chain otherwise.
+int wave_lin2_fuse_tail(WaveSeg& S, int k, bool merge, hipEvent_t signal) {
+    rc_ctx* ctx = S.ctx;
+    const int B = ctx->B;
+    if (int rc = launch_problems(ctx, S.group(k, G_LIN2), nullptr, S.aux, true)) return rc;
+    const bool fuse = S.rows(S.P.n_valid, k - kFuseStage) > 0, tail = S.rows(S.P.n_valid, k - kTailStage) > 0;
+    bool merged = false, carried = false;
+    if (tail) {
+        const FrameBuffers& tgt = ctx->ring2[k % kRing];
+        S.wt.x4l = tgt.x4l; S.wt.x6l = tgt.x6l; S.wt.flags2 = tgt.flags2; S.wt.wsteps = tgt.wsteps;
+    }
+    if (merge && fuse && tail)
+        merged = carried = rc_launch_fuse_tail(ctx->ring2[(k - kTailStage) % kRing], ctx->ring2[(k - kFuseStage) % kRing], S.io0, S.prm, ctx->body, B, S.wt, S.aux, signal);
+    if (!merged && fuse) rc_launch_fuse(ctx->ring2[(k - kFuseStage) % kRing], S.io0, S.prm, B, S.aux);
+    if (!merged && tail) {
+        rc_launch_tail(ctx->ring2[(k - kTailStage) % kRing], S.io0, S.prm, ctx->body, B, 0, S.aux, nullptr, &S.wt, signal);
+        carried = true;
+    }
+    if (signal && !carried) HIP_TRY(ctx, hipEventRecord(signal, S.aux));
+    return RC_OK;
+}
+
+inline int wave_wait(rc_ctx* ctx, int k, hipStream_t s, std::initializer_list<hipEvent_t> waits) {   // events of tick k - 1: tick 0 has none; null = none
+    if (k > 0) for (hipEvent_t w : waits) if (w) HIP_TRY(ctx, hipStreamWaitEvent(s, w, 0));
+    return RC_OK;
+}
+
+// One wide launch of tick k: the problems `ps` on stream s behind `waits`. `signal` rides on the launch itself where one goes out
+// (launch_problems) and is recorded behind it otherwise.
+int wave_issue(rc_ctx* ctx, int k, hipStream_t s, std::initializer_list<hipEvent_t> waits, const std::vector<GemmProblem>& ps, hipEvent_t signal) {
+    if (int rc = wave_wait(ctx, k, s, waits)) return rc;
+    bool carried = false;
+    if (int rc = launch_problems(ctx, ps, nullptr, s, false, signal, &carried)) return rc;
+    if (signal && !carried) HIP_TRY(ctx, hipEventRecord(signal, s));
+    return RC_OK;
+}
+
+// Tick k of the three stream engines. Events with index e belong to this tick, with ep to the previous one; each line reads
+// stream <- {what it waits for}, what it launches, what it signals. tests/test_wave_streams.py models exactly these edges.
+int stream_tick(WaveSeg& S, int k) {
+    rc_ctx* ctx = S.ctx;
+    const int e = k & 3, ep = (k + 3) & 3;
+    hipStream_t st = S.st, aux = S.aux, w2 = ctx->wide2_stream.get(), w3 = ctx->wide3_stream.get();
+    hipEvent_t main_p = ctx->ev_main[ep].get(), aux_p = ctx->ev_aux[ep].get(), w2_p = ctx->ev_wide2[ep].get(), w3_p = ctx->ev_wide3[ep].get(),
+               head_p = ctx->ev_head[ep].get();
+    hipEvent_t main_e = ctx->ev_main[e].get(), aux_e = ctx->ev_aux[e].get(), w2_e = ctx->ev_wide2[e].get(), w3_e = ctx->ev_wide3[e].get(),
+               head_e = ctx->ev_head[e].get();
+    bool init_now = false;                                                     // init_net problems in this tick
+    for (int q = W2_INIT0; q < W2_PROB; ++q) init_now = init_now || S.rows(S.P.n_reach, k - w2_stage(q)) > 0;
+    if (S.eng == ENG_TRI) {
+        // {linear1, init_net} read what the second stream wrote in tick k - 1 and nothing else: the head of its tick. prep reads no layer
+        // step either: in front of the waits. Then each net's chain h(t) -> h(t + 1) on a stream of its own, behind the previous linear1.
+        std::vector<GemmProblem> l1, rnn6, h512;
+        for (const GemmProblem& p : S.group(k, G_REST)) (p.epi != RC_EPI_LSTM ? l1 : (p.H == 1024 ? rnn6 : h512)).push_back(p);
+        if (int rc = wave_issue(ctx, k, aux, {}, l1, head_e)) return rc;
+        wave_prep(S, k);
+        if (int rc = wave_wait(ctx, k, aux, {w3_p, main_p, w2_p})) return rc;
+        if (int rc = wave_lin2_fuse_tail(S, k, true, aux_e)) return rc;
+        if (int rc = wave_issue(ctx, k, w2, {head_p}, rnn6, w2_e)) return rc;
+        // The H = 512 nets NEED linear1(k - 1) like the other two, and the END of the second stream's previous tick only behind an init_net
+        // state write of its tail (rnn2 l0): RC_SEQ_H5_EARLY=1 issues exactly that (the edges tests/test_wave_streams.py models) and is
+        // slower -- the three layer-step launches do better in step with each other (profiles/r06_resident_notes.txt). Default: the end, always.
+        static const int h5_early = tune_env("RC_SEQ_H5_EARLY", 0);
+        const bool early = h5_early && S.rows(S.P.n_reach, k - 1 - kTailStage) == 0;
+        if (int rc = wave_issue(ctx, k, w3, {early ? head_p : aux_p}, h512, w3_e)) return rc;
+        if (int rc = wave_issue(ctx, k, st, {head_p}, S.group(k, G_BIG), main_e)) return rc;
+    } else if (S.eng == ENG_SPLIT) {
+        // {H = 512 nets, linear1} only needs the second stream's previous tick and its own predecessor, {rnn6, rnn4} only the previous
+        // linear1 (init_net also the previous fuse): the former runs up to a tick ahead and fills the CUs the latter's last round leaves idle
+        if (int rc = wave_wait(ctx, k, aux, {main_p, w2_p})) return rc;
+        wave_prep(S, k);
+        if (int rc = wave_lin2_fuse_tail(S, k, false, aux_e)) return rc;
+        if (int rc = wave_issue(ctx, k, w2, {aux_p}, S.group(k, G_REST), w2_e)) return rc;
+        if (int rc = wave_issue(ctx, k, st, {w2_p, init_now ? aux_p : nullptr}, S.group(k, G_BIG), main_e)) return rc;
+    } else {
+        // Both wide launches on the caller's stream. Only linear1 and init_net READ what the second stream wrote in the previous tick: the
+        // wait stands in front of the launch that holds them, and {rnn6, rnn4} follows the previous tick without a barrier packet
+        // (legal with the third copy of the hidden state, RC_HBUF: it WRITES h where linear2 of the previous tick still reads)
+        if (int rc = wave_wait(ctx, k, aux, {main_p})) return rc;
+        wave_prep(S, k);
+        if (int rc = wave_lin2_fuse_tail(S, k, false, aux_e)) return rc;
+        if (int rc = wave_issue(ctx, k, st, {init_now ? aux_p : nullptr}, S.group(k, G_BIG), nullptr)) return rc;
+        if (int rc = wave_issue(ctx, k, st, {init_now ? nullptr : aux_p}, S.group(k, G_REST), main_e)) return rc;
+    }
+    ctx->stat_ticks += 1;
+    return RC_OK;
+}
+
+// ---- resident layer-step kernel ----------------------------------------------------------------------------------------------------
+// On streams, a tick's layer steps are launches: every launch ends in a drain of the CUs it held, starts behind an event, and its
+// workgroups queue for CUs against the other streams' (profiles/r06_lds_kernel_notes.txt, r06_timeline_tri_high.txt). Here ONE launch
+// carries the layer steps of the whole segment (rc_gemm_lds.hip: rc_gemm_resident_kernel): its workgroups take items tick after tick from
+// a queue in device memory, ordered by counters instead of events, and leave the other CUs to the second stream, whose chain [init_net] ->
+// prep -> [all items of the previous tick] -> linear2 -> fuse -> tail talks to the layer steps through one flag and one counter per tick.
+// Same items, same arithmetic: bitwise the streams' result.
+struct ResidentWords { int *item_base, *done, *tick_done, *words; };           // res_ints_d; words: head, (unused), flag_tail, abort
+
+// The table: per tick its layer steps AND its linear1 problems as items (as launches on the CUs the resident kernel leaves they took 86-197 us
+// of every tick, profiles/r06_timeline_resident_l1_*.txt), slab region = tick % 4 (a tick starts behind every item of the tick before the
+// previous one), and what each problem reads of the previous tick. init_net's layers stay launches of the second stream: init_l[tick].
+int build_resident_ticks(WaveSeg& S, std::vector<std::vector<GemmProblem>>& init_l) {
+    rc_ctx* ctx = S.ctx;
+    int run = 0;
+    for (int k = 0; k < S.P.n_ticks; ++k) {
+        std::vector<GemmProblem> ls;
+        for (int g : {G_BIG, G_REST})
+            for (GemmProblem& p : S.group(k, g)) {
+                if (p.epi == RC_EPI_LSTM) { p.mr = 16; p.nc = 8; }
+                else if (p.epi == RC_EPI_RELU && p.out_packed && p.N % 128 == 0 && p.Kp % 128 == 0 && p.out_bit == 0 && p.out_col0 == 0 && p.seg[0].par_mode == 0 &&
+                         p.out != ctx->hid1 && p.out != ctx->hid2) { }
+                else { init_l[k].push_back(p); continue; }
+                p.m_tiles = 1;                                                 // (B <= 256: one row tile, whatever the tick's row count)
+                ls.push_back(p);
+            }
+        ResidentTick& T = ctx->res_ticks_h[k];
+        const size_t region = (size_t)(k & 3);
+        size_t tiles = 0;
+        T.B = ctx->B;
+        T.n = build_lds_problems(ctx, ls, nullptr, ctx->lds_slab.get() + region * ctx->lds_region_tiles * RC_LDS_SLAB_FLOATS,
+                                 ctx->lds_tickets.get() + region * ctx->lds_region_tiles, T.p, RC_RES_MAXP, &T.n_items, &tiles, true);
+        if (T.n != (int)ls.size()) return fail(ctx, RC_ERR_INVALID, "resident engine: more problems in a tick than its table holds");
+        if (tiles > ctx->lds_region_tiles) return fail(ctx, RC_ERR_INVALID, "resident engine: more tiles in a tick than a slab region holds");
+        const bool tail_wrote = S.rows(S.P.n_reach, k - 1 - kTailStage) > 0;
+        for (int i = 0; i < RC_RES_MAXP; ++i) {
+            T.dep[i][0] = T.dep[i][1] = -1; T.dep_items[i][0] = T.dep_items[i][1] = 0;
+            T.need_tail[i] = 0;
+            if (i >= T.n) continue;
+            const bool lstm = T.p[i].epi == RC_EPI_LSTM;
+            T.need_tail[i] = lstm ? ((tail_wrote && T.p[i].H == 512) ? 1 : 0) : 1;
+            if (k == 0 || !lstm) continue;
+            const ResidentTick& Tp = ctx->res_ticks_h[k - 1];
+            for (int j = 0; j < Tp.n; ++j) {
+                const int items_j = (j + 1 < Tp.n ? Tp.p[j + 1].wg_base : Tp.n_items) - Tp.p[j].wg_base;
+                const bool lstm_j = Tp.p[j].epi == RC_EPI_LSTM;
+                if (lstm_j && Tp.p[j].hstate == T.p[i].hstate) { T.dep[i][0] = j; T.dep_items[i][0] = items_j; }                           // its own h(t - 1), c
+                if ((const float*)(lstm_j ? Tp.p[j].hstate : Tp.p[j].out) == T.p[i].seg[0].base) { T.dep[i][1] = j; T.dep_items[i][1] = items_j; }   // layer 0's h | relu(linear1)
+            }
+        }
+        ctx->res_base_h[k] = run;
+        run += T.n_items;
+    }
+    ctx->res_base_h[S.P.n_ticks] = run;
+    return RC_OK;
+}
+
+int run_resident_segment(WaveSeg& S) {
+    rc_ctx* ctx = S.ctx;
+    hipStream_t st = S.st, aux = S.aux;
+    const int res_wgs = std::min(240, std::max(8, ctx->resident_wgs));
+    if (int rc = ensure_lds_pool(ctx)) return rc;
+    if (!ctx->res_abort_h) {                                                  // (read by the next rc_sequence call: kept until rc_destroy)
+        HIP_TRY(ctx, rc_alloc(ctx->res_abort_h, 1));
+        ctx->res_abort_h[0] = 0;
+    }
+    const size_t nt = (size_t)S.P.n_ticks;
+    if (nt > ctx->res_cap) {
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        const size_t cap = nt + nt / 4 + 64;
+        HIP_TRY(ctx, rc_grow(ctx->res_cap, nt, cap, ctx->res_ticks_d, cap, ctx->res_ticks_h, cap,
+                             ctx->res_ints_d, cap * (RC_RES_MAXP + 2) + 1 + 4 + 16, ctx->res_base_h, cap + 1));   // (+ 16: the sums of a -DRC_RES_PROF build)
+    }
+    const size_t cap = ctx->res_cap;
+    ResidentWords W{};
+    W.item_base = ctx->res_ints_d.get(); W.done = W.item_base + cap + 1; W.tick_done = W.done + cap * RC_RES_MAXP; W.words = W.tick_done + cap;
+    std::vector<std::vector<GemmProblem>> init_l(nt);
+    if (int rc = build_resident_ticks(S, init_l)) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->res_ticks_d.get(), ctx->res_ticks_h.get(), nt * sizeof(ResidentTick), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(W.item_base, ctx->res_base_h.get(), (nt + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(W.done, 0, (cap * (RC_RES_MAXP + 1) + 4 + 16) * sizeof(int), st));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_main[6].get(), st));
+    HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_main[6].get(), 0));
+    ResidentArgs R{};
+    R.ticks = ctx->res_ticks_d.get(); R.item_base = W.item_base; R.n_ticks = S.P.n_ticks;
+    R.head = W.words; R.done = W.done; R.tick_done = W.tick_done;
+    R.flag_tail = W.words + 2; R.abort = W.words + 3;
+    R.spin_bound = (unsigned long long)std::max(1, tune_env("RC_SEQ_RESIDENT_BOUND_MS", 2000)) * 100000ull;   // wall_clock64: 100 MHz
+    {
+        hipEvent_t ta = nullptr, tb = nullptr;
+        if (ctx->timing && !timing_pair(ctx, &ta, &tb)) return fail(ctx, RC_ERR_HIP, "hipEventCreate");
+        if (ta) HIP_TRY(ctx, hipEventRecord(ta, st));
+        rc_launch_gemm_resident(R, res_wgs, st);
+        if (tb) HIP_TRY(ctx, hipEventRecord(tb, st));
+    }
+    ctx->stat_lds_launches += 1;
+    // second stream, tick k: [init_net] -> prep -> [every item of tick k - 1] -> linear2 -> fuse -> tail -> flag_tail = k + 1
+    for (int k = 0; k < S.P.n_ticks; ++k) {
+        if (int rc = launch_problems(ctx, init_l[k], nullptr, aux, false)) return rc;
+        wave_prep(S, k);
+        if (k > 0) rc_launch_flag_wait(W.tick_done + (k - 1), ctx->res_ticks_h[k - 1].n_items, W.words + 3, R.spin_bound, aux);
+        if (int rc = wave_lin2_fuse_tail(S, k, false, nullptr)) return rc;
+        rc_launch_flag_set(W.words + 2, k + 1, aux);
+        ctx->stat_ticks += 1;
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[0].get(), aux));
+    HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[0].get(), 0));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->res_abort_h.get(), W.words + 3, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipGetLastError());
+#ifdef RC_RES_PROF
+    {   // profiling builds (tools/probe_resprof.so): where the resident workgroups' time went, per item
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        unsigned long long ph[5];
+        const unsigned long long* pd = (const unsigned long long*)(((unsigned long long)(W.words + 4) + 7ull) & ~7ull);
+        if (hipMemcpy(ph, pd, sizeof(ph), hipMemcpyDeviceToHost) == hipSuccess && ph[2] > 0)
+            std::fprintf(stderr, "[res prof] %d ticks, %llu items on %d workgroups; per item: wait %.2f us, item %.2f us, release %.2f us, take %.2f us; per workgroup %.2f ms\n",
+                         S.P.n_ticks, ph[2], res_wgs, ph[0] / 100.0 / ph[2], ph[1] / 100.0 / ph[2], ph[3] / 100.0 / ph[2], ph[4] / 100.0 / ph[2],
+                         (ph[0] + ph[1] + ph[3] + ph[4]) / 100.0 / 1000.0 / res_wgs);
+    }
+#endif
+    ctx->stat_resident_segments += 1;
+    return RC_OK;
+}
+
+// Frames t0 .. t_last of a rc_sequence call on the wavefront engine: upload the plan's table, let the engine's streams join the caller's,
+// issue every tick (or the resident segment), and let the caller's stream wait for the last tick of every other stream.
 int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0, int t_last, hipStream_t st) {
     if (int rc = ensure_wave2_buffers(ctx)) return rc;
     if (!ctx->wave2_valid) if (int rc = build_wave2_problems(ctx)) return rc;
     const int B = ctx->B;
-    const rc_params_dev prm = dev_params(ctx->prm);
-    const bool two = ctx->seq_two_streams;
-    hipStream_t aux = two ? ctx->aux_stream.get() : st;
-    // the plan's table: frame every row starts at every tick
-    const size_t need = (size_t)P.n_prep * B;
+    const size_t need = (size_t)P.n_prep * B;                                  // the plan's table: frame every row starts at every tick
     if (need > ctx->frame_at_cap) {
         HIP_TRY(ctx, hipDeviceSynchronize());                               // nothing in flight (on any of the engine's streams) may still read the old table
         if (int rc = reserve_frame_at(ctx, need, need + need / 4 + 4096)) return rc;
@@ -1139,405 +1448,34 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
     std::memcpy(ctx->frame_at_h.get(), P.frame_at.data(), need * sizeof(int));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->frame_at_d.get(), ctx->frame_at_h.get(), need * sizeof(int), hipMemcpyHostToDevice, st));
 
-    static const bool narrow_fill = tune_env("RC_SEQ_NARROW_FILL", 1) != 0;
-    static const bool lin1_wide = tune_env("RC_SEQ_LIN1_WIDE", 1) != 0;
-    static const bool merge_h512 = tune_env("RC_SEQ_MERGE_H512", 1) != 0;
-    static const bool merge_big = tune_env("RC_SEQ_MERGE_BIG", 1) != 0;
-    const int last_group = merge_h512 ? 2 : 3;
-    static const bool late_wait = tune_env("RC_SEQ_LATE_WAIT", 1) != 0;
-    static const bool merge_fill = tune_env("RC_SEQ_MERGE_FILL", 0) != 0;    // measured: 20-frame calls 907-914k with, 918-925k without
-    auto cnt = [&](const std::vector<int>& v, int tick) { return tick >= 0 && tick < P.n_prep ? v[tick] : 0; };
-    static const bool ext_events = tune_env("RC_SEQ_EXT_EVENTS", 1) != 0;   // tick hand-over events carried by the last dispatch itself (+0.5 %)
-    // The two wide launches of a tick on two streams: {H = 512 nets, linear1} only needs the second stream's work of the previous tick
-    // and its own predecessor, {rnn6, rnn4} only the previous linear1 -- so the former may run up to a tick ahead, its tiles filling
-    // the CUs the latter's last round leaves idle, and no launch waits behind the drain of the other (a 6-7 us gap each, on one stream)
-    // Measured (same box, body-frames/s, one stream vs two): batch 256 mixed 980k -> 1,031k, all-visible 1,204k -> 1,264k, 20-frame
-    // calls 862k -> 917k, fp32 MFMA 662k -> 725k, batch 1024 970k -> 1,012k, 128: 613k -> 631k, 64: 398k -> 418k; batch 32: 329k ->
-    // 299k, 16: 214k -> 178k (a tick there is launch latency, and a third stream adds two hand-overs to it): from 48 rows.
-    static const int split_main_env = tune_env("RC_SEQ_SPLIT_MAIN", -1);      // 0 / 1 force, default: by batch
-    const bool split_main = (split_main_env < 0 ? B >= RC_SPLIT_MAIN_MIN_BATCH : split_main_env != 0) && two && merge_h512 &&
-                            merge_big && !merge_fill && ext_events;
-    hipStream_t s2 = ctx->h512_stream.get(), s4 = ctx->lin1_stream.get();
-    static const int regroup_env = tune_env("RC_SEQ_REGROUP", 1);
-    static const int lin1_env = tune_env("RC_SEQ_LIN1_STREAM", 1);
-    const bool regroup = split_main && regroup_env != 0 && ctx->gemm_split && ctx->lds_min_rows > 0 && B >= ctx->lds_min_batch;   // (with the shared-weight kernel only)
-    const bool lin1_own = regroup && lin1_env != 0;
-    // tri: THREE streams of layer steps -- rnn4 | rnn6 | the H = 512 nets -- and {linear1, init_net} at the head of the second stream's
-    // tick. Each net's chain h(t) -> h(t + 1) then follows its own predecessor only; the drain of one launch is filled by the other two.
-    static const int tri_env = tune_env("RC_SEQ_TRI", 1);
-    const bool tri = lin1_own && tri_env != 0;
-    static const int tri_swap_env = tune_env("RC_SEQ_TRI_SWAP", 0);
-    const bool tri_swap = tri && tri_swap_env != 0;
-    // prep in front of the second stream's waits for the layer steps (it reads none of them): all-visible 256 frames 1,374k -> 1,399k
-    static const int prep_early = tune_env("RC_SEQ_PREP_EARLY", 1);
-    // 64-row tile shapes of the wide launches. With both launches of a tick on one stream rnn4 ran best on 64 x 80 tiles (256 tiles
-    // per layer = whole rounds of the 256 CUs); on two streams the other launch fills what a round leaves idle and the 64 x 128 tile's
-    // 13 % fewer operand bytes per MFMA win: mixed 512 frames 1,030k -> 1,120k, all-visible 1,208k -> 1,258k, batch 1024 999k -> 1,088k
-    int t4[2] = {4, split_main ? 8 : 5}, t6[2] = {4, 8}, t5[2] = {4, 8};
-    tile_env("RC_SEQ_RNN4", &t4[0], &t4[1]);
-    tile_env("RC_SEQ_RNN6", &t6[0], &t6[1]);
-    tile_env("RC_SEQ_H512", &t5[0], &t5[1]);
-    // rows of a problem from which it runs 64-row tiles (split products). 128 until the ticks ran on two streams; measured then, 128 ->
-    // 64 -> 33 rows: batch 80 486k -> 519k -> 541k body-frames/s, batch 128 638k -> 773k -> 787k (the rnn4 / rnn6 problems of a mixed
-    // batch have 60-127 rows), batch 256 and 1024 unchanged: a half-filled 64-row tile still halves the weight bytes of two 32-row tiles
-    static const int tile64_rows = tune_env("RC_SEQ_TILE64_ROWS", 33);
-    auto collect = [&](int k, int g, bool allow_narrow = true) -> std::vector<GemmProblem> {   // problems of group g with rows at tick k
-        std::vector<GemmProblem> ps;
-        for (int qi = 0; qi < W2_PROB; ++qi) {
-            const int q = (merge_big && qi < 4) ? (qi ^ 2) : qi;               // rnn6 (kTick 2, 3) in front of rnn4 (0, 1): longest tiles first
-            if (w2_group(q, merge_h512, merge_big, regroup) != g) continue;
-            const int e = k - w2_stage(q);
-            if (e < 0 || e >= P.n_prep) continue;
-            const int net = q < RC_TICK_PROB ? kTick[q].net : -1;
-            const int kind = q < RC_TICK_PROB ? kTick[q].kind : 4;                 // 4: init_net layer
-            const int riders = P.n_rider[e];
-            const int rows = kind == 4 ? P.n_reach[e] : ((net == N4 || net == N6) ? P.n_vis[e] + riders : P.n_valid[e]);
-            if (rows <= 0) continue;
-            GemmProblem p = ctx->wave2_prob[(size_t)(e % kRing) * W2_PROB + q];
-            if (kind == 0 || kind == 1) {                                      // relu(linear1) of the frame started at tick e: one of three buffers
-                float* x1 = e % 3 == 0 ? ctx->net[net].x1 : (e % 3 == 1 ? ctx->x1_alt[net] : ctx->x1_alt2[net]);
-                if (kind == 0) p.out = x1; else p.seg[0].base = x1;
+    const WaveEngine eng = pick_wave_engine(ctx);
+    WaveSeg S{ctx, P, io0, st, ctx->aux_stream.get(), eng, wave_tiles(eng), dev_params(ctx->prm), WavePrep{}, WaveTail{}};
+    for (int i = 0; i < 6; ++i) S.wp.steps[i] = ctx->net[i].steps;
+    S.wp.cx4l = ctx->fb.x4l; S.wp.cx6l = ctx->fb.x6l;
+    S.wt.on = 1; S.wt.t_last = t_last;
+    S.wt.steps4 = ctx->net[N4].steps; S.wt.steps6 = ctx->net[N6].steps;
+    S.wt.cx4l = ctx->fb.x4l; S.wt.cx6l = ctx->fb.x6l;
+    hipStream_t w2 = ctx->wide2_stream.get(), w3 = ctx->wide3_stream.get();
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_main[7].get(), st));                    // the engine's streams join (also: the table upload)
+    HIP_TRY(ctx, hipStreamWaitEvent(S.aux, ctx->ev_main[7].get(), 0));
+    if (eng != ENG_PLAIN) HIP_TRY(ctx, hipStreamWaitEvent(w2, ctx->ev_main[7].get(), 0));
+    if (eng == ENG_TRI) HIP_TRY(ctx, hipStreamWaitEvent(w3, ctx->ev_main[7].get(), 0));
+    if (resident_segment(ctx, eng, P)) {
+        if (int rc = run_resident_segment(S)) return rc;
+    } else {
+        for (int k = 0; k < P.n_ticks; ++k) if (int rc = stream_tick(S, k)) return rc;
+        const int last = (P.n_ticks - 1) & 3;
+        if (P.n_ticks > 0) {
+            HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[last].get(), 0));
+            if (eng != ENG_PLAIN) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_wide2[last].get(), 0));
+            if (eng == ENG_TRI) {
+                HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_head[last].get(), 0));
+                HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_wide3[last].get(), 0));
+                HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_main[last].get(), 0));
             }
-            if (kind == 1 || kind == 2) {
-                const NetDev& n = ctx->net[net];
-                int mr, nc;
-                if (ctx->gemm_split && ctx->lds_min_rows > 0 && B >= ctx->lds_min_batch && rows >= ctx->lds_min_rows) {   // the shared-weight kernel (rc_gemm_lds.hip)
-                    mr = 16; nc = 8;
-                } else if (ctx->gemm_split && rows >= tile64_rows) {           // (split products: the K loop is operand-bound, 64-row tiles)
-                    const int* t = n.H == 512 ? t5 : (n.H == 1024 ? t6 : t4);
-                    mr = t[0]; nc = t[1];
-                } else {
-                    pick_tile(n.H, rows, &mr, &nc);
-                }
-                p.mr = mr; p.nc = nc; p.n_tiles = n.H / (4 * nc);
-            } else if (kind == 0 || kind == 4) {
-                if (rows <= 16) { p.mr = 1; p.nc = 1; p.n_tiles = (p.N + 15) / 16; }
-                else if (kind == 0 && lin1_wide && ctx->gemm_split && rows >= tile64_rows) {
-                    // linear1 rides in the last wide launch behind its 256 LSTM tiles: as 544 tiles of 32 x 64 (K = 128 / 256: two
-                    // k-blocks, i.e. all prologue and epilogue) it added two rounds, ~18 us of a 245 us tick; 136 tiles of 64 x 128 add one
-                    const int np = round_up(p.N, 64);
-                    if (np % 128 == 0) { p.mr = 4; p.nc = 8; p.n_tiles = np / 128; }
-                }
-            }
-            p.m_tiles = (rows + 16 * p.mr - 1) / (16 * p.mr);
-            if (rows == B && kind != 4) {                                      // every row: no compaction needed
-                p.flags = nullptr; p.flag_bit = 0;
-                if (riders == 0 && (net == N4 || net == N6) && P.n_vis[e] == B) {
-                    p.alt_base = nullptr; p.sel_flags = nullptr; p.sel_bit = 0; p.out_flags = nullptr; p.out_bit = 0;
-                }
-            }
-            ps.push_back(p);
         }
-        // Filling and draining ticks (and ticks of lagging rows) carry fewer problems per launch: when the launch would leave
-        // half of the CUs without a tile, the 64 x 128 tiles are cut to 64 x 64 (twice the tiles, half as long each).
-        if (g < 4 && narrow_fill && allow_narrow) {
-            int total = 0;
-            for (const GemmProblem& p : ps) total += p.n_tiles * p.m_tiles;
-            if (total > 0 && total <= 128)
-                for (GemmProblem& p : ps)
-                    if (p.epi == RC_EPI_LSTM && p.mr == 4 && p.nc == 8) { p.nc = 4; p.n_tiles *= 2; }
-        }
-        return ps;
-    };
-    auto group = [&](int k, int g, hipStream_t s, hipEvent_t stop = nullptr, bool* launched = nullptr) -> int {
-        return launch_problems(ctx, collect(k, g), nullptr, s, g == 5, stop, launched);   // linear2 on the fp32-input kernel, as in run_stage
-    };
-    WavePrep wp{};
-    for (int i = 0; i < 6; ++i) wp.steps[i] = ctx->net[i].steps;
-    wp.cx4l = ctx->fb.x4l; wp.cx6l = ctx->fb.x6l;
-    WaveTail wt{};
-    wt.on = 1; wt.t_last = t_last;
-    wt.steps4 = ctx->net[N4].steps; wt.steps6 = ctx->net[N6].steps;
-    wt.cx4l = ctx->fb.x4l; wt.cx6l = ctx->fb.x6l;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_main[7].get(), st));                    // the second stream joins (also: the table upload)
-    if (two) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_main[7].get(), 0));
-    if (split_main) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_main[7].get(), 0));
-    if (lin1_own) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_main[7].get(), 0));
-    // ---- resident layer-step kernel ------------------------------------------------------------------------------------------------
-    // On streams, a tick's layer steps are launches: every launch ends in a drain of the CUs it held, starts behind an event, and its
-    // workgroups queue for CUs against the other streams' (one shared-weight workgroup holds a CU): the CUs hold an item 70-76 % of the
-    // time (profiles/r06_lds_kernel_notes.txt), and the second stream's short kernels wait for a CU at every launch of their chain
-    // (profiles/r06_timeline_tri_high.txt). Here ONE launch of `res_wgs` workgroups carries the layer steps of the whole segment
-    // (rc_gemm_lds.hip: rc_gemm_resident_kernel): its workgroups take items tick after tick from a queue in device memory, ordered by
-    // counters instead of events, and leave 256 - res_wgs CUs to the second stream, whose chain linear1 -> prep -> [all layer steps of
-    // the previous tick] -> linear2 -> fuse -> tail now talks to the layer steps through two flags and one counter per tick.
-    // Same items, same arithmetic: bitwise the streams' result.
-    const int res_wgs = std::min(240, std::max(8, ctx->resident_wgs));
-    const bool resident = tri && ctx->resident_on && B <= 256 && P.n_ticks > 0 && !(ctx->timing && ctx->timing_mode != 3);
-    if (resident) {
-        if (int rc = ensure_lds_pool(ctx)) return rc;
-        if (!ctx->res_abort_h) {                                              // (read by the next rc_sequence call: kept until rc_destroy)
-            HIP_TRY(ctx, rc_alloc(ctx->res_abort_h, 1));
-            ctx->res_abort_h[0] = 0;
-        }
-        const size_t nt = (size_t)P.n_ticks;
-        if (nt > ctx->res_cap) {
-            HIP_TRY(ctx, hipDeviceSynchronize());
-            const size_t cap = nt + nt / 4 + 64;
-            HIP_TRY(ctx, rc_grow(ctx->res_cap, nt, cap, ctx->res_ticks_d, cap, ctx->res_ticks_h, cap,
-                                 ctx->res_ints_d, cap * (RC_RES_MAXP + 2) + 1 + 4 + 16, ctx->res_base_h, cap + 1));   // (+ 16: the sums of a -DRC_RES_PROF build)
-        }
-        const size_t cap = ctx->res_cap;
-        int* item_base_d = ctx->res_ints_d.get();
-        int* done_d = item_base_d + cap + 1;
-        int* tick_done_d = done_d + cap * RC_RES_MAXP;
-        int* words_d = tick_done_d + cap;                                    // head, (unused), flag_tail, abort
-        // The table: per tick its layer steps AND its linear1 problems as items (linear1 as its own launches on the 32 CUs the resident
-        // kernel leaves took 86-197 us of every tick, profiles/r06_timeline_resident_l1_*.txt; as items they are 34 of ~580 per tick),
-        // slab region = tick % 4 (a tick starts behind every item of the tick before the previous one), and what each problem reads of
-        // the previous tick. init_net's three layers stay launches of the second stream (a handful of ticks per sequence).
-        std::vector<std::vector<GemmProblem>> init_l(nt);
-        int run = 0;
-        for (int k = 0; k < P.n_ticks; ++k) {
-            std::vector<GemmProblem> ls;
-            for (int g = 0; g <= last_group; ++g)
-                for (GemmProblem& p : collect(k, g)) {
-                    if (p.epi == RC_EPI_LSTM) { p.mr = 16; p.nc = 8; }
-                    else if (p.epi == RC_EPI_RELU && p.out_packed && p.N % 128 == 0 && p.Kp % 128 == 0 && p.out_bit == 0 && p.out_col0 == 0 && p.seg[0].par_mode == 0 &&
-                             p.out != ctx->hid1 && p.out != ctx->hid2) { }
-                    else { init_l[k].push_back(p); continue; }
-                    p.m_tiles = 1;                                             // (B <= 256: one row tile, whatever the tick's row count)
-                    ls.push_back(p);
-                }
-            ResidentTick& T = ctx->res_ticks_h[k];
-            const size_t region = (size_t)(k & 3);
-            size_t tiles = 0;
-            T.B = B;
-            T.n = build_lds_problems(ctx, ls, nullptr, ctx->lds_slab.get() + region * ctx->lds_region_tiles * RC_LDS_SLAB_FLOATS,
-                                     ctx->lds_tickets.get() + region * ctx->lds_region_tiles, T.p, RC_RES_MAXP, &T.n_items, &tiles, true);
-            if (T.n != (int)ls.size()) return fail(ctx, RC_ERR_INVALID, "resident engine: more problems in a tick than its table holds");
-            if (tiles > ctx->lds_region_tiles) return fail(ctx, RC_ERR_INVALID, "resident engine: more tiles in a tick than a slab region holds");
-            const bool tail_wrote = cnt(P.n_reach, k - 1 - kTailStage) > 0;
-            for (int i = 0; i < RC_RES_MAXP; ++i) {
-                T.dep[i][0] = T.dep[i][1] = -1; T.dep_items[i][0] = T.dep_items[i][1] = 0;
-                T.need_tail[i] = 0;
-                if (i >= T.n) continue;
-                const bool lstm = T.p[i].epi == RC_EPI_LSTM;
-                T.need_tail[i] = lstm ? ((tail_wrote && T.p[i].H == 512) ? 1 : 0) : 1;
-                if (k == 0 || !lstm) continue;
-                const ResidentTick& Tp = ctx->res_ticks_h[k - 1];
-                for (int j = 0; j < Tp.n; ++j) {
-                    const int items_j = (j + 1 < Tp.n ? Tp.p[j + 1].wg_base : Tp.n_items) - Tp.p[j].wg_base;
-                    const bool lstm_j = Tp.p[j].epi == RC_EPI_LSTM;
-                    if (lstm_j && Tp.p[j].hstate == T.p[i].hstate) { T.dep[i][0] = j; T.dep_items[i][0] = items_j; }                           // its own h(t - 1), c
-                    if ((const float*)(lstm_j ? Tp.p[j].hstate : Tp.p[j].out) == T.p[i].seg[0].base) { T.dep[i][1] = j; T.dep_items[i][1] = items_j; }   // layer 0's h | relu(linear1)
-                }
-            }
-            ctx->res_base_h[k] = run;
-            run += T.n_items;
-        }
-        ctx->res_base_h[nt] = run;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->res_ticks_d.get(), ctx->res_ticks_h.get(), nt * sizeof(ResidentTick), hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(item_base_d, ctx->res_base_h.get(), (nt + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemsetAsync(done_d, 0, (cap * (RC_RES_MAXP + 1) + 4 + 16) * sizeof(int), st));
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_main[6].get(), st));
-        HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_main[6].get(), 0));
-        ResidentArgs R{};
-        R.ticks = ctx->res_ticks_d.get(); R.item_base = item_base_d; R.n_ticks = P.n_ticks;
-        R.head = words_d; R.done = done_d; R.tick_done = tick_done_d;
-        R.flag_tail = words_d + 2; R.abort = words_d + 3;
-        R.spin_bound = (unsigned long long)std::max(1, tune_env("RC_SEQ_RESIDENT_BOUND_MS", 2000)) * 100000ull;   // wall_clock64: 100 MHz
-        {
-            hipEvent_t ta = nullptr, tb = nullptr;
-            if (ctx->timing && !timing_pair(ctx, &ta, &tb)) return fail(ctx, RC_ERR_HIP, "hipEventCreate");
-            if (ta) HIP_TRY(ctx, hipEventRecord(ta, st));
-            rc_launch_gemm_resident(R, res_wgs, st);
-            if (tb) HIP_TRY(ctx, hipEventRecord(tb, st));
-        }
-        ctx->stat_lds_launches += 1;
-        // second stream, tick k: [init_net] -> prep -> [every item of tick k - 1] -> linear2 -> fuse -> tail -> flag_tail = k + 1
-        for (int k = 0; k < P.n_ticks; ++k) {
-            if (int rc = launch_problems(ctx, init_l[k], nullptr, aux, false)) return rc;
-            if (k < P.n_prep) {
-                wp.frame_at = ctx->frame_at_d.get() + (size_t)k * B;
-                wp.first_tick = k == 0 ? 1 : 0;
-                rc_launch_prep_wave(ctx->ring2[k % kRing], io0, prm, B, wp, aux);
-            }
-            if (k > 0) rc_launch_flag_wait(tick_done_d + (k - 1), ctx->res_ticks_h[k - 1].n_items, words_d + 3, R.spin_bound, aux);
-            if (int rc = group(k, 5, aux)) return rc;
-            if (cnt(P.n_valid, k - kFuseStage) > 0) rc_launch_fuse(ctx->ring2[(k - kFuseStage) % kRing], io0, prm, B, aux);
-            if (cnt(P.n_valid, k - kTailStage) > 0) {
-                const FrameBuffers& tgt = ctx->ring2[k % kRing];
-                wt.x4l = tgt.x4l; wt.x6l = tgt.x6l; wt.flags2 = tgt.flags2; wt.wsteps = tgt.wsteps;
-                rc_launch_tail(ctx->ring2[(k - kTailStage) % kRing], io0, prm, ctx->body, B, 0, aux, nullptr, &wt, nullptr);
-            }
-            rc_launch_flag_set(words_d + 2, k + 1, aux);
-            ctx->stat_ticks += 1;
-        }
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[0].get(), aux));
-        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[0].get(), 0));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->res_abort_h.get(), words_d + 3, sizeof(int), hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipGetLastError());
-#ifdef RC_RES_PROF
-        {   // profiling builds (tools/probe_resprof.so): where the resident workgroups' time went, per item
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            unsigned long long ph[5];
-            const unsigned long long* pd = (const unsigned long long*)(((unsigned long long)(words_d + 4) + 7ull) & ~7ull);
-            if (hipMemcpy(ph, pd, sizeof(ph), hipMemcpyDeviceToHost) == hipSuccess && ph[2] > 0)
-                std::fprintf(stderr, "[res prof] %d ticks, %llu items on %d workgroups; per item: wait %.2f us, item %.2f us, release %.2f us, take %.2f us; per workgroup %.2f ms\n",
-                             P.n_ticks, ph[2], res_wgs, ph[0] / 100.0 / ph[2], ph[1] / 100.0 / ph[2], ph[3] / 100.0 / ph[2], ph[4] / 100.0 / ph[2],
-                             (ph[0] + ph[1] + ph[3] + ph[4]) / 100.0 / 1000.0 / res_wgs);
-        }
-#endif
-        ctx->stat_resident_segments += 1;
-        ctx->stat_wave_frames += t_last - t0 + 1;
-        return RC_OK;
     }
-    for (int k = 0; k < P.n_ticks; ++k) {
-        const int e = k & 3, ep = (k + 3) & 3;
-        std::vector<GemmProblem> tri_l1, tri_ls6, tri_ls5;
-        if (tri) {
-            // {linear1, init_net} of tick k read what the second stream wrote in tick k - 1 and nothing else: at the head of this tick's
-            // second-stream work, in front of its waits for the layer steps of tick k - 1
-            for (const GemmProblem& p : collect(k, last_group)) (p.epi != RC_EPI_LSTM ? tri_l1 : (p.H == 1024 ? tri_ls6 : tri_ls5)).push_back(p);
-            bool sigl = false;
-            if (int rc = launch_problems(ctx, tri_l1, nullptr, aux, false, ctx->ev_lin1[e].get(), &sigl)) return rc;
-            if (!sigl) HIP_TRY(ctx, hipEventRecord(ctx->ev_lin1[e].get(), aux));
-        }
-        // ---- per-row kernels and linear2 of tick k (second stream: after the previous tick's wide launches)
-        const bool prep_first = tri && prep_early != 0 && k < P.n_prep;
-        if (prep_first) {
-            wp.frame_at = ctx->frame_at_d.get() + (size_t)k * B;
-            wp.first_tick = k == 0 ? 1 : 0;
-            rc_launch_prep_wave(ctx->ring2[k % kRing], io0, prm, B, wp, aux);
-        }
-        if (tri && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_h5[ep].get(), 0));
-        if (two && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_main[ep].get(), 0));
-        if (split_main && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_h512[ep].get(), 0));
-        if (lin1_own && !tri && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(aux, ctx->ev_lin1[ep].get(), 0));   // (init_net's last layer -> the tail)
-        if (k < P.n_prep && !prep_first) {
-            wp.frame_at = ctx->frame_at_d.get() + (size_t)k * B;
-            wp.first_tick = k == 0 ? 1 : 0;
-            rc_launch_prep_wave(ctx->ring2[k % kRing], io0, prm, B, wp, aux);   // (before the tail: it initialises the tail's target slot)
-        }
-        if (int rc = group(k, 5, aux)) return rc;                               // linear2 of stages 4 and 8 ...
-        bool aux_signalled = false;
-        static const int fuse_tail_env = tune_env("RC_SEQ_FUSE_TAIL", 1);
-        bool merged = false;
-        if (fuse_tail_env && tri && cnt(P.n_valid, k - kFuseStage) > 0 && cnt(P.n_valid, k - kTailStage) > 0) {     // ... then their consumers, in ONE launch
-            const FrameBuffers& tgt = ctx->ring2[k % kRing];
-            wt.x4l = tgt.x4l; wt.x6l = tgt.x6l; wt.flags2 = tgt.flags2; wt.wsteps = tgt.wsteps;
-            aux_signalled = two && ext_events;
-            merged = rc_launch_fuse_tail(ctx->ring2[(k - kTailStage) % kRing], ctx->ring2[(k - kFuseStage) % kRing], io0, prm, ctx->body, B, wt, aux,
-                                         aux_signalled ? ctx->ev_aux[e].get() : nullptr);
-            if (!merged) aux_signalled = false;
-        }
-        if (!merged && cnt(P.n_valid, k - kFuseStage) > 0) rc_launch_fuse(ctx->ring2[(k - kFuseStage) % kRing], io0, prm, B, aux);
-        if (!merged && cnt(P.n_valid, k - kTailStage) > 0) {
-            const FrameBuffers& tgt = ctx->ring2[k % kRing];
-            wt.x4l = tgt.x4l; wt.x6l = tgt.x6l; wt.flags2 = tgt.flags2; wt.wsteps = tgt.wsteps;
-            aux_signalled = two && ext_events;
-            rc_launch_tail(ctx->ring2[(k - kTailStage) % kRing], io0, prm, ctx->body, B, 0, aux, nullptr, &wt, aux_signalled ? ctx->ev_aux[e].get() : nullptr);
-        }
-        if (two && !aux_signalled) HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[e].get(), aux));
-        // ---- the GEMM stages of tick k (caller's stream: after the previous tick's second-stream work)
-        // Of the caller's-stream launches only linear1 (and init_net) READ what the second stream wrote in the previous tick, and
-        // with the groups merged they sit in the LAST launch: the wait goes in front of that one (late_wait), and the first launch
-        // of the tick follows the previous tick's last one without a barrier packet in between (+1-3 %). What made this illegal
-        // with two copies of the hidden state -- the first launch WRITES h of rnn4 / rnn6 where linear2 of the previous tick, on
-        // the second stream, still reads -- is what the third copy is for (RC_HBUF).
-        bool init_now = false;
-        for (int q = W2_INIT0; q < W2_PROB; ++q) init_now = init_now || cnt(P.n_reach, k - w2_stage(q)) > 0;
-        std::vector<GemmProblem> gp[4];
-        size_t n_prob = 0;
-        long long n_tiles = 0;
-        for (int g = 0; g <= last_group; ++g) {
-            gp[g] = collect(k, g);
-            n_prob += gp[g].size();
-            for (const GemmProblem& p : gp[g]) n_tiles += (long long)p.n_tiles * p.m_tiles;
-        }
-        bool main_signalled = false;
-        hipEvent_t stop_ev = (two && ext_events) ? ctx->ev_main[e].get() : nullptr;
-        if (tri) {
-            bool sig6 = false, sig5 = false, sig0 = false;
-            // (tri_swap: rnn4 -- the longest chain of a tick -- on the context's own stream, which may carry a queue priority
-            // (RC_SEQ_H512_PRIO), rnn6 on the caller's)
-            hipStream_t s_r6 = tri_swap ? st : s2, s_r4 = tri_swap ? s2 : st;
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s_r6, ctx->ev_lin1[ep].get(), 0));
-            if (int rc = launch_problems(ctx, tri_ls6, nullptr, s_r6, false, ctx->ev_h512[e].get(), &sig6)) return rc;
-            if (!sig6) HIP_TRY(ctx, hipEventRecord(ctx->ev_h512[e].get(), s_r6));
-            // The H = 512 nets' stream waits for the END of the second stream's previous tick. It NEEDS only linear1(k - 1) -- the head of
-            // that tick, behind that stream's tick k - 2, which covers every buffer the layer steps rewrite -- and the end only behind an
-            // init_net state write of its tail (rnn2 l0). RC_SEQ_H5_EARLY=1 issues exactly that (race free on the stream model), and is
-            // SLOWER: all-visible 1,458k -> 1,405k, mixed 1,211k -> 1,182k body-frames/s -- the three layer-step launches of a tick do
-            // better in step with each other than spread over the tick (profiles/r06_resident_notes.txt).
-            static const int h5_early = tune_env("RC_SEQ_H5_EARLY", 0);
-            if (k > 0 && h5_early && cnt(P.n_reach, k - 1 - kTailStage) == 0) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_lin1[ep].get(), 0));
-            else if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_aux[ep].get(), 0));
-            if (int rc = launch_problems(ctx, tri_ls5, nullptr, s4, false, ctx->ev_h5[e].get(), &sig5)) return rc;
-            if (!sig5) HIP_TRY(ctx, hipEventRecord(ctx->ev_h5[e].get(), s4));
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s_r4, ctx->ev_lin1[ep].get(), 0));
-            for (int g = 0; g < last_group; ++g)
-                if (!gp[g].empty()) {
-                    bool sig = false;
-                    if (int rc = launch_problems(ctx, gp[g], nullptr, s_r4, false, sig0 ? nullptr : ctx->ev_main[e].get(), &sig)) return rc;
-                    sig0 = sig0 || sig;
-                }
-            if (!sig0) HIP_TRY(ctx, hipEventRecord(ctx->ev_main[e].get(), s_r4));
-            main_signalled = true;
-        } else if (lin1_own) {
-            // Regrouped tick with {linear1, init_net} on a stream of its own: linear1(k) needs only the second stream's work of tick k - 1,
-            // so it runs beside the previous tick's layer steps instead of behind them, and neither wide launch waits for the other's
-            // END any more -- {rnn4} on the caller's stream follows its predecessor as soon as linear1(k - 1) is done (the chain
-            // h(t) -> h(t + 1) of rnn4 runs back to back), {rnn6, H = 512} likewise behind the second stream's previous tick.
-            std::vector<GemmProblem> l1, ls;
-            for (const GemmProblem& p : gp[last_group]) (p.epi == RC_EPI_LSTM ? ls : l1).push_back(p);
-            bool sigl = false, sig2 = false, sig0 = false;
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s4, ctx->ev_aux[ep].get(), 0));
-            if (int rc = launch_problems(ctx, l1, nullptr, s4, false, ctx->ev_lin1[e].get(), &sigl)) return rc;
-            if (!sigl) HIP_TRY(ctx, hipEventRecord(ctx->ev_lin1[e].get(), s4));
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_aux[ep].get(), 0));      // (rnn2 l0 behind the tail's init_net state write)
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_lin1[ep].get(), 0));
-            if (int rc = launch_problems(ctx, ls, nullptr, s2, false, ctx->ev_h512[e].get(), &sig2)) return rc;
-            if (!sig2) HIP_TRY(ctx, hipEventRecord(ctx->ev_h512[e].get(), s2));
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_lin1[ep].get(), 0));
-            for (int g = 0; g < last_group; ++g)
-                if (!gp[g].empty()) {
-                    bool sig = false;
-                    if (int rc = launch_problems(ctx, gp[g], nullptr, st, false, sig0 ? nullptr : ctx->ev_main[e].get(), &sig)) return rc;
-                    sig0 = sig0 || sig;
-                }
-            main_signalled = sig0;
-        } else if (split_main) {
-            // {H = 512 nets, linear1} (reads what the second stream wrote in tick k - 1) on its own stream ...
-            bool sig2 = false, sig0 = false;
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(s2, ctx->ev_aux[ep].get(), 0));
-            if (int rc = launch_problems(ctx, gp[last_group], nullptr, s2, false, ctx->ev_h512[e].get(), &sig2)) return rc;
-            if (!sig2) HIP_TRY(ctx, hipEventRecord(ctx->ev_h512[e].get(), s2));
-            // ... {rnn6, rnn4 (+ init_net)} behind the previous tick's linear1 (init_net also reads the previous tick's fuse)
-            if (k > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_h512[ep].get(), 0));
-            if (k > 0 && init_now && !regroup) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep].get(), 0));
-            for (int g = 0; g < last_group; ++g)
-                if (!gp[g].empty()) {
-                    bool sig = false;
-                    if (int rc = launch_problems(ctx, gp[g], nullptr, st, false, sig0 ? nullptr : ctx->ev_main[e].get(), &sig)) return rc;
-                    sig0 = sig0 || sig;
-                }
-            main_signalled = sig0;
-        } else if (merge_fill && n_prob > 0 && n_prob <= RC_MAX_PROB && n_tiles <= 512) {
-            // a filling / draining tick (or one of lagging rows): everything fits two rounds of one launch -- no boundary at all, but
-            // the stream wait is back in front of the tick's first launch: a wash (off by default)
-            if (two && k > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep].get(), 0));
-            std::vector<GemmProblem> all;
-            for (int g = 0; g <= last_group; ++g) all.insert(all.end(), gp[g].begin(), gp[g].end());
-            if (int rc = launch_problems(ctx, all, nullptr, st, false, stop_ev, &main_signalled)) return rc;
-        } else {
-            const bool late = late_wait && merge_h512 && !init_now;
-            if (two && k > 0 && !late) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep].get(), 0));
-            for (int g = 0; g <= last_group; ++g) {
-                if (two && k > 0 && late && g == last_group) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[ep].get(), 0));
-                if (int rc = launch_problems(ctx, gp[g], nullptr, st, false, g == last_group ? stop_ev : nullptr, g == last_group ? &main_signalled : nullptr)) return rc;
-            }
-        }
-        if (two && !main_signalled) HIP_TRY(ctx, hipEventRecord(ctx->ev_main[e].get(), st));
-        ctx->stat_ticks += 1;
-    }
-    if (two && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[(P.n_ticks - 1) & 3].get(), 0));
-    if (split_main && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_h512[(P.n_ticks - 1) & 3].get(), 0));
-    if (lin1_own && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_lin1[(P.n_ticks - 1) & 3].get(), 0));
-    if (tri && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_h5[(P.n_ticks - 1) & 3].get(), 0));
-    if (tri && P.n_ticks > 0) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_main[(P.n_ticks - 1) & 3].get(), 0));
-    HIP_TRY(ctx, hipGetLastError());
     ctx->stat_wave_frames += t_last - t0 + 1;
     return RC_OK;
 }

@@ -1,12 +1,12 @@
-"""Stream-level hazards of the wavefront engine's tick (rc_api.cpp: run_wave2_segment), on an abstract model (no GPU).
+"""Stream-level hazards of the wavefront engine's tick (rc_api.cpp: stream_tick), on an abstract model (no GPU).
 
 tests/test_wave_plan.py checks WHICH tick every step of every row runs at. This file checks that, given those ticks, the way
 a tick is issued is race free: kernels are nodes on streams, stream order and the engine's event waits are the only ordering,
 the problems of one merged launch run concurrently. Every pair of accesses to one buffer with a write among them must be
-ordered by happens-before -- for the two-stream tick (batch >= 48: {rnn6, rnn4 (+ init_net)} on the caller's stream,
-{H = 512 nets, linear1} on a third one, per-row kernels + linear2 on the second) and for the one-stream tick with the late
-wait. The same model shows what the third copy of the hidden state (RC_HBUF) and the third relu(linear1) buffer are for:
-with two copies each the corresponding race appears.
+ordered by happens-before -- for the split engine's tick ("two"; batch >= 48: {rnn6, rnn4 (+ init_net)} on the caller's stream,
+{H = 512 nets, linear1} on a third one, per-row kernels + linear2 on the second), for the plain engine's ("one": both wide
+launches on the caller's stream, the wait in front of the last) and for the tri engine's. The same model shows what the third
+copy of the hidden state (RC_HBUF) and the third relu(linear1) buffer are for: with two copies each the corresponding race appears.
 
 Buffers: per ring slot (16) the frame's inputs / inter-stage vectors / flags; per sub-net relu(linear1) [x1 copies], h[layer]
 [hbuf copies] and c[layer]; the init_net chain. A frame started at tick e is step e of every sub-net (all rows visible from
@@ -51,7 +51,7 @@ def frame_ops(e, hbuf, x1buf, init=True):
 def build_tri(hbuf, x1buf, init=True):
     """Round 6, contexts on the shared-weight kernel: THREE streams of layer steps -- G4 {rnn4} on the caller's, G6 {rnn6} and G5 {the
     H = 512 nets} on streams of the context -- and L1 {linear1 of every net, init_net} at the head of the second stream's tick, in
-    front of that stream's waits for the layer steps of the previous tick (rc_api.cpp: run_wave2_segment, `tri`)."""
+    front of that stream's waits for the layer steps of the previous tick (rc_api.cpp: stream_tick, ENG_TRI)."""
     names = ("L1", "prep", "lin2", "fuse", "tail", "G4", "G6", "G5")
     per_tick = {k: {n: [] for n in names} for k in range(TICKS)}
     for e in range(TICKS):
@@ -181,7 +181,8 @@ def test_the_third_state_copy_and_the_third_linear1_buffer_are_what_make_it_so()
 
 
 def test_the_regrouped_two_stream_tick_and_the_three_stream_tick_need_the_same_copies():
-    """Round 6: {rnn4} alone on the caller's stream with rnn6 + init_net beside the H = 512 nets (RC_SEQ_TRI=0), and the three-stream tick."""
+    """Round 6: {rnn4} alone on the caller's stream with rnn6 + init_net beside the H = 512 nets (the regrouped two-stream tick the
+    tri engine superseded: docs/DESIGN_HISTORY.md 6.1), and the tri engine's tick."""
     assert races("two", g0_nets=("rnn4",), init_in="G2") == []
     r = races("tri", hbuf=2, init=False)
     assert r and all(b[0] == "h" for b, _, _ in r)
