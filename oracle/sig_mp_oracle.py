@@ -228,13 +228,14 @@ def gmof(x, sigma):
 class OracleBody:
     """SMPL-format body restricted to what the path consumes: 24 joints + the 33 landmark vertices."""
 
-    def __init__(self, body, vertex_ids=C.mp_mask):
+    def __init__(self, body, vertex_ids=C.mp_mask, dtype=F32):
+        """``dtype``: the precision the body is built and used in (float64 for oracle/smplify_f64.py)."""
         self.parent = [int(p) for p in body["parent"]]
-        J = torch.as_tensor(body["J"], dtype=F32)
-        vt = torch.as_tensor(body["v_template"], dtype=F32)
+        J = torch.as_tensor(body["J"], dtype=dtype)
+        vt = torch.as_tensor(body["v_template"], dtype=dtype)
         self.j_rest = J - J[:1]                                               # model.py:87
         self.v_rest = (vt - J[:1])[list(vertex_ids)]
-        self.w = torch.as_tensor(body["weights"], dtype=F32)[list(vertex_ids)]   # [V,24]
+        self.w = torch.as_tensor(body["weights"], dtype=dtype)[list(vertex_ids)]   # [V,24]
         par = torch.tensor([0] + self.parent[1:])
         self.par = par
         self.bone = self.j_rest - self.j_rest[par]                            # spatial.py:148-167
@@ -271,7 +272,7 @@ class OracleBody:
         """local rotations [B,24,3,3] + root position -> (global rot, joints [B,24,3], vertices [B,V,3]);
         blend the 24 joint transforms per vertex, then apply (model.py:229-241)."""
         pose = pose.reshape(-1, 24, 3, 3)
-        G, P = [pose[:, 0]], [torch.zeros(pose.shape[0], 3)]
+        G, P = [pose[:, 0]], [torch.zeros(pose.shape[0], 3, dtype=pose.dtype)]
         for i in range(1, 24):
             p = self.parent[i]
             G.append(G[p] @ pose[:, i])

@@ -33,7 +33,18 @@ def _imu_aa(ori):
     return O.rotation_matrix_to_axis_angle(ori.reshape(-1, 3, 3)).reshape(ori.shape[0], 18)
 
 
-def test_closure_matches_reference_capture(g, runner):
+def _within_the_term_bound(g, body, loss, gp, gt, use_head=False):
+    """In addition to the whole-gradient bars: loss and each of the 25 groups (24 joints, translation) against the float64 closure on
+    `body`, error / Bound <= 1 (oracle/smplify_f64.Bound, the bound of tests/test_gpu_smplify_terms.py)."""
+    from oracle import smplify_f64 as F
+    c = F.Case("capture", "ev", t(g["ev_pose"]), t(g["ev_tran"]), t(g["ev_kp"]), t(g["ev_ref3d"]), t(g["ev_imu_ori"]), t(g["ev_K"]), use_head=use_head)
+    _, bound, _ = F.bound_of(body, c)
+    r, lr = bound.ratios(gp, gt), bound.loss_ratio(loss)
+    print(f"capture (use_head={use_head}): worst group {F.GROUP_NAMES[int(r.argmax())]} error/Bound {r.max():.3f}, loss {lr:.3f}")
+    assert float(r.max()) <= 1.0 and lr <= 1.0, (F.GROUP_NAMES[int(r.argmax())], float(r.max()), lr)
+
+
+def test_closure_matches_reference_capture(g, runner, synth_assets):
     """Loss to 1e-5 relative and gradient to 1e-4 of its scale against the reference's own autograd through the
     6890-vertex mesh (the same bars tests/test_smplify_oracle.py holds the oracle to)."""
     loss, gp, gt = runner.loss_and_grad(t(g["ev_pose"]), t(g["ev_tran"]), t(g["ev_kp"]), t(g["ev_ref3d"]), _imu_aa(t(g["ev_imu_ori"])),
@@ -42,6 +53,7 @@ def test_closure_matches_reference_capture(g, runner):
     gs = max(np.abs(g["ev_grad_pose"]).max(), np.abs(g["ev_grad_tran"]).max())
     assert float((gp.cpu() - t(g["ev_grad_pose"])).abs().max()) <= 1e-4 * gs
     assert float((gt.cpu() - t(g["ev_grad_tran"])).abs().max()) <= 1e-4 * gs
+    _within_the_term_bound(g, synth_assets["body"], loss, gp, gt)
 
 
 def test_use_head_variant_matches_reference_capture(g, synth_assets):
@@ -53,6 +65,7 @@ def test_use_head_variant_matches_reference_capture(g, synth_assets):
     gs = max(np.abs(g["evh_grad_pose"]).max(), np.abs(g["evh_grad_tran"]).max())
     assert float((gp.cpu() - t(g["evh_grad_pose"])).abs().max()) <= 1e-4 * gs
     assert float((gt.cpu() - t(g["evh_grad_tran"])).abs().max()) <= 1e-4 * gs
+    _within_the_term_bound(g, synth_assets["body"], loss, gp, gt, use_head=True)
     pose = S.batch_rodrigues(t(g["ev_pose"]).view(-1, 3)).view(-1, 24, 3, 3)
     res = r.get_fitting_loss(pose, t(g["ev_tran"]), t(g["ev_kp"]), t(g["ev_K"]))
     assert float((res.cpu() - t(g["evh_residual"])).abs().max()) <= 1e-4 * float(g["evh_residual"].max())
@@ -72,6 +85,7 @@ def test_shape_variant_matches_reference_capture(g, synth_assets):
     gs = max(np.abs(g["evs_grad_pose"]).max(), np.abs(g["evs_grad_tran"]).max())
     assert float((gp.cpu() - t(g["evs_grad_pose"])).abs().max()) <= 1e-4 * gs
     assert float((gt.cpu() - t(g["evs_grad_tran"])).abs().max()) <= 1e-4 * gs
+    _within_the_term_bound(g, r.model._body, loss, gp, gt)                 # the shaped body the context holds
     assert abs(float(g["evs_loss"]) - float(g["ev_loss"])) > 1e-3 * abs(float(g["ev_loss"]))        # the shape matters
     pose = S.batch_rodrigues(t(g["ev_pose"]).view(-1, 3)).view(-1, 24, 3, 3)
     res = r.get_fitting_loss(pose, t(g["ev_tran"]), t(g["ev_kp"]), t(g["ev_K"]))
