@@ -107,6 +107,35 @@ int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const
                 const float* oric, int64_t rs_ori, const float* first_tran, uint32_t flags, float* pose_out,
                 int64_t rs_pose, float* tran_out, int64_t rs_tran, void* stream);
 
+/* rc_sequence for rows of DIFFERENT lengths, without padding: len_host HOST int32[batch], 0 <= len_host[b] <= T; every other argument
+ * as rc_sequence (the [row][t] layout keeps T frames per row). Row b runs frames 0 .. len_host[b] - 1 and nothing else:
+ *   - its pose_out / tran_out of those frames, its (h, c) of all six sub-nets, its fusion state (rc_get_fusion_state, including a
+ *     pending updater step and that step's inputs) and its trace are BITWISE what rc_sequence(T = len_host[b]) leaves for that row in
+ *     a context of the same batch and gemm mode: a row's bits depend neither on the batch, the tile shape or the engine, nor on the
+ *     other rows' lengths;
+ *   - output elements of frames t >= len_host[b] are NOT WRITTEN and inputs of those frames are NOT READ (NaN / inf there change
+ *     nothing); a row of length 0 is untouched altogether -- `flags` / first_tran of frame 0 do not apply to it. first_tran and
+ *     `flags` keep their meaning for frame 0 of every row of length >= 1;
+ *   - a row whose last frame is occluded leaves its deferred rnn6 / rnn4 step pending in the context's own buffers, as the last
+ *     frame of a uniform call does -- at frame len_host[b] - 1, while the other rows go on. A following call (rc_sequence or
+ *     rc_sequence_rows) continues every row from where it stopped, so a long recording can be streamed in chunks beside shorter ones.
+ * Every engine of rc_set_sequence_mode runs such a call (wavefront ticks launch only the problems that still have rows, the
+ * frame-stepped launches select the rows that still have the frame and pick their tiles for that many; frames that no row has are not
+ * launched), the resident layer-step kernel included. Calls longer than RC_SEQ_MAX_PLAN_FRAMES are planned in pieces as before, the
+ * lengths clipped per piece. Synchronisation as rc_sequence: at most the read-back of the plan, per piece (the lengths are staged in
+ * two pinned halves taken in turn, so a call only makes sure that the upload of the call before the previous one has left its half --
+ * long done by then). len_host is consumed before the call returns. Rows of one common length run exactly the launches of rc_sequence(T = that length).
+ * RC_ERR_INVALID (nothing enqueued) on a null len_host or a length < 0 or > T.
+ * rc_get_sequence_row_frames: row-frames computed by rc_sequence / rc_sequence_rows since rc_create (batch * T per uniform call, the
+ * sum of the lengths per ragged one); rc_get_sequence_stats keeps counting frame INDICES run by each engine, and ticks.
+ * rc_plan_wave_rows: rc_plan_wave (below) with per-row ends, len HOST int32[B], 0 <= len[b] <= T: row b starts frames
+ * t0 .. len[b] - 1 only, its last frame books no rider, and a row with len[b] <= t0 books nothing (a step pending in front of the
+ * segment stays pending). len[b] == T for every row gives rc_plan_wave's outputs. */
+int rc_sequence_rows(rc_ctx* ctx, int32_t T, const int32_t* len_host, const float* j2dc, int64_t rs_j2d, const float* accc,
+                     int64_t rs_acc, const float* oric, int64_t rs_ori, const float* first_tran, uint32_t flags, float* pose_out,
+                     int64_t rs_pose, float* tran_out, int64_t rs_tran, void* stream);
+int rc_get_sequence_row_frames(rc_ctx* ctx, int64_t* body_frames);
+
 /* Arithmetic of the GEMM products of EVERY launch of a context (linear layers, LSTM gate GEMMs, init_net):
  *   mode 0: v_mfma_f32_16x16x4_f32 -- fp32 operands, bitwise an fma chain per output element;
  *   mode 1: split-bf16 products on v_mfma_f32_16x16x32_bf16 -- every fp32 operand is the exact sum of three bf16 numbers
@@ -172,6 +201,9 @@ int rc_plan_sequence(const int8_t* codes, int32_t B, int32_t T, const int32_t* p
 int rc_plan_wave(const int8_t* codes, int32_t B, int32_t T, int32_t t0, const int32_t* first_reach, const int32_t* pend,
                  int32_t use_imu_updater, int32_t use_vision_updater, int32_t* frame_at, int64_t frame_at_cap,
                  int32_t* n_ticks, int32_t* n_prep, int32_t* counts, double* est_us);
+int rc_plan_wave_rows(const int8_t* codes, int32_t B, int32_t T, int32_t t0, const int32_t* len, const int32_t* first_reach,
+                      const int32_t* pend, int32_t use_imu_updater, int32_t use_vision_updater, int32_t* frame_at, int64_t frame_at_cap,
+                      int32_t* n_ticks, int32_t* n_prep, int32_t* counts, double* est_us);
 
 /* ---- live / streaming mode (BASELINE config 5) ------------------------------------------------------------- */
 /* The live_server.py loop (live_server.py:40-48): one frame per call, HOST tensors in and out exactly like

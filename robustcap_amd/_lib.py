@@ -50,6 +50,8 @@ SIGNATURES = {
     "rc_reset": (_I32, [_P, _P, _P]),
     "rc_step": (_I32, [_P, _P, _P, _P, _P, _U32, _P, _P, _P]),
     "rc_sequence": (_I32, [_P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _U32, _P, _I64, _P, _I64, _P]),
+    "rc_sequence_rows": (_I32, [_P, _I32, _P, _P, _I64, _P, _I64, _P, _I64, _P, _U32, _P, _I64, _P, _I64, _P]),
+    "rc_get_sequence_row_frames": (_I32, [_P, C.POINTER(_I64)]),
     "rc_set_gemm_mode": (_I32, [_P, _I32]),
     "rc_get_gemm_mode": (_I32, [_P]),
     "rc_default_gemm_mode": (_I32, [_I32]),
@@ -61,6 +63,7 @@ SIGNATURES = {
     "rc_get_resident_stats": (_I32, [_P, C.POINTER(_I64), C.POINTER(_I64)]),
     "rc_plan_sequence": (_I32, [_P, _I32, _I32, _P, _U32, _I32, _P]),
     "rc_plan_wave": (_I32, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I64, C.POINTER(_I32), C.POINTER(_I32), _P, _P]),
+    "rc_plan_wave_rows": (_I32, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _I64, C.POINTER(_I32), C.POINTER(_I32), _P, _P]),
     "rc_live_begin": (_I32, [_P]),
     "rc_live_step": (_I32, [_P, _P, _P, _P, _P, _U32, _P, _P]),
     "rc_live_end": (_I32, [_P]),

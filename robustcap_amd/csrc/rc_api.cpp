@@ -197,6 +197,15 @@ struct rc_ctx {
     PinBuf<int> scan_state_h;            // pinned: first_reach[B] then pend[B] (as ints)
     size_t scan_cap = 0;
     long long stat_wave_frames = 0, stat_stepped_frames = 0, stat_ticks = 0;
+    long long stat_row_frames = 0;       // row-frames computed by sequence calls (rc_get_sequence_row_frames)
+    // rc_sequence_rows: the call's per-row lengths, device + pinned (grow-only, released with the context). The pinned copy has two halves
+    // that calls take in turn, each with an event that says its upload has left it: a call only ever waits for the upload of the call
+    // BEFORE the previous one, which has long run.
+    DevBuf<int> row_len_d;
+    PinBuf<int> row_len_h;               // [2][row_len_cap]
+    size_t row_len_cap = 0;
+    HipEvent row_len_ev[2];
+    unsigned row_len_turn = 0;
     // per-row-cursor wavefront engine (run_wave2_segment)
     bool ring2_ready = false;
     FrameBuffers ring2[16];              // ring slots: inter-stage buffers, updater inputs, frame index and step numbers per row
@@ -784,12 +793,27 @@ rc_params_dev dev_params(const rc_params& p) {
     return d;
 }
 
+int tune_env(const char* name, int dflt);
+
 int step_impl(rc_ctx* ctx, const FrameIO& io, uint32_t flags, hipStream_t st, bool with_tr = true, bool skip_prep = false,
-              const FrameIO* next_io = nullptr) {   // skip_prep / next_io: the previous / this frame's tail runs the next prep
+              const FrameIO* next_io = nullptr,     // skip_prep / next_io: the previous / this frame's tail runs the next prep
+              int n_live = -1) {                    // rc_sequence_rows: rows that have this frame (-1: all of them)
     const int B = ctx->B;
     const FrameBuffers& fb = ctx->fb;
     const rc_params_dev prm = dev_params(ctx->prm);
     const int first = (flags & RC_FLAG_FIRST_FRAME) ? 1 : 0;
+    // Some rows have ended: the prep gives the others RC_ROW2_VALID, which selects the rows of the nets that step on every frame (as in
+    // a ring slot of the wavefront engine), and the tiles are picked for the rows that are left. All rows alive: the launches of rc_sequence.
+    const bool some_ended = io.len && n_live >= 0 && n_live < B;
+    // Tiles for the rows that are left (1: those of the full batch; A/B runs). The opposite of the wavefront engine's choice (collect), both
+    // measured on 72 rows x 600 with lengths on [150, 600]: 157.9 ms against 175.4 ms here (profiles/ragged_sequence_bench.txt).
+    static const bool rows_as_padded = tune_env("RC_SEQ_STEPPED_ROWS_AS_PADDED", 0) != 0;
+    auto every = [&](int net, const float* x, int ldx, Out y) {
+        Stage s{net, some_ended ? (int)RC_ROW2_VALID : 0, x, ldx, y, some_ended ? fb.flags2 : nullptr};
+        if (some_ended && !rows_as_padded) s.rows_hint = n_live;
+        return s;
+    };
+    auto merged = [&](Stage s) { if (some_ended && !rows_as_padded) s.rows_hint = n_live; return s; };
 
     if (!skip_prep) rc_launch_prep(fb, io, prm, B, first, st);
     // deferred vision updater of the previous frame (L264-271) for rows that step again now: rnn6 then rnn4 in the
@@ -805,11 +829,11 @@ int step_impl(rc_ctx* ctx, const FrameIO& io, uint32_t flags, hipStream_t st, bo
     // inertial pose branch (L144) + visual pose branch (L153); rnn4 also takes the rows whose deferred updater
     // step is still pending and that do not step on camera keypoints this frame (they read x4l)
     // (longest tiles first: the short ones of the other nets then fill the gaps at the end of the launch)
-    if (int rc = run_stage(ctx, {Stage{N4, (int)RC_ROW2_M4, fb.x4, 256, Out{fb.x6, 256, 171, true}, fb.flags2, fb.x4l,
-                                       (int)RC_ROW_VIS, (int)RC_ROW_VIS},
-                                 Stage{N2, 0, fb.x2, 128, Out{fb.x3, 256, 72, true}}}, true, nullptr, st)) return rc;
+    if (int rc = run_stage(ctx, {merged(Stage{N4, (int)RC_ROW2_M4, fb.x4, 256, Out{fb.x6, 256, 171, true}, fb.flags2, fb.x4l,
+                                              (int)RC_ROW_VIS, (int)RC_ROW_VIS}),
+                                 every(N2, fb.x2, 128, Out{fb.x3, 256, 72, true})}, true, nullptr, st)) return rc;
     if (first) {                                                           // L155-156: rnn6 on every row
-        if (int rc = run_stage(ctx, {Stage{N6, 0, fb.x6, 256, Out{fb.pc, 4, 0, false}}}, true, nullptr, st)) return rc;
+        if (int rc = run_stage(ctx, {every(N6, fb.x6, 256, Out{fb.pc, 4, 0, false})}, true, nullptr, st)) return rc;
     }
     rc_launch_fuse(fb, io, prm, B, st);
     // velocity, visual translation, pose, contact (L145, L161/165, L169-170) + rnn2.init_net (L181-182)
@@ -819,10 +843,10 @@ int step_impl(rc_ctx* ctx, const FrameIO& io, uint32_t flags, hipStream_t st, bo
         init.push_back(dense_problem(ctx, ctx->init[1], seg(ctx->hid1, 512, 0), Out{ctx->hid2, 1024, 0, true}, true, RC_ROW_REACH, fb.flags, nullptr, false));
         init.push_back(dense_problem(ctx, ctx->init[2], seg(ctx->hid2, 1024, 0), Out{fb.init_out, 2048, 0, false}, false, RC_ROW_REACH, fb.flags, nullptr, false));
     }
-    if (int rc = run_stage(ctx, {Stage{N6, (int)RC_ROW2_M6, fb.x6, 256, Out{fb.pc, 4, 0, false}, fb.flags2, fb.x6l,
-                                       (int)RC_ROW_PC, (int)RC_ROW_PC},
-                                 Stage{N3, 0, fb.x3, 256, Out{fb.vr, 4, 0, false}},
-                                 Stage{N7, 0, fb.x78, 256, Out{fb.r6d, 144, 0, false}}, Stage{N8, 0, fb.x78, 256, Out{fb.contact, 2, 0, false}}},
+    if (int rc = run_stage(ctx, {merged(Stage{N6, (int)RC_ROW2_M6, fb.x6, 256, Out{fb.pc, 4, 0, false}, fb.flags2, fb.x6l,
+                                              (int)RC_ROW_PC, (int)RC_ROW_PC}),
+                                 every(N3, fb.x3, 256, Out{fb.vr, 4, 0, false}),
+                                 every(N7, fb.x78, 256, Out{fb.r6d, 144, 0, false}), every(N8, fb.x78, 256, Out{fb.contact, 2, 0, false})},
                            true, &init, st)) return rc;
     // tail: fusion logic + landmarks; rows in the occluded regime get their updater inputs (x6l, x4l) and a
     // pending mark -- the two sub-net steps themselves run at the start of the next frame (or in rc_get_state)
@@ -879,7 +903,9 @@ int tune_env(const char* name, int dflt) {
 // Frame-stepped launch plan of a rc_sequence call from the regime codes (pure host logic, exposed as rc_plan_sequence for
 // tests): the three transition launches are needed on the frames where some row carries a deferred updater step INTO a frame
 // it steps on camera keypoints (net/sig_mp.py:264-271 then L149-153).
-void plan_sequence(const signed char* codes, int B, int T, const int* pend, bool first_frame, bool use_vision_updater, unsigned char* mode) {
+// len (rc_sequence_rows; may be null): row b has frames 0 .. len[b] - 1 only -- a row that has ended asks for nothing and keeps its mark.
+void plan_sequence(const signed char* codes, int B, int T, const int* pend, bool first_frame, bool use_vision_updater, unsigned char* mode,
+                   const int* len = nullptr) {
     std::vector<unsigned char> pd(B);
     for (int b = 0; b < B; ++b) pd[b] = pend[b] != 0;
     for (int t = 0; t < T; ++t) {
@@ -887,6 +913,7 @@ void plan_sequence(const signed char* codes, int B, int T, const int* pend, bool
         bool need_tr = false;
         const bool ff = t == 0 && first_frame;
         for (int b = 0; b < B; ++b) {
+            if (len && t >= len[b]) continue;
             if (pd[b] && (c[b] >= 1 || ff)) need_tr = true;                    // rnn4 steps on the camera keypoints (L149)
             pd[b] = (c[b] == 0 && use_vision_updater) ? 1 : 0;                 // L264 (non-live)
         }
@@ -927,28 +954,37 @@ struct WavePlan {
     std::vector<int> n_valid, n_vis, n_rider, n_reach;   // rows per slot (index = tick that initialises it)
     double est_wave_us = 0.0, est_stepped_us = 0.0;
     int lag_max = 0;                           // largest lag of a row's last frame behind the batch (ticks)
+    std::vector<int> n_done;                   // rc_sequence_rows: rows whose frames have all started before slot k (empty: a uniform plan)
+    int done(int k) const { return k >= 0 && k < (int)n_done.size() ? n_done[k] : 0; }
 };
 
 // t0: first frame of the segment (1 when frame 0 takes first_frame / first_tran and runs frame-stepped); first_reach / pend:
-// the rows' state in front of frame t0.
+// the rows' state in front of frame t0. len (rc_sequence_rows; may be null = T for every row): row b runs frames t0 .. len[b] - 1 of
+// the segment; its last frame leaves its updater step pending while the other rows go on, and a row without a frame books nothing.
 void plan_wave(const signed char* codes, int B, int T, int t0, const int* first_reach, const int* pend, bool use_imu_updater,
-               bool use_vision_updater, const double* cost, WavePlan& P) {
+               bool use_vision_updater, const double* cost, WavePlan& P, const int* len = nullptr) {
     const int n_frames = T - t0;
+    std::vector<int> n_live((size_t)(n_frames > 0 ? n_frames : 0), 0);      // rows that have frame t0 + i
     std::vector<int> entry((size_t)B * (n_frames > 0 ? n_frames : 0));
     auto grow = [&](int tick) {
         if ((int)P.n_valid.size() <= tick) { P.n_valid.resize(tick + 1, 0); P.n_vis.resize(tick + 1, 0); P.n_rider.resize(tick + 1, 0); P.n_reach.resize(tick + 1, 0); }
     };
     int need = 0, n_prep = 0;
     P.lag_max = 0;
+    std::vector<int> done_from;                                             // per row: first slot at which the row has ended
     std::vector<unsigned char> tr_frame((size_t)(n_frames > 0 ? n_frames : 0), 0);
     for (int b = 0; b < B; ++b) {
         int e_prev = -1, ready_any = 0, ready_vis = 0;
         bool fr = first_reach[b] != 0;
         bool pd = pend[b] != 0 && use_vision_updater;
+        const int Tb = len ? std::min(len[b], T) : T;                       // this row's end
+        if (len) done_from.push_back(Tb <= t0 ? 0 : -1);
+        if (Tb <= t0) continue;
         if (pd) { grow(0); P.n_rider[0] += 1; ready_vis = 1; need = std::max(need, kRiderSpan); n_prep = std::max(n_prep, 1); }
-        for (int f = t0; f < T; ++f) {
+        for (int f = t0; f < Tb; ++f) {
             const int c = codes[(size_t)f * B + b];
             const bool vis = c >= 1;
+            n_live[f - t0] += 1;
             int e = std::max(e_prev + 1, ready_any);
             if (vis) e = std::max(e, ready_vis);
             entry[(size_t)b * n_frames + (f - t0)] = e;
@@ -958,7 +994,7 @@ void plan_wave(const signed char* codes, int B, int T, int t0, const int* first_
             if (pd && vis) tr_frame[f - t0] = 1;                            // frame-stepped plan: transition launches on this frame
             if (fr && c == 2 && use_imu_updater) { fr = false; P.n_reach[e] += 1; ready_any = e + kRideStage - 1; }   // L178-183
             pd = c == 0 && use_vision_updater;                              // L264
-            if (pd && f != T - 1) {
+            if (pd && f != Tb - 1) {
                 const int ride = e + kRideStage;
                 grow(ride);
                 P.n_rider[ride] += 1;
@@ -970,14 +1006,21 @@ void plan_wave(const signed char* codes, int B, int T, int t0, const int* first_
             n_prep = std::max(n_prep, e + 1);
             e_prev = e;
         }
-        if (n_frames > 0) P.lag_max = std::max(P.lag_max, e_prev - (n_frames - 1));
+        P.lag_max = std::max(P.lag_max, e_prev - (Tb - t0 - 1));
+        if (len) done_from.back() = e_prev + 1;
     }
     P.n_ticks = need;
     P.n_prep = n_prep;
     grow(n_prep > 0 ? n_prep - 1 : 0);
     P.frame_at.assign((size_t)n_prep * B, -1);
+    P.n_done.clear();
+    if (len) {
+        P.n_done.assign((size_t)n_prep + 1, 0);
+        for (int d : done_from) if (d <= n_prep) P.n_done[d] += 1;
+        for (int k = 1; k <= n_prep; ++k) P.n_done[k] += P.n_done[k - 1];
+    }
     for (int b = 0; b < B; ++b)
-        for (int i = 0; i < n_frames; ++i) P.frame_at[(size_t)entry[(size_t)b * n_frames + i] * B + b] = t0 + i;
+        for (int i = 0; i < (len ? std::min(len[b], T) : T) - t0; ++i) P.frame_at[(size_t)entry[(size_t)b * n_frames + i] * B + b] = t0 + i;
     // cost model for the engine choice. A tick = the stream hand-over + its layer steps: a layer step with >= 96 rows costs its
     // round of wide tiles (rnn4 43 us, rnn6 27.5 us, an H = 512 net 8 us: profiles/r03_timeline_mixed.txt), with fewer rows it
     // streams its weights through small tiles (~0.45 of that); cost[0] scales the whole estimate (1.0 = these figures).
@@ -1001,7 +1044,16 @@ void plan_wave(const signed char* codes, int B, int T, int t0, const int* first_
         }
     }
     P.est_stepped_us = 0.0;
-    for (int i = 0; i < n_frames; ++i) P.est_stepped_us += cost[2] + (tr_frame[i] ? cost[3] : 0.0);
+    // A frame-stepped frame with every row (or >= 96 rows, the wide-tile bound above) costs cost[2]; with fewer rows its launches stream the
+    // weights through small tiles, down to the same 0.45 of it; a frame that no row has is not launched.
+    // (The share is NOT a measured constant: no ragged frame-stepped timing went into it. It is the wave model's small-tile factor, made
+    // continuous in the row count, and it only has to rank the two engines for a long thin tail.)
+    const int rows_full = std::min(B, 96);
+    for (int i = 0; i < n_frames; ++i) {
+        if (n_live[i] == 0) continue;
+        const double share = n_live[i] >= rows_full ? 1.0 : 0.45 + 0.55 * n_live[i] / rows_full;
+        P.est_stepped_us += cost[2] * share + (tr_frame[i] ? cost[3] : 0.0);
+    }
 }
 
 static int ensure_wave2_buffers_once(rc_ctx* ctx) {
@@ -1147,6 +1199,7 @@ int reserve_frame_at(rc_ctx* ctx, size_t need, size_t want) {
 std::vector<GemmProblem> collect(const rc_ctx* ctx, const WavePlan& P, WaveEngine eng, const WaveTiles& tiles, int k, int g) {
     // rows of a problem from which it runs 64-row tiles (split products): a half-filled 64-row tile still halves the weight bytes of two 32-row tiles
     static const int tile64_rows = tune_env("RC_SEQ_TILE64_ROWS", 33);
+    static const bool rows_as_padded = tune_env("RC_SEQ_ROWS_AS_PADDED", 1) != 0;      // 0: choose for the rows that are left (A/B runs)
     const int B = ctx->B;
     std::vector<GemmProblem> ps;
     for (int qi = 0; qi < W2_PROB; ++qi) {
@@ -1159,6 +1212,10 @@ std::vector<GemmProblem> collect(const rc_ctx* ctx, const WavePlan& P, WaveEngin
         const int riders = P.n_rider[e];
         const int rows = kind == 4 ? P.n_reach[e] : ((net == N4 || net == N6) ? P.n_vis[e] + riders : P.n_valid[e]);
         if (rows <= 0) continue;
+        // Kernel and tile shape of a problem are chosen for `rows_k` rows. In a plan with per-row ends (rc_sequence_rows) that is the count
+        // the PADDED call would have at this slot -- a padding row is occluded: it steps every net, rnn4 / rnn6 as a rider -- so a batch
+        // that thins out stays on the kernel and tiles of the full batch; the row tiles still follow the rows that are there.
+        const int rows_k = kind == 4 ? rows : rows + (rows_as_padded ? P.done(e) : 0);
         GemmProblem p = ctx->wave2_prob[(size_t)(e % kRing) * W2_PROB + q];
         if (kind == 0 || kind == 1) {                                          // relu(linear1) of the frame started at tick e: one of three buffers
             float* x1 = e % 3 == 0 ? ctx->net[net].x1 : (e % 3 == 1 ? ctx->x1_alt[net] : ctx->x1_alt2[net]);
@@ -1167,18 +1224,18 @@ std::vector<GemmProblem> collect(const rc_ctx* ctx, const WavePlan& P, WaveEngin
         if (kind == 1 || kind == 2) {
             const NetDev& n = ctx->net[net];
             int mr, nc;
-            if (lds_problem(ctx, rows)) {                                      // the shared-weight kernel (rc_gemm_lds.hip)
+            if (lds_problem(ctx, rows_k)) {                                    // the shared-weight kernel (rc_gemm_lds.hip)
                 mr = 16; nc = 8;
-            } else if (ctx->gemm_split && rows >= tile64_rows) {               // (split products: the K loop is operand-bound, 64-row tiles)
+            } else if (ctx->gemm_split && rows_k >= tile64_rows) {               // (split products: the K loop is operand-bound, 64-row tiles)
                 const int* t = n.H == 512 ? tiles.t5 : (n.H == 1024 ? tiles.t6 : tiles.t4);
                 mr = t[0]; nc = t[1];
             } else {
-                pick_tile(n.H, rows, &mr, &nc);
+                pick_tile(n.H, rows_k, &mr, &nc);
             }
             p.mr = mr; p.nc = nc; p.n_tiles = n.H / (4 * nc);
         } else if (kind == 0 || kind == 4) {
-            if (rows <= 16) { p.mr = 1; p.nc = 1; p.n_tiles = (p.N + 15) / 16; }
-            else if (kind == 0 && ctx->gemm_split && rows >= tile64_rows) {
+            if (rows_k <= 16) { p.mr = 1; p.nc = 1; p.n_tiles = (p.N + 15) / 16; }
+            else if (kind == 0 && ctx->gemm_split && rows_k >= tile64_rows) {
                 // linear1 rides in a wide launch behind its 256 LSTM tiles: as 544 tiles of 32 x 64 (K = 128 / 256: two k-blocks, i.e. all
                 // prologue and epilogue) it added two rounds, ~18 us of a 245 us tick; 136 tiles of 64 x 128 add one
                 const int np = round_up(p.N, 64);
@@ -1451,7 +1508,7 @@ int run_wave2_segment(rc_ctx* ctx, const WavePlan& P, const FrameIO& io0, int t0
     const WaveEngine eng = pick_wave_engine(ctx);
     WaveSeg S{ctx, P, io0, st, ctx->aux_stream.get(), eng, wave_tiles(eng), dev_params(ctx->prm), WavePrep{}, WaveTail{}};
     for (int i = 0; i < 6; ++i) S.wp.steps[i] = ctx->net[i].steps;
-    S.wp.cx4l = ctx->fb.x4l; S.wp.cx6l = ctx->fb.x6l;
+    S.wp.cx4l = ctx->fb.x4l; S.wp.cx6l = ctx->fb.x6l; S.wp.t0 = t0;
     S.wt.on = 1; S.wt.t_last = t_last;
     S.wt.steps4 = ctx->net[N4].steps; S.wt.steps6 = ctx->net[N6].steps;
     S.wt.cx4l = ctx->fb.x4l; S.wt.cx6l = ctx->fb.x6l;
@@ -1927,20 +1984,34 @@ int rc_step(rc_ctx* ctx, const float* j2dc, const float* accc, const float* oric
     return mark_eager(ctx, (hipStream_t)stream);
 }
 
-int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const float* accc, int64_t rs_acc, const float* oric,
-                int64_t rs_ori, const float* first_tran, uint32_t flags, float* pose_out, int64_t rs_pose, float* tran_out,
-                int64_t rs_tran, void* stream) {
-    if (int rc = check_ready(ctx)) return rc;
-    if (T == 0) return RC_OK;                                               // (evaluate.py:75-83 over no frames: nothing happens, whatever the pointers)
-    ctx->live_prev_known = false;
-    if (T < 0 || !j2dc || !accc || !oric || !pose_out || !tran_out) return fail(ctx, RC_ERR_INVALID, "rc_sequence: bad argument");
+// rc_sequence (len == nullptr) and rc_sequence_rows: frames [off, off + T) of a call whose per-row lengths are len[B] (HOST; their device
+// copy is ctx->row_len_d), the pointers standing at frame `off`. Row b has frames 0 .. min(len[b] - off, T) - 1 of this piece.
+static int sequence_impl(rc_ctx* ctx, int32_t T, const int32_t* len, int32_t off, const float* j2dc, int64_t rs_j2d, const float* accc,
+                         int64_t rs_acc, const float* oric, int64_t rs_ori, const float* first_tran, uint32_t flags, float* pose_out,
+                         int64_t rs_pose, float* tran_out, int64_t rs_tran, void* stream) {
+    std::vector<int> rows_len;                                              // this piece's per-row lengths (empty: every row runs every frame)
+    if (len) {
+        rows_len.resize(ctx->B);
+        int longest = 0;
+        bool same = true;
+        for (int b = 0; b < ctx->B; ++b) {
+            rows_len[b] = std::max(0, std::min(len[b] - off, T));
+            longest = std::max(longest, rows_len[b]);
+            same = same && rows_len[b] == rows_len[0];
+        }
+        if (longest == 0) return RC_OK;                                     // no row has a frame here: nothing is enqueued
+        T = longest;                                                        // frames that no row has are not launched
+        if (same) rows_len.clear();                                         // ... and rows of one length are a uniform call
+    }
+    const int* L = rows_len.empty() ? nullptr : rows_len.data();
+    const int* len_d = L ? ctx->row_len_d.get() : nullptr;
     // Very long calls are planned in pieces: the plan's tables (regime codes, frame_at) grow with batch x frames, and a piece
     // boundary costs one pipeline drain (8 of 4,096 ticks) and one more read-back.
     const int32_t kMaxPlanFrames = std::max(8, tune_env("RC_SEQ_MAX_PLAN_FRAMES", 4096));     // (read per call: tests shrink it)
     if (T > kMaxPlanFrames && ctx->seq_mode && !ctx->prm.live) {
         for (int32_t a = 0; a < T; a += kMaxPlanFrames) {
             const int32_t n = std::min(kMaxPlanFrames, T - a);
-            if (int rc = rc_sequence(ctx, n, j2dc + (int64_t)a * 99, rs_j2d, accc + (int64_t)a * 18, rs_acc, oric + (int64_t)a * 54, rs_ori,
+            if (int rc = sequence_impl(ctx, n, L ? len : nullptr, off + a, j2dc + (int64_t)a * 99, rs_j2d, accc + (int64_t)a * 18, rs_acc, oric + (int64_t)a * 54, rs_ori,
                                      a == 0 ? first_tran : nullptr, a == 0 ? flags : 0u, pose_out + (int64_t)a * 216, rs_pose,
                                      tran_out + (int64_t)a * 3, rs_tran, stream)) return rc;
         }
@@ -1949,8 +2020,20 @@ int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const
     hipStream_t st = (hipStream_t)stream;
     auto io_at = [&](int t) {
         return FrameIO{j2dc + (int64_t)t * 99, accc + (int64_t)t * 18, oric + (int64_t)t * 54, t == 0 ? first_tran : nullptr,
-                       pose_out + (int64_t)t * 216, tran_out + (int64_t)t * 3, rs_j2d, rs_acc, rs_ori, rs_pose, rs_tran};
+                       pose_out + (int64_t)t * 216, tran_out + (int64_t)t * 3, rs_j2d, rs_acc, rs_ori, rs_pose, rs_tran, len_d, off + t};
     };
+    std::vector<int> n_live;                                                // rows that have frame t (the host knows: tile choice)
+    if (L) {
+        n_live.assign((size_t)T + 1, 0);
+        for (int b = 0; b < ctx->B; ++b) n_live[L[b]] += 1;                 // rows ending at t ...
+        for (int t = T - 1, run = n_live[T]; t >= 0; --t) { const int ends = n_live[t]; n_live[t] = run; run += ends; }   // ... -> rows with L > t
+        n_live.resize(T);
+    }
+    {
+        long long rf = 0;
+        if (L) for (int b = 0; b < ctx->B; ++b) rf += L[b]; else rf = (long long)ctx->B * T;
+        ctx->stat_row_frames += rf;
+    }
     // Launch plan: with sequence mode on (and not live: the landmark refresh counter is not modelled on the host) one
     // pre-pass classifies every (frame, row), the host reads the codes back ONCE per call (the only synchronisation of
     // `stream` in this call) and picks, per frame, the wavefront engine, or the frame-stepped launches with or without
@@ -1970,7 +2053,7 @@ int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const
             HIP_TRY(ctx, hipStreamSynchronize(st));                             // nothing in flight may still read the old tables
             if (int rc = reserve_plan_tables(ctx, T)) return rc;
         }
-        rc_launch_scan_conf(j2dc, rs_j2d, B, T, ctx->prm.conf_lo, ctx->prm.conf_hi, ctx->scan_codes_d.get(), st);
+        rc_launch_scan_conf(j2dc, rs_j2d, B, T, ctx->prm.conf_lo, ctx->prm.conf_hi, ctx->scan_codes_d.get(), st, nullptr, len_d, off);
         HIP_TRY(ctx, hipMemcpyAsync(ctx->scan_codes_h.get(), ctx->scan_codes_d.get(), need, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->scan_state_h.get(), ctx->fb.first_reach, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
         unsigned char* pend_b = reinterpret_cast<unsigned char*>(ctx->scan_state_h.get() + 2 * B);     // pinned, like the other two
@@ -1997,19 +2080,20 @@ int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const
             std::vector<int> fr(ctx->scan_state_h.get(), ctx->scan_state_h.get() + B), pd(ctx->scan_state_h.get() + B, ctx->scan_state_h.get() + 2 * B);
             if (w0) {
                 for (int b = 0; b < B; ++b) {
+                    if (L && L[b] < 1) continue;                                 // the row has no frame 0: its state stays
                     const int c = ctx->scan_codes_h[b];
                     if (fr[b] && c == 2 && imu) fr[b] = 0;
                     pd[b] = (c == 0 && vup) ? 1 : 0;
                 }
             }
             const double cost[4] = {ctx->cost_tick_us, ctx->cost_tick_small_us, ctx->cost_frame_us, ctx->cost_tr_us};
-            plan_wave(ctx->scan_codes_h.get(), B, T, w0, fr.data(), pd.data(), imu, vup, cost, wplan);
+            plan_wave(ctx->scan_codes_h.get(), B, T, w0, fr.data(), pd.data(), imu, vup, cost, wplan, L);
             if (ctx->seq_mode == 2 || wplan.est_wave_us < wplan.est_stepped_us) wave2_from = w0;
             static const bool dbg = tune_env("RC_SEQ_DEBUG", 0) != 0;
             if (dbg) std::fprintf(stderr, "rc_sequence plan: T=%d ticks=%d lag_max=%d est_wave=%.0f us est_stepped=%.0f us -> %s\n", T, wplan.n_ticks,
                                   wplan.lag_max, wplan.est_wave_us, wplan.est_stepped_us, wave2_from >= 0 ? "wavefront" : "frame-stepped");
         }
-        plan_sequence(ctx->scan_codes_h.get(), B, T, ctx->scan_state_h.get() + B, ff, vup, mode.data());    // transition-launch marks of stepped frames
+        plan_sequence(ctx->scan_codes_h.get(), B, T, ctx->scan_state_h.get() + B, ff, vup, mode.data(), L);    // transition-launch marks of stepped frames
     }
     bool prep_done = false;                 // the previous frame's tail kernel already ran this frame's prep
     for (int t = 0; t < T;) {
@@ -2023,13 +2107,54 @@ int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const
             // one wave does both (one launch boundary and the prep kernel's start-up latency less per frame)
             const bool chain = t + 1 < T && t + 1 != wave2_from;
             const FrameIO next = chain ? io_at(t + 1) : FrameIO{};
-            if (int rc = step_impl(ctx, io_at(t), t == 0 ? flags : 0u, st, mode[t] == SEQ_STEPPED_TR, prep_done, chain ? &next : nullptr)) return rc;
+            if (int rc = step_impl(ctx, io_at(t), t == 0 ? flags : 0u, st, mode[t] == SEQ_STEPPED_TR, prep_done, chain ? &next : nullptr,
+                                   L ? n_live[t] : -1)) return rc;
             prep_done = chain;
             ctx->stat_stepped_frames += 1;
             ++t;
         }
     }
     return mark_eager(ctx, st);
+}
+
+int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const float* accc, int64_t rs_acc, const float* oric,
+                int64_t rs_ori, const float* first_tran, uint32_t flags, float* pose_out, int64_t rs_pose, float* tran_out,
+                int64_t rs_tran, void* stream) {
+    if (int rc = check_ready(ctx)) return rc;
+    if (T == 0) return RC_OK;                                               // (evaluate.py:75-83 over no frames: nothing happens, whatever the pointers)
+    ctx->live_prev_known = false;
+    if (T < 0 || !j2dc || !accc || !oric || !pose_out || !tran_out) return fail(ctx, RC_ERR_INVALID, "rc_sequence: bad argument");
+    return sequence_impl(ctx, T, nullptr, 0, j2dc, rs_j2d, accc, rs_acc, oric, rs_ori, first_tran, flags, pose_out, rs_pose, tran_out, rs_tran, stream);
+}
+
+int rc_sequence_rows(rc_ctx* ctx, int32_t T, const int32_t* len_host, const float* j2dc, int64_t rs_j2d, const float* accc, int64_t rs_acc,
+                     const float* oric, int64_t rs_ori, const float* first_tran, uint32_t flags, float* pose_out, int64_t rs_pose,
+                     float* tran_out, int64_t rs_tran, void* stream) {
+    if (int rc = check_ready(ctx)) return rc;
+    if (T < 0 || !len_host || !j2dc || !accc || !oric || !pose_out || !tran_out) return fail(ctx, RC_ERR_INVALID, "rc_sequence_rows: bad argument");
+    const size_t B = (size_t)ctx->B;
+    for (size_t b = 0; b < B; ++b)
+        if (len_host[b] < 0 || len_host[b] > T) return fail(ctx, RC_ERR_INVALID, "rc_sequence_rows: a row's length is outside 0 .. T");
+    if (T == 0) return RC_OK;
+    ctx->live_prev_known = false;
+    hipStream_t st = (hipStream_t)stream;
+    // the lengths travel once per call: pinned copy -> device copy on `stream`, in front of everything that reads them
+    for (HipEvent& ev : ctx->row_len_ev)                                      // (before the capacity moves: a failure here is retried whole)
+        if (!ev) HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ev), hipEventDisableTiming));
+    const unsigned turn = ctx->row_len_turn++ & 1u;
+    if (B > ctx->row_len_cap) HIP_TRY(ctx, rc_grow(ctx->row_len_cap, B, B, ctx->row_len_d, B, ctx->row_len_h, 2 * B));
+    else HIP_TRY(ctx, hipEventSynchronize(ctx->row_len_ev[turn].get()));      // this half's last upload (two calls ago) has left it
+    int* len_h = ctx->row_len_h.get() + turn * B;
+    std::memcpy(len_h, len_host, B * sizeof(int));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->row_len_d.get(), len_h, B * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(ctx->row_len_ev[turn].get(), st));
+    return sequence_impl(ctx, T, len_h, 0, j2dc, rs_j2d, accc, rs_acc, oric, rs_ori, first_tran, flags, pose_out, rs_pose, tran_out, rs_tran, stream);
+}
+
+int rc_get_sequence_row_frames(rc_ctx* ctx, int64_t* body_frames) {
+    if (!ctx || !body_frames) return RC_ERR_INVALID;
+    *body_frames = ctx->stat_row_frames;
+    return RC_OK;
 }
 
 int rc_set_gemm_mode(rc_ctx* ctx, int32_t mode) {
@@ -2092,13 +2217,13 @@ int rc_plan_sequence(const int8_t* codes, int32_t B, int32_t T, const int32_t* p
     return RC_OK;
 }
 
-int rc_plan_wave(const int8_t* codes, int32_t B, int32_t T, int32_t t0, const int32_t* first_reach, const int32_t* pend,
-                 int32_t use_imu_updater, int32_t use_vision_updater, int32_t* frame_at, int64_t frame_at_cap, int32_t* n_ticks,
-                 int32_t* n_prep, int32_t* counts, double* est_us) {
+static int plan_wave_abi(const int8_t* codes, int32_t B, int32_t T, int32_t t0, const int32_t* len, const int32_t* first_reach,
+                         const int32_t* pend, int32_t use_imu_updater, int32_t use_vision_updater, int32_t* frame_at, int64_t frame_at_cap,
+                         int32_t* n_ticks, int32_t* n_prep, int32_t* counts, double* est_us) {
     if (!codes || !first_reach || !pend || !n_ticks || !n_prep || B < 1 || T < 1 || t0 < 0 || t0 >= T) return RC_ERR_INVALID;
     WavePlan P;
     const double cost[4] = {1.0, 13.0, 285.0, 55.0};
-    plan_wave(reinterpret_cast<const signed char*>(codes), B, T, t0, first_reach, pend, use_imu_updater != 0, use_vision_updater != 0, cost, P);
+    plan_wave(reinterpret_cast<const signed char*>(codes), B, T, t0, first_reach, pend, use_imu_updater != 0, use_vision_updater != 0, cost, P, len);
     *n_ticks = P.n_ticks;
     *n_prep = P.n_prep;
     if (est_us) { est_us[0] = P.est_wave_us; est_us[1] = P.est_stepped_us; }
@@ -2110,6 +2235,22 @@ int rc_plan_wave(const int8_t* codes, int32_t B, int32_t T, int32_t t0, const in
             counts[2 * P.n_prep + k] = P.n_rider[k]; counts[3 * P.n_prep + k] = P.n_reach[k];
         }
     return RC_OK;
+}
+
+int rc_plan_wave(const int8_t* codes, int32_t B, int32_t T, int32_t t0, const int32_t* first_reach, const int32_t* pend,
+                 int32_t use_imu_updater, int32_t use_vision_updater, int32_t* frame_at, int64_t frame_at_cap, int32_t* n_ticks,
+                 int32_t* n_prep, int32_t* counts, double* est_us) {
+    return plan_wave_abi(codes, B, T, t0, nullptr, first_reach, pend, use_imu_updater, use_vision_updater, frame_at, frame_at_cap, n_ticks, n_prep,
+                         counts, est_us);
+}
+
+int rc_plan_wave_rows(const int8_t* codes, int32_t B, int32_t T, int32_t t0, const int32_t* len, const int32_t* first_reach,
+                      const int32_t* pend, int32_t use_imu_updater, int32_t use_vision_updater, int32_t* frame_at, int64_t frame_at_cap,
+                      int32_t* n_ticks, int32_t* n_prep, int32_t* counts, double* est_us) {
+    if (!len || B < 1) return RC_ERR_INVALID;
+    for (int b = 0; b < B; ++b) if (len[b] < 0 || len[b] > T) return RC_ERR_INVALID;
+    return plan_wave_abi(codes, B, T, t0, len, first_reach, pend, use_imu_updater, use_vision_updater, frame_at, frame_at_cap, n_ticks, n_prep,
+                         counts, est_us);
 }
 
 int rc_live_end(rc_ctx* ctx) {

@@ -19,7 +19,11 @@
 
 __global__ __launch_bounds__(64) void rc_prep_kernel(FrameBuffers fb, FrameIO io, rc_params_dev prm, int B, int first_frame) {
     const int row = blockIdx.x;
-    prep_body(fb, io, prm, row, threadIdx.x, first_frame, fb.pend[row], fb.uv_count[row]);
+    if (!rc_row_live(io, row, io.t)) {                                     // rc_sequence_rows: the row has ended -- no GEMM problem selects it,
+        if (threadIdx.x == 0) { fb.flags[row] = 0; fb.flags2[row] = 0; }   // its inputs are not read, its state and trace stay
+        return;
+    }
+    prep_body(fb, io, prm, row, threadIdx.x, first_frame, fb.pend[row], fb.uv_count[row], io.len ? RC_ROW2_VALID : 0u);
 }
 
 // Per-row-cursor wavefront engine (rc_api.cpp: run_wave2_segment): the prep of one TICK. Row `row` starts frame
@@ -35,7 +39,8 @@ __global__ __launch_bounds__(64 * RPB) void rc_prep_wave_kernel(FrameBuffers fb,
     const int row = blockIdx.x * RPB + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= B) return;
     const int f = w.frame_at[row];
-    const bool rider = w.first_tick && prm.use_vision_updater && fb.pend[row] != 0;
+    // (a row without a frame in this segment -- rc_sequence_rows -- keeps its pending step where it is)
+    const bool rider = w.first_tick && prm.use_vision_updater && fb.pend[row] != 0 && rc_row_live(io, row, io.t + w.t0);
     unsigned fl = 0;
     if (f >= 0) {
         FrameIO iof = io;
@@ -75,6 +80,7 @@ __device__ __forceinline__ void fuse_body(const FrameBuffers& fb, const FrameIO&
     if (row >= B) return;
     int frame = 0;
     if (fb.frame) { frame = fb.frame[row]; if (frame < 0) return; }       // ring slot of the per-row-cursor engine: bubble
+    else if (!rc_row_live(io, row, io.t)) return;                         // frame-stepped launch of rc_sequence_rows: the row has ended
     const int regime = fb.regime[row];
     if (j == 23) {                                                        // L178-180
         if (regime == 2 && prm.use_imu_updater && fb.first_reach[row]) {
@@ -350,11 +356,15 @@ __global__ void rc_flush_flags_kernel(FrameBuffers fb, int B) {
 // compares) so that the host's launch plan and the device's row flags can never disagree. Also rc_conf_mean (means != nullptr).
 // codes[t * B + row] = 0 (c <= lo), 1 (lo < c < hi), 2 (c >= hi), means[t * B + row] = c. Four waves per workgroup, one (row, frame) each.
 __global__ __launch_bounds__(256) void rc_scan_conf_kernel(const float* j2d, long long row_stride, int B, int T, double conf_lo,
-                                                          double conf_hi, signed char* codes, float* means) {
+                                                          double conf_hi, signed char* codes, float* means, const int* len, int len_t0) {
     const long long item = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (item >= (long long)B * T) return;
     const int t = (int)(item / B), row = (int)(item % B);
+    if (len && len_t0 + t >= len[row]) {                                   // rc_sequence_rows: not a frame of this row -- not read; -1 is no regime
+        if (lane == 0 && codes) codes[item] = -1;
+        return;
+    }
     const float* kp = j2d + row * row_stride + (long long)t * 99;
     const float cf = lane < 33 ? kp[3 * lane + 2] : 0.f;
     const float c = rc_conf_mean33(cf);
@@ -379,11 +389,11 @@ static int rc_wave_rows_per_wg() {
 }
 
 void rc_launch_scan_conf(const float* j2d, long long row_stride, int B, int T, double conf_lo, double conf_hi, signed char* codes,
-                         hipStream_t st, float* means) {
+                         hipStream_t st, float* means, const int* len, int len_t0) {
     const long long items = (long long)B * T;
     if (items <= 0) return;
     hipLaunchKernelGGL(rc_scan_conf_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, j2d, row_stride, B, T, conf_lo, conf_hi, codes,
-                       means);
+                       means, len, len_t0);
 }
 void rc_launch_advance_steps(int* const* steps6, int n_frames, int B, hipStream_t st) {
     StepPtrs sp;

@@ -214,8 +214,15 @@ __device__ __forceinline__ void tail_impl(FrameBuffers fb, FrameIO io, const rc_
         if (frame < 0) return;                                             // bubble: the whole wave leaves
         io.j2d += (long long)frame * 99; io.acc += (long long)frame * 18; io.ori += (long long)frame * 54;
         io.pose_out += (long long)frame * 216; io.tran_out += (long long)frame * 3;
+    } else if (!rc_row_live(io, row, io.t)) {                              // frame-stepped launch of rc_sequence_rows: the row has ended; the whole
+        if (has_next && lane == 0) { fb.flags[row] = 0; fb.flags2[row] = 0; }   // wave leaves (the next frame's prep: no problem selects the row)
+        return;
     }
-    const bool wave_ride = wt.on && frame != wt.t_last;                    // updater inputs ride the target slot
+    // the row's last frame of the segment: the segment's, or (rc_sequence_rows) the row's own last frame of the call, whichever comes first
+    int t_end = wt.t_last;
+    if (wt.on && io.len) t_end = min(t_end, io.len[row] - 1 - io.t);
+    const bool wave_ride = wt.on && frame != t_end;                        // updater inputs ride the target slot
+    const bool next_live = has_next && rc_row_live(io_next, row, io_next.t);
     // ---- every global read of this wave, requested up front (one memory latency instead of a chain of ~10: this kernel is a
     // dependent-latency chain, 1,560 B of I/O per body). The state reads are safe to hoist: only this wave writes its row.
     BodyStage<64> bst;
@@ -232,7 +239,7 @@ __device__ __forceinline__ void tail_impl(FrameBuffers fb, FrameIO io, const rc_
     }
     const float acc_l = tr_.acc_l, ori_l = tr_.ori_l;
     PrepIn nin;
-    if (has_next) prep_load(nin, io_next, row, lane);
+    if (next_live) prep_load(nin, io_next, row, lane);
     if constexpr (!WL) bst.store(&s_body, lane);                          // (LDS: visible to the wave after the first barrier)
     const BodyConst* body = &s_body;
     float lpf[6], ltr[3], g[3], pc[3], vr[3], flr[6][3], Rcr[9], ftr[3];
@@ -501,7 +508,8 @@ __device__ __forceinline__ void tail_impl(FrameBuffers fb, FrameIO io, const rc_
             fb.c2[fb.c2_layer_stride + row * 512 + e] = src[1536 + e];
         }
     }
-    if (has_next) prep_compute(fb, nin, prm, row, lane, 0, pend_next, uvc_next);
+    if (next_live) prep_compute(fb, nin, prm, row, lane, 0, pend_next, uvc_next, io_next.len ? RC_ROW2_VALID : 0u);
+    else if (has_next && lane == 0) { fb.flags[row] = 0; fb.flags2[row] = 0; }   // this was the row's last frame of the call
     if constexpr (LIVE) RC_LT(2, 9);
 }
 

@@ -200,6 +200,7 @@ struct WavePrep {
     int* steps[6];          // the sub-nets' per-row step counters
     const float *cx4l, *cx6l;
     int first_tick;
+    int t0;                 // first frame of the segment: a row whose frames end in front of it keeps its pending step
 };
 // rc_tail_kernel in the per-row-cursor engine: the vision updater's two sub-net steps of a frame "ride" the ring slot that
 // is initialised at the tick its tail runs (target slot); the last frame of the segment leaves them pending instead.
@@ -217,7 +218,13 @@ struct FrameIO {
     const float *j2d, *acc, *ori, *first_tran;
     float *pose_out, *tran_out;
     long long s_j2d, s_acc, s_ori, s_pose, s_tran;      // row strides (elements)
+    // rc_sequence_rows: row b of the call runs frames 0 .. len[b] - 1 only (DEVICE int32[B]; nullptr = every row runs every frame).
+    // t = index, in the call `len` belongs to, of the frame these pointers stand at (a ring slot's frame index counts from it).
+    const int* len;
+    int t;
 };
+// "row `row` has a frame at call index `t`" / "... and it is the row's last of the call" (wave-uniform where a wave owns a row)
+__host__ __device__ inline bool rc_row_live(const FrameIO& io, int row, int t) { return !io.len || t < io.len[row]; }
 
 struct rc_params_dev {
     double conf_lo, conf_hi, tran_filter_num;
@@ -314,7 +321,7 @@ void rc_aql_destroy(AqlChain* c);
 
 void rc_launch_gemm(const GemmLaunch& L, int total_wg, hipStream_t s, hipEvent_t stop = nullptr);
 void rc_launch_scan_conf(const float* j2d, long long row_stride, int B, int T, double conf_lo, double conf_hi, signed char* codes, hipStream_t s,
-                         float* means = nullptr);
+                         float* means = nullptr, const int* len = nullptr, int len_t0 = 0);   // len: frames t with len_t0 + t >= len[row] are not read, code -1
 void rc_launch_advance_steps(int* const* steps6, int n_frames, int B, hipStream_t s);
 bool rc_gemm_is_w32(const GemmLaunch& L);       // true: the launch runs on rc_gemm_split48_w32_kernel
 bool rc_gemm_is_small(const GemmLaunch& L);     // true: the launch runs on rc_gemm_small_kernel (16-row tiles only)

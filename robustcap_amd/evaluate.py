@@ -117,7 +117,7 @@ def first_translations(dataset, rows):
 
 def run_dataset(dataset, state_dict, body, use_first_tran=True, use_flat_floor=True, rows=None, device="cuda",
                 run_smplify=False, gmm=None, smplify_info=None, image_size=(1920, 1080), smplify_workers=4, nets=None,
-                gemm_mode=None):
+                gemm_mode=None, ragged=False):
     """Run every (sequence, camera) row of ``dataset`` (or the given subset) through the net; rows are sharded over
     the ranks of the initialised process group and gathered. Returns {(i, j): (pose [T,24,3,3], tran [T,3])} on the CPU.
 
@@ -132,7 +132,8 @@ def run_dataset(dataset, state_dict, body, use_first_tran=True, use_flat_floor=T
     ~0.4 s) once and only reset for the next dataset (an entry is reused only for the very same ``state_dict`` object).
     ``gemm_mode``: product arithmetic of the GEMMs (False fp32 MFMA, True split-bf16 products); None picks the library's
     default for the TOTAL number of rows of the run, not for this rank's shard, so a row's result does not depend on
-    the number of ranks (``Net.default_gemm_mode``)."""
+    the number of ranks (``Net.default_gemm_mode``). ``ragged=True`` hands every row's own length to ``forward_sequence``: the
+    padding frames behind a short row are neither computed nor read; the frames returned are bitwise those of the padded run."""
     all_rows = rows_of(dataset) if rows is None else list(rows)
     Tmax = max(len(dataset["pose"][i]) for i, _ in all_rows)
     split = Net.default_gemm_mode(len(all_rows)) if gemm_mode is None else bool(gemm_mode)
@@ -154,7 +155,9 @@ def run_dataset(dataset, state_dict, body, use_first_tran=True, use_flat_floor=T
             net.set_gemm_mode(split)
         net.use_flat_floor = use_flat_floor
         net.gravityc = grav
-        out_p, out_t = net.forward_sequence(j2d, acc, ori, first_tran=ft if use_first_tran else None, first_frame=not use_first_tran)
+        lengths = [len(dataset["pose"][i]) for i, _ in mine] if ragged else None
+        out_p, out_t = net.forward_sequence(j2d, acc, ori, first_tran=ft if use_first_tran else None, first_frame=not use_first_tran,
+                                            lengths=lengths)
         if run_smplify:
             _refine_rows(dataset, mine, body, gmm, out_p, out_t, ori, image_size, device, smplify_info, smplify_workers)
         return out_p, out_t

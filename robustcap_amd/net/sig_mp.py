@@ -443,11 +443,21 @@ class Net:
         return a.value
 
     @torch.no_grad()
-    def forward_sequence(self, j2dc, accc, oric, first_tran=None, first_frame=False):
+    def forward_sequence(self, j2dc, accc, oric, first_tran=None, first_frame=False, lengths=None):
         """The evaluate.py frame loop (evaluate.py:75-83) for B sequences of T frames in one call.
-        Inputs [B,T,33,3], [B,T,6,3], [B,T,6,3,3]; returns device tensors pose [B,T,24,3,3], tran [B,T,3]."""
+        Inputs [B,T,33,3], [B,T,6,3], [B,T,6,3,3]; returns device tensors pose [B,T,24,3,3], tran [B,T,3].
+
+        ``lengths`` (a sequence of B ints or an int tensor, 0 <= lengths[b] <= T; None: every row runs T frames): row b runs its
+        first ``lengths[b]`` frames only (rc_sequence_rows) -- no padding is computed, the inputs past a row's length are never read,
+        and the row's state afterwards is that of a call of its own length, so a later call continues it. The returned tensors keep
+        the shape [B,T,...]; their elements past a row's length are UNSPECIFIED (uninitialised memory)."""
         B = self.batch
         T = j2dc.shape[1]
+        if lengths is not None:
+            lens = np.ascontiguousarray(torch.as_tensor(lengths).detach().cpu().numpy().astype(np.int64).reshape(-1))
+            if lens.shape[0] != B or (lens < 0).any() or (lens > T).any():
+                raise ValueError(f"lengths: {B} values in 0 .. {T} expected")
+            lens = np.ascontiguousarray(lens.astype(np.int32))
         if T == 0:                                                          # (the reference's loop over no frames: nothing happens)
             return torch.empty(B, 0, 24, 3, 3, device=self.device), torch.empty(B, 0, 3, device=self.device)
         self._sync_gravity()
@@ -455,12 +465,25 @@ class Net:
         ft = None if first_tran is None else self._prep(first_tran, (B, 3))
         pose = torch.empty(B, T, 24, 3, 3, device=self.device)
         tran = torch.empty(B, T, 3, device=self.device)
-        rc = self._lib.rc_sequence(self._ctx, T, _lib.ptr(j2dc), rs_j, _lib.ptr(accc), rs_a, _lib.ptr(oric), rs_o, _lib.ptr(ft),
-                                   _lib.RC_FLAG_FIRST_FRAME if first_frame else 0, _lib.ptr(pose), T * 216, _lib.ptr(tran), T * 3,
-                                   _lib.stream_ptr())
-        _lib.check(self._ctx, rc, "rc_sequence")
+        flags = _lib.RC_FLAG_FIRST_FRAME if first_frame else 0
+        if lengths is None:
+            rc = self._lib.rc_sequence(self._ctx, T, _lib.ptr(j2dc), rs_j, _lib.ptr(accc), rs_a, _lib.ptr(oric), rs_o, _lib.ptr(ft),
+                                       flags, _lib.ptr(pose), T * 216, _lib.ptr(tran), T * 3, _lib.stream_ptr())
+            _lib.check(self._ctx, rc, "rc_sequence")
+        else:
+            rc = self._lib.rc_sequence_rows(self._ctx, T, lens.ctypes.data_as(C.c_void_p), _lib.ptr(j2dc), rs_j, _lib.ptr(accc), rs_a,
+                                            _lib.ptr(oric), rs_o, _lib.ptr(ft), flags, _lib.ptr(pose), T * 216, _lib.ptr(tran), T * 3,
+                                            _lib.stream_ptr())
+            _lib.check(self._ctx, rc, "rc_sequence_rows")
         self.__dict__["_keep"] = (j2dc, accc, oric, ft)
         return pose, tran
+
+    def sequence_row_frames(self):
+        """Row-frames computed by ``forward_sequence`` since construction (rc_get_sequence_row_frames): B * T per uniform call, the
+        sum of ``lengths`` per ragged one."""
+        n = C.c_int64()
+        _lib.check(self._ctx, self._lib.rc_get_sequence_row_frames(self._ctx, C.byref(n)), "rc_get_sequence_row_frames")
+        return n.value
 
     @staticmethod
     def default_gemm_mode(total_rows):

@@ -9,6 +9,12 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def split_products(kernel_name):
+    """The shared-weight kernel (rc_gemm_lds_kernel) only ever runs split-bf16 products, like the kernels that carry "split" in their name."""
+    k = kernel_name or ""
+    return "split" in k or "lds" in k
+
+
 def main():
     conf = sys.argv[1] if len(sys.argv) > 1 else "mixed"
     rows = []
@@ -23,7 +29,7 @@ def main():
         d = json.loads(line[-1])
         rf = d["roofline"] or {}
         rows.append({"batch": B, "body_frames_per_s": d["value"], "ms_per_step": d["ms_per_step"], "gemm_frac": rf.get("frac"),
-                     "path_frac": rf.get("path_frac"), "products": "split-bf16" if "split" in (rf.get("kernel") or "") else "fp32 MFMA"})
+                     "path_frac": rf.get("path_frac"), "products": "split-bf16" if split_products(rf.get("kernel")) else "fp32 MFMA"})
     print(json.dumps({"command": f"python bench.py --batch B --steps 256 (96 for B >= 1024) --warmup 16 --conf {conf} --full --no-cpu-baseline --no-variants",
                       "note": "contexts of batch >= 48 use the split-bf16 products, smaller ones the fp32 MFMA (launch-chain and weight-streaming bound)",
                       "sweep": rows}, indent=1))
