@@ -300,6 +300,9 @@ def test_batched_sequence_vs_oracle(synth_assets):
     assert maxdiff(joint_positions(synth_assets["body"], pose.cpu(), tran.cpu()), joint_positions(synth_assets["body"], op, ot)) <= 1e-4
     tr = net.get_trace()
     assert tr[:, 3].tolist() == ora.trace["n_floor"].tolist()
+    assert tr[:, 5].tolist() == ora.trace["use_vel"].long().tolist()       # velocity branch, stance foot, jump reset of the last frame
+    assert tr[:, 6].tolist() == ora.trace["foot"].tolist()
+    assert tr[:, 7].tolist() == ora.trace["far"].long().tolist()
 
 
 def test_step_api_equals_sequence_api_bitwise(synth_assets):
