@@ -12,16 +12,9 @@
 // synchronisation. rc_sequence runs whole calls on the per-row-cursor wavefront engine instead (run_wave2_segment below): the
 // same stages skewed over consecutive ticks and a ring of slots, two or three wide launches per tick on one to three streams.
 #include "../../include/robustcap_hip.h"
-#include "rc_internal.h"
+#include "rc_ctx.h"
 
 #include <algorithm>
-#if defined(__x86_64__) || defined(_M_X64)
-#include <immintrin.h>
-#define RC_STORE_FENCE() _mm_sfence()          // posted writes to the device's BAR leave the write-combining buffers in program order
-#else
-#define RC_STORE_FENCE() __atomic_thread_fence(__ATOMIC_SEQ_CST)
-#endif
-
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -45,216 +38,16 @@
 #define RC_NC1280 10      // 16-column blocks per rnn4 LSTM tile (probe builds: 8 lets two workgroups share a CU's LDS)
 #endif
 
-namespace {
-
-thread_local std::string g_create_error;
-
-struct NetSpec { const char* name; int in, H, out; };
-const NetSpec kNets[6] = {{"rnn2", 72, 512, 69},  {"rnn3", 141, 512, 3},   {"rnn4", 171, 1280, 69},
-                          {"rnn6", 240, 1024, 3}, {"rnn7", 141, 512, 144}, {"rnn8", 141, 512, 2}};
-enum { N2 = 0, N3 = 1, N4 = 2, N6 = 3, N7 = 4, N8 = 5 };
-const int kInit[3][2] = {{69, 512}, {512, 1024}, {1024, 2048}};
-
-inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
-struct Dense {       // packed dense layer
-    float* W = nullptr; float* b = nullptr;
-    void* Ws = nullptr;                  // split-bf16 planes of W
-    float* Wrm = nullptr;                // narrow layers (linear2): the matrix as loaded, row-major [N][K] (rc_live.hip)
-    int K = 0, N = 0, Kp = 0, Np = 0;
-    int mr = 2, nc = 4;                  // tile shape: 16*mr rows x 16*nc columns
-};
-struct NetDev {
-    Dense lin1, lin2;
-    float* Wl[2] = {nullptr, nullptr};   // LSTM layers, K' = 2H, N' = 4H (tile-interleaved gates)
-    void* Wls[2] = {nullptr, nullptr};   // their split-bf16 planes
-    float* bl[2] = {nullptr, nullptr};
-    float* h = nullptr;                  // [layer][copy of RC_HBUF][B][H]
-    float* c = nullptr;                  // [layer][B][H]
-    int* steps = nullptr;                // [B]
-    float* x1 = nullptr;                 // relu(linear1) scratch [B][H]
-    float* part = nullptr;               // lean live frame: per-tile partial sums of linear2 [H / 4][RC_LIVE_MAXB][outp]
-    int in = 0, H = 0, out = 0;
-    int nc = 4;                          // 16-column blocks per LSTM tile (4*nc hidden units x 4 gates)
-    int mr = 2;                          // 16-row blocks per LSTM tile
-};
-
-}  // namespace
-
-struct rc_ctx {
-    int B = 0;
-    int Bp = 0;                          // B rounded up to the 32-row tile (row count of rc_pk buffers)
-    int dev = 0;
-    rc_params prm{};
-    NetDev net[6];
-    Dense init[3];
-    float *hid1 = nullptr, *hid2 = nullptr, *xtmp = nullptr;
-    FrameBuffers fb{};
-    BodyConst* body = nullptr;
-    float *mesh_vt = nullptr, *mesh_w = nullptr;      // full mesh (metrics only): v_template [V,3], weights [V,24]
-    int mesh_V = 0;
-    float* mesh_kM = nullptr;                         // keypoint regressor folded with the skinning data [n_used][24][4] (metrics only)
-    int mesh_nk = 0;
-    std::vector<float> mesh_vt_h, mesh_w_h, mesh_Jr_h; // host copies: the fold is recomputed when mesh, regressor or root change
-    float jroot_h[3] = {0.f, 0.f, 0.f};
-    bool fold_dirty = false;
-    DevBuf<float> sweep_scratch;                      // per-frame transforms + slab partial sums of the mesh sweeps (grow-only)
-    size_t sweep_scratch_cap = 0;
-    unsigned long long ign_mask = RC_IGN_DEFAULT;     // smplify: landmarks with zeroed confidence
-    bool have_body = false, have_weights = false;
-    std::map<std::string, std::vector<float>> staged;    // host copy of the tensors loaded since the last rc_finalize_weights
-                                                         // (released there: a context does not hold 254 MB of host memory)
-    std::vector<DevBuf<char>> allocs;
-    std::vector<std::pair<void*, size_t>> alloc_bytes;   // (pointer, bytes) of every dev_alloc that is not a weight: state + scratch
-    std::vector<DevBuf<char>> weight_allocs;   // packed weights of the current rc_finalize_weights (freed by the next one)
-    bool alloc_weights = false;          // dev_alloc books into weight_allocs
-    // ordering between the eager entry points (caller's stream) and the live graph (private stream)
-    HipEvent eager_ev;
-    bool eager_dirty = false;
-    std::string err;
-    // live mode: one captured frame on a private stream, pinned host staging
-    HipStream live_stream;
-    HipGraph live_graph;
-    HipGraphExec live_exec;
-    PinBuf<float> live_in_h, live_out_h;                    // pinned: [B,171] and [B,219]
-    DevBuf<float> live_in_d, live_out_d, live_ft_d;
-    float *live_in_io = nullptr, *live_out_io = nullptr;    // what the frame kernels read / write (device copy or mapped host memory)
-    bool live_zero_copy = false;
-    bool live_eager = false;
-    HipGraph live_graph_notr;                               // the same frame without the transition launches
-    HipGraphExec live_exec_notr;
-    std::vector<unsigned char> live_maybe_pend;             // host-side, conservative: row may carry a deferred updater step
-    bool live_prev_known = false;
-    // the lean live frame (rc_live.hip): seven launches for the steady-state frame of a small batch
-    int live_lean = 1;                                      // RC_LIVE_LEAN: 0 = the frame-stepped plan for every live frame
-    int live_lean_nc = 1;                                   // RC_LIVE_LEAN_NC: 16-column blocks per LSTM tile (1 or 2)
-    HipGraph live_graph_lean;
-    HipGraphExec live_exec_lean;
-    LiveFrame live_frame{};
-    int live_aql_on = 1;                                    // RC_LIVE_AQL: 0 = lean frames by hipGraphLaunch only
-    AqlChain* live_aql = nullptr;                           // the lean frame as pre-built AQL packets on a queue of its own (rc_aql.cpp)
-    std::string live_aql_note;                              // why the AQL path is not in use (empty when it is)
-    // the idle-time pre-step (rc_live.hip: rc_live_pre): the recurrent halves of the next frame's layer steps, computed behind a frame
-    // when the caller leaves the device idle between frames (a 60 fps stream: 16.6 ms)
-    int live_prestep = 1;                                   // RC_LIVE_PRESTEP: 0 = never
-    // RC_LIVE_SPIN: the first kernel of the NEXT lean frame is launched at the end of rc_live_step and waits on the device for the frame (rc_live.hip)
-    bool live_spin = false, live_spin_always = false;       // RC_LIVE_SPIN (opt-in since round 6: a paced caller's waiting kernel keeps ~84 workgroups polling between frames --
-                                                            // fine on a dedicated box, hostile on a shared one): 1 behind frames of a paced caller, 2 behind every lean frame
-    volatile unsigned* spin_mb = nullptr;                   // mailbox, host-writable device memory: [0] command, [16] decision
-    float* spin_in = nullptr;                               // the frame's inputs, same allocation
-    PinBuf<unsigned> spin_state_h;                          // pinned: 3 = the waiting kernel gave up
-    int aql_prog_spin[2] = {-1, -1}, aql_prog_spin_pre[2] = {-1, -1};   // by mailbox (frames queued ahead alternate between two)
-    int spin_pending = -1;                                  // program whose first kernel is waiting
-    int spin_pending_par = 0, spin_next_par = 0;            // its mailbox / the next one's
-    unsigned long long spin_pending_seq = 0;                // its frame number on the chain
-    bool live_spin_b2b = true;                              // RC_LIVE_SPIN_B2B: a back-to-back caller's next frame is queued while this one runs, its K1 beside it
-    bool spin_valid = false;                                // nothing has touched weights / state since it was launched
-    long long stat_live_spin = 0, stat_live_spin_lost = 0;  // frames that started from a waiting K1 / waiting K1s sent away or timed out
-    bool live_arm = true;                                   // RC_LIVE_ARM=0 switches it off: a paced caller leaves a barrier packet waiting at the head of the queue
-    double live_prestep_idle_us = 500.0;                    // RC_LIVE_PRESTEP_IDLE_US: idle time in front of a frame from which the next pre-step is enqueued
-    DevBuf<float> live_pre_buf;                             // [tiles of the twelve layer steps][2 waves][64 lanes][4]
-    int aql_prog_lean = -1, aql_prog_lean_pre = -1, aql_prog_pre = -1;     // programs of the AQL chain
-    bool live_pre_valid = false;                            // a pre-step of the CURRENT state is in the queue (or done)
-    bool live_have_return = false;
-    std::chrono::steady_clock::time_point live_last_return{};
-    long long stat_live_pre = 0;
-    PinBuf<int> live_status_h;                              // pinned + mapped: set by a lean frame that met an init_net trigger
-    std::vector<unsigned char> live_may_reach;              // host-side, conservative: the row may still trigger init_net (L178-183)
-    long long stat_live_lean = 0, stat_live_full = 0;
-    long long stat_live_replayed = 0;                       // lean frames whose own check (K1) found them off the lean plan: replayed on the full capture
-    DevBuf<int> live_abort_d;                               // LiveFrame.abort
-    bool live_blind = false;                                // RC_LIVE_MIRROR_BLIND=1 (tests): no host-side mirror of the transition / init_net flags
-    double live_prof_us[4] = {0.0, 0.0, 0.0, 0.0};          // host time of rc_live_step: staging + choice | enqueue | wait | copy out (sums, lean frames)
-    long long live_prof_n = 0;
-    double live_prof_last[6] = {0, 0, 0, 0, 0, 0};          // the same split of the most recent lean frame + {started from a waiting kernel, used a pre-step}
-    // timing of the gate GEMM launches
-    bool timing = false;
-    int timing_mode = 1;                 // 1: every gate-GEMM launch, 2: only the wide-tile kernels, 3: only the shared-weight kernel (rc_gemm_lds_kernel)
-    std::vector<std::pair<HipEvent, HipEvent>> ev_pool;
-    size_t ev_used = 0;
-    double timed_ms = 0.0;
-    double timed_busy_ms = 0.0;          // time with at least one timed launch running (launches on two streams overlap)
-    long long timed_launches = 0;
-    // sequence mode of rc_sequence: launch planner + per-row-cursor wavefront engine (run_wave2_segment)
-    bool gemm_split = false;             // products of every GEMM as split-bf16 partial products (rc_set_gemm_mode)
-    bool live_launch = false;            // set while a live frame is captured / launched (GemmLaunch.live)
-    unsigned live_nt_mask = 63u;         // sub-nets (bit = kNets index) whose weights a live frame streams with non-temporal loads
-    int seq_mode = 1;                    // 0 = always frame-stepped, 1 = plan per call (cost estimate), 2 = wavefront whenever long enough
-    int seq_min_frames = 8;              // calls shorter than this are neither planned nor skewed (no pre-pass, no synchronisation)
-    float* x1_alt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // second relu(linear1) buffer per net
-    int tile6[2] = {0, 0}, tile378[2] = {0, 0}, tile2[2] = {0, 0}, tile4[2] = {0, 0};   // LSTM tile shapes of full-batch stages (0 = pick_tile)
-    bool ring2_failed = false;           // ensure_wave2_buffers failed once: not retried
-    // streams of a tick beside the caller's (stream_tick; caller's stream: plain both wide launches | split {rnn6, rnn4, init_net} | tri rnn4)
-    HipStream aux_stream;                // the second stream, every engine: prep, linear2, fuse, tail; tri also {linear1, init_net} at the head of its tick
-    HipStream wide2_stream;              // plain: unused | split: {H = 512 nets, linear1} | tri: rnn6
-    HipEvent ev_main[8], ev_aux[8], ev_wide2[4];   // [tick & 3]: the last wide launch of the caller's stream | the end of aux_stream's tick | wide2_stream's
-                                                   // launch is done (ev_main[6], [7]: the engine's streams join the caller's)
-    HipStream wide3_stream;              // tri only: the H = 512 nets
-    HipEvent ev_head[4], ev_wide3[4];    // tri only: {linear1, init_net} at the head of aux_stream's tick | wide3_stream's launch is done
-    float* x1_alt2[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // third relu(linear1) buffer per net (linear1 runs up to a tick ahead of its readers)
-    DevBuf<signed char> scan_codes_d;    // [cap] regime code per (frame, row)
-    PinBuf<signed char> scan_codes_h;    // pinned
-    PinBuf<int> scan_state_h;            // pinned: first_reach[B] then pend[B] (as ints)
-    size_t scan_cap = 0;
-    long long stat_wave_frames = 0, stat_stepped_frames = 0, stat_ticks = 0;
-    long long stat_row_frames = 0;       // row-frames computed by sequence calls (rc_get_sequence_row_frames)
-    // rc_sequence_rows: the call's per-row lengths, device + pinned (grow-only, released with the context). The pinned copy has two halves
-    // that calls take in turn, each with an event that says its upload has left it: a call only ever waits for the upload of the call
-    // BEFORE the previous one, which has long run.
-    DevBuf<int> row_len_d;
-    PinBuf<int> row_len_h;               // [2][row_len_cap]
-    size_t row_len_cap = 0;
-    HipEvent row_len_ev[2];
-    unsigned row_len_turn = 0;
-    // per-row-cursor wavefront engine (run_wave2_segment)
-    bool ring2_ready = false;
-    FrameBuffers ring2[16];              // ring slots: inter-stage buffers, updater inputs, frame index and step numbers per row
-    std::vector<GemmProblem> wave2_prob; // [16 slots][W2_PROB]
-    bool wave2_valid = false;
-    DevBuf<int> frame_at_d;              // [cap] host plan: frame every row starts at every tick
-    PinBuf<int> frame_at_h;              // pinned
-    size_t frame_at_cap = 0;
-    double cost_tick_us = 1.0, cost_tick_small_us = 13.0, cost_frame_us = 285.0, cost_tr_us = 55.0;   // engine choice (plan_wave): scale of the
-                                                         // per-layer tick estimate, hand-over per tick, frame-stepped frame, its transition launches
-    SmplifyOwner smplify;                // optimiser work space (rc_smplify_api.cpp)
-    SubnetOwner subnet;                  // scratch of rc_subnet_forward (rc_subnet_api.cpp)
-    int trace_next = 0;                  // tile-trace slot counter (tools/tile_trace.py)
-    long long stat_wide_launches = 0;    // launches of the wide-tile kernels (rc_get_launch_stats)
-    // shared-weight gate GEMM (rc_gemm_lds.hip): LSTM layer steps of >= lds_min_rows rows in split-product mode
-    // Two thresholds (round 6, second session; tools/ab_batch.py): a CONTEXT takes the shared-weight kernel and the three-stream tick from
-    // lds_min_batch rows (batch 64 loses a sixth with them: 688k -> 576k mixed), and inside such a context a PROBLEM runs on it from
-    // lds_min_rows rows (the rnn4 / rnn6 problems of a mixed batch hold only the rows that see the camera). One threshold of 160 for both
-    // (first session) left batch 96-128 on the 64-row tiles: batch 128 mixed 858k -> 933k, all-visible 1,073k -> 1,173k; 96: 691k -> 752k.
-    int lds_min_rows = 64;               // RC_LDS_MIN_ROWS (0 = never); default: half the batch, within 64 .. 160 (batch 256: 128 = 160 within the noise, 64 costs 0.7 %)
-    int lds_min_batch = 65;              // RC_LDS_MIN_BATCH: batch 72 / 80 / 88 mixed 528 / 587 / 653k on 64-row tiles (two row tiles, the second mostly padding) -> 585 / 654 / 691k;
-                                         // 64 rows and fewer keep the one-reader 64-row launches (688k against 576k)
-    int lds_ksplit[3] = {1, 2, 2};       // RC_LDS_KSPLIT_512 / _1024 / _1280: workgroups per tile (1: both K halves in one workgroup; the H = 512
-                                         // nets' items are short -- 2 x 16 k-blocks -- and a hand-over per tile costs more than it levels: +1 %)
-    DevBuf<float> lds_slab;              // [kLdsRegions][lds_region_tiles][RC_LDS_SLAB_FLOATS]: half sums in flight, one region per launch
-    DevBuf<int> lds_tickets;             // [kLdsRegions][lds_region_tiles]
-    size_t lds_region_tiles = 0;
-    unsigned lds_rot = 0;
-    // resident layer-step kernel of the wavefront engine (run_resident_segment)
-    DevBuf<ResidentTick> res_ticks_d;        // [res_cap]
-    PinBuf<ResidentTick> res_ticks_h;        // pinned
-    DevBuf<int> res_ints_d;                  // item_base [res_cap + 1] | done [res_cap][RC_RES_MAXP] | tick_done [res_cap] | head, flag_l1, flag_tail, abort
-    PinBuf<int> res_base_h;                  // pinned: item_base
-    PinBuf<int> res_abort_h;                 // pinned: the abort word of the last segment (allocated with the first resident segment)
-    size_t res_cap = 0;
-    long long stat_resident_segments = 0, stat_resident_aborts = 0;
-    bool live_selfcheck_ran = false;         // rc_live_begin compared the packet chain with the graph replay (live_selfcheck)
-    bool resident_on = false;                // rc_set_resident / RC_SEQ_RESIDENT
-    int resident_wgs = 224;                  // workgroups of the resident kernel (RC_SEQ_RESIDENT_WGS; the CUs it leaves run the second stream)
-    long long stat_lds_launches = 0;
-    long long stat_w32_launches = 0;         // of the wide launches: those on rc_gemm_split48_w32_kernel (contexts of 33-64 rows)
-};
-
-namespace {
+static thread_local std::string g_create_error;
 
 int fail(rc_ctx* ctx, int code, const std::string& msg) {
     if (ctx) ctx->err = msg; else g_create_error = msg;
     return code;
 }
+
+namespace {
+
+const int kInit[3][2] = {{69, 512}, {512, 1024}, {1024, 2048}};
 
 template <typename T>
 int dev_alloc(rc_ctx* ctx, T** p, size_t count, bool zero = true) {
@@ -267,32 +60,6 @@ int dev_alloc(rc_ctx* ctx, T** p, size_t count, bool zero = true) {
     return RC_OK;
 }
 
-// Eager work was enqueued on the caller's stream `st`: the next live-graph replay (private stream) must wait for it.
-// (The other direction needs nothing: rc_live_step synchronises its stream before it returns.)
-// A frame queued ahead of its inputs (RC_LIVE_SPIN / the back-to-back queue-ahead: its first kernel polls a mailbox on the device) is sent
-// away and waited for BEFORE anything else touches the context: its kernels change nothing once dismissed (LiveFrame.abort -- K4 skips
-// its relu(linear1) store as well since round 6), but a kernel left polling would hold CUs through a long rc_sequence and leave 100 ms later.
-int dismiss_queued_frame(rc_ctx* ctx) {
-    if (ctx->spin_pending < 0 || !ctx->live_aql || !ctx->spin_mb) return RC_OK;
-    const int par = ctx->spin_pending_par;
-    ctx->spin_mb[32 * par] = 2u;
-    RC_STORE_FENCE();
-    const int arc = rc_aql_wait_frame(ctx->live_aql);
-    ctx->spin_state_h[4 * par] = 0;
-    ctx->stat_live_spin_lost += 1;
-    ctx->spin_pending = -1;
-    return arc == 0 ? RC_OK : fail(ctx, RC_ERR_HIP, "the live frame queued ahead did not leave");
-}
-
-int mark_eager(rc_ctx* ctx, hipStream_t st) {
-    ctx->live_pre_valid = false;         // the state the pre-step read is no longer the state the next live frame starts from
-    ctx->spin_valid = false;
-    if (int rc = dismiss_queued_frame(ctx)) return rc;
-    if (!ctx->eager_ev) return RC_OK;
-    HIP_TRY(ctx, hipEventRecord(ctx->eager_ev.get(), st));
-    ctx->eager_dirty = true;
-    return RC_OK;
-}
 
 // MFMA-B fragment order (v_mfma_f32_16x16x4_f32): for 16-column block cb and 16-wide k-chunk q, lane l = kq*16 + j
 // holds the float4 W'[cb*16 + j][16q + 4kq + 0..3]; blocks are laid out [cb][q][lane][4] so that a wave's K slice of
@@ -782,6 +549,8 @@ int run_stage(rc_ctx* ctx, const std::vector<Stage>& nets, bool with_lin2, const
     return RC_OK;
 }
 
+}  // namespace
+
 rc_params_dev dev_params(const rc_params& p) {
     rc_params_dev d{};
     d.conf_lo = p.conf_lo; d.conf_hi = p.conf_hi; d.tran_filter_num = p.tran_filter_num;
@@ -793,11 +562,9 @@ rc_params_dev dev_params(const rc_params& p) {
     return d;
 }
 
-int tune_env(const char* name, int dflt);
-
-int step_impl(rc_ctx* ctx, const FrameIO& io, uint32_t flags, hipStream_t st, bool with_tr = true, bool skip_prep = false,
-              const FrameIO* next_io = nullptr,     // skip_prep / next_io: the previous / this frame's tail runs the next prep
-              int n_live = -1) {                    // rc_sequence_rows: rows that have this frame (-1: all of them)
+int step_impl(rc_ctx* ctx, const FrameIO& io, uint32_t flags, hipStream_t st, bool with_tr, bool skip_prep,
+              const FrameIO* next_io,     // skip_prep / next_io: the previous / this frame's tail runs the next prep
+              int n_live) {                    // rc_sequence_rows: rows that have this frame (-1: all of them)
     const int B = ctx->B;
     const FrameBuffers& fb = ctx->fb;
     const rc_params_dev prm = dev_params(ctx->prm);
@@ -855,11 +622,11 @@ int step_impl(rc_ctx* ctx, const FrameIO& io, uint32_t flags, hipStream_t st, bo
     return RC_OK;
 }
 
+namespace {
+
 // run every pending (deferred) updater step now: state then equals the reference's at the end of its frame
 int flush_pending(rc_ctx* ctx, hipStream_t st) {
-    ctx->live_pre_valid = false;
-    ctx->spin_valid = false;
-    if (int rc = dismiss_queued_frame(ctx)) return rc;
+    if (int rc = live_discard_ahead(ctx)) return rc;
     if (!ctx->have_weights || !ctx->prm.use_vision_updater) return RC_OK;
     const FrameBuffers& fb = ctx->fb;
     rc_launch_flush_flags(fb, ctx->B, st);
@@ -895,10 +662,14 @@ const TickStage kTick[RC_TICK_PROB] = {
     {3, N4, 4, G_LIN2}, {3, N2, 4, G_LIN2}, {3, N6, 8, G_LIN2}, {3, N3, 8, G_LIN2}, {3, N7, 8, G_LIN2}, {3, N8, 8, G_LIN2}};
 const int kFuseStage = 4, kTailStage = 8, kInitStage = 5;
 
+}  // namespace
+
 int tune_env(const char* name, int dflt) {
     const char* v = std::getenv(name);
     return v && *v ? std::atoi(v) : dflt;
 }
+
+namespace {
 
 // Frame-stepped launch plan of a rc_sequence call from the regime codes (pure host logic, exposed as rc_plan_sequence for
 // tests): the three transition launches are needed on the frames where some row carries a deferred updater step INTO a frame
@@ -1582,6 +1353,8 @@ int reserve_plan_tables(rc_ctx* ctx, int T) {
     return reserve_frame_at(ctx, fneed, fneed);
 }
 
+}  // namespace
+
 int check_ready(rc_ctx* ctx) {
     if (!ctx) return RC_ERR_INVALID;
     if (!ctx->have_weights) return fail(ctx, RC_ERR_STATE, "weights not finalized (rc_finalize_weights)");
@@ -1589,7 +1362,6 @@ int check_ready(rc_ctx* ctx) {
     return RC_OK;
 }
 
-}  // namespace
 
 // =============================================================================================== C ABI
 const BodyConst* rc_ctx_body(rc_ctx* ctx) { return ctx->have_body ? ctx->body : nullptr; }
@@ -1614,66 +1386,6 @@ SubnetOwner& rc_ctx_subnet(rc_ctx* ctx) { return ctx->subnet; }
 SmplifyOwner& rc_ctx_smplify(rc_ctx* ctx) { return ctx->smplify; }
 unsigned long long rc_ctx_ign_mask(rc_ctx* ctx) { return ctx->ign_mask; }
 
-// Begin-time self-check of the AQL packet chain (round-4/5 review): ONE lean frame on a fixed synthetic input, once as the graph replay
-// of the captured launches and once as the pre-built packets on the context's own HSA queue, from the same state -- every small device
-// buffer of the context (recurrent state, fusion state, scratch; weights excluded) is saved first and put back after each run, so the
-// check leaves no trace. Outputs must agree bit for bit (same kernels, same arguments); if they do not, or the chain does not retire, the
-// chain is dropped and live frames replay the graph (rc_get_live_backend tells). RC_LIVE_AQL_SELFCHECK=0 skips it, =2 forces the
-// mismatch path (tests/test_gpu_live.py). live_server.py:40-48 is the loop this protects.
-std::string live_selfcheck(rc_ctx* ctx) {
-    static const int mode = std::getenv("RC_LIVE_AQL_SELFCHECK") ? std::atoi(std::getenv("RC_LIVE_AQL_SELFCHECK")) : 1;
-    if (mode == 0 || !ctx->live_aql || ctx->aql_prog_lean < 0 || !ctx->live_exec_lean || !ctx->live_zero_copy) return std::string();
-    const size_t B = ctx->B;
-    hipStream_t st = ctx->live_stream.get();
-    if (hipDeviceSynchronize() != hipSuccess) return "self-check: device synchronisation failed";
-    // save
-    const size_t kMaxBytes = 8u << 20;
-    std::vector<std::pair<void*, size_t>> regs;
-    size_t total = 0;
-    for (const auto& r : ctx->alloc_bytes) if (r.second <= kMaxBytes) { regs.push_back(r); total += r.second; }
-    std::vector<char> save(total);
-    size_t off = 0;
-    for (const auto& r : regs) { if (hipMemcpy(save.data() + off, r.first, r.second, hipMemcpyDeviceToHost) != hipSuccess) return "self-check: state read-back failed"; off += r.second; }
-    auto restore = [&]() -> bool {
-        size_t o = 0;
-        for (const auto& r : regs) { if (hipMemcpy(r.first, save.data() + o, r.second, hipMemcpyHostToDevice) != hipSuccess) return false; o += r.second; }
-        ctx->live_status_h[0] = 0;
-        return hipDeviceSynchronize() == hipSuccess;
-    };
-    // a mid-confidence frame (no init_net trigger, no deferred updater step): identity orientations, small accelerations, a plausible skeleton
-    std::vector<float> in_keep(ctx->live_in_h.get(), ctx->live_in_h.get() + B * 171), out_keep(ctx->live_out_h.get(), ctx->live_out_h.get() + B * 219);
-    for (size_t b = 0; b < B; ++b) {
-        float* j = ctx->live_in_h.get() + b * 99;
-        for (int k = 0; k < 33; ++k) { j[3 * k] = 0.05f * (float)((k * 7) % 11 - 5) / 5.0f; j[3 * k + 1] = 0.08f * (float)((k * 5) % 13 - 6) / 6.0f; j[3 * k + 2] = 0.75f; }
-        float* a = ctx->live_in_h.get() + B * 99 + b * 18;
-        for (int k = 0; k < 18; ++k) a[k] = 0.01f * (float)(k % 5 - 2);
-        float* o = ctx->live_in_h.get() + B * 117 + b * 54;
-        for (int k = 0; k < 54; ++k) o[k] = (k % 9 == 0 || k % 9 == 4 || k % 9 == 8) ? 1.0f : 0.0f;
-    }
-    std::string verdict;
-    std::vector<float> out_graph(B * 219), out_aql(B * 219);
-    int status_graph = 0, status_aql = 0;
-    for (size_t q = 0; q < B * 219; ++q) ctx->live_out_h[q] = -7.0f;
-    if (hipGraphLaunch(ctx->live_exec_lean.get(), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) verdict = "self-check: graph replay of the lean frame failed";
-    status_graph = ctx->live_status_h[0];
-    std::copy(ctx->live_out_h.get(), ctx->live_out_h.get() + B * 219, out_graph.begin());
-    if (!restore() && verdict.empty()) verdict = "self-check: state restore failed";
-    if (verdict.empty()) {
-        for (size_t q = 0; q < B * 219; ++q) ctx->live_out_h[q] = -7.0f;
-        if (rc_aql_run(ctx->live_aql, ctx->aql_prog_lean) != 0) verdict = "self-check: the packet chain did not retire";
-        status_aql = ctx->live_status_h[0];
-        std::copy(ctx->live_out_h.get(), ctx->live_out_h.get() + B * 219, out_aql.begin());
-        if (mode == 2) { uint32_t u; std::memcpy(&u, &out_aql[0], 4); u ^= 1u; std::memcpy(&out_aql[0], &u, 4); }      // forced mismatch (test hook)
-        if (!restore() && verdict.empty()) verdict = "self-check: state restore failed";
-    }
-    std::copy(in_keep.begin(), in_keep.end(), ctx->live_in_h.get());
-    std::copy(out_keep.begin(), out_keep.end(), ctx->live_out_h.get());
-    if (verdict.empty() && (status_graph != status_aql || std::memcmp(out_graph.data(), out_aql.data(), B * 219 * sizeof(float)) != 0)) {
-        verdict = "self-check: packet chain and graph replay disagree on the probe frame";
-    }
-    ctx->live_selfcheck_ran = true;
-    return verdict;
-}
 
 extern "C" {
 
@@ -1702,21 +1414,9 @@ int rc_create(int32_t batch, int32_t live, rc_ctx** out) {
     ctx->B = batch;
     ctx->Bp = round_up(batch, RC_MT);
     (void)hipGetDevice(&ctx->dev);
-    (void)hipEventCreateWithFlags(rc_out(ctx->eager_ev), hipEventDisableTiming);      // (without it the live graph does not wait for eager work)
     rc_default_params(live, &ctx->prm);
     ctx->gemm_split = tune_env("RC_GEMM_SPLIT", batch >= RC_SPLIT_MIN_BATCH ? 1 : 0) != 0;
-    ctx->live_eager = tune_env("RC_LIVE_EAGER", 0) != 0;
-    ctx->live_nt_mask = (unsigned)tune_env("RC_LIVE_NT_MASK", 63);
-    ctx->live_lean = tune_env("RC_LIVE_LEAN", 1);
-    ctx->live_lean_nc = tune_env("RC_LIVE_LEAN_NC", 1) == 2 ? 2 : 1;
-    ctx->live_aql_on = tune_env("RC_LIVE_AQL", 1);
-    ctx->live_prestep = tune_env("RC_LIVE_PRESTEP", 1);
-    ctx->live_prestep_idle_us = (double)tune_env("RC_LIVE_PRESTEP_IDLE_US", 500);
-    ctx->live_arm = tune_env("RC_LIVE_ARM", 1) != 0;
-    ctx->live_spin = tune_env("RC_LIVE_SPIN", 0) != 0;
-    ctx->live_spin_always = tune_env("RC_LIVE_SPIN", 0) >= 2;
-    ctx->live_spin_b2b = tune_env("RC_LIVE_SPIN_B2B", 1) != 0;
-    ctx->live_blind = tune_env("RC_LIVE_MIRROR_BLIND", 0) != 0;
+    live_create(ctx);
     ctx->seq_mode = tune_env("RC_SEQ_MODE", 1);          // 0 frame-stepped, 1 plan + cost estimate, 2 wavefront whenever long enough
     if (ctx->seq_mode < 0 || ctx->seq_mode > 2) ctx->seq_mode = 1;
     ctx->cost_tick_us = tune_env("RC_COST_TICK_PCT", 100) / 100.0;
@@ -1965,8 +1665,7 @@ int rc_set_gravity(rc_ctx* ctx, const float* g) {
 
 int rc_reset(rc_ctx* ctx, const uint8_t* row_mask, void* stream) {
     if (!ctx) return RC_ERR_INVALID;
-    ctx->live_prev_known = false;
-    ctx->live_may_reach.assign(ctx->B, 1);
+    live_forget_last_frame(ctx, true);
     float* h[6]; float* c[6]; int H[6];
     for (int i = 0; i < 6; ++i) { h[i] = ctx->net[i].h; c[i] = ctx->net[i].c; H[i] = ctx->net[i].H; }
     rc_launch_reset(ctx->fb, h, c, H, row_mask, ctx->B, (hipStream_t)stream);
@@ -1977,7 +1676,7 @@ int rc_reset(rc_ctx* ctx, const uint8_t* row_mask, void* stream) {
 int rc_step(rc_ctx* ctx, const float* j2dc, const float* accc, const float* oric, const float* first_tran, uint32_t flags,
             float* pose_out, float* tran_out, void* stream) {
     if (int rc = check_ready(ctx)) return rc;
-    ctx->live_prev_known = false;                      // the live path's host-side flag mirror no longer knows the last frame
+    live_forget_last_frame(ctx);                       // the live path's host-side flag mirror no longer knows the last frame
     if (!j2dc || !accc || !oric || !pose_out || !tran_out) return fail(ctx, RC_ERR_INVALID, "rc_step: null buffer");
     FrameIO io{j2dc, accc, oric, first_tran, pose_out, tran_out, 99, 18, 54, 216, 3};
     if (int rc = step_impl(ctx, io, flags, (hipStream_t)stream)) return rc;
@@ -2122,7 +1821,7 @@ int rc_sequence(rc_ctx* ctx, int32_t T, const float* j2dc, int64_t rs_j2d, const
                 int64_t rs_tran, void* stream) {
     if (int rc = check_ready(ctx)) return rc;
     if (T == 0) return RC_OK;                                               // (evaluate.py:75-83 over no frames: nothing happens, whatever the pointers)
-    ctx->live_prev_known = false;
+    live_forget_last_frame(ctx);
     if (T < 0 || !j2dc || !accc || !oric || !pose_out || !tran_out) return fail(ctx, RC_ERR_INVALID, "rc_sequence: bad argument");
     return sequence_impl(ctx, T, nullptr, 0, j2dc, rs_j2d, accc, rs_acc, oric, rs_ori, first_tran, flags, pose_out, rs_pose, tran_out, rs_tran, stream);
 }
@@ -2136,7 +1835,7 @@ int rc_sequence_rows(rc_ctx* ctx, int32_t T, const int32_t* len_host, const floa
     for (size_t b = 0; b < B; ++b)
         if (len_host[b] < 0 || len_host[b] > T) return fail(ctx, RC_ERR_INVALID, "rc_sequence_rows: a row's length is outside 0 .. T");
     if (T == 0) return RC_OK;
-    ctx->live_prev_known = false;
+    live_forget_last_frame(ctx);
     hipStream_t st = (hipStream_t)stream;
     // the lengths travel once per call: pinned copy -> device copy on `stream`, in front of everything that reads them
     for (HipEvent& ev : ctx->row_len_ev)                                      // (before the capacity moves: a failure here is retried whole)
@@ -2251,426 +1950,6 @@ int rc_plan_wave_rows(const int8_t* codes, int32_t B, int32_t T, int32_t t0, con
     for (int b = 0; b < B; ++b) if (len[b] < 0 || len[b] > T) return RC_ERR_INVALID;
     return plan_wave_abi(codes, B, T, t0, len, first_reach, pend, use_imu_updater, use_vision_updater, frame_at, frame_at_cap, n_ticks, n_prep,
                          counts, est_us);
-}
-
-int rc_live_end(rc_ctx* ctx) {
-    if (!ctx) return RC_ERR_INVALID;
-    // (order: the packet chain goes before the buffers its packets read, every graph exec before its graph)
-    ctx->live_exec.reset(); ctx->live_graph.reset(); ctx->live_exec_notr.reset();
-    if (ctx->live_aql) { rc_aql_destroy(ctx->live_aql); ctx->live_aql = nullptr; }     // (waits for a pre-step still in flight; tells a waiting K1 to leave)
-    ctx->spin_mb = nullptr; ctx->spin_in = nullptr; ctx->spin_pending = -1; ctx->spin_valid = false;
-    for (int q = 0; q < 2; ++q) ctx->aql_prog_spin[q] = ctx->aql_prog_spin_pre[q] = -1;
-    ctx->spin_state_h.reset(); ctx->live_pre_buf.reset();
-    ctx->aql_prog_lean = ctx->aql_prog_lean_pre = ctx->aql_prog_pre = -1;
-    ctx->live_pre_valid = false; ctx->live_have_return = false;
-    ctx->live_exec_lean.reset(); ctx->live_graph_lean.reset(); ctx->live_status_h.reset(); ctx->live_abort_d.reset();
-    ctx->live_graph_notr.reset(); ctx->live_stream.reset();
-    ctx->live_in_h.reset(); ctx->live_out_h.reset(); ctx->live_in_d.reset(); ctx->live_out_d.reset(); ctx->live_ft_d.reset();
-    return RC_OK;
-}
-
-int rc_live_begin(rc_ctx* ctx) {
-    if (int rc = check_ready(ctx)) return rc;
-    rc_live_end(ctx);
-    const size_t B = ctx->B;
-    HIP_TRY(ctx, hipStreamCreateWithFlags(rc_out(ctx->live_stream), hipStreamNonBlocking));
-    HIP_TRY(ctx, rc_alloc(ctx->live_in_h, B * 171, hipHostMallocMapped));
-    HIP_TRY(ctx, rc_alloc(ctx->live_out_h, B * 219, hipHostMallocMapped));
-    HIP_TRY(ctx, rc_alloc_all(ctx->live_in_d, B * 171, ctx->live_out_d, B * 219, ctx->live_ft_d, B * 3));
-    // Small batches: the frame kernels read the 684 B / body of inputs and write the 876 B of outputs straight from / to
-    // the pinned host buffers (two copy nodes and their barriers cost more than the PCIe reads). Larger batches keep
-    // H2D -> frame -> D2H. Layout: inputs [j2dc B*99 | accc B*18 | oric B*54], outputs [pose B*216 | tran B*3].
-    ctx->live_zero_copy = B <= 16;
-    ctx->live_in_io = ctx->live_in_d.get();
-    ctx->live_out_io = ctx->live_out_d.get();
-    if (ctx->live_zero_copy) {
-        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->live_in_io, ctx->live_in_h.get(), 0));
-        HIP_TRY(ctx, hipHostGetDevicePointer((void**)&ctx->live_out_io, ctx->live_out_h.get(), 0));
-    }
-    hipStream_t st = ctx->live_stream.get();
-    const bool timing = ctx->timing;
-    struct TimingGuard { rc_ctx* c; bool v; ~TimingGuard() { c->timing = v; } } timing_guard{ctx, timing};   // restored on every exit path
-    ctx->timing = false;
-    // Two captures of the frame: with and without the three transition launches. rc_live_step replays the short one
-    // when the host can rule out that any row carries a deferred updater step into a frame it steps on camera data.
-    FrameIO io{ctx->live_in_io, ctx->live_in_io + B * 99, ctx->live_in_io + B * 117, nullptr,
-               ctx->live_out_io, ctx->live_out_io + B * 216, 99, 18, 54, 216, 3};
-    int rc = RC_OK;
-    for (int v = 0; v < 2 && !rc; ++v) {
-        HIP_TRY(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_in_d.get(), ctx->live_in_h.get(), B * 171 * sizeof(float), hipMemcpyHostToDevice, st);
-        ctx->live_launch = true;
-        rc = step_impl(ctx, io, 0u, st, v == 0);
-        ctx->live_launch = false;
-        if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_out_h.get(), ctx->live_out_d.get(), B * 219 * sizeof(float), hipMemcpyDeviceToHost, st);
-        HipGraph& g = v == 0 ? ctx->live_graph : ctx->live_graph_notr;
-        const hipError_t e = hipStreamEndCapture(st, rc_out(g));
-        if (!rc && e != hipSuccess) rc = fail(ctx, RC_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        if (!rc && hipGraphInstantiate(rc_out(v == 0 ? ctx->live_exec : ctx->live_exec_notr), g.get(), nullptr, nullptr, 0) != hipSuccess)
-            rc = fail(ctx, RC_ERR_HIP, "hipGraphInstantiate");
-    }
-    // The lean plan of the steady-state frame (rc_live.hip): seven launches. rc_live_step replays it when the frame needs neither a
-    // transition step nor init_net and is not a sequence start; every other frame takes the captures above.
-    // (fp32-MFMA contexts only: the lean kernels stream the fp32 weights, a context switched to split products keeps one arithmetic)
-    // The lean plan is an OPTION on top of the two captures above: whatever fails in here (an allocation, its capture, the AQL chain) leaves
-    // the context on those captures with a note (rc_get_live_backend), and never fails rc_live_begin (round-4 advice).
-    if (!rc && ctx->live_lean && B <= RC_LIVE_MAXB && !ctx->gemm_split) {
-        ctx->live_aql_note.clear();
-        auto lean_setup = [&]() -> std::string {
-            if (rc_alloc(ctx->live_status_h, 1, hipHostMallocMapped) != hipSuccess) return "lean frame: status word allocation failed";
-            ctx->live_status_h[0] = 0;
-            if (rc_alloc(ctx->live_abort_d, 16) != hipSuccess || hipMemset(ctx->live_abort_d.get(), 0, 64) != hipSuccess) return "lean frame: abort word allocation failed";
-            LiveFrame& F = ctx->live_frame;
-            F = LiveFrame{};
-            for (int i = 0; i < 6; ++i) {
-                const NetDev& n = ctx->net[i];
-                LiveNet& l = F.net[i];
-                l.W1 = n.lin1.W; l.b1 = n.lin1.b;
-                for (int q = 0; q < 2; ++q) { l.Wl[q] = n.Wl[q]; l.bl[q] = n.bl[q]; }
-                l.W2 = n.lin2.Wrm; l.b2 = n.lin2.b;
-                l.x1 = n.x1; l.h = n.h; l.c = n.c; l.part = n.part; l.steps = n.steps;
-                l.H = n.H; l.out = n.out; l.outp = round_up(n.out, 4); l.Kp1 = n.lin1.Kp;
-                l.BpH = (long long)ctx->Bp * n.H;
-            }
-            F.fb = ctx->fb; F.io = io; F.prm = dev_params(ctx->prm); F.body = ctx->body; F.B = (int)B; F.nc = ctx->live_lean_nc;
-            if (hipHostGetDevicePointer((void**)&F.status, ctx->live_status_h.get(), 0) != hipSuccess) return "lean frame: status word not mapped";
-            F.abort = ctx->live_abort_d.get();
-            std::vector<LiveKernel> plan(RC_LIVE_KERNELS);
-            const int nk = rc_live_plan(F, plan.data());
-            if (nk != RC_LIVE_KERNELS) return "lean frame: sub-net sizes these kernels are not compiled for";
-            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) return "lean frame: hipStreamBeginCapture failed";
-            if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_in_d.get(), ctx->live_in_h.get(), B * 171 * sizeof(float), hipMemcpyHostToDevice, st);
-            rc_launch_live_frame(F, st);
-            if (!ctx->live_zero_copy) (void)hipMemcpyAsync(ctx->live_out_h.get(), ctx->live_out_d.get(), B * 219 * sizeof(float), hipMemcpyDeviceToHost, st);
-            const hipError_t e = hipStreamEndCapture(st, rc_out(ctx->live_graph_lean));      // (always ended: the stream must not stay in capture mode)
-            if (e != hipSuccess) return std::string("lean frame: hipStreamEndCapture: ") + hipGetErrorString(e);
-            if (hipGraphInstantiate(rc_out(ctx->live_exec_lean), ctx->live_graph_lean.get(), nullptr, nullptr, 0) != hipSuccess) return "lean frame: hipGraphInstantiate failed";
-            // ... and the same seven dispatches as pre-built AQL packets (rc_aql.cpp); without them the graph above is replayed.
-            // Not under a tool that intercepts the HSA queues (rocprofv3's interception crashes on packets written straight into the ring --
-            // ROCm 7.2; traces then show the graph replay of the same kernels; a debugger's or tracer's runtime hooks are treated alike).
-            // RC_LIVE_AQL=2 insists.
-            const char* preload = std::getenv("LD_PRELOAD");
-            bool tool = std::getenv("ROCP_TOOL_LIBRARIES") || std::getenv("HSA_TOOLS_LIB") || std::getenv("ROCPROFILER_REGISTER_FORCE_LOAD") ||
-                        std::getenv("ROCR_DEBUG_AGENT") || std::getenv("HSA_ENABLE_DEBUG");
-            for (const char* sub : {"rocprof", "roctracer", "rocm-debug", "rocgdb", "omnitrace", "rocprofiler"}) tool = tool || (preload && std::strstr(preload, sub));
-            if (tool && ctx->live_aql_on == 1) ctx->live_aql_note = "a profiling / debugging tool intercepts the HSA queues";
-            else if (ctx->live_aql_on && ctx->live_zero_copy && !ctx->live_eager) {
-                char msg[256] = {0};
-                if (rc_aql_create(ctx->dev, &ctx->live_aql, msg, (int)sizeof(msg)) != 0) { ctx->live_aql = nullptr; ctx->live_aql_note = msg; }
-                else if ((ctx->aql_prog_lean = rc_aql_add(ctx->live_aql, plan.data(), nk, 1, msg, (int)sizeof(msg))) < 0) {
-                    rc_aql_destroy(ctx->live_aql); ctx->live_aql = nullptr; ctx->live_aql_note = msg;
-                } else if (ctx->live_prestep && F.nc == 1) {
-                    // the pre-step and the frame that starts from its partial sums: two more programs on the same queue; without them
-                    // (an allocation or a symbol failed) the chain simply keeps the one frame program
-                    const size_t nf = (size_t)rc_live_pre_floats(F);
-                    if (rc_alloc(ctx->live_pre_buf, nf) == hipSuccess && hipMemset(ctx->live_pre_buf.get(), 0, nf * sizeof(float)) == hipSuccess) {
-                        std::vector<LiveKernel> plan2(RC_LIVE_KERNELS), plan3(2);
-                        const int n3 = rc_live_pre_plan(F, ctx->live_pre_buf.get(), plan3.data());
-                        if (rc_live_plan(F, plan2.data(), ctx->live_pre_buf.get()) == RC_LIVE_KERNELS && n3 >= 1) {
-                            ctx->aql_prog_lean_pre = rc_aql_add(ctx->live_aql, plan2.data(), RC_LIVE_KERNELS, 1, msg, (int)sizeof(msg));
-                            if (ctx->aql_prog_lean_pre >= 0) ctx->aql_prog_pre = rc_aql_add(ctx->live_aql, plan3.data(), n3, 0, msg, (int)sizeof(msg));
-                        }
-                    } else { ctx->live_pre_buf.reset(); (void)hipGetLastError(); }
-                    if (ctx->aql_prog_pre < 0) ctx->aql_prog_lean_pre = -1;
-                }
-                // RC_LIVE_SPIN: the same programs once more with the inputs and a mailbox in host-writable device memory; their first
-                // kernel is launched ahead of the frame and waits there (rc_live_k1)
-                if (ctx->live_aql && (ctx->live_spin || ctx->live_spin_b2b) && ctx->aql_prog_lean >= 0 && RC_LIVE_KERNELS * 6 + 8 <= 64) {
-                    void* shared = nullptr;
-                    unsigned* state_d = nullptr;
-                    if (rc_aql_alloc_shared(ctx->live_aql, 4096 + B * 171 * sizeof(float), &shared) == 0 &&
-                        rc_alloc(ctx->spin_state_h, 16, hipHostMallocMapped) == hipSuccess &&
-                        hipHostGetDevicePointer((void**)&state_d, ctx->spin_state_h.get(), 0) == hipSuccess) {
-                        for (int q = 0; q < 16; ++q) ctx->spin_state_h[q] = 0;
-                        ctx->spin_mb = (volatile unsigned*)shared;
-                        ctx->spin_in = (float*)((char*)shared + 4096);
-                        for (int q = 0; q < 64; ++q) ctx->spin_mb[q] = 0u;
-                        LiveFrame Fs = F;
-                        Fs.io.j2d = ctx->spin_in; Fs.io.acc = ctx->spin_in + B * 99; Fs.io.ori = ctx->spin_in + B * 117;
-                        std::vector<LiveKernel> ps(RC_LIVE_KERNELS);
-                        bool ok = true;
-                        for (int par = 0; par < 2 && ok; ++par) {                   // two mailboxes (and give-up marks): the next frame is queued while this one may still be read
-                            Fs.spin_mb = (unsigned*)shared + 32 * par; Fs.spin_state = state_d + 4 * par;
-                            if (rc_live_plan(Fs, ps.data()) == RC_LIVE_KERNELS) ctx->aql_prog_spin[par] = rc_aql_add(ctx->live_aql, ps.data(), RC_LIVE_KERNELS, 1, msg, (int)sizeof(msg));
-                            ok = ctx->aql_prog_spin[par] >= 0;
-                            if (ok && ctx->aql_prog_lean_pre >= 0 && rc_live_plan(Fs, ps.data(), ctx->live_pre_buf.get()) == RC_LIVE_KERNELS)
-                                ctx->aql_prog_spin_pre[par] = rc_aql_add(ctx->live_aql, ps.data(), RC_LIVE_KERNELS, 1, msg, (int)sizeof(msg));
-                        }
-                        if (!ok) ctx->aql_prog_spin[0] = ctx->aql_prog_spin[1] = -1;
-                        if (ctx->aql_prog_spin_pre[0] < 0 || ctx->aql_prog_spin_pre[1] < 0) ctx->aql_prog_spin_pre[0] = ctx->aql_prog_spin_pre[1] = -1;
-                        if (ok) rc_aql_set_mailbox(ctx->live_aql, ctx->spin_mb);
-                    }
-                    if (ctx->aql_prog_spin[0] < 0) { ctx->spin_mb = nullptr; ctx->spin_in = nullptr; (void)hipGetLastError(); }
-                }
-            } else ctx->live_aql_note = "switched off";
-            return std::string();
-        };
-        const std::string why = lean_setup();
-        if (!why.empty()) {                                                // back to the two full captures
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) { HipGraph g; (void)hipStreamEndCapture(st, rc_out(g)); }
-            (void)hipGetLastError();
-            ctx->live_exec_lean.reset(); ctx->live_graph_lean.reset();
-            ctx->live_aql_note = why;
-        } else if (ctx->live_aql) {
-            const std::string bad = live_selfcheck(ctx);
-            if (!bad.empty()) {                                            // drop the chain, keep the lean graph: frames replay it
-                rc_aql_destroy(ctx->live_aql); ctx->live_aql = nullptr;
-                ctx->spin_mb = nullptr; ctx->spin_in = nullptr; ctx->spin_pending = -1; ctx->spin_valid = false;
-                for (int q = 0; q < 2; ++q) ctx->aql_prog_spin[q] = ctx->aql_prog_spin_pre[q] = -1;
-                ctx->aql_prog_lean = ctx->aql_prog_lean_pre = ctx->aql_prog_pre = -1;
-                ctx->live_pre_valid = false;
-                ctx->live_aql_note = bad;
-            }
-        }
-    }
-    ctx->timing = timing;
-    ctx->live_maybe_pend.assign(B, 1);
-    ctx->live_may_reach.assign(B, 1);
-    ctx->live_prev_known = false;
-    return rc;
-}
-
-int rc_live_step(rc_ctx* ctx, const float* j2dc, const float* accc, const float* oric, const float* first_tran, uint32_t flags,
-                 float* pose, float* tran) {
-    if (!ctx || !ctx->live_exec) return ctx ? fail(ctx, RC_ERR_STATE, "rc_live_step: call rc_live_begin first") : RC_ERR_INVALID;
-    if (!j2dc || !accc || !oric || !pose || !tran) return fail(ctx, RC_ERR_INVALID, "rc_live_step: null buffer");
-    const size_t B = ctx->B;
-    hipStream_t st = ctx->live_stream.get();
-    const auto t_in = std::chrono::steady_clock::now();
-    // how long the caller left the device alone since the previous frame returned: a 60 fps stream idles 16.6 ms, a benchmark loop none
-    const double idle_us = ctx->live_have_return ? std::chrono::duration<double, std::micro>(t_in - ctx->live_last_return).count() : 0.0;
-    bool waited_eager = false;
-    if (ctx->eager_dirty) {          // e.g. reset_states() on the caller's stream just before this frame
-        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->eager_ev.get(), 0));
-        ctx->eager_dirty = false;
-        waited_eager = true;
-    }
-    std::memcpy(ctx->live_in_h.get(), j2dc, B * 99 * sizeof(float));
-    std::memcpy(ctx->live_in_h.get() + B * 99, accc, B * 18 * sizeof(float));
-    std::memcpy(ctx->live_in_h.get() + B * 117, oric, B * 54 * sizeof(float));
-    // Host-side, CONSERVATIVE mirror of two device flags (rc_prep_kernel): a row needs a transition step iff it carries
-    // a deferred updater step (previous frame had c <= lo) and steps on camera data now (c > lo or first frame). The
-    // margin covers the difference between this double mean and the device's float32 mean in the reference's order
-    // (rc_conf_mean33); any doubt, or an unknown previous frame, selects the full graph, where unneeded transition tiles
-    // simply exit.
-    bool need_tr = !ctx->live_prev_known;
-    bool maybe_reach = false;        // some row may trigger init_net in this frame (c >= hi on a row that has not yet, L178-183)
-    {
-        const double lo = ctx->prm.conf_lo, hi = ctx->prm.conf_hi, margin = 1e-4;
-        if (ctx->live_may_reach.size() != B) ctx->live_may_reach.assign(B, 1);
-        for (size_t b = 0; b < B; ++b) {
-            double acc = 0.0;
-            for (int k = 0; k < 33; ++k) acc += (double)j2dc[(b * 33 + k) * 3 + 2];
-            const double c = acc / 33.0;
-            const bool maybe_vis = !(c < lo - margin) || (flags & RC_FLAG_FIRST_FRAME);
-            if (ctx->live_maybe_pend[b] && maybe_vis) need_tr = true;
-            ctx->live_maybe_pend[b] = (ctx->prm.use_vision_updater && !(c > lo + margin)) ? 1 : 0;
-            if (ctx->prm.use_imu_updater && ctx->live_may_reach[b]) {
-                if (!(c < hi - margin)) maybe_reach = true;
-                if (c > hi + margin) ctx->live_may_reach[b] = 0;          // it fires in this frame at the latest (frames like this one never take the lean plan)
-            }
-        }
-        ctx->live_prev_known = true;
-    }
-    if (ctx->live_blind) { need_tr = false; maybe_reach = false; }       // tests: every frame is offered to the lean plan, whose own check decides
-    const bool lean = ctx->live_exec_lean && !need_tr && !maybe_reach && !first_tran && !(flags & RC_FLAG_FIRST_FRAME);
-    const auto t_staged = std::chrono::steady_clock::now();
-    bool aql_done = false;
-    const bool use_pre = lean && ctx->live_aql && ctx->live_pre_valid && ctx->aql_prog_lean_pre >= 0;
-    ctx->live_pre_valid = false;                                  // (whatever this frame is, it moves the state on)
-    // A first kernel launched ahead of this frame (RC_LIVE_SPIN) is waiting on the device: it takes the frame if the frame is what it was
-    // launched for (lean, same program, nothing touched weights or state since, and it has not given up); otherwise it is sent away.
-    bool spin_go = false;
-    if (ctx->spin_pending >= 0 && ctx->live_aql) {
-        const int par = ctx->spin_pending_par;
-        const int want = use_pre ? ctx->aql_prog_spin_pre[par] : ctx->aql_prog_spin[par];
-        const bool gone = __atomic_load_n(ctx->spin_state_h.get() + 4 * par, __ATOMIC_ACQUIRE) == 3u;
-        spin_go = lean && !gone && ctx->spin_valid && ctx->spin_pending == want && !waited_eager;
-        if (spin_go) {
-            std::memcpy(ctx->spin_in, ctx->live_in_h.get(), B * 171 * sizeof(float));
-            RC_STORE_FENCE();
-            ctx->spin_mb[32 * par] = 1u;                                    // go: behind the inputs (stores to the device are posted in order; 0.1 us of host time)
-            RC_STORE_FENCE();
-        } else {
-            // skip: the kernel leaves and the six behind it change nothing (LiveFrame.abort); frames on this queue are ordered behind them, a
-            // frame on the HIP stream waits for them here (a kernel that has given up is no longer there to read the word)
-            ctx->spin_mb[32 * par] = 2u;
-            RC_STORE_FENCE();
-            if (!(lean && ctx->live_aql) && rc_aql_wait_frame(ctx->live_aql) != 0) return fail(ctx, RC_ERR_HIP, "rc_live_step: the frame queued ahead did not leave");
-            ctx->spin_state_h[4 * par] = 0;
-            ctx->stat_live_spin_lost += 1;
-            ctx->spin_pending = -1;
-        }
-    }
-    // the next frame queued ahead (all seven packets; its first kernel waits on the device for the command word): mailbox and give-up mark cleared first
-    auto queue_ahead = [&](const bool with_pre, const bool beside) {
-        const int par = ctx->spin_next_par;
-        const int prog = (with_pre && ctx->aql_prog_spin_pre[par] >= 0) ? ctx->aql_prog_spin_pre[par] : ctx->aql_prog_spin[par];
-        ctx->spin_mb[32 * par] = 0u; ctx->spin_mb[32 * par + 16] = 0u;
-        RC_STORE_FENCE();
-        ctx->spin_state_h[4 * par] = 0;
-        if (rc_aql_submit_ahead(ctx->live_aql, prog, beside ? 1 : 0) == 0) {
-            ctx->spin_pending = prog; ctx->spin_pending_par = par; ctx->spin_pending_seq = rc_aql_seq(ctx->live_aql);
-            ctx->spin_next_par = par ^ 1; ctx->spin_valid = true;
-        }
-    };
-    if (!(lean && ctx->live_aql) && ctx->live_aql) {
-        // this frame runs on the HIP stream: a pre-step still in the HSA queue must not read the state while the frame rewrites it
-        if (rc_aql_wait_background(ctx->live_aql) != 0) return fail(ctx, RC_ERR_HIP, "rc_live_step: the pre-step did not complete");
-    }
-    if (first_tran || (flags & RC_FLAG_FIRST_FRAME)) {           // sequence start: ordinary enqueue path
-        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_in_d.get(), ctx->live_in_h.get(), B * 171 * sizeof(float), hipMemcpyHostToDevice, st));
-        if (first_tran) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_ft_d.get(), first_tran, B * 3 * sizeof(float), hipMemcpyHostToDevice, st));
-        FrameIO io{ctx->live_in_io, ctx->live_in_io + B * 99, ctx->live_in_io + B * 117, first_tran ? ctx->live_ft_d.get() : nullptr,
-                   ctx->live_out_io, ctx->live_out_io + B * 216, 99, 18, 54, 216, 3};
-        if (int rc = step_impl(ctx, io, flags, st)) return rc;
-        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_out_h.get(), ctx->live_out_d.get(), B * 219 * sizeof(float), hipMemcpyDeviceToHost, st));
-    } else if (lean) {
-        if (ctx->live_aql) {
-            if (waited_eager) HIP_TRY(ctx, hipStreamSynchronize(st));        // the AQL queue is not ordered behind the stream: wait here
-            int arc = 0;
-            const int plain = use_pre ? ctx->aql_prog_lean_pre : ctx->aql_prog_lean;
-            const int my_par = ctx->spin_pending_par;
-            unsigned long long my_seq = ctx->spin_pending_seq;
-            if (spin_go) ctx->spin_pending = -1;
-            else { arc = rc_aql_submit_ahead(ctx->live_aql, plain, 0); my_seq = rc_aql_seq(ctx->live_aql); }
-            // A back-to-back caller (no idle time in front of this call): the NEXT frame is queued now, its first kernel beside this frame's last ones --
-            // when the caller comes back that kernel has its arguments and weights and is polling. (A paced caller's is queued behind the pre-step, below.)
-            if (arc == 0 && ctx->live_spin_b2b && ctx->aql_prog_spin[0] >= 0 && ctx->spin_pending < 0 && idle_us < ctx->live_prestep_idle_us) queue_ahead(false, true);
-            if (arc == 0) arc = rc_aql_wait_seq(ctx->live_aql, my_seq);
-            if (spin_go && arc == 0 && __atomic_load_n(ctx->spin_state_h.get() + 4 * my_par, __ATOMIC_ACQUIRE) == 3u) {
-                // the waiting kernel gave up in the very moment the frame arrived: the six kernels behind it have changed nothing
-                // (LiveFrame.abort) -- the frame runs on the ordinary program, in front of which nothing may be waiting
-                ctx->spin_state_h[4 * my_par] = 0;
-                ctx->stat_live_spin_lost += 1;
-                if (ctx->spin_pending >= 0) { ctx->spin_mb[32 * ctx->spin_pending_par] = 2u; RC_STORE_FENCE(); ctx->spin_pending = -1; ctx->stat_live_spin_lost += 1; }
-                arc = rc_aql_run(ctx->live_aql, plain);
-            } else if (spin_go && arc == 0) ctx->stat_live_spin += 1;
-            if (arc != 0) {
-                // The frame did not retire in time (a tool on the queue, a wedged device): the chain is dropped -- its destructor waits
-                // for whatever is still in flight before the ring and the argument blocks go -- and the following frames replay the
-                // captured graph of the same seven kernels. THIS frame's state is unknown: the caller gets the error.
-                rc_aql_destroy(ctx->live_aql);
-                ctx->live_aql = nullptr;
-                ctx->live_aql_note = "an AQL frame did not complete: back on hipGraphLaunch";
-                ctx->aql_prog_lean = ctx->aql_prog_lean_pre = ctx->aql_prog_pre = -1;
-                for (int q = 0; q < 2; ++q) ctx->aql_prog_spin[q] = ctx->aql_prog_spin_pre[q] = -1;
-                ctx->spin_pending = -1; ctx->spin_mb = nullptr; ctx->spin_in = nullptr;
-                ctx->live_prev_known = false;
-                return fail(ctx, RC_ERR_HIP, "rc_live_step: the AQL frame did not complete (later frames use the graph replay)");
-            }
-            aql_done = true;
-        } else if (ctx->live_eager) rc_launch_live_frame(ctx->live_frame, st);
-        else HIP_TRY(ctx, hipGraphLaunch(ctx->live_exec_lean.get(), st));
-        ctx->stat_live_lean += 1;
-    } else if (ctx->live_eager) {                                // tuning (RC_LIVE_EAGER=1): the 11-14 launches enqueued directly
-        FrameIO io{ctx->live_in_io, ctx->live_in_io + B * 99, ctx->live_in_io + B * 117, nullptr,
-                   ctx->live_out_io, ctx->live_out_io + B * 216, 99, 18, 54, 216, 3};
-        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_in_d.get(), ctx->live_in_h.get(), B * 171 * sizeof(float), hipMemcpyHostToDevice, st));
-        if (int rc = step_impl(ctx, io, 0u, st, need_tr)) return rc;
-        if (!ctx->live_zero_copy) HIP_TRY(ctx, hipMemcpyAsync(ctx->live_out_h.get(), ctx->live_out_d.get(), B * 219 * sizeof(float), hipMemcpyDeviceToHost, st));
-    } else {
-        HIP_TRY(ctx, hipGraphLaunch(need_tr ? ctx->live_exec.get() : ctx->live_exec_notr.get(), st));
-    }
-    const auto t_enq = std::chrono::steady_clock::now();
-    // A frame is ~100 us of GPU work: poll for its completion instead of sleeping on the stream (the blocking wait's wake-up
-    // costs a sizeable fraction of that); after ~2 ms fall back to the blocking call.
-    if (!aql_done) {
-        const auto t_spin = std::chrono::steady_clock::now();
-        hipError_t q;
-        while ((q = hipStreamQuery(st)) == hipErrorNotReady) {
-            if (std::chrono::steady_clock::now() - t_spin > std::chrono::milliseconds(2)) break;
-        }
-        if (q != hipSuccess && q != hipErrorNotReady) return fail(ctx, RC_ERR_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(q));
-        (void)hipGetLastError();
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    if (!lean) ctx->stat_live_full += 1;
-    if (lean && ctx->live_status_h[0] != 0) {
-        // The lean plan's own check (rc_live_k1) found the frame off the plan -- a transition step or an init_net trigger the host-side
-        // mirror above did not foresee. Its kernels have changed nothing (LiveFrame.abort): the frame runs again on the full capture,
-        // from the inputs still staged in the pinned buffer.
-        ctx->live_status_h[0] = 0;
-        ctx->stat_live_lean -= 1;
-        ctx->stat_live_full += 1;
-        ctx->stat_live_replayed += 1;
-        HIP_TRY(ctx, hipGraphLaunch(ctx->live_exec.get(), st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    const auto t_done = std::chrono::steady_clock::now();
-    std::memcpy(pose, ctx->live_out_h.get(), B * 216 * sizeof(float));
-    std::memcpy(tran, ctx->live_out_h.get() + B * 216, B * 3 * sizeof(float));
-    // The pre-step of the NEXT frame, behind this one in the queue, when the caller paces its frames (the idle time in front of this call
-    // says so): it streams half of the weights while the device would otherwise idle, and a caller that comes back at once -- a
-    // throughput loop -- would only wait for it.
-    if (ctx->live_aql && ctx->aql_prog_pre >= 0 && idle_us >= ctx->live_prestep_idle_us) {
-        if (rc_aql_submit(ctx->live_aql, ctx->aql_prog_pre) == 0) { ctx->live_pre_valid = true; ctx->stat_live_pre += 1; }
-    }
-    if (ctx->live_aql && ctx->live_spin && ctx->aql_prog_spin[0] >= 0 && ctx->spin_pending < 0 && lean && idle_us < 50000.0 && (ctx->live_spin_always || idle_us >= ctx->live_prestep_idle_us)) {
-        queue_ahead(ctx->live_pre_valid, false);                            // (RC_LIVE_SPIN) behind this frame and its pre-step
-    } else if (ctx->live_aql && ctx->live_arm && ctx->spin_pending < 0 && idle_us >= ctx->live_prestep_idle_us) (void)rc_aql_arm(ctx->live_aql);
-    if (lean) {
-        const auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-            return std::chrono::duration<double, std::micro>(b - a).count();
-        };
-        ctx->live_prof_us[0] += us(t_in, t_staged); ctx->live_prof_us[1] += us(t_staged, t_enq); ctx->live_prof_us[2] += us(t_enq, t_done);
-        const auto t_out = std::chrono::steady_clock::now();
-        ctx->live_prof_us[3] += us(t_done, t_out);
-        ctx->live_prof_n += 1;
-        ctx->live_prof_last[0] = us(t_in, t_staged); ctx->live_prof_last[1] = us(t_staged, t_enq);
-        ctx->live_prof_last[2] = us(t_enq, t_done); ctx->live_prof_last[3] = us(t_done, t_out);
-        ctx->live_prof_last[4] = spin_go ? 1.0 : 0.0; ctx->live_prof_last[5] = use_pre ? 1.0 : 0.0;
-    }
-    ctx->live_last_return = std::chrono::steady_clock::now();
-    ctx->live_have_return = true;
-    return RC_OK;
-}
-
-int rc_get_live_backend(rc_ctx* ctx, int32_t* lean_captured, int32_t* aql, char* note, int32_t note_len) {
-    if (!ctx) return RC_ERR_INVALID;
-    if (lean_captured) *lean_captured = ctx->live_exec_lean ? 1 : 0;
-    if (aql) *aql = ctx->live_aql ? 1 : 0;
-    if (note && note_len > 0) std::snprintf(note, (size_t)note_len, "%s", ctx->live_aql_note.c_str());
-    return RC_OK;
-}
-
-int rc_get_live_prestep(rc_ctx* ctx, int64_t* presteps, int32_t* available) {
-    if (!ctx) return RC_ERR_INVALID;
-    if (presteps) *presteps = ctx->stat_live_pre;
-    if (available) *available = (ctx->live_aql && ctx->aql_prog_pre >= 0) ? 1 : 0;
-    return RC_OK;
-}
-
-int rc_get_live_spin(rc_ctx* ctx, int64_t* taken, int64_t* lost) {
-    if (!ctx) return RC_ERR_INVALID;
-    if (taken) *taken = ctx->stat_live_spin;
-    if (lost) *lost = ctx->stat_live_spin_lost;
-    return RC_OK;
-}
-
-int rc_get_live_replayed(rc_ctx* ctx, int64_t* frames) {
-    if (!ctx || !frames) return RC_ERR_INVALID;
-    *frames = ctx->stat_live_replayed;
-    return RC_OK;
-}
-
-int rc_get_live_last_profile(rc_ctx* ctx, double* us6) {
-    if (!ctx || !us6) return RC_ERR_INVALID;
-    for (int q = 0; q < 6; ++q) us6[q] = ctx->live_prof_last[q];
-    return RC_OK;
-}
-int rc_get_live_profile(rc_ctx* ctx, double* avg_us4) {
-    if (!ctx || !avg_us4) return RC_ERR_INVALID;
-    for (int q = 0; q < 4; ++q) avg_us4[q] = ctx->live_prof_n ? ctx->live_prof_us[q] / (double)ctx->live_prof_n : 0.0;
-    return RC_OK;
-}
-
-int rc_get_live_stats(rc_ctx* ctx, int64_t* lean_frames, int64_t* full_frames) {
-    if (!ctx) return RC_ERR_INVALID;
-    if (lean_frames) *lean_frames = ctx->stat_live_lean;
-    if (full_frames) *full_frames = ctx->stat_live_full;
-    return RC_OK;
 }
 
 int rc_r6d_to_rotmat(const float* r6d, float* R, int64_t n, void* stream) {

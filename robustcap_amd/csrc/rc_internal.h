@@ -497,7 +497,12 @@ template <class Cap, class... BufsAndCounts> hipError_t rc_grow(Cap& cap, size_t
     return e;
 }
 
-// narrow view of the context for rc_smplify_api.cpp and rc_subnet_api.cpp (the struct itself lives in rc_api.cpp)
+// the live session of a context (rc_live_api.cpp; the type is complete there only)
+struct LiveSession;
+__attribute__((visibility("hidden"))) void rc_live_free(LiveSession* s);   // delete s
+using LiveOwner = std::unique_ptr<LiveSession, RcRelease<rc_live_free>>;
+
+// narrow view of the context for rc_smplify_api.cpp and rc_subnet_api.cpp (the struct itself lives in rc_ctx.h)
 struct rc_ctx;
 struct SmplifyState;
 const BodyConst* rc_ctx_body(rc_ctx* ctx);                 // nullptr until rc_set_body
