@@ -1,4 +1,5 @@
-// The context behind the C ABI, for the two files that work on all of it: rc_api.cpp and rc_live_api.cpp. (rc_smplify_api.cpp and
+// The context behind the C ABI, for the three files that work on all of it: rc_api.cpp (context, weights, problem builders, gate-GEMM
+// launcher, frame-stepped plan), rc_sequence_api.cpp (the sequence engine) and rc_live_api.cpp (the live session). (rc_smplify_api.cpp and
 // rc_subnet_api.cpp see it through the rc_ctx_* accessors of rc_internal.h.)
 #pragma once
 #include "../../include/robustcap_hip.h"
@@ -67,6 +68,7 @@ struct rc_ctx {
     bool alloc_weights = false;          // dev_alloc books into weight_allocs
     std::string err;
     LiveOwner live;                      // the live session: stream, captures, packet chain, host mirror, knobs and counters (rc_live_api.cpp)
+    SeqOwner seq;                        // the sequence engine of rc_sequence: planner's tables, ring, streams and events, resident tables, knobs and counters (rc_sequence_api.cpp)
     // timing of the gate GEMM launches
     bool timing = false;
     int timing_mode = 1;                 // 1: every gate-GEMM launch, 2: only the wide-tile kernels, 3: only the shared-weight kernel (rc_gemm_lds_kernel)
@@ -75,47 +77,11 @@ struct rc_ctx {
     double timed_ms = 0.0;
     double timed_busy_ms = 0.0;          // time with at least one timed launch running (launches on two streams overlap)
     long long timed_launches = 0;
-    // sequence mode of rc_sequence: launch planner + per-row-cursor wavefront engine (run_wave2_segment)
+    // the gate-GEMM launcher (launch_problems)
     bool gemm_split = false;             // products of every GEMM as split-bf16 partial products (rc_set_gemm_mode)
     bool live_launch = false;            // set while a live frame is captured / launched (GemmLaunch.live)
     unsigned live_nt_mask = 63u;         // sub-nets (bit = kNets index) whose weights a live frame streams with non-temporal loads
-    int seq_mode = 1;                    // 0 = always frame-stepped, 1 = plan per call (cost estimate), 2 = wavefront whenever long enough
-    int seq_min_frames = 8;              // calls shorter than this are neither planned nor skewed (no pre-pass, no synchronisation)
-    float* x1_alt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // second relu(linear1) buffer per net
     int tile6[2] = {0, 0}, tile378[2] = {0, 0}, tile2[2] = {0, 0}, tile4[2] = {0, 0};   // LSTM tile shapes of full-batch stages (0 = pick_tile)
-    bool ring2_failed = false;           // ensure_wave2_buffers failed once: not retried
-    // streams of a tick beside the caller's (stream_tick; caller's stream: plain both wide launches | split {rnn6, rnn4, init_net} | tri rnn4)
-    HipStream aux_stream;                // the second stream, every engine: prep, linear2, fuse, tail; tri also {linear1, init_net} at the head of its tick
-    HipStream wide2_stream;              // plain: unused | split: {H = 512 nets, linear1} | tri: rnn6
-    HipEvent ev_main[8], ev_aux[8], ev_wide2[4];   // [tick & 3]: the last wide launch of the caller's stream | the end of aux_stream's tick | wide2_stream's
-                                                   // launch is done (ev_main[6], [7]: the engine's streams join the caller's)
-    HipStream wide3_stream;              // tri only: the H = 512 nets
-    HipEvent ev_head[4], ev_wide3[4];    // tri only: {linear1, init_net} at the head of aux_stream's tick | wide3_stream's launch is done
-    float* x1_alt2[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // third relu(linear1) buffer per net (linear1 runs up to a tick ahead of its readers)
-    DevBuf<signed char> scan_codes_d;    // [cap] regime code per (frame, row)
-    PinBuf<signed char> scan_codes_h;    // pinned
-    PinBuf<int> scan_state_h;            // pinned: first_reach[B] then pend[B] (as ints)
-    size_t scan_cap = 0;
-    long long stat_wave_frames = 0, stat_stepped_frames = 0, stat_ticks = 0;
-    long long stat_row_frames = 0;       // row-frames computed by sequence calls (rc_get_sequence_row_frames)
-    // rc_sequence_rows: the call's per-row lengths, device + pinned (grow-only, released with the context). The pinned copy has two halves
-    // that calls take in turn, each with an event that says its upload has left it: a call only ever waits for the upload of the call
-    // BEFORE the previous one, which has long run.
-    DevBuf<int> row_len_d;
-    PinBuf<int> row_len_h;               // [2][row_len_cap]
-    size_t row_len_cap = 0;
-    HipEvent row_len_ev[2];
-    unsigned row_len_turn = 0;
-    // per-row-cursor wavefront engine (run_wave2_segment)
-    bool ring2_ready = false;
-    FrameBuffers ring2[16];              // ring slots: inter-stage buffers, updater inputs, frame index and step numbers per row
-    std::vector<GemmProblem> wave2_prob; // [16 slots][W2_PROB]
-    bool wave2_valid = false;
-    DevBuf<int> frame_at_d;              // [cap] host plan: frame every row starts at every tick
-    PinBuf<int> frame_at_h;              // pinned
-    size_t frame_at_cap = 0;
-    double cost_tick_us = 1.0, cost_tick_small_us = 13.0, cost_frame_us = 285.0, cost_tr_us = 55.0;   // engine choice (plan_wave): scale of the
-                                                         // per-layer tick estimate, hand-over per tick, frame-stepped frame, its transition launches
     SmplifyOwner smplify;                // optimiser work space (rc_smplify_api.cpp)
     SubnetOwner subnet;                  // scratch of rc_subnet_forward (rc_subnet_api.cpp)
     int trace_next = 0;                  // tile-trace slot counter (tools/tile_trace.py)
@@ -134,16 +100,6 @@ struct rc_ctx {
     DevBuf<int> lds_tickets;             // [kLdsRegions][lds_region_tiles]
     size_t lds_region_tiles = 0;
     unsigned lds_rot = 0;
-    // resident layer-step kernel of the wavefront engine (run_resident_segment)
-    DevBuf<ResidentTick> res_ticks_d;        // [res_cap]
-    PinBuf<ResidentTick> res_ticks_h;        // pinned
-    DevBuf<int> res_ints_d;                  // item_base [res_cap + 1] | done [res_cap][RC_RES_MAXP] | tick_done [res_cap] | head, flag_l1, flag_tail, abort
-    PinBuf<int> res_base_h;                  // pinned: item_base
-    PinBuf<int> res_abort_h;                 // pinned: the abort word of the last segment (allocated with the first resident segment)
-    size_t res_cap = 0;
-    long long stat_resident_segments = 0, stat_resident_aborts = 0;
-    bool resident_on = false;                // rc_set_resident / RC_SEQ_RESIDENT
-    int resident_wgs = 224;                  // workgroups of the resident kernel (RC_SEQ_RESIDENT_WGS; the CUs it leaves run the second stream)
     long long stat_lds_launches = 0;
     long long stat_w32_launches = 0;         // of the wide launches: those on rc_gemm_split48_w32_kernel (contexts of 33-64 rows)
 };
@@ -156,6 +112,49 @@ int check_ready(rc_ctx* ctx);
 rc_params_dev dev_params(const rc_params& p);
 int step_impl(rc_ctx* ctx, const FrameIO& io, uint32_t flags, hipStream_t st, bool with_tr = true, bool skip_prep = false,
               const FrameIO* next_io = nullptr, int n_live = -1);
+// ... what the sequence engine takes from the problem builders and the gate-GEMM launcher, and nothing beyond that:
+template <typename T>
+int dev_alloc(rc_ctx* ctx, T** p, size_t count, bool zero = true) {
+    DevBuf<char> q;
+    HIP_TRY(ctx, rc_alloc(q, count * sizeof(T)));
+    if (zero) HIP_TRY(ctx, hipMemset(q.get(), 0, count * sizeof(T)));
+    *p = reinterpret_cast<T*>(q.get());
+    if (!ctx->alloc_weights) ctx->alloc_bytes.emplace_back(q.get(), count * sizeof(T));      // (what live_selfcheck saves and puts back: state + scratch)
+    (ctx->alloc_weights ? ctx->weight_allocs : ctx->allocs).push_back(std::move(q));
+    return RC_OK;
+}
+struct Out { float* p; int ld; int col0; bool packed; };   // destination of a dense layer
+struct Stage {                 // which rows of which net, reading which (rc_pk) input buffer, writing where
+    int net; int flag_bit; const float* x; int ldx; Out y;
+    const unsigned char* flags = nullptr;      // row-selection byte array (default: fb.flags)
+    const float* x_alt = nullptr;              // input of rows lacking sel_bit in fb.flags (deferred updater step)
+    int sel_bit = 0;
+    int out_bit = 0;                           // linear2 writes only rows with this bit in fb.flags
+    int rows_hint = -1;                        // expected active rows (-1 = the whole batch): picks the LSTM tile shape
+};
+GemmSeg seg(const float* base, int ld, int K, int mode = RC_PAR_NONE, long long stride = 0);
+GemmProblem dense_problem(const rc_ctx* ctx, const Dense& d, GemmSeg a, Out out, bool relu, int flag_bit, const unsigned char* flags, int* steps,
+                          bool open_step);
+GemmProblem lin1_problem(const rc_ctx* c, const Stage& s);
+GemmProblem lstm_problem(const rc_ctx* c, const Stage& s, int layer);
+GemmProblem lin2_problem(const rc_ctx* c, const Stage& s);
+bool tile_env(const char* name, int* mr, int* nc);
+void pick_tile(int H, int rows, int* mr, int* nc);
+// "This problem runs on the shared-weight kernel (rc_gemm_lds.hip)": a CONTEXT takes it (and the tri engine) in split-product mode from
+// lds_min_batch rows, a PROBLEM inside such a context from lds_min_rows rows.
+inline bool lds_context(const rc_ctx* c) { return c->gemm_split && c->lds_min_rows > 0 && c->B >= c->lds_min_batch; }
+inline bool lds_problem(const rc_ctx* c, int rows) { return lds_context(c) && rows >= c->lds_min_rows; }
+int ensure_lds_pool(rc_ctx* ctx);
+bool timing_pair(rc_ctx* ctx, hipEvent_t* a, hipEvent_t* b);
+int build_lds_problems(rc_ctx* ctx, const std::vector<GemmProblem>& ps, const unsigned char* flags_override, float* slab, int* tickets,
+                       LdsProblem* out, int max_p, int* items, size_t* tiles_out, bool resident_order = false);
+int launch_problems(rc_ctx* ctx, std::vector<GemmProblem> ps, const unsigned char* flags_override, hipStream_t st, bool fp32 = false,
+                    hipEvent_t stop = nullptr, bool* launched = nullptr);
+// rc_sequence_api.cpp
+void seq_create(rc_ctx* ctx);                                 // rc_create: the RC_SEQ_* / RC_COST_* knobs are read here, once per context
+int seq_prepare(rc_ctx* ctx);                                 // rc_finalize_weights: ring, streams, launch tables, the plan's tables for 1024 frames
+void seq_weights_changed(rc_ctx* ctx);                        // ... and in front of it: the launch tables hold pointers to the old weights
+bool seq_is_engine_stream(const rc_ctx* ctx, hipStream_t st); // st is the engine's second stream (the launcher's debug self-test keeps off it)
 // rc_live_api.cpp
 void live_create(rc_ctx* ctx);                                // rc_create: the RC_LIVE_* knobs are read here, once per context
 void live_forget_last_frame(rc_ctx* ctx, bool rows_reset = false);   // an eager entry is about to move the state: the host mirror no longer knows

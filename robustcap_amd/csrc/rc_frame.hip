@@ -26,7 +26,7 @@ __global__ __launch_bounds__(64) void rc_prep_kernel(FrameBuffers fb, FrameIO io
     prep_body(fb, io, prm, row, threadIdx.x, first_frame, fb.pend[row], fb.uv_count[row], io.len ? RC_ROW2_VALID : 0u);
 }
 
-// Per-row-cursor wavefront engine (rc_api.cpp: run_wave2_segment): the prep of one TICK. Row `row` starts frame
+// Per-row-cursor wavefront engine (rc_sequence_api.cpp: run_wave2_segment): the prep of one TICK. Row `row` starts frame
 // w.frame_at[row] of the call in ring slot `fb`, or nothing (-1: the row waits for a feedback step of an earlier frame, or has
 // no frame left). It opens the step of every sub-net the frame will take -- the step NUMBER travels with the slot (wsteps), so
 // that the stages of several frames of a row can be in flight while the row's counters move on. On the first tick of a

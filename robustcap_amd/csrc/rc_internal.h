@@ -132,7 +132,7 @@ void rc_launch_gemm_lds(const LdsLaunch& L, int total_wg, hipStream_t s, hipEven
 // ---- resident layer-step kernel (rc_gemm_lds.hip: rc_gemm_resident_kernel) ----------------------------------
 // One launch carries the LSTM layer steps of EVERY tick of a wavefront-engine segment: its workgroups stay on their CUs and take work
 // items (the items of rc_gemm_lds_kernel, tick after tick, longest first inside a tick) from one queue in device memory. What stream
-// order and events did between launches, counters in device memory do between items (rc_api.cpp: run_wave2_resident).
+// order and events did between launches, counters in device memory do between items (rc_sequence_api.cpp: run_resident_segment).
 struct ResidentTick {
     int n, B;                             // the tick's problems, as one launch of the shared-weight kernel would carry them
     LdsProblem p[RC_RES_MAXP];
@@ -501,6 +501,11 @@ template <class Cap, class... BufsAndCounts> hipError_t rc_grow(Cap& cap, size_t
 struct LiveSession;
 __attribute__((visibility("hidden"))) void rc_live_free(LiveSession* s);   // delete s
 using LiveOwner = std::unique_ptr<LiveSession, RcRelease<rc_live_free>>;
+
+// the sequence engine of a context (rc_sequence_api.cpp; the type is complete there only)
+struct SeqEngine;
+__attribute__((visibility("hidden"))) void rc_seq_free(SeqEngine* e);      // delete e
+using SeqOwner = std::unique_ptr<SeqEngine, RcRelease<rc_seq_free>>;
 
 // narrow view of the context for rc_smplify_api.cpp and rc_subnet_api.cpp (the struct itself lives in rc_ctx.h)
 struct rc_ctx;

@@ -1,4 +1,4 @@
-"""Resident layer-step kernel of the wavefront engine (rc_gemm_lds.hip: rc_gemm_resident_kernel; rc_api.cpp: run_resident_segment).
+"""Resident layer-step kernel of the wavefront engine (rc_gemm_lds.hip: rc_gemm_resident_kernel; rc_sequence_api.cpp: run_resident_segment).
 
 north_star asks for "a fused persistent kernel ... hidden state kept ... across timesteps"; the reference's whole-sequence form is
 articulate/utils/torch/rnn.py:129-133 and its frame loop net/sig_mp.py:113-274. One launch carries the LSTM layer steps and linear1 layers

@@ -4,6 +4,7 @@ The engine runs the same per-row chain of operations as the frame-stepped launch
 be bitwise equal to them -- in every regime: occluded rows lag the batch instead of stopping it (their vision-updater steps
 ride later ring slots), init_net makes a row wait for its tail. Against the reference the bar is the usual 1e-4 m / 0.1
 degrees on every captured non-live sequence (tests/golden/seq_*.npz)."""
+import ctypes as C
 import glob
 import os
 
@@ -206,3 +207,44 @@ def test_very_long_calls_are_planned_in_pieces(synth_assets, monkeypatch):
     assert torch.equal(a4[0], b4[0]) and torch.equal(a6[1], b6[1])
     assert sb[0] == T - 1 and sa[0] + sa[1] == T and sa[1] <= 1 + 7              # (a last piece shorter than min_frames is frame-stepped)
     assert sa[2] > sb[2] + 2 * 8                                                 # every piece drains its pipeline
+
+
+@pytest.mark.parametrize("B,resident", [(2, False), (160, True)], ids=["streams", "resident"])
+def test_plan_table_grows_inside_a_segment(B, resident, synth_assets):
+    """rc_finalize_weights reserves frame_at for 1024 + 64 initialising ticks; run_wave2_segment grows it for a plan that has more. 240 frames,
+    frame 0 stepped (first_frame), every row visible (mid regime) on the even frames and occluded on the odd ones: a visible / occluded pair
+    costs a row 10 ticks, the plan has 1,191 initialising ticks of 1,199. Bitwise the frame-stepped context, all six states included.
+    resident: the smallest batch of tests/test_gpu_resident.py, a 24-frame call first, so the 240-frame call grows the resident tables a
+    second time as well."""
+    from robustcap_amd import _lib
+    T = 240
+    m = synth.make_motion(31, 2, T, synth_assets["body"], conf="high")
+    m = {k: np.concatenate([v] * ((B + 1) // 2), 0)[:B].copy() for k, v in m.items()}
+    m["j2dc"][..., 2] = np.where(np.arange(T) % 2 == 0, 0.75, 0.5).astype(np.float32)[None, :, None]
+    warm = m["j2dc"][:, :24].copy()
+    warm[..., 2] = 0.75
+    conf = m["j2dc"][:, :, 0, 2].T                                              # [T][B]; thresholds of a non-live context: 0.7, 0.8
+    codes = np.ascontiguousarray(np.where(conf >= 0.8, 2, np.where(conf > 0.7, 1, 0)).astype(np.int8))
+    fr, pd = np.ones(B, np.int32), np.zeros(B, np.int32)                        # in front of frame 1: init_net not run, frame 0 visible
+    nt, npre = C.c_int32(), C.c_int32()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.load().rc_plan_wave(p(codes), B, T, 1, p(fr), p(pd), 1, 1, None, 0, C.byref(nt), C.byref(npre), None, None)
+    assert npre.value > 1024 + 64 and (nt.value, npre.value) == (1199, 1191)    # more than the tables of rc_finalize_weights hold
+    outs = []
+    for seq in (True, False):
+        net = _net(synth_assets, B, seq)
+        net.gravityc = t(m["gravityc"])
+        net.set_resident(resident and seq)
+        if resident:
+            net.forward_sequence(t(warm), t(m["accc"][:, :24]), t(m["oric"][:, :24]), first_frame=True)
+        before = net.sequence_stats()
+        pose, tran = net.forward_sequence(t(m["j2dc"]), t(m["accc"]), t(m["oric"]), first_frame=True)
+        torch.cuda.synchronize()
+        stats = tuple(a - b for a, b in zip(net.sequence_stats(), before))
+        outs.append((pose.cpu(), tran.cpu(), [net.get_state(n) for n in ("rnn2", "rnn3", "rnn4", "rnn6", "rnn7", "rnn8")], stats, net.resident_stats()))
+    (wp, wt, ws, wstat, wres), (sp, st, ss, sstat, _) = outs
+    assert wstat == (T - 1, 1, 1199) and sstat == (0, T, 0)
+    assert wres == ((2, 0) if resident else (0, 0))                             # both calls on the resident kernel, no wait ran out
+    assert torch.equal(wp, sp) and torch.equal(wt, st)
+    for (hw, cw), (hs, cs) in zip(ws, ss):
+        assert torch.equal(hw, hs) and torch.equal(cw, cs)

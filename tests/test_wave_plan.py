@@ -13,7 +13,7 @@ import pytest
 
 from robustcap_amd import _lib
 
-# stage of every (net, launch kind) of a frame: linear1, LSTM l0, LSTM l1, linear2 (rc_api.cpp: kTick)
+# stage of every (net, launch kind) of a frame: linear1, LSTM l0, LSTM l1, linear2 (rc_sequence_api.cpp: kTick)
 FIRST = {"rnn2": 1, "rnn4": 1, "rnn6": 5, "rnn3": 5, "rnn7": 5, "rnn8": 5}
 FUSE, TAIL, RING = 4, 8, 16                                             # fuse / tail follow linear2 within stage 4 / 8
 

@@ -1,4 +1,4 @@
-"""Stream-level hazards of the wavefront engine's tick (rc_api.cpp: stream_tick), on an abstract model (no GPU).
+"""Stream-level hazards of the wavefront engine's tick (rc_sequence_api.cpp: stream_tick), on an abstract model (no GPU).
 
 tests/test_wave_plan.py checks WHICH tick every step of every row runs at. This file checks that, given those ticks, the way
 a tick is issued is race free: kernels are nodes on streams, stream order and the engine's event waits are the only ordering,
@@ -51,7 +51,7 @@ def frame_ops(e, hbuf, x1buf, init=True):
 def build_tri(hbuf, x1buf, init=True):
     """Round 6, contexts on the shared-weight kernel: THREE streams of layer steps -- G4 {rnn4} on the caller's, G6 {rnn6} and G5 {the
     H = 512 nets} on streams of the context -- and L1 {linear1 of every net, init_net} at the head of the second stream's tick, in
-    front of that stream's waits for the layer steps of the previous tick (rc_api.cpp: stream_tick, ENG_TRI)."""
+    front of that stream's waits for the layer steps of the previous tick (rc_sequence_api.cpp: stream_tick, ENG_TRI)."""
     names = ("L1", "prep", "lin2", "fuse", "tail", "G4", "G6", "G5")
     per_tick = {k: {n: [] for n in names} for k in range(TICKS)}
     for e in range(TICKS):
