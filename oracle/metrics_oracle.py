@@ -6,6 +6,7 @@ numpy/torch-CPU restatement of
   articulate/evaluator.py:100-129      PositionErrorEvaluator
 Pinned by tests/test_metrics_oracle.py against tests/golden/metrics.npz (captured from the reference itself by
 oracle/capture_metrics.py with a synthetic body and a synthetic J_regressor).
+The SVD here is float32 like the reference's; oracle/metrics_f64.py is the float64 restatement the device is held to.
 """
 import numpy as np
 import torch

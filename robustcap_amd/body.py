@@ -342,7 +342,9 @@ def position_error(p, t, device="cuda"):
 
 def reconstruction_error(S1, S2, device="cuda"):
     """utils.reconstruction_error(S1, S2, reduction=None) (utils.py:189-203): per-frame mean point distance after
-    Procrustes alignment of S1 [n,k,3] onto S2 [n,k,3]. Returns a device tensor [n]."""
+    Procrustes alignment of S1 [n,k,3] onto S2 [n,k,3]. Returns a device tensor [n]. Computed in float64 on the float32 inputs
+    and rounded once. Where every point of a set of S1 is the same point (var1 = 0: the reference divides by zero) the scale is
+    taken as 0 and the value is mean_j |S2_j - mean(S2)|; sets that are equal value for value give exactly 0."""
     a, b = _f32c(S1, torch.device(device)), _f32c(S2, torch.device(device))
     if a.shape != b.shape or a.dim() != 3 or a.shape[2] != 3:
         raise ValueError("S1 and S2 must both be [n, k, 3]")

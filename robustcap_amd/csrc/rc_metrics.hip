@@ -29,57 +29,60 @@
 
 namespace {
 
-// eigen-decomposition of a symmetric 3x3 matrix by cyclic Jacobi; A is destroyed (its diagonal becomes the spectrum),
-// V receives the eigenvectors as columns (a product of rotations: det V = +1). Every index is a compile-time constant
-// (the p, q, k loops are unrolled): the matrices live in registers, no scratch.
-__device__ __forceinline__ void jacobi3(double (&A)[3][3], double (&V)[3][3]) {
+// right singular vectors of a 3x3 matrix by a one-sided (Hestenes) Jacobi: W enters as K and leaves as K V with mutually
+// orthogonal columns (w_i = s_i u_i), V (a product of rotations: det V = +1) holds the right singular vectors as columns.
+// Working on K itself keeps a small singular direction to eps * s_1 / s_i; the eigenvectors of K^T K, which this replaces,
+// had eps * (s_1 / s_i)^2 and lost the second direction of a thin point set (s_2 / s_1 ~ 1e-8) altogether.
+// Every index is a compile-time constant (the p, q, k loops are unrolled): the matrices live in registers, no scratch.
+__device__ __forceinline__ void hestenes3(double (&W)[3][3], double (&V)[3][3]) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 12; ++sweep) {
-        const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-        if (off < 1e-300) break;
+    for (int sweep = 0; sweep < 16; ++sweep) {
+        bool rotated = false;
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
             for (int q = p + 1; q < 3; ++q) {
-                if (fabs(A[p][q]) < 1e-300) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double al = W[0][p] * W[0][p] + W[1][p] * W[1][p] + W[2][p] * W[2][p];
+                const double be = W[0][q] * W[0][q] + W[1][q] * W[1][q] + W[2][q] * W[2][q];
+                const double ga = W[0][p] * W[0][q] + W[1][p] * W[1][q] + W[2][p] * W[2][q];
+                if (ga * ga <= 1e-30 * al * be) continue;           // orthogonal to 1e-15 (or a zero column): nothing to do
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
                 const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {                       // A <- A J
-                    const double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][q] = s * akp + c * akq;
-                }
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {                       // A <- J^T A
-                    const double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[q][k] = s * apk + c * aqk;
-                }
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
+                for (int k = 0; k < 3; ++k) {                       // W <- W J, V <- V J
+                    const double wkp = W[k][p], wkq = W[k][q];
+                    W[k][p] = c * wkp - s * wkq;
+                    W[k][q] = s * wkp + c * wkq;
                     const double vkp = V[k][p], vkq = V[k][q];
                     V[k][p] = c * vkp - s * vkq;
                     V[k][q] = s * vkp + c * vkq;
                 }
             }
+        if (!rotated) break;
     }
 }
 
 // mean over the nk points of |s R x1 + t - x2| for the optimal similarity transform (utils.py:138-203).
-// K = X1^T X2 = U S V^T; R = V Z U^T with Z = diag(1, 1, sign det(U V^T)): built from the eigenvectors of K^T K,
-// u_i = K v_i / s_i for the two largest singular values and u_3 = u_1 x u_2, which absorbs Z.
+// K = X1^T X2 = U S V^T; R = V Z U^T with Z = diag(1, 1, sign det(U V^T)): the right singular vectors come from a one-sided
+// Jacobi on K itself (hestenes3), u_i = K v_i / s_i for the two largest singular values, v_3 = v_1 x v_2 and
+// u_3 = u_1 x u_2, which absorbs Z (DESIGN_HISTORY.md 3.5 describes the K^T K route this had before). s_2 -> 0 (collinear
+// sets, two points): u_2 is then any unit vector orthogonal to u_1, or zero -- the points lie on the axis either way.
+// Every point of S1 equal (var1 = 0; the reference divides by zero): scale = 0, the result is mean |x2 - mu2|.
+// S1 == S2 value for value: exactly 0 (identical poses give three zeros in rc_mesh_metrics).
 // p1 / p2 are memory (LDS or global); everything else is named registers.
 __device__ double procrustes_error(const float (*p1)[3], const float (*p2)[3], int nk) {
     double mu1[3] = {0, 0, 0}, mu2[3] = {0, 0, 0};
+    bool same = true;
     for (int j = 0; j < nk; ++j) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { mu1[c] += p1[j][c]; mu2[c] += p2[j][c]; }
+        for (int c = 0; c < 3; ++c) { mu1[c] += p1[j][c]; mu2[c] += p2[j][c]; same = same && p1[j][c] == p2[j][c]; }
     }
+    if (same) return 0.0;                                            // equal sets: exactly 0, not the 1e-16 of R ~ I, scale ~ 1
 #pragma unroll
     for (int c = 0; c < 3; ++c) { mu1[c] /= nk; mu2[c] /= nk; }
     double K[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, var1 = 0.0;
@@ -92,14 +95,16 @@ __device__ double procrustes_error(const float (*p1)[3], const float (*p2)[3], i
 #pragma unroll
             for (int c = 0; c < 3; ++c) K[r][c] += a[r] * b[c];
     }
-    double A[3][3], V[3][3];
+    double W[3][3], V[3][3];
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) A[r][c] = K[0][r] * K[0][c] + K[1][r] * K[1][c] + K[2][r] * K[2][c];
-    jacobi3(A, V);
-    // the two leading right singular vectors: eigen-columns of the two largest eigenvalues (selects, no index arrays)
-    const double l0 = A[0][0], l1 = A[1][1], l2 = A[2][2];
+        for (int c = 0; c < 3; ++c) W[r][c] = K[r][c];
+    hestenes3(W, V);
+    // the two leading right singular vectors: columns of the two largest |w_i|^2 (selects, no index arrays)
+    const double l0 = W[0][0] * W[0][0] + W[1][0] * W[1][0] + W[2][0] * W[2][0];
+    const double l1 = W[0][1] * W[0][1] + W[1][1] * W[1][1] + W[2][1] * W[2][1];
+    const double l2 = W[0][2] * W[0][2] + W[1][2] * W[1][2] + W[2][2] * W[2][2];
     const int first = (l0 >= l1 && l0 >= l2) ? 0 : ((l1 >= l2) ? 1 : 2);
     const int second = first == 0 ? (l1 >= l2 ? 1 : 2) : (first == 1 ? (l0 >= l2 ? 0 : 2) : (l0 >= l1 ? 0 : 1));
     double v[3][3];                                                  // v[i] = i-th right singular vector
