@@ -333,6 +333,45 @@ int rc_lstm_step(rc_ctx* ctx, const char* net, const float* x, const uint8_t* ro
 #define RC_SUBNET_SCRATCH_BYTES (256ll << 20)
 int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
                       const float* init_h, const float* init_c, float* final_h, float* final_c, void* stream);
+/* Training of one sub-net (the loop of articulate/utils/torch/train.py:117-122: loss_fn(net(d), l) -> backward() -> step()), split as
+ * the project is: the reverse recurrence in HIP, every time-parallel reduction left to the caller (robustcap_amd/train.py).
+ *
+ * rc_subnet_forward_tape: rc_subnet_forward (rnn.py:121-133) with the same arguments, contract, plan and bits of y / final_* in each
+ * gemm mode, which also records what back-propagation needs. acts DEVICE [3, F, H], F = sum T_i, rows in the caller's order like x:
+ * relu(linear1), h of LSTM layer 0, h of layer 1 at every frame. tape DEVICE, opaque, rc_subnet_tape_floats(...) floats (host-only
+ * entry, nothing enqueued): init_c by rank [2, n, H], then per layer the post-activation gates i, f, g, o [F, 4H] and c [F, H] in the
+ * plan's row order -- 40 * H bytes per frame. RC_ERR_INVALID also when the allocation behind acts or tape ends before the call's
+ * extent (nothing enqueued). Stateless with respect to the context like rc_subnet_forward. */
+int rc_subnet_forward_tape(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
+                           const float* init_h, const float* init_c, float* final_h, float* final_c, float* acts, float* tape,
+                           void* stream);
+int rc_subnet_tape_floats(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, int64_t* floats);
+/* Back-propagation through time of the two LSTM layers of rc_subnet_forward_tape(net, n, lengths_host) (eval mode: no dropout), on the
+ * same plan, chunks last to first: per step one launch of the sub-net GEMM kernel forms dh_rec = dG(t + 1) . W_hh on the layer's
+ * transposed pack (built on the device from the fp32 packing on first use; 20 * H * H bytes per layer) in the context's gemm mode, and
+ * its epilogue the cell's backward; per chunk and layer one tall launch forms dG . W_ih.
+ * In: tape; d_h1 DEVICE [F, H], the gradient of layer 1's h at every frame in the caller's order (dy . W2); d_final_h / d_final_c
+ * [2, n, H] or NULL (zeros): the gradients of final_h / final_c. Out: d_gates [2, F, 4H], the gradients of the gate pre-activations
+ * of layers 0 and 1, caller's rows, torch's columns g * H + u (g over i, f, g, o); d_a [F, H], the gradient of layer 0's input
+ * relu(linear1) (the caller applies the relu mask from acts[0]); d_init_h / d_init_c [2, n, H] or NULL. The weight gradients are the
+ * caller's reductions d_gates^T . input over all frames. Scratch (grow-only, released by rc_destroy): per chunk 20 * H bytes per row
+ * within the forward's chunk buffers, beside them 80 * H bytes of state per sequence of a group. RC_ERR_INVALID on the forward's
+ * cases, a null tape / d_h1 / d_gates / d_a, or when the allocation behind one of them ends before the call's extent (nothing
+ * enqueued). Ordered with the other sub-net calls like them. */
+int rc_subnet_backward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* tape, const float* d_h1,
+                       const float* d_final_h, const float* d_final_c, float* d_gates, float* d_a, float* d_init_h, float* d_init_c,
+                       void* stream);
+/* The optimiser step's way back (train.py:117-122: optimizer.step()): the tensors of ONE sub-net, already on the device, into every
+ * device array rc_finalize_weights derives from them -- both packings of linear1 / linear2 (and the row-major copy of a narrow
+ * linear2), the padded biases, both packings and the summed, permuted bias of each LSTM layer, for rnn2 the init_net layers, and the
+ * transposed packs of rc_subnet_backward -- by element-wise kernels with the host packing's index arithmetic and truncation split,
+ * bitwise what a reload of the same values gives. IN PLACE: every pointer held by launch tables, the sequence engine and a captured live
+ * frame stays valid; the other sub-nets are untouched. tensors_dev: HOST array of `count` DEVICE pointers in the order of the
+ * sub-net's keys in Net.state_dict() (per LSTM layer weight_ih, weight_hh, bias_ih, bias_hh; linear1.weight, .bias; linear2.weight,
+ * .bias; rnn2: init_net.0 / .2 / .4 weight, bias): 12 tensors, rnn2 18. Ordered after all work the context has enqueued on any stream
+ * (a device synchronise at entry) and before anything enqueued later (the call returns when its kernels on `stream` are done).
+ * RC_ERR_INVALID on an unknown net, a wrong count or a null tensor; RC_ERR_STATE before rc_finalize_weights. */
+int rc_update_subnet_weights(rc_ctx* ctx, const char* net, const void* const* tensors_dev, int32_t count, void* stream);
 /* RNNWithInit.init_net (articulate/utils/torch/rnn.py:195-201, used at :207-219): Linear(69,512) ReLU Linear(512,1024) ReLU
  * Linear(1024,2048) on v DEVICE [n, 69] -> out DEVICE [n, 2048], on the packed weights of rnn2.init_net in the context's gemm mode. */
 int rc_init_net_forward(rc_ctx* ctx, int32_t n, const float* v, float* out, void* stream);

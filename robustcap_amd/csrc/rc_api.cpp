@@ -674,6 +674,7 @@ int rc_ctx_init_net(rc_ctx* ctx, SubnetDense out[3]) {
 }
 int rc_ctx_net_index(const char* name) { return net_index(name); }
 int rc_ctx_gemm_split(rc_ctx* ctx) { return ctx->gemm_split ? 1 : 0; }
+long long rc_ctx_weights_epoch(rc_ctx* ctx) { return ctx->weights_epoch; }
 SubnetOwner& rc_ctx_subnet(rc_ctx* ctx) { return ctx->subnet; }
 SmplifyOwner& rc_ctx_smplify(rc_ctx* ctx) { return ctx->smplify; }
 unsigned long long rc_ctx_ign_mask(rc_ctx* ctx) { return ctx->ign_mask; }
@@ -841,10 +842,50 @@ int rc_finalize_weights(rc_ctx* ctx) {
     ctx->weight_allocs.clear();
     ctx->have_weights = false;
     seq_weights_changed(ctx);
+    ctx->weights_epoch += 1;
     ctx->alloc_weights = true;
     const int rc = finalize_weights_impl(ctx);
     ctx->alloc_weights = false;
     return rc;
+}
+
+// One sub-net's tensors, already on the device, into every device array finalize_weights_impl derives from them -- in place, so every pointer
+// held by the launch tables, the sequence engine and a captured live frame stays valid. Order of tensors_dev: the sub-net's keys of
+// Net.state_dict() (per layer weight_ih, weight_hh, bias_ih, bias_hh; linear1 weight, bias; linear2 weight, bias; rnn2: init_net 0, 2, 4).
+int rc_update_subnet_weights(rc_ctx* ctx, const char* net, const void* const* tensors_dev, int32_t count, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    if (!net || !tensors_dev) return fail(ctx, RC_ERR_INVALID, "rc_update_subnet_weights: null argument");
+    const int ni = net_index(net);
+    if (ni < 0) return fail(ctx, RC_ERR_INVALID, std::string("rc_update_subnet_weights: unknown net ") + net);
+    const int want = ni == N2 ? 18 : 12;
+    if (count != want) return fail(ctx, RC_ERR_INVALID, "rc_update_subnet_weights: " + std::string(net) + " has " + std::to_string(want) + " tensors");
+    for (int i = 0; i < count; ++i)
+        if (!tensors_dev[i]) return fail(ctx, RC_ERR_INVALID, "rc_update_subnet_weights: null tensor");
+    if (!ctx->have_weights) return fail(ctx, RC_ERR_STATE, "rc_update_subnet_weights: weights not finalized");
+    hipStream_t st = (hipStream_t)stream;
+    auto T = [&](int i) { return static_cast<const float*>(tensors_dev[i]); };
+    // ordered after everything the context has enqueued on any of its streams (and what a live session computed ahead is dropped) ...
+    live_forget_last_frame(ctx);
+    if (int rc = live_discard_ahead(ctx)) return rc;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    NetDev& n = ctx->net[ni];
+    auto dense = [&](Dense& d, const float* W, const float* b) -> int {
+        rc_launch_repack_dense(W, d.N, d.K, d.Np, d.Kp, d.W, d.Ws, st);
+        if (d.Wrm) HIP_TRY(ctx, hipMemcpyAsync(d.Wrm, W, (size_t)d.N * d.K * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(d.b, b, (size_t)d.N * sizeof(float), hipMemcpyDeviceToDevice, st));   // (the padding stays zero)
+        return RC_OK;
+    };
+    for (int l = 0; l < 2; ++l) rc_launch_repack_lstm(T(4 * l), T(4 * l + 1), T(4 * l + 2), T(4 * l + 3), n.H, n.Wl[l], n.Wls[l], n.bl[l], st);
+    if (int rc = dense(n.lin1, T(8), T(9))) return rc;
+    if (int rc = dense(n.lin2, T(10), T(11))) return rc;
+    if (ni == N2)
+        for (int q = 0; q < 3; ++q)
+            if (int rc = dense(ctx->init[q], T(12 + 2 * q), T(13 + 2 * q))) return rc;
+    rc_subnet_retranspose(ctx->subnet.get(), ni, n.Wl, n.H, ctx->weights_epoch, st);
+    HIP_TRY(ctx, hipGetLastError());
+    // ... and before anything enqueued later, on whatever stream
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return RC_OK;
 }
 
 static int finalize_weights_impl(rc_ctx* ctx) {

@@ -60,6 +60,7 @@ struct rc_ctx {
     size_t sweep_scratch_cap = 0;
     unsigned long long ign_mask = RC_IGN_DEFAULT;     // smplify: landmarks with zeroed confidence
     bool have_body = false, have_weights = false;
+    long long weights_epoch = 0;         // counts rc_finalize_weights (rc_subnet_backward: its transposed packs are derived from the packings)
     std::map<std::string, std::vector<float>> staged;    // host copy of the tensors loaded since the last rc_finalize_weights
                                                          // (released there: a context does not hold 254 MB of host memory)
     std::vector<DevBuf<char>> allocs;

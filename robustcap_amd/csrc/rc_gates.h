@@ -25,3 +25,30 @@ __device__ __forceinline__ void rc_lstm_cell(float gi, float gf, float gg, float
     c_new = __builtin_fmaf(fg, c_prev, ig * cg);
     h_new = og * rc_gate_tanh(c_new);
 }
+
+// The same update, also returning the four gate activations (the tape of rc_subnet_forward_tape): the operations of rc_lstm_cell in
+// its order, so that c' and h' keep their bits.
+__device__ __forceinline__ void rc_lstm_cell_acts(float gi, float gf, float gg, float go, float c_prev, float& c_new, float& h_new,
+                                                  float& ig, float& fg, float& cg, float& og) {
+    ig = rc_gate_sigmoid(gi); fg = rc_gate_sigmoid(gf);
+    cg = rc_gate_tanh(gg); og = rc_gate_sigmoid(go);
+    c_new = __builtin_fmaf(fg, c_prev, ig * cg);
+    h_new = og * rc_gate_tanh(c_new);
+}
+
+// One cell of back-propagation through time (eval-mode aten::lstm; the loop of articulate/utils/torch/train.py:117-122 reaches it through
+// loss.backward()). In: the recorded activations i, f, g, o, c(t) and c(t - 1), dh = the gradient of h(t) from the layer above plus
+// the recurrent one, dc_next = the gradient of c(t) carried from step t + 1. Out: the gradients of the four gate PRE-activations
+// (sigma' = s (1 - s), tanh' = 1 - g^2) and dc_prev, the gradient carried to step t - 1. tanh(c) is formed as the forward formed it.
+__device__ __forceinline__ void rc_lstm_cell_backward(float ig, float fg, float cg, float og, float c, float c_prev, float dh, float dc_next,
+                                                      float& dgi, float& dgf, float& dgg, float& dgo, float& dc_prev) {
+    const float tc = rc_gate_tanh(c);
+    const float d_o = dh * tc;
+    const float dc = dc_next + dh * og * (1.0f - tc * tc);
+    const float d_i = dc * cg, d_g = dc * ig, d_f = dc * c_prev;
+    dc_prev = dc * fg;
+    dgi = d_i * ig * (1.0f - ig);
+    dgf = d_f * fg * (1.0f - fg);
+    dgg = d_g * (1.0f - cg * cg);
+    dgo = d_o * og * (1.0f - og);
+}

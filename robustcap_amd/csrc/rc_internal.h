@@ -527,7 +527,8 @@ unsigned long long rc_ctx_ign_mask(rc_ctx* ctx);
 // the weight k-blocks of a column tile staged once per workgroup in LDS and applied to all its rows. It forms the K quarters
 // [c0, c1) of the packed weights (the per-wave chains of gemm_tile: quarter q = packed k [q Kp / 4, (q + 1) Kp / 4)) with the chains'
 // instructions (rc_mma.h) and sums them in gemm_tile's order, so every output has the bits of the stepped launches.
-enum { RC_SG_DENSE = 0, RC_SG_RELU = 1, RC_SG_HALF = 2, RC_SG_LSTM = 3 };
+enum { RC_SG_DENSE = 0, RC_SG_RELU = 1, RC_SG_HALF = 2, RC_SG_LSTM = 3,
+       RC_SG_BPLAIN = 4, RC_SG_BSTEP = 5 };   // backward through time (rc_subnet_backward): the kernel's BWD instantiation
 struct SubGemm {
     const float* A;          // rc_pk order, [rows, lda]; the chains read A column k - a_koff for packed k
     int lda, a_koff, M;
@@ -548,8 +549,32 @@ struct SubGemm {
     float* hout;             // h(t): rc_pk(row, unit, H)
     float* hseq;             // ... and the chunk's sequence buffer rc_pk(hseq_row0 + row, unit, H)
     long long hseq_row0;
+    // LSTM, recording (rc_subnet_forward_tape; null otherwise): the step's rows of the tape, in plan order
+    float* tape_g;           // [rows, 4H] gate activations, packed column order (unit * 4 + i, f, g, o)
+    float* tape_c;           // [rows, H] c(t)
+    // BPLAIN: out[row' * ldo + col] = ((q0 + q1) + q2) + q3, row' = out_map ? out_map[row] : row (no bias)
+    // BSTEP (one reverse step of a layer over the active prefix; A = dG(t + 1) in rc_pk order, weights = the transposed pack's W_hh
+    // columns): dh = (row < n_next ? sum : dfin_h[row, u]) + dh_above, then the per-unit recurrences of rc_lstm_cell_backward on the
+    // step's tape rows (tape_g, tape_c; c_prev) and the carried dc (cst, in place); dG(t) goes to hout (rc_pk, the next step's A),
+    // hseq (the chunk's buffer) and dgates (the caller's rows, torch's column order g * H + u)
+    int n_next;              // rows still running at step t + 1 (the others enter here with dfin_h and the dc the state was set to)
+    const float* dfin_h;     // [rows, H]
+    const float* dh_above;   // [*, H]: row dha_map ? dha_map[row] : row
+    const int* dha_map;
+    const float* c_prev;     // [rows, H]: c(t - 1) of the step's rows (the tape's previous step, or init_c by rank)
+    float* dgates;           // [*, 4H] at row out_map[row]
 };
 void rc_launch_subnet_gemm(const SubGemm& G, int split, int tall, hipStream_t s);   // tall: 256-row tiles whatever M
+void rc_launch_subnet_gemm_bwd(const SubGemm& G, int split, int tall, hipStream_t s);   // epi RC_SG_BPLAIN / RC_SG_BSTEP, the same tile dispatch
+// dst[map[j] * cols + k] = src[rc_pk(j, k, ld)] for j < rows, k < cols (a chunk's sequence buffer -> the caller's rows)
+void rc_launch_subnet_unpack(const float* src, int ld, const int* map, float* dst, int cols, int rows, hipStream_t s);
+// backward state of ranks [0, nr) <-> sequences perm[r] (n: sequences in src / dst, [2, n, H]; a, b: per layer [rows, H], ls floats apart).
+// in = 1: a, b (either may be null) from src_a, src_b (zeros where null); in = 0: dst_b (may be null) from b
+void rc_launch_subnet_bstate(float* a, float* b, long long ls, const float* src_a, const float* src_b, float* dst_b, const int* perm,
+                             int nr, int n, int H, int in, hipStream_t s);
+// transposed operand of an LSTM layer from its fp32 packing Wl (Np = 4H, Kp = 2H): the same packing with Np = 2H, Kp = 4H of
+// WT[n'][k'] = Wl's value at (column k', k = n'), as the fp32 pack WT and the three bf16 planes WTs
+void rc_launch_subnet_transpose(const float* Wl, int H, float* WT, void* WTs, hipStream_t s);
 // dst[rc_pk(j, k, ld)] = k < cols ? src[map[j] * cols + k] : 0 for j < rows, k < ld (user rows -> zero-padded A operand)
 void rc_launch_subnet_pack(const float* src, int cols, const int* map, float* dst, int ld, int rows, hipStream_t s);
 // state of sequence perm[r] <-> row r < nr (n: sequences in h, c). hp: per layer (hp + l * hl) two copies of h in rc_pk order, ps floats apart; cp: per layer
@@ -557,6 +582,10 @@ void rc_launch_subnet_pack(const float* src, int cols, const int* map, float* ds
 // in = 0: h, c (either may be null) from copy par[r] of hp and from cp
 void rc_launch_subnet_state(float* hp, long long hl, long long ps, const int* par, float* cp, long long cl, float* h, float* c,
                             const int* perm, int nr, int n, int H, int in, hipStream_t s);
+// in-place repack on the device (rc_update_subnet_weights): the index arithmetic and truncation split of pack_weights / pack_weights_split
+void rc_launch_repack_dense(const float* Wsrc, int N, int K, int Np, int Kp, float* W, void* Ws, hipStream_t s);
+void rc_launch_repack_lstm(const float* wi, const float* wh, const float* bi, const float* bh, int H, float* W, void* Ws, float* bl,
+                           hipStream_t s);
 
 // narrow view of the context for rc_subnet_api.cpp
 struct SubnetState;
@@ -566,6 +595,9 @@ int rc_ctx_subnet_net(rc_ctx* ctx, int net, SubnetNet* out);     // net: kNets i
 int rc_ctx_init_net(rc_ctx* ctx, SubnetDense out[3]);
 int rc_ctx_net_index(const char* name);
 int rc_ctx_gemm_split(rc_ctx* ctx);
+long long rc_ctx_weights_epoch(rc_ctx* ctx);               // counts rc_finalize_weights: what was derived from the packed weights is stale
 void rc_subnet_free(SubnetState* s);                       // delete s
 using SubnetOwner = std::unique_ptr<SubnetState, RcRelease<rc_subnet_free>>;
 SubnetOwner& rc_ctx_subnet(rc_ctx* ctx);
+// the transposed packs of net ni that exist are rebuilt from the layers' fp32 packings Wl on stream s (rc_update_subnet_weights)
+void rc_subnet_retranspose(SubnetState* S, int ni, const float* const Wl[2], int H, long long epoch, hipStream_t s);

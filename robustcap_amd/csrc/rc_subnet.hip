@@ -16,7 +16,8 @@
 
 #define RC_SG_STAGE 4         // k-blocks of weights staged in LDS per round
 
-template <int MR, int NC, bool SPLIT>
+// BWD: the epilogues of the reverse recurrence (RC_SG_BPLAIN, RC_SG_BSTEP) in place of the forward's; the K loop is the same code.
+template <int MR, int NC, bool SPLIT, bool BWD = false>
 __global__ __launch_bounds__(256) void rc_subnet_gemm_kernel(const SubGemm G) {
     constexpr int U = SPLIT ? 192 : 128;                 // uint4 per (16-column block, 32-k block): three bf16 planes, or two fp32 chunks
     constexpr int ROWS = 64 * MR, COLS = 16 * NC, LD = COLS + 4;
@@ -94,6 +95,38 @@ __global__ __launch_bounds__(256) void rc_subnet_gemm_kernel(const SubGemm G) {
         const int row = m0 + rl, col = cb0 * 16 + 4 * q4;
         if (row >= G.M || col >= G.ncb * 16 || col >= G.N) continue;
         f32x4 v = *reinterpret_cast<const f32x4*>(&s_o[rl * LD + 4 * q4]);
+        if constexpr (BWD) {
+            if (G.epi == RC_SG_BPLAIN) {
+                const long long orow = G.out_map ? G.out_map[row] : row;
+                *reinterpret_cast<f32x4*>(&G.out[orow * G.ldo + col]) = v;
+                continue;
+            }
+            // RC_SG_BSTEP: columns = four consecutive hidden units
+            const long long ci = (long long)row * G.H + col;
+            if (row >= G.n_next) v = *reinterpret_cast<const f32x4*>(&G.dfin_h[ci]);     // the sequence's last frame: no step t + 1
+            const long long arow = G.dha_map ? G.dha_map[row] : row;
+            v += *reinterpret_cast<const f32x4*>(&G.dh_above[arow * G.H + col]);
+            const f32x4 c4 = *reinterpret_cast<const f32x4*>(&G.tape_c[ci]);
+            const f32x4 cp4 = *reinterpret_cast<const f32x4*>(&G.c_prev[ci]);
+            const f32x4 dcn = *reinterpret_cast<const f32x4*>(&G.cst[ci]);
+            f32x4 dcp, dg[4];                                                 // dg[gate][unit]
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(&G.tape_g[(long long)row * 4 * G.H + 4 * (col + q)]);
+                float d0, d1, d2, d3, dp;
+                rc_lstm_cell_backward(a[0], a[1], a[2], a[3], c4[q], cp4[q], v[q], dcn[q], d0, d1, d2, d3, dp);
+                const f32x4 d = {d0, d1, d2, d3};
+                dcp[q] = dp;
+                *reinterpret_cast<f32x4*>(&G.hout[rc_pk(row, 4 * (col + q), 4 * G.H)]) = d;
+                *reinterpret_cast<f32x4*>(&G.hseq[rc_pk(G.hseq_row0 + row, 4 * (col + q), 4 * G.H)]) = d;
+                dg[0][q] = d[0]; dg[1][q] = d[1]; dg[2][q] = d[2]; dg[3][q] = d[3];
+            }
+            *reinterpret_cast<f32x4*>(&G.cst[ci]) = dcp;
+            float* dr = G.dgates + (long long)G.out_map[row] * 4 * G.H + col;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4*>(dr + (long long)g * G.H) = dg[g];
+            continue;
+        }
         if (G.epi == RC_SG_HALF) {
             *reinterpret_cast<f32x4*>(&G.out[(long long)row * G.ldo + col]) = v;
             continue;
@@ -105,8 +138,13 @@ __global__ __launch_bounds__(256) void rc_subnet_gemm_kernel(const SubGemm G) {
             const int unit = col >> 2;
             const long long ci = (long long)row * G.H + unit;
             float cn, hn;
-            rc_lstm_cell(g4[0], g4[1], g4[2], g4[3], G.cst[ci], cn, hn);
+            float ai, af, ag, ao;
+            rc_lstm_cell_acts(g4[0], g4[1], g4[2], g4[3], G.cst[ci], cn, hn, ai, af, ag, ao);
             G.cst[ci] = cn;
+            if (G.tape_g) {
+                *reinterpret_cast<f32x4*>(&G.tape_g[(long long)row * 4 * G.H + col]) = f32x4{ai, af, ag, ao};
+                G.tape_c[ci] = cn;
+            }
             G.hout[rc_pk(row, unit, G.H)] = hn;
             G.hseq[rc_pk(G.hseq_row0 + row, unit, G.H)] = hn;
             continue;
@@ -120,7 +158,8 @@ __global__ __launch_bounds__(256) void rc_subnet_gemm_kernel(const SubGemm G) {
     }
 }
 
-void rc_launch_subnet_gemm(const SubGemm& G, int split, int tall, hipStream_t s) {
+template <bool BWD>
+static void launch_subnet_gemm(const SubGemm& G, int split, int tall, hipStream_t s) {
     if (G.M <= 0) return;
     // tall launches (every frame of a chunk; init_net): 256-row tiles whatever M, so each staged weight k-block serves 256 A rows. A time
     // step's active rows: 256-row tiles above 512 rows, else 64-row tiles, 16 columns wide at most 64 rows (more workgroups streaming
@@ -130,14 +169,17 @@ void rc_launch_subnet_gemm(const SubGemm& G, int split, int tall, hipStream_t s)
     const dim3 grid((G.M + 64 * mr - 1) / (64 * mr), (cbs + nc - 1) / nc), block(256);
 #define RC_SG_GO(MR, NC)                                                                                   \
     do {                                                                                                   \
-        if (split) hipLaunchKernelGGL((rc_subnet_gemm_kernel<MR, NC, true>), grid, block, 0, s, G);       \
-        else hipLaunchKernelGGL((rc_subnet_gemm_kernel<MR, NC, false>), grid, block, 0, s, G);            \
+        if (split) hipLaunchKernelGGL((rc_subnet_gemm_kernel<MR, NC, true, BWD>), grid, block, 0, s, G);  \
+        else hipLaunchKernelGGL((rc_subnet_gemm_kernel<MR, NC, false, BWD>), grid, block, 0, s, G);       \
     } while (0)
     if (mr == 4) RC_SG_GO(4, 4);
     else if (nc == 4) RC_SG_GO(1, 4);
     else RC_SG_GO(1, 1);
 #undef RC_SG_GO
 }
+
+void rc_launch_subnet_gemm(const SubGemm& G, int split, int tall, hipStream_t s) { launch_subnet_gemm<false>(G, split, tall, s); }
+void rc_launch_subnet_gemm_bwd(const SubGemm& G, int split, int tall, hipStream_t s) { launch_subnet_gemm<true>(G, split, tall, s); }
 
 __global__ void rc_subnet_pack_kernel(const float* src, int cols, const int* map, float* dst, int ld, int rows) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -178,4 +220,102 @@ void rc_launch_subnet_state(float* hp, long long hl, long long ps, const int* pa
     const long long tot = 2ll * nr * H;
     hipLaunchKernelGGL(rc_subnet_state_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, hp, hl, ps, par, cp, cl, h, c, perm,
                        nr, n, H, in);
+}
+
+__global__ void rc_subnet_unpack_kernel(const float* src, int ld, const int* map, float* dst, int cols, int rows) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)rows * cols) return;
+    const int j = (int)(idx / cols), k = (int)(idx - (long long)j * cols);
+    dst[(long long)map[j] * cols + k] = src[rc_pk(j, k, ld)];
+}
+
+void rc_launch_subnet_unpack(const float* src, int ld, const int* map, float* dst, int cols, int rows, hipStream_t s) {
+    const long long n = (long long)rows * cols;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(rc_subnet_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, ld, map, dst, cols, rows);
+}
+
+__global__ void rc_subnet_bstate_kernel(float* a, float* b, long long ls, const float* src_a, const float* src_b, float* dst_b,
+                                        const int* perm, int nr, int n, int H, int in) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= 2ll * nr * H) return;
+    const int l = (int)(idx / ((long long)nr * H));
+    const long long rem = idx - (long long)l * nr * H;
+    const int r = (int)(rem / H);
+    const long long user = ((long long)l * n + perm[r]) * H + (rem - (long long)r * H);
+    if (in) {
+        if (a) a[l * ls + rem] = src_a ? src_a[user] : 0.0f;
+        if (b) b[l * ls + rem] = src_b ? src_b[user] : 0.0f;
+    } else if (dst_b) {
+        dst_b[user] = b[l * ls + rem];
+    }
+}
+
+void rc_launch_subnet_bstate(float* a, float* b, long long ls, const float* src_a, const float* src_b, float* dst_b, const int* perm,
+                             int nr, int n, int H, int in, hipStream_t s) {
+    const long long tot = 2ll * nr * H;
+    hipLaunchKernelGGL(rc_subnet_bstate_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a, b, ls, src_a, src_b, dst_b, perm,
+                       nr, n, H, in);
+}
+
+// ---- packings written on the device: the index arithmetic and the truncation split of pack_weights / pack_weights_split (rc_api.cpp) ----
+// value v of logical element (column n, k) of a matrix packed with Kp: into the fp32 pack W and the three bf16 planes Ws
+__device__ __forceinline__ void rc_pack_store(float* W, unsigned short* Ws, int Kp, int n, int k, float v) {
+    const int cb = n >> 4, j = n & 15;
+    W[((((long long)cb * (Kp / RC_KC) + (k >> 4)) * 64 + ((k >> 2) & 3) * 16 + j) << 2) + (k & 3)] = v;
+    const unsigned u = __float_as_uint(v), uh = u & 0xffff0000u;
+    const float r1 = v - __uint_as_float(uh);
+    const unsigned um = __float_as_uint(r1) & 0xffff0000u;
+    const float r2 = r1 - __uint_as_float(um);
+    const int kb = k >> 5, r = k & 31, lane = ((r & 15) >> 2) * 16 + j, e = (r >> 4) * 4 + (r & 3);
+    const long long base = (((long long)cb * (Kp / 32) + kb) * 3) * 512 + lane * 8 + e;
+    Ws[base] = (unsigned short)(uh >> 16);
+    Ws[base + 512] = (unsigned short)(um >> 16);
+    Ws[base + 1024] = (unsigned short)(__float_as_uint(r2) >> 16);
+}
+
+__global__ void rc_subnet_transpose_kernel(const float* Wl, int H, float* WT, unsigned short* WTs) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= 8ll * H * H) return;
+    const int n = (int)(idx / (4 * H)), k = (int)(idx - (long long)n * 4 * H);      // the transposed operand's column n < 2H and k < 4H
+    // Wl's element (column k, k index n): [cb][q][lane][4] with Q = 2H / 16
+    const float v = Wl[((((long long)(k >> 4) * (2 * H / RC_KC) + (n >> 4)) * 64 + ((n >> 2) & 3) * 16 + (k & 15)) << 2) + (n & 3)];
+    rc_pack_store(WT, WTs, 4 * H, n, k, v);
+}
+
+void rc_launch_subnet_transpose(const float* Wl, int H, float* WT, void* WTs, hipStream_t s) {
+    const long long n = 8ll * H * H;
+    hipLaunchKernelGGL(rc_subnet_transpose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Wl, H, WT, (unsigned short*)WTs);
+}
+
+// ---- in-place repack of one sub-net's tensors (rc_update_subnet_weights): what make_dense / rc_finalize_weights pack on the host ---------
+// dense layer from the row-major tensor W [N, K]: element (n, k) of the padded [Np, Kp] matrix, zeros in the padding
+__global__ void rc_repack_dense_kernel(const float* Wsrc, int N, int K, int Np, int Kp, float* W, unsigned short* Ws) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)Np * Kp) return;
+    const int n = (int)(idx / Kp), k = (int)(idx - (long long)n * Kp);
+    rc_pack_store(W, Ws, Kp, n, k, (n < N && k < K) ? Wsrc[(long long)n * K + k] : 0.0f);
+}
+
+void rc_launch_repack_dense(const float* Wsrc, int N, int K, int Np, int Kp, float* W, void* Ws, hipStream_t s) {
+    const long long n = (long long)Np * Kp;
+    hipLaunchKernelGGL(rc_repack_dense_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Wsrc, N, K, Np, Kp, W, (unsigned short*)Ws);
+}
+
+// LSTM layer from weight_ih, weight_hh [4H, H] and the two biases [4H]: packed column n' <-> torch row g * H + 4 * cb + u (cb = n' / 16,
+// u = (n' % 16) / 4, g = n' % 4), k < H from weight_ih, else weight_hh; bl[n'] = bias_ih + bias_hh of that row
+__global__ void rc_repack_lstm_kernel(const float* wi, const float* wh, const float* bi, const float* bh, int H, float* W, unsigned short* Ws,
+                                      float* bl) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= 8ll * H * H) return;
+    const int np = (int)(idx / (2 * H)), k = (int)(idx - (long long)np * 2 * H);
+    const long long r = (long long)(np & 3) * H + 4 * (np >> 4) + ((np & 15) >> 2);
+    rc_pack_store(W, Ws, 2 * H, np, k, k < H ? wi[r * H + k] : wh[r * H + (k - H)]);
+    if (k == 0) bl[np] = bi[r] + bh[r];
+}
+
+void rc_launch_repack_lstm(const float* wi, const float* wh, const float* bi, const float* bh, int H, float* W, void* Ws, float* bl,
+                           hipStream_t s) {
+    const long long n = 8ll * H * H;
+    hipLaunchKernelGGL(rc_repack_lstm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, wi, wh, bi, bh, H, W, (unsigned short*)Ws, bl);
 }

@@ -8,6 +8,13 @@
 // A chunk holds as many steps as keep its buffers within RC_SUBNET_SCRATCH_BYTES; more sequences than one step's worth of rows fit
 // there are run as independent groups. The recurrent state of a group lives in buffers of its own (two copies of h per layer: step
 // t reads copy (t - 1) & 1 and writes copy t & 1, so a sequence that has ended keeps its last h in copy (T_i - 1) & 1).
+//
+// Training of one sub-net (articulate/utils/torch/train.py:117-122): rc_subnet_forward_tape is the same forward on the same plan, which
+// also copies the chunk's sequence buffers to the caller's rows (acts) and records every step's gate activations and c in plan order
+// (tape); rc_subnet_backward walks the plan's chunks and steps backwards. Its only sequential part, dh_rec = dG(t + 1) . W_hh, is the
+// same kernel on the layer's transposed pack (built on the device from the fp32 packing, on first use) with the cell's backward as
+// its epilogue; dG . W_ih of a whole chunk is one tall launch per layer. Weight gradients are reductions over all frames and are left
+// to the caller (robustcap_amd/train.py).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <numeric>
@@ -29,9 +36,21 @@ struct SubnetState {                 // (grow-only buffers; the context's destru
     HipEvent ev;                     // the last upload from ihost
     HipEvent done;                   // the end of the last call's work (a call on another stream waits for it: the scratch is shared)
     long long calls = 0, frames = 0, chunks = 0;
+    // backward through time
+    DevBuf<float> bst;               // state of a group: per layer two copies of dG [npad, 4H] (rc_pk), d_final_h [npad, H], carried dc [npad, H]
+    size_t bst_floats = 0;
+    struct TPack { DevBuf<float> W; DevBuf<uint16_t> Ws; long long epoch = -1; } tp[6][2];   // transposed operand per net and layer
 };
 
 void rc_subnet_free(SubnetState* s) { delete s; }
+
+void rc_subnet_retranspose(SubnetState* S, int ni, const float* const Wl[2], int H, long long epoch, hipStream_t s) {
+    if (!S) return;
+    for (int l = 0; l < 2; ++l) {
+        SubnetState::TPack& t = S->tp[ni][l];
+        if (t.W && t.epoch == epoch) rc_launch_subnet_transpose(Wl[l], H, t.W.get(), t.Ws.get(), s);
+    }
+}
 
 namespace {
 
@@ -52,54 +71,45 @@ SubGemm dense(const SubnetDense& d, const float* A, int M, float* out, int ldo, 
     return g;
 }
 
-}  // namespace
+// ---- host plan, shared by every entry: ranks by length (longest first), start rows, groups, chunks, row maps ----------------------
+struct Chunk {
+    int g0, g1, t0, t1;              // ranks [g0, g1) of the group, steps [t0, t1)
+    long long frame0;                // first plan row of the chunk
+    std::vector<long long> off;      // off[t - t0]: first row of step t within the chunk; off.back(): rows of the chunk
+    int next_rows;                   // rows of the group still running at step t1 (0 at the group's end)
+};
+struct Plan {
+    long long total = 0, max_rows = 0;
+    int max_group = 0;
+    std::vector<Chunk> chunks;
+    std::vector<int> ih;             // [n] rank -> sequence | [n] final copy per rank | [total] plan row -> caller's row
+};
 
-extern "C" {
-
-int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
-                      const float* init_h, const float* init_c, float* final_h, float* final_c, void* stream) {
-    if (!ctx) return RC_ERR_INVALID;
-    if (!net || !lengths_host || !x || !y) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_subnet_forward: null argument");
-    const int ni = rc_ctx_net_index(net);
-    if (ni < 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (std::string("rc_subnet_forward: unknown net ") + net).c_str());
-    if (n < 1) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_subnet_forward: no sequences");
-    for (int i = 0; i < n; ++i)
-        if (lengths_host[i] < 1) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_subnet_forward: every sequence needs at least one frame");
-    SubnetNet w;
-    if (rc_ctx_subnet_net(ctx, ni, &w)) return rc_ctx_fail(ctx, RC_ERR_STATE, "rc_subnet_forward: weights not finalized");
-    const int split = rc_ctx_gemm_split(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    SubnetState* S = state(ctx);
-    const int H = w.H, Kp1 = w.lin1.Kp;
-
-    // ---- host plan: ranks by length (longest first), start rows, groups, chunks, row maps ----------------------------------------
+// rows_max: rows of a chunk (and ranks of a group) at most, a multiple of 16
+bool make_plan(int n, const int32_t* lengths, long long rows_max, Plan& P) {
     std::vector<long long> start(n);
     long long total = 0;
-    for (int i = 0; i < n; ++i) { start[i] = total; total += lengths_host[i]; }
+    for (int i = 0; i < n; ++i) { start[i] = total; total += lengths[i]; }
     std::vector<int> perm(n);
     std::iota(perm.begin(), perm.end(), 0);
-    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return lengths_host[a] > lengths_host[b]; });
-    const long long row_bytes = 4ll * (Kp1 + 6ll * H);                   // X, relu(linear1) | h of layer 1, x halves (4H), h of layer 0
-    const long long rows_max = std::max(16ll, RC_SUBNET_SCRATCH_BYTES / row_bytes / 16 * 16);
-    struct Chunk { int g0, g1, t0, t1; long long frame0; std::vector<long long> off; };   // off[t - t0]: first row of step t
-    std::vector<Chunk> chunks;
-    std::vector<int> ih(2 * (size_t)n + (size_t)total);
-    int* iperm = ih.data();
-    int* ipar = ih.data() + n;
-    int* imap = ih.data() + 2 * (size_t)n;
-    long long frame = 0, max_rows = 0;
-    int max_group = 0;
-    for (int r = 0; r < n; ++r) { iperm[r] = perm[r]; ipar[r] = (lengths_host[perm[r]] - 1) & 1; }
+    std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return lengths[a] > lengths[b]; });
+    P.total = total;
+    P.ih.assign(2 * (size_t)n + (size_t)total, 0);
+    int* iperm = P.ih.data();
+    int* ipar = P.ih.data() + n;
+    int* imap = P.ih.data() + 2 * (size_t)n;
+    long long frame = 0;
+    for (int r = 0; r < n; ++r) { iperm[r] = perm[r]; ipar[r] = (lengths[perm[r]] - 1) & 1; }
     for (int g0 = 0; g0 < n; g0 += (int)rows_max) {
         const int g1 = (int)std::min<long long>(n, g0 + rows_max);
-        max_group = std::max(max_group, g1 - g0);
-        const int tmax = lengths_host[perm[g0]];
+        P.max_group = std::max(P.max_group, g1 - g0);
+        const int tmax = lengths[perm[g0]];
         int active = g1 - g0;                                             // n_t of the group
         for (int t = 0; t < tmax;) {
-            Chunk c{g0, g1, t, t, frame, {}};
+            Chunk c{g0, g1, t, t, frame, {}, 0};
             long long rows = 0;
             while (t < tmax) {
-                while (active > 0 && lengths_host[perm[g0 + active - 1]] <= t) --active;
+                while (active > 0 && lengths[perm[g0 + active - 1]] <= t) --active;
                 if (rows > 0 && rows + active > rows_max) break;
                 c.off.push_back(rows);
                 for (int r = 0; r < active; ++r) imap[frame + rows + r] = (int)(start[perm[g0 + r]] + t);
@@ -107,23 +117,49 @@ int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* le
                 ++t;
             }
             c.t1 = t;
+            c.next_rows = t < tmax ? active : 0;
             c.off.push_back(rows);
             frame += rows;
-            max_rows = std::max(max_rows, rows);
-            chunks.push_back(std::move(c));
+            P.max_rows = std::max(P.max_rows, rows);
+            P.chunks.push_back(std::move(c));
         }
     }
-    if (frame != total) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_subnet_forward: internal plan mismatch");
+    return frame == total;
+}
 
-    // ---- scratch (grow-only) and the upload of the plan -----------------------------------------------------------------------------
-    // The scratch is shared by every call of the context: a call on another stream than the previous one waits for that call's work.
-    if (S->done) HIP_TRY(ctx, hipStreamWaitEvent(st, S->done.get(), 0));
-    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->done), hipEventDisableTiming));
-    // (grow-only scratch, contents not kept; releasing the old buffer waits for the work that still reads it)
-    const long long R = r16(max_rows), G = r16(max_group);
-    const size_t n_buf = (size_t)(R * (Kp1 + 6ll * H)), n_st = (size_t)(6 * G * H);
-    HIP_TRY(ctx, rc_grow(S->buf_floats, n_buf, n_buf, S->buf, n_buf));
-    HIP_TRY(ctx, rc_grow(S->st_floats, n_st, n_st, S->st, n_st));
+// rows of a chunk at most: X, relu(linear1) | h of layer 1, x halves (4H), h of layer 0 per row within RC_SUBNET_SCRATCH_BYTES. The backward
+// pass needs less per row (dG 4H, dh from above H) and runs on the same plan.
+long long plan_rows_max(const SubnetNet& w) {
+    const long long row_bytes = 4ll * (w.lin1.Kp + 6ll * w.H);
+    return std::max(16ll, RC_SUBNET_SCRATCH_BYTES / row_bytes / 16 * 16);
+}
+
+long long tape_floats(const SubnetNet& w, int n, long long total) { return 2ll * n * w.H + 10ll * total * w.H; }
+
+// the device allocation behind p holds at least `bytes` from p on
+bool dev_holds(const void* p, long long bytes) {
+    void* base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return (long long)((const char*)base + size - (const char*)p) >= bytes;
+}
+
+// validates what every entry takes; on RC_OK: *ni, *w
+int check_args(rc_ctx* ctx, const char* what, const char* net, int32_t n, const int32_t* lengths_host, bool others_null, int* ni, SubnetNet* w) {
+    const std::string f(what);
+    if (!net || !lengths_host || others_null) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + ": null argument").c_str());
+    *ni = rc_ctx_net_index(net);
+    if (*ni < 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + ": unknown net " + net).c_str());
+    if (n < 1) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + ": no sequences").c_str());
+    for (int i = 0; i < n; ++i)
+        if (lengths_host[i] < 1) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + ": every sequence needs at least one frame").c_str());
+    if (rc_ctx_subnet_net(ctx, *ni, w)) return rc_ctx_fail(ctx, RC_ERR_STATE, (f + ": weights not finalized").c_str());
+    return RC_OK;
+}
+
+// the call's turn at the shared scratch, the plan's upload
+int upload_plan(rc_ctx* ctx, SubnetState* S, const Plan& P, hipStream_t st) {
+    const std::vector<int>& ih = P.ih;
     HIP_TRY(ctx, rc_grow(S->ibuf_ints, ih.size(), ih.size(), S->ibuf, ih.size()));
     if (S->ev) HIP_TRY(ctx, hipEventSynchronize(S->ev.get()));            // the previous call's upload has left the staging buffer
     else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->ev), hipEventDisableTiming));
@@ -131,6 +167,35 @@ int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* le
     std::copy(ih.begin(), ih.end(), S->ihost.get());
     HIP_TRY(ctx, hipMemcpyAsync(S->ibuf.get(), S->ihost.get(), ih.size() * sizeof(int), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipEventRecord(S->ev.get(), st));
+    return RC_OK;
+}
+
+// acts, tape: both null (rc_subnet_forward) or both set (rc_subnet_forward_tape)
+int forward_impl(rc_ctx* ctx, const char* what, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
+                 const float* init_h, const float* init_c, float* final_h, float* final_c, float* acts, float* tape, bool record,
+                 hipStream_t st) {
+    int ni;
+    SubnetNet w;
+    if (int rc = check_args(ctx, what, net, n, lengths_host, !x || !y || (record && (!acts || !tape)), &ni, &w)) return rc;
+    const int split = rc_ctx_gemm_split(ctx);
+    SubnetState* S = state(ctx);
+    const int H = w.H, Kp1 = w.lin1.Kp;
+    Plan P;
+    if (!make_plan(n, lengths_host, plan_rows_max(w), P)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (std::string(what) + ": internal plan mismatch").c_str());
+    const long long total = P.total;
+    if (record && (!dev_holds(tape, 4 * tape_floats(w, n, total)) || !dev_holds(acts, 12ll * total * H)))
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (std::string(what) + ": acts or tape smaller than the call needs (rc_subnet_tape_floats)").c_str());
+
+    // ---- scratch (grow-only) and the upload of the plan -----------------------------------------------------------------------------
+    // The scratch is shared by every call of the context: a call on another stream than the previous one waits for that call's work.
+    if (S->done) HIP_TRY(ctx, hipStreamWaitEvent(st, S->done.get(), 0));
+    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->done), hipEventDisableTiming));
+    // (grow-only scratch, contents not kept; releasing the old buffer waits for the work that still reads it)
+    const long long R = r16(P.max_rows), G = r16(P.max_group);
+    const size_t n_buf = (size_t)(R * (Kp1 + 6ll * H)), n_st = (size_t)(6 * G * H);
+    HIP_TRY(ctx, rc_grow(S->buf_floats, n_buf, n_buf, S->buf, n_buf));
+    HIP_TRY(ctx, rc_grow(S->st_floats, n_st, n_st, S->st, n_st));
+    if (int rc = upload_plan(ctx, S, P, st)) return rc;
 
     float* X = S->buf.get();                       // [R, Kp1]  packed input
     float* A1 = X + R * Kp1;                 // [R, H]    relu(linear1); then h of layer 1 (A1 is dead once layer 0's x half is formed)
@@ -139,13 +204,16 @@ int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* le
     const long long ps = G * H, hl = 3 * G * H;   // state: per layer [copy 0 | copy 1 | c]
     float* hst = S->st.get();
     float* cst = hst + 2 * G * H;
+    // tape: init_c by rank [2, n, H] | per layer: gate activations [total, 4H], c [total, H], rows in plan order
+    float* tape_l[2] = {nullptr, nullptr};
+    if (record) for (int l = 0; l < 2; ++l) tape_l[l] = tape + 2ll * n * H + l * 5ll * total * H;
 
     // final_* of the group of ranks [g0, g1): every rank's h from the copy its last step wrote
     auto finish = [&](int g0, int g1) {
         rc_launch_subnet_state(hst, hl, ps, S->ibuf.get() + n + g0, cst, hl, final_h, final_c, S->ibuf.get() + g0, g1 - g0, n, H, 0, st);
     };
     int g0 = -1, g1 = -1;
-    for (const Chunk& c : chunks) {
+    for (const Chunk& c : P.chunks) {
         const long long M = c.off.back();
         const int* map = S->ibuf.get() + 2 * (size_t)n + c.frame0;
         if (c.g0 != g0) {                    // a new group: its state from init_* (or zeros)
@@ -153,9 +221,12 @@ int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* le
             g0 = c.g0; g1 = c.g1;
             rc_launch_subnet_state(hst, hl, ps, nullptr, cst, hl, const_cast<float*>(init_h), const_cast<float*>(init_c), S->ibuf.get() + g0,
                                    g1 - g0, n, H, 1, st);
+            if (record) rc_launch_subnet_bstate(nullptr, tape + (long long)g0 * H, (long long)n * H, nullptr, init_c, nullptr, S->ibuf.get() + g0,
+                                                g1 - g0, n, H, 1, st);
         }
         rc_launch_subnet_pack(x, w.in, map, X, Kp1, (int)M, st);
         rc_launch_subnet_gemm(dense(w.lin1, X, (int)M, A1, H, true, true, nullptr), split, 1, st);
+        if (record) rc_launch_subnet_unpack(A1, H, map, acts, H, (int)M, st);
         for (int l = 0; l < 2; ++l) {
             SubGemm half{};
             half.A = l == 0 ? A1 : H0; half.lda = H; half.a_koff = 0; half.M = (int)M;
@@ -171,13 +242,151 @@ int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* le
                 s.pre = PRE + o * 4 * H; s.ldp = 4 * H; s.H = H;
                 s.cst = cst + l * hl; s.hout = hst + l * hl + (t & 1) * ps;
                 s.hseq = l == 0 ? H0 : A1; s.hseq_row0 = o;
+                if (record) {
+                    s.tape_g = tape_l[l] + (c.frame0 + o) * 4 * H;
+                    s.tape_c = tape_l[l] + 4 * total * H + (c.frame0 + o) * H;
+                }
                 rc_launch_subnet_gemm(s, split, 0, st);
             }
+            if (record) rc_launch_subnet_unpack(l == 0 ? H0 : A1, H, map, acts + (l + 1) * total * H, H, (int)M, st);
         }
         rc_launch_subnet_gemm(dense(w.lin2, A1, (int)M, y, w.out, false, false, map), split, 1, st);
         S->chunks += 1;
     }
     finish(g0, g1);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(S->done.get(), st));
+    S->calls += 1;
+    S->frames += total;
+    return RC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
+                      const float* init_h, const float* init_c, float* final_h, float* final_c, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    return forward_impl(ctx, "rc_subnet_forward", net, n, lengths_host, x, y, init_h, init_c, final_h, final_c, nullptr, nullptr, false,
+                        (hipStream_t)stream);
+}
+
+int rc_subnet_forward_tape(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
+                           const float* init_h, const float* init_c, float* final_h, float* final_c, float* acts, float* tape,
+                           void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    return forward_impl(ctx, "rc_subnet_forward_tape", net, n, lengths_host, x, y, init_h, init_c, final_h, final_c, acts, tape, true,
+                        (hipStream_t)stream);
+}
+
+int rc_subnet_tape_floats(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, int64_t* floats) {
+    if (!ctx) return RC_ERR_INVALID;
+    int ni;
+    SubnetNet w;
+    if (int rc = check_args(ctx, "rc_subnet_tape_floats", net, n, lengths_host, !floats, &ni, &w)) return rc;
+    long long total = 0;
+    for (int i = 0; i < n; ++i) total += lengths_host[i];
+    *floats = tape_floats(w, n, total);
+    return RC_OK;
+}
+
+int rc_subnet_backward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* tape, const float* d_h1,
+                       const float* d_final_h, const float* d_final_c, float* d_gates, float* d_a, float* d_init_h, float* d_init_c,
+                       void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    const char* what = "rc_subnet_backward";
+    int ni;
+    SubnetNet w;
+    if (int rc = check_args(ctx, what, net, n, lengths_host, !tape || !d_h1 || !d_gates || !d_a, &ni, &w)) return rc;
+    const int split = rc_ctx_gemm_split(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    SubnetState* S = state(ctx);
+    const int H = w.H;
+    Plan P;
+    if (!make_plan(n, lengths_host, plan_rows_max(w), P)) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_subnet_backward: internal plan mismatch");
+    const long long total = P.total;
+    if (!dev_holds(tape, 4 * tape_floats(w, n, total)) || !dev_holds(d_h1, 4ll * total * H) || !dev_holds(d_gates, 32ll * total * H) ||
+        !dev_holds(d_a, 4ll * total * H))
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_subnet_backward: tape, d_h1, d_gates or d_a smaller than the call needs");
+
+    if (S->done) HIP_TRY(ctx, hipStreamWaitEvent(st, S->done.get(), 0));
+    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->done), hipEventDisableTiming));
+    const long long R = r16(P.max_rows), G = r16(P.max_group);
+    const size_t n_buf = (size_t)(R * 5ll * H), n_bst = (size_t)(20 * G * H);
+    HIP_TRY(ctx, rc_grow(S->buf_floats, n_buf, n_buf, S->buf, n_buf));
+    HIP_TRY(ctx, rc_grow(S->bst_floats, n_bst, n_bst, S->bst, n_bst));
+    // the transposed operands: built from the fp32 packing on first use and after a reload (rc_update_subnet_weights rewrites them itself)
+    const long long epoch = rc_ctx_weights_epoch(ctx);
+    for (int l = 0; l < 2; ++l) {
+        SubnetState::TPack& t = S->tp[ni][l];
+        if (t.epoch == epoch) continue;
+        if (!t.W) HIP_TRY(ctx, rc_alloc_all(t.W, (size_t)8 * H * H, t.Ws, (size_t)24 * H * H));
+        rc_launch_subnet_transpose(w.Wl[l], H, t.W.get(), t.Ws.get(), st);
+        t.epoch = epoch;
+    }
+    if (int rc = upload_plan(ctx, S, P, st)) return rc;
+
+    float* DG = S->buf.get();                 // [R, 4H] rc_pk: dG of the layer being stepped, every frame of the chunk
+    float* DH = DG + R * 4 * H;               // [R, H]: layer 0's dh from above = dG1 . W_ih1
+    const long long ls = 10 * G * H, cps = 4 * G * H;   // state: per layer [dG copy 0 | dG copy 1 | d_final_h | dc]
+    float* bst = S->bst.get();
+    const float* tape_l[2] = {tape + 2ll * n * H, tape + 2ll * n * H + 5ll * total * H};
+    const long long wh_f = 4ll * H * H, wh_s = 12ll * H * H;             // the W_hh columns [H, 2H) of a transposed pack
+    auto gemm = [&](int l, const float* A, int M, bool hh) {
+        const SubnetState::TPack& t = S->tp[ni][l];
+        SubGemm g{};
+        g.A = A; g.lda = 4 * H; g.a_koff = 0; g.M = M;
+        g.W = t.W.get() + (hh ? wh_f : 0); g.Ws = t.Ws.get() + (hh ? wh_s : 0);
+        g.Kp = 4 * H; g.ncb = H / 16; g.c0 = 0; g.c1 = 4; g.N = H; g.H = H;
+        return g;
+    };
+    for (size_t ci = P.chunks.size(); ci-- > 0;) {
+        const Chunk& c = P.chunks[ci];
+        const long long M = c.off.back();
+        const int* perm = S->ibuf.get() + c.g0;
+        const int* map = S->ibuf.get() + 2 * (size_t)n + c.frame0;
+        const int nr = c.g1 - c.g0;
+        if (c.next_rows == 0)                // the group's last chunk: its state from d_final_* (or zeros)
+            rc_launch_subnet_bstate(bst + 2 * cps, bst + 2 * cps + G * H, ls, d_final_h, d_final_c, nullptr, perm, nr, n, H, 1, st);
+        for (int l = 1; l >= 0; --l) {
+            float* sl = bst + l * ls;
+            for (int t = c.t1 - 1; t >= c.t0; --t) {
+                const long long o = c.off[t - c.t0];
+                SubGemm s = gemm(l, sl + ((t + 1) & 1) * cps, (int)(c.off[t - c.t0 + 1] - o), true);
+                s.epi = RC_SG_BSTEP;
+                s.n_next = t + 1 < c.t1 ? (int)(c.off[t - c.t0 + 2] - c.off[t - c.t0 + 1]) : c.next_rows;
+                s.dfin_h = sl + 2 * cps;
+                s.dh_above = l == 1 ? d_h1 : DH + o * H;
+                s.dha_map = l == 1 ? map + o : nullptr;
+                s.tape_g = const_cast<float*>(tape_l[l]) + (c.frame0 + o) * 4 * H;
+                s.tape_c = const_cast<float*>(tape_l[l]) + 4 * total * H + (c.frame0 + o) * H;
+                if (t > c.t0) s.c_prev = tape_l[l] + 4 * total * H + (c.frame0 + c.off[t - c.t0 - 1]) * H;
+                else if (t > 0) {
+                    const Chunk& p = P.chunks[ci - 1];                    // (the same group: its chunks are consecutive, in time order)
+                    s.c_prev = tape_l[l] + 4 * total * H + (p.frame0 + p.off[p.off.size() - 2]) * H;
+                } else s.c_prev = tape + ((long long)l * n + c.g0) * H;
+                s.cst = sl + 2 * cps + G * H;
+                s.hout = sl + (t & 1) * cps;
+                s.hseq = DG; s.hseq_row0 = o;
+                s.dgates = d_gates + l * total * 4 * H; s.out_map = map + o;
+                rc_launch_subnet_gemm_bwd(s, split, 0, st);
+            }
+            if (c.t0 == 0 && d_init_h) {     // dh_rec of "step -1": dG(0) . W_hh, to the caller's sequences
+                SubGemm s = gemm(l, sl, nr, true);
+                s.epi = RC_SG_BPLAIN; s.out = d_init_h + (long long)l * n * H; s.ldo = H; s.out_map = perm;
+                rc_launch_subnet_gemm_bwd(s, split, 0, st);
+            }
+            SubGemm tall = gemm(l, DG, (int)M, false);
+            tall.epi = RC_SG_BPLAIN; tall.ldo = H;
+            if (l == 1) tall.out = DH;
+            else { tall.out = d_a; tall.out_map = map; }
+            rc_launch_subnet_gemm_bwd(tall, split, 1, st);
+        }
+        if (c.t0 == 0 && d_init_c)
+            rc_launch_subnet_bstate(nullptr, bst + 2 * cps + G * H, ls, nullptr, nullptr, d_init_c, perm, nr, n, H, 0, st);
+        S->chunks += 1;
+    }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(S->done.get(), st));
     S->calls += 1;

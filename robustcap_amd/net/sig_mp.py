@@ -251,8 +251,8 @@ class Net:
         raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     # ---------------------------------------------------------------------------------- sub-nets over ragged sequences
-    def _subnet_forward(self, name, x, init=None, return_state=False):
-        """net.rnnK(x, init): rc_subnet_forward on the current stream. Bad input raises ValueError before anything is enqueued."""
+    def _subnet_check(self, name, x, init):
+        """The argument checks of net.rnnK(x, init) (and of a SubnetTrainer's call): the sequences as tensors and (h0, c0) or (None, None)."""
         nin, H, nout = _SUBNETS[name]
         if isinstance(x, torch.Tensor) or not isinstance(x, (list, tuple)) or len(x) == 0:
             raise ValueError(f"{name}: x must be a non-empty list of [T_i, {nin}] tensors")
@@ -269,6 +269,37 @@ class Net:
             if tuple(h0.shape) != (2, N, H) or tuple(c0.shape) != (2, N, H):
                 raise ValueError(f"{name}: init shapes {tuple(h0.shape)}, {tuple(c0.shape)}, expected [2, {N}, {H}] each")
             h0, c0 = self._prep(h0, (2, N, H)), self._prep(c0, (2, N, H))
+        return xs, h0, c0
+
+    @staticmethod
+    def _rnn2_check(x):
+        """The argument checks of net.rnn2(x): the sequences and the x_init of every one (checked before init_net runs: a bad call
+        enqueues nothing)."""
+        if isinstance(x, torch.Tensor) or not isinstance(x, (list, tuple)) or len(x) == 0:
+            raise ValueError("rnn2: x must be a non-empty list of (x_i [T_i, 72], x_init_i [69])")
+        if not all(isinstance(e, (list, tuple)) and len(e) == 2 for e in x):
+            raise ValueError("rnn2: every element of x must be a pair (x_i, x_init_i)")
+        xs = [e[0] for e in x]
+        v = [torch.as_tensor(e[1]) for e in x]
+        if any(t.numel() != 69 for t in v):
+            raise ValueError("rnn2: every x_init_i must hold 69 values")
+        for i, t in enumerate(xs):
+            t = torch.as_tensor(t)
+            if t.dim() != 2 or t.shape[1] != 72 or t.shape[0] < 1:
+                raise ValueError(f"rnn2: sequence {i} has shape {tuple(t.shape)}, expected [T >= 1, 72]")
+        return xs, v
+
+    def trainable(self, name):
+        """A ``SubnetTrainer`` of sub-net ``name`` ("rnn2" .. "rnn8"): its parameters as torch.nn.Parameters on the device and a
+        differentiable ``tr(xs, init)`` with the values of ``net.rnnK(xs, init)`` (robustcap_amd/train.py)."""
+        from ..train import SubnetTrainer
+        return SubnetTrainer(self, name)
+
+    def _subnet_forward(self, name, x, init=None, return_state=False):
+        """net.rnnK(x, init): rc_subnet_forward on the current stream. Bad input raises ValueError before anything is enqueued."""
+        nin, H, nout = _SUBNETS[name]
+        xs, h0, c0 = self._subnet_check(name, x, init)
+        N = len(xs)
         lengths = [int(t.shape[0]) for t in xs]
         xcat = torch.cat([t.to(device=self.device, dtype=torch.float32) for t in xs]).contiguous()
         y = torch.empty(sum(lengths), nout, device=self.device)
@@ -295,18 +326,8 @@ class Net:
 
     def _rnn_with_init_forward(self, x, return_state=False):
         """RNNWithInit.forward (rnn.py:207-219): the initial state regressed by init_net from every sequence's x_init."""
-        if isinstance(x, torch.Tensor) or not isinstance(x, (list, tuple)) or len(x) == 0:
-            raise ValueError("rnn2: x must be a non-empty list of (x_i [T_i, 72], x_init_i [69])")
-        if not all(isinstance(e, (list, tuple)) and len(e) == 2 for e in x):
-            raise ValueError("rnn2: every element of x must be a pair (x_i, x_init_i)")
-        xs = [e[0] for e in x]
-        v = [torch.as_tensor(e[1]).to(device=self.device, dtype=torch.float32).reshape(-1) for e in x]
-        if any(t.numel() != 69 for t in v):
-            raise ValueError("rnn2: every x_init_i must hold 69 values")
-        for i, t in enumerate(xs):                                       # (checked before init_net runs: a bad call enqueues nothing)
-            t = torch.as_tensor(t)
-            if t.dim() != 2 or t.shape[1] != 72 or t.shape[0] < 1:
-                raise ValueError(f"rnn2: sequence {i} has shape {tuple(t.shape)}, expected [T >= 1, 72]")
+        xs, v = self._rnn2_check(x)
+        v = [t.to(device=self.device, dtype=torch.float32).reshape(-1) for t in v]
         s = self._init_net_forward(torch.stack(v)).view(-1, 2, 2, 512).permute(1, 2, 0, 3)
         return self._subnet_forward("rnn2", xs, (s[0].contiguous(), s[1].contiguous()), return_state)
 
