@@ -303,6 +303,7 @@ int build_lds_problems(rc_ctx* ctx, const std::vector<GemmProblem>& ps, const un
         p.h_par_stride = g.h_par_stride; p.H = g.H; p.step_off = g.step_off;
         p.m_tiles = g.m_tiles; p.Qs = g.Kp / 32;
         p.epi = g.epi;
+        p.block_pick = ctx->lds_block_pick && ctx->B <= 256 && g.m_tiles == 1 ? 1 : 0;
         if (g.epi == RC_EPI_LSTM) {
             p.n_tiles = g.H / 32;
             p.ksplit = ctx->lds_ksplit[g.H == 512 ? 0 : (g.H == 1024 ? 1 : 2)];
@@ -713,6 +714,7 @@ int rc_create(int32_t batch, int32_t live, rc_ctx** out) {
     seq_create(ctx);
     ctx->lds_min_rows = tune_env("RC_LDS_MIN_ROWS", std::min(160, std::max(64, batch / 2)));
     ctx->lds_min_batch = tune_env("RC_LDS_MIN_BATCH", ctx->lds_min_batch);
+    ctx->lds_block_pick = tune_env("RC_LDS_BLOCK_PICK", 1) != 0;
     ctx->lds_ksplit[0] = tune_env("RC_LDS_KSPLIT_512", 1) == 1 ? 1 : 2;
     // rnn6: one workgroup per tile up to 160 rows (batch 80 / 128 mixed 642 -> 675k / 910 -> 956k, 128 all-visible 1,123 -> 1,165k, 160: +1.4 %),
     // the K halves on two workgroups above (batch 256: 1,400 vs 1,384k all-visible, 1,189 vs 1,182k mixed)

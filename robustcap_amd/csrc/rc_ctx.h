@@ -97,6 +97,8 @@ struct rc_ctx {
                                          // 64 rows and fewer keep the one-reader 64-row launches (688k against 576k)
     int lds_ksplit[3] = {1, 2, 2};       // RC_LDS_KSPLIT_512 / _1024 / _1280: workgroups per tile (1: both K halves in one workgroup; the H = 512
                                          // nets' items are short -- 2 x 16 k-blocks -- and a hand-over per tile costs more than it levels: +1 %)
+    bool lds_block_pick = true;          // RC_LDS_BLOCK_PICK (0 = always the compacted row list): one-tile contexts (<= 256 rows) pick the rows of a flagged problem
+                                         // by 16-row storage block where that costs the busiest SIMD no extra block -- aligned activation loads
     DevBuf<float> lds_slab;              // [kLdsRegions][lds_region_tiles][RC_LDS_SLAB_FLOATS]: half sums in flight, one region per launch
     DevBuf<int> lds_tickets;             // [kLdsRegions][lds_region_tiles]
     size_t lds_region_tiles = 0;

@@ -79,6 +79,9 @@ constexpr int kWaves = 8;                     // waves per workgroup
 constexpr int kStage = 8 * 3 * 1024;          // bytes of one k-block of weight planes in the ring: [column block][plane][lane] x 16 B
 constexpr int kRing = 4;                      // stages (a power of two; three are in use at any time)
 constexpr int kPW = 3;                        // LDS-DMA pieces per wave and k-block (one column block's three planes)
+constexpr int kCnt = 3 * kWaves;              // ints of the row scan's scratch: per wave its count (+ active-block bits), then its ballot (two words)
+constexpr int kRowIdle = (int)0x80000000u;    // s_rows entry in block mode: a row of an active storage block that does not step (multiplied, never stored)
+constexpr int kRowMask = 0x7fffffff;
 
 #define RC_MFMA(A, B, C) C = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), C, 0, 0, 0)
 
@@ -332,26 +335,64 @@ __device__ __forceinline__ int lds_item(const PP Lp, const int Ln, const int LB,
         if (tid < 256) s_rows[tid] = lo + min(tid, nrows - 1);
         __syncthreads();
     } else {
-        int total = 0;
+        // Block mode (P.block_pick: one-tile contexts, B <= 256 -- one pass of the scan, lo = 0). The compacted list makes every 16-row compute
+        // block behind the first idle row straddle two 16-row STORAGE blocks: each activation load of a wave then gathers from two 1 KiB pieces
+        // of the rc_pk layout instead of reading one. With a few idle rows scattered over the tile the list needs as many blocks as there are
+        // storage blocks with an active row, so the tile takes those storage blocks whole, every row in its own (row & 15) slot, whenever that
+        // puts no extra block on the busiest SIMD: ceil(A / 4) == ceil(ceil(R / 16) / 4) for A active blocks, R active rows. Idle rows of an
+        // active block are multiplied (h and the inputs are padded to a multiple of 16 rows) and never stored. The rule is a function of the
+        // flags alone: the two workgroups of a pair choose alike. A row's MFMA chain depends on that row alone: the results do not change.
+        int total = 0, nact = 0;
+        bool blocks = false;
+        const bool pick = P.block_pick != 0 && B <= 256;           // (uniform; without it the scan does what it always did)
         for (int base = 0; base < B && total < lo + 256; base += kWaves * 64) {
             const int r = base + tid;
             const bool f = r < B && (P.flags[r] & P.flag_bit);
             const unsigned long long bal = __ballot(f);
-            if (lane == 0) s_cnt[wave] = __popcll(bal);
+            if (lane == 0) {
+                int cnt = __popcll(bal);
+                if (pick) {
+                    const unsigned lo32 = (unsigned)bal, hi32 = (unsigned)(bal >> 32);
+                    const unsigned bm = ((lo32 & 0xffffu) ? 1u : 0u) | ((lo32 >> 16) ? 2u : 0u) | ((hi32 & 0xffffu) ? 4u : 0u) | ((hi32 >> 16) ? 8u : 0u);
+                    cnt |= (int)(bm << 16);                        // bits 16..19: which of the wave's four storage blocks hold an active row
+                    s_cnt[kWaves + 2 * wave] = (int)lo32;
+                    s_cnt[kWaves + 2 * wave + 1] = (int)hi32;
+                }
+                s_cnt[wave] = cnt;
+            }
             __syncthreads();
             int woff = 0, sum = 0;
 #pragma unroll
             for (int w = 0; w < kWaves; ++w) {
-                const int cw = s_cnt[w];
+                const int cw = s_cnt[w] & 0xffff;
                 woff += (w < wave) ? cw : 0;
                 sum += cw;
             }
-            const int idx = total + woff + __popcll(bal & ((1ull << lane) - 1ull));
-            if (f && idx >= lo && idx < lo + 256) s_rows[idx - lo] = r;
+            unsigned amask = 0;                                    // active storage blocks of rows 0 .. 255 (waves 0 .. 3 hold them)
+            if (pick && sum > 0) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) amask |= (unsigned)(s_cnt[w] >> 16) << (4 * w);
+                nact = __popc(amask);
+                blocks = ((nact + 3) >> 2) == ((((sum + 15) >> 4) + 3) >> 2);
+            }
+            if (blocks) {
+                if (tid < 16 * nact) {
+                    int blk = 0, seen = 0;                         // the (tid / 16)-th active storage block
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        if ((amask >> j) & 1u) { if (seen == (tid >> 4)) blk = j; ++seen; }
+                    }
+                    const unsigned w16 = (unsigned)s_cnt[kWaves + (blk >> 1)] >> (16 * (blk & 1));
+                    s_rows[tid] = (16 * blk + (tid & 15)) | (((w16 >> (tid & 15)) & 1u) ? 0 : kRowIdle);
+                }
+            } else {
+                const int idx = total + woff + __popcll(bal & ((1ull << lane) - 1ull));
+                if (f && idx >= lo && idx < lo + 256) s_rows[idx - lo] = r;
+            }
             total += sum;
             __syncthreads();
         }
-        nrows = min(256, total - lo);
+        nrows = blocks ? 16 * nact : min(256, total - lo);
         if (nrows <= 0) return 0;                                   // (uniform: both halves of the tile leave, no flag is raised)
         if (tid < 256 && tid >= nrows) s_rows[tid] = s_rows[0];
         __syncthreads();
@@ -361,9 +402,14 @@ __device__ __forceinline__ int lds_item(const PP Lp, const int Ln, const int LB,
     // hold ceil or floor of nblk / 4 between them
     const int nblk = (nrows + 15) >> 4;
     const int nr = wave + 8 < nblk ? 2 : (wave < nblk ? 1 : 0);    // row blocks this wave multiplies (uniform in the wave)
-    const int row_r[2] = {s_rows[16 * wave + i], s_rows[16 * (wave + 8) + i]};
+    // Block mode: an idle row of the batch's last storage block may lie behind row B - 1 -- what is sized B, not Bp, is read at a clamped row.
+    // An idle row's step counter is whatever its last step left (0: none yet, and (0 - 1) % RC_HBUF is -1 -- a copy of h in FRONT of the
+    // buffer): it is not read, the row multiplies the copies of step 1.
+    const int e_r[2] = {s_rows[16 * wave + i], s_rows[16 * (wave + 8) + i]};
+    const int row_r[2] = {e_r[0] & kRowMask, e_r[1] & kRowMask};
+    const int row_c[2] = {min(row_r[0], B - 1), min(row_r[1], B - 1)};
     const bool need_st = (P.seg[0].par_mode | P.seg[1].par_mode) != 0;
-    const int st_r[2] = {need_st ? P.steps[row_r[0]] + P.step_off : 0, need_st ? P.steps[row_r[1]] + P.step_off : 0};
+    const int st_r[2] = {need_st ? (e_r[0] >= 0 ? P.steps[row_c[0]] + P.step_off : 1) : 0, need_st ? (e_r[1] >= 0 ? P.steps[row_c[1]] + P.step_off : 1) : 0};
 
     const bool dense = WITH_DENSE && P.epi != RC_EPI_LSTM;      // (relu(linear1) items exist in the resident kernel's tables only)
     f32x4 acc0[2][8], acc1[2][8];             // the two quarter chains of the current half
@@ -376,7 +422,7 @@ __device__ __forceinline__ int lds_item(const PP Lp, const int Ln, const int LB,
             const int st = st_r[r];
             const int par = sg.par_mode == RC_PAR_SRC ? ((st - 1) % RC_HBUF) : (sg.par_mode == RC_PAR_DST ? (st % RC_HBUF) : 0);
             const float* a_base = sg.base;
-            if (WITH_DENSE && P.sel_bit != 0 && !(P.sel_flags[row_r[r]] & P.sel_bit)) a_base = P.alt[kh];      // a rider's row: its deferred input
+            if (WITH_DENSE && P.sel_bit != 0 && !(P.sel_flags[row_c[r]] & P.sel_bit)) a_base = P.alt[kh];      // a rider's row: its deferred input
             hc.pa[r] = a_base + (long long)par * sg.par_stride + rc_pk(row_r[r], 4 * kq, sg.ld);
         }
         hc.pw = reinterpret_cast<const u32x4*>(P.Ws) + ((long long)(n_tile * 8 + wave) * Qs + (long long)kh * Qh) * 192 + lane;
@@ -431,7 +477,9 @@ __device__ __forceinline__ int lds_item(const PP Lp, const int Ln, const int LB,
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             rr_[r] = 16 * (wave + 8 * r) + 4 * kq + q;
-            r2_[r] = s_rows[rr_[r] < nrows ? rr_[r] : 0];
+            const int e_ = s_rows[rr_[r] < nrows ? rr_[r] : 0];
+            if (e_ < 0) rr_[r] = 256;                             // an idle row of an active block: computed, not stored (ok below)
+            r2_[r] = min(e_ & kRowMask, B - 1);
             dst_[r] = 0;
         }
 #pragma unroll
@@ -440,7 +488,9 @@ __device__ __forceinline__ int lds_item(const PP Lp, const int Ln, const int LB,
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             rr_[r] = 16 * (wave + 8 * r) + 4 * kq + q;
-            r2_[r] = s_rows[rr_[r] < nrows ? rr_[r] : 0];
+            const int e_ = s_rows[rr_[r] < nrows ? rr_[r] : 0];
+            if (e_ < 0) rr_[r] = 256;                             // an idle row of an active block: computed, not stored (ok below)
+            r2_[r] = min(e_ & kRowMask, B - 1);
             dst_[r] = (P.steps[r2_[r]] + P.step_off) % RC_HBUF;
 #pragma unroll
             for (int j = 0; j < 8; ++j) c_prev[r][j] = P.cstate[(long long)r2_[r] * P.H + n_tile * 32 + j * 4 + u];
@@ -528,7 +578,7 @@ __device__ __forceinline__ int lds_item(const PP Lp, const int Ln, const int LB,
 __global__ __launch_bounds__(kWaves * 64, 1) void rc_gemm_lds_kernel(const LdsLaunch L) {
     __shared__ __attribute__((aligned(1024))) unsigned char ring[kRing * kStage];
     __shared__ int s_rows[256];
-    __shared__ int s_cnt[kWaves];
+    __shared__ int s_cnt[kCnt];
     int pi;
     (void)lds_item<RC_LDS_MAXP, false, const LdsProblem*>(L.p, L.n, L.B, (int)blockIdx.x, ring, s_rows, s_cnt, &pi);
 }
@@ -572,7 +622,7 @@ __device__ __forceinline__ void resident_wait(const ResidentArgs& R, const __att
 __global__ __launch_bounds__(kWaves * 64, 1) void rc_gemm_resident_kernel(const ResidentArgs R) {
     __shared__ __attribute__((aligned(1024))) unsigned char ring[kRing * kStage];
     __shared__ int s_rows[256];
-    __shared__ int s_cnt[kWaves];
+    __shared__ int s_cnt[kCnt];
     __shared__ int s_item;
     const int total = R.item_base[R.n_ticks];
     int k = 0;

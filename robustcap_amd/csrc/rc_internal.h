@@ -120,7 +120,8 @@ struct LdsProblem {
     float* out;
     const float* alt[2];
     const unsigned char* sel_flags;
-    int epi, ldo, sel_bit, pad_;
+    int epi, ldo, sel_bit;
+    int block_pick;         // 1: a tile whose active rows fill as many 16-row blocks as it has storage blocks with an active row takes those blocks whole (rc_gemm_lds.hip: block mode)
 };
 struct LdsLaunch {
     int n, B;
