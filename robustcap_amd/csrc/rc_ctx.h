@@ -1,12 +1,13 @@
-// The context behind the C ABI, for the three files that work on all of it: rc_api.cpp (context, weights, problem builders, gate-GEMM
-// launcher, frame-stepped plan), rc_sequence_api.cpp (the sequence engine) and rc_live_api.cpp (the live session). (rc_smplify_api.cpp and
-// rc_subnet_api.cpp see it through the rc_ctx_* accessors of rc_internal.h.)
+// The context behind the C ABI, for the four files that work on all of it: rc_api.cpp (context, weights, frame-stepped plan, op wrappers),
+// rc_gemm_api.cpp (problem builders, gate-GEMM launcher), rc_sequence_api.cpp (the sequence engine) and rc_live_api.cpp (the live session).
+// (rc_smplify_api.cpp and rc_subnet_api.cpp see it through the rc_ctx_* accessors of rc_internal.h.)
 #pragma once
 #include "../../include/robustcap_hip.h"
 #include "rc_internal.h"
 
 #include <map>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -70,41 +71,9 @@ struct rc_ctx {
     std::string err;
     LiveOwner live;                      // the live session: stream, captures, packet chain, host mirror, knobs and counters (rc_live_api.cpp)
     SeqOwner seq;                        // the sequence engine of rc_sequence: planner's tables, ring, streams and events, resident tables, knobs and counters (rc_sequence_api.cpp)
-    // timing of the gate GEMM launches
-    bool timing = false;
-    int timing_mode = 1;                 // 1: every gate-GEMM launch, 2: only the wide-tile kernels, 3: only the shared-weight kernel (rc_gemm_lds_kernel)
-    std::vector<std::pair<HipEvent, HipEvent>> ev_pool;
-    size_t ev_used = 0;
-    double timed_ms = 0.0;
-    double timed_busy_ms = 0.0;          // time with at least one timed launch running (launches on two streams overlap)
-    long long timed_launches = 0;
-    // the gate-GEMM launcher (launch_problems)
-    bool gemm_split = false;             // products of every GEMM as split-bf16 partial products (rc_set_gemm_mode)
-    bool live_launch = false;            // set while a live frame is captured / launched (GemmLaunch.live)
-    unsigned live_nt_mask = 63u;         // sub-nets (bit = kNets index) whose weights a live frame streams with non-temporal loads
-    int tile6[2] = {0, 0}, tile378[2] = {0, 0}, tile2[2] = {0, 0}, tile4[2] = {0, 0};   // LSTM tile shapes of full-batch stages (0 = pick_tile)
+    GemmOwner gemm;                      // the gate-GEMM launcher: arithmetic mode, tile and shared-weight knobs, slab pool, launch timing and counters (rc_gemm_api.cpp)
     SmplifyOwner smplify;                // optimiser work space (rc_smplify_api.cpp)
     SubnetOwner subnet;                  // scratch of rc_subnet_forward (rc_subnet_api.cpp)
-    int trace_next = 0;                  // tile-trace slot counter (tools/tile_trace.py)
-    long long stat_wide_launches = 0;    // launches of the wide-tile kernels (rc_get_launch_stats)
-    // shared-weight gate GEMM (rc_gemm_lds.hip): LSTM layer steps of >= lds_min_rows rows in split-product mode
-    // Two thresholds (round 6, second session; tools/ab_batch.py): a CONTEXT takes the shared-weight kernel and the three-stream tick from
-    // lds_min_batch rows (batch 64 loses a sixth with them: 688k -> 576k mixed), and inside such a context a PROBLEM runs on it from
-    // lds_min_rows rows (the rnn4 / rnn6 problems of a mixed batch hold only the rows that see the camera). One threshold of 160 for both
-    // (first session) left batch 96-128 on the 64-row tiles: batch 128 mixed 858k -> 933k, all-visible 1,073k -> 1,173k; 96: 691k -> 752k.
-    int lds_min_rows = 64;               // RC_LDS_MIN_ROWS (0 = never); default: half the batch, within 64 .. 160 (batch 256: 128 = 160 within the noise, 64 costs 0.7 %)
-    int lds_min_batch = 65;              // RC_LDS_MIN_BATCH: batch 72 / 80 / 88 mixed 528 / 587 / 653k on 64-row tiles (two row tiles, the second mostly padding) -> 585 / 654 / 691k;
-                                         // 64 rows and fewer keep the one-reader 64-row launches (688k against 576k)
-    int lds_ksplit[3] = {1, 2, 2};       // RC_LDS_KSPLIT_512 / _1024 / _1280: workgroups per tile (1: both K halves in one workgroup; the H = 512
-                                         // nets' items are short -- 2 x 16 k-blocks -- and a hand-over per tile costs more than it levels: +1 %)
-    bool lds_block_pick = true;          // RC_LDS_BLOCK_PICK (0 = always the compacted row list): one-tile contexts (<= 256 rows) pick the rows of a flagged problem
-                                         // by 16-row storage block where that costs the busiest SIMD no extra block -- aligned activation loads
-    DevBuf<float> lds_slab;              // [kLdsRegions][lds_region_tiles][RC_LDS_SLAB_FLOATS]: half sums in flight, one region per launch
-    DevBuf<int> lds_tickets;             // [kLdsRegions][lds_region_tiles]
-    size_t lds_region_tiles = 0;
-    unsigned lds_rot = 0;
-    long long stat_lds_launches = 0;
-    long long stat_w32_launches = 0;         // of the wide launches: those on rc_gemm_split48_w32_kernel (contexts of 33-64 rows)
 };
 
 #pragma GCC visibility push(hidden)
@@ -115,7 +84,6 @@ int check_ready(rc_ctx* ctx);
 rc_params_dev dev_params(const rc_params& p);
 int step_impl(rc_ctx* ctx, const FrameIO& io, uint32_t flags, hipStream_t st, bool with_tr = true, bool skip_prep = false,
               const FrameIO* next_io = nullptr, int n_live = -1);
-// ... what the sequence engine takes from the problem builders and the gate-GEMM launcher, and nothing beyond that:
 template <typename T>
 int dev_alloc(rc_ctx* ctx, T** p, size_t count, bool zero = true) {
     DevBuf<char> q;
@@ -126,6 +94,9 @@ int dev_alloc(rc_ctx* ctx, T** p, size_t count, bool zero = true) {
     (ctx->alloc_weights ? ctx->weight_allocs : ctx->allocs).push_back(std::move(q));
     return RC_OK;
 }
+// rc_gemm_api.cpp: what the other three files take from the problem builders and the gate-GEMM launcher, and nothing beyond that
+int gemm_create(rc_ctx* ctx);                                 // rc_create: every launcher knob (RC_GEMM_SPLIT, RC_LDS_*, RC_TILE_*, RC_LIVE_NT_MASK) is read
+                                                              // here, once per context; a tile width that does not divide H fails (no HIP call)
 struct Out { float* p; int ld; int col0; bool packed; };   // destination of a dense layer
 struct Stage {                 // which rows of which net, reading which (rc_pk) input buffer, writing where
     int net; int flag_bit; const float* x; int ldx; Out y;
@@ -143,23 +114,39 @@ GemmProblem lstm_problem(const rc_ctx* c, const Stage& s, int layer);
 GemmProblem lin2_problem(const rc_ctx* c, const Stage& s);
 bool tile_env(const char* name, int* mr, int* nc);
 void pick_tile(int H, int rows, int* mr, int* nc);
+bool gemm_split(const rc_ctx* c);                             // the context's products are split-bf16 partial products (rc_set_gemm_mode)
 // "This problem runs on the shared-weight kernel (rc_gemm_lds.hip)": a CONTEXT takes it (and the tri engine) in split-product mode from
-// lds_min_batch rows, a PROBLEM inside such a context from lds_min_rows rows.
-inline bool lds_context(const rc_ctx* c) { return c->gemm_split && c->lds_min_rows > 0 && c->B >= c->lds_min_batch; }
-inline bool lds_problem(const rc_ctx* c, int rows) { return lds_context(c) && rows >= c->lds_min_rows; }
-int ensure_lds_pool(rc_ctx* ctx);
-bool timing_pair(rc_ctx* ctx, hipEvent_t* a, hipEvent_t* b);
+// RC_LDS_MIN_BATCH rows, a PROBLEM inside such a context from RC_LDS_MIN_ROWS rows.
+bool lds_context(const rc_ctx* c);
+bool lds_problem(const rc_ctx* c, int rows);
+// Region r (< 12) of the shared-weight kernel's pool, which is allocated with the first call: the half-sum slabs and tickets of the launches
+// that may be in flight at once (launch_problems rotates through all of them, the resident table uses tick & 3), and the tiles a region holds.
+struct LdsRegion { float* slab; int* tickets; size_t tiles; };
+int lds_region(rc_ctx* ctx, size_t r, LdsRegion* out);
 int build_lds_problems(rc_ctx* ctx, const std::vector<GemmProblem>& ps, const unsigned char* flags_override, float* slab, int* tickets,
                        LdsProblem* out, int max_p, int* items, size_t* tiles_out, bool resident_order = false);
 int launch_problems(rc_ctx* ctx, std::vector<GemmProblem> ps, const unsigned char* flags_override, hipStream_t st, bool fp32 = false,
                     hipEvent_t stop = nullptr, bool* launched = nullptr);
+// One gate-GEMM launch with an event pair round it where rc_gemm_timing asks for one: mode 1 times every kind, mode 2 all but the small-tile
+// kernel's, mode 3 only the shared-weight and resident kernels'. `issue` launches on st and nothing else.
+enum LaunchKind { LAUNCH_SHARED, LAUNCH_WIDE, LAUNCH_SMALL, LAUNCH_RESIDENT };
+int timed_launch_impl(rc_ctx* ctx, hipStream_t st, LaunchKind kind, void (*issue)(void*), void* arg);
+template <class F> int timed_launch(rc_ctx* ctx, hipStream_t st, LaunchKind kind, F&& issue) {
+    return timed_launch_impl(ctx, st, kind, [](void* f) { (*static_cast<std::remove_reference_t<F>*>(f))(); }, &issue);
+}
+bool resident_launch_fits_timing(const rc_ctx* c);            // false while a timing mode is on that also covers launches the resident segment replaces
+void count_resident_launch(rc_ctx* ctx);                      // the resident kernel's launch counts with the shared-weight kernel's (rc_get_launch_stats)
+// Scope guards: while one lives, launches are those of a live frame being captured / launched (GemmLaunch.live) | no launch is timed, and
+// the previous setting returns on every exit path.
+struct LiveLaunchScope { rc_ctx* ctx; explicit LiveLaunchScope(rc_ctx* c); ~LiveLaunchScope(); };
+struct TimingSuspended { rc_ctx* ctx; bool was; explicit TimingSuspended(rc_ctx* c); ~TimingSuspended(); };
 // rc_sequence_api.cpp
 void seq_create(rc_ctx* ctx);                                 // rc_create: the RC_SEQ_* / RC_COST_* knobs are read here, once per context
 int seq_prepare(rc_ctx* ctx);                                 // rc_finalize_weights: ring, streams, launch tables, the plan's tables for 1024 frames
 void seq_weights_changed(rc_ctx* ctx);                        // ... and in front of it: the launch tables hold pointers to the old weights
 bool seq_is_engine_stream(const rc_ctx* ctx, hipStream_t st); // st is the engine's second stream (the launcher's debug self-test keeps off it)
 // rc_live_api.cpp
-void live_create(rc_ctx* ctx);                                // rc_create: the RC_LIVE_* knobs are read here, once per context
+void live_create(rc_ctx* ctx);                                // rc_create: the RC_LIVE_* knobs are read here, once per context (RC_LIVE_NT_MASK: gemm_create)
 void live_forget_last_frame(rc_ctx* ctx, bool rows_reset = false);   // an eager entry is about to move the state: the host mirror no longer knows
                                                               // the last frame (rows_reset: and any row may trigger init_net again)
 int live_discard_ahead(rc_ctx* ctx);                          // what the session computed or queued ahead of the next frame no longer holds

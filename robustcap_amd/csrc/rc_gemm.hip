@@ -54,7 +54,7 @@ __device__ __forceinline__ float tanhf_(float x) { return rc_gate_tanh(x); }
 //   MR x NC = 4 x 5 : 64 rows x 20 units (rnn4, H = 1280)    (4 + 5) KiB per 80 MFMAs  = 230 B per 64 cycles
 //             4 x 4 : 64 rows x 16 units (rnn6, H = 1024)    (4 + 4) KiB per 64 MFMAs  = 256 B
 //             2 x 4 : 32 rows x 16 units (H = 512, dense)    (2 + 4) KiB per 32 MFMAs  = 384 B
-//             2 x 8 / 2 x 10: 32-row variants of the big nets (the ones in use: see rc_api.cpp)
+//             2 x 8 / 2 x 10: 32-row variants of the big nets (the ones in use: see rc_gemm_api.cpp)
 //             1 x 1 : 16 rows x 4 units: few-row stages (regime transitions, batch 1): 320/256/128 tiles per layer so
 //                     that every CU streams a slice of the weights (a 32 x 160 tile would leave 224 CUs idle)
 //             1 x 2 : 16 rows x 32 columns for linear2 (N = 2..144): 3x the workgroups of a 32 x 64 tile -- these
@@ -534,7 +534,7 @@ void rc_launch_gemm(const GemmLaunch& L, int total_wg, hipStream_t s, hipEvent_t
     const dim3 g(total_wg), b(RC_NW * 64);
 #define RC_GO(K) do { if (stop) hipExtLaunchKernelGGL(K, g, b, 0, s, nullptr, stop, 0, L); else hipLaunchKernelGGL(K, g, b, 0, s, L); } while (0)
     if (rc_gemm_is_small(L)) {
-        bool single_reader = L.live != 0;      // a live frame's launch (rc_api.cpp: launch_problems)
+        bool single_reader = L.live != 0;      // a live frame's launch (rc_gemm_api.cpp: launch_problems)
         for (int q = 0; q < L.n; ++q) single_reader = single_reader && L.p[q].m_tiles == 1;
         if (L.split) RC_GO(rc_gemm_small_split_kernel);
         else if (single_reader) RC_GO(rc_gemm_small_nt_kernel);

@@ -251,7 +251,7 @@ __device__ __forceinline__ void k_half(const HalfArgs& c, f32x4 (&acc0)[2][8], f
     // bf[]: one column block ahead); it is free to copy or spill that register the next instruction. The launch-per-tick kernel never gave
     // it a reason to; the resident kernel's longer-lived state does, and its register allocation spills in front of the loop headers -- a
     // fragment not yet landed was spilled and reloaded as the register's OLD content: garbage in column block 0 of the first k-block
-    // (found with RC_DBG_DENSE_ITEMS, rc_api.cpp). So in front of a loop header everything lands and is tied to its registers. Cost: two
+    // (found with RC_DBG_DENSE_ITEMS, rc_gemm_api.cpp). So in front of a loop header everything lands and is tied to its registers. Cost: two
     // exposed memory latencies per half, ~5 % of an item (RC_LAND=0 builds, profiles/r06_resident_notes.txt).
 #define LAND_ALL()                                                                                                          \
     do {                                                                                                                    \

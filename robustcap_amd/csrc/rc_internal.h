@@ -508,6 +508,11 @@ struct SeqEngine;
 __attribute__((visibility("hidden"))) void rc_seq_free(SeqEngine* e);      // delete e
 using SeqOwner = std::unique_ptr<SeqEngine, RcRelease<rc_seq_free>>;
 
+// the gate-GEMM launcher of a context (rc_gemm_api.cpp; the type is complete there only)
+struct GemmLauncher;
+__attribute__((visibility("hidden"))) void rc_gemm_free(GemmLauncher* g);  // delete g
+using GemmOwner = std::unique_ptr<GemmLauncher, RcRelease<rc_gemm_free>>;
+
 // narrow view of the context for rc_smplify_api.cpp and rc_subnet_api.cpp (the struct itself lives in rc_ctx.h)
 struct rc_ctx;
 struct SmplifyState;

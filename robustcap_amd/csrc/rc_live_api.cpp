@@ -153,7 +153,6 @@ void live_create(rc_ctx* ctx) {
     LiveKept k;
     (void)hipEventCreateWithFlags(rc_out(k.eager_ev), hipEventDisableTiming);      // (without it the live graph does not wait for eager work)
     k.eager = tune_env("RC_LIVE_EAGER", 0) != 0;
-    ctx->live_nt_mask = (unsigned)tune_env("RC_LIVE_NT_MASK", 63);
     k.lean = tune_env("RC_LIVE_LEAN", 1);
     k.lean_nc = tune_env("RC_LIVE_LEAN_NC", 1) == 2 ? 2 : 1;
     k.aql_on = tune_env("RC_LIVE_AQL", 1);
@@ -460,9 +459,8 @@ int capture_full(rc_ctx* ctx, LiveSession& s, bool with_tr, HipGraph& graph, Hip
     hipStream_t st = s.stream.get();
     int rc = RC_OK;
     const std::string what = s.io.capture(st, [&] {
-        ctx->live_launch = true;
+        LiveLaunchScope live_frame(ctx);
         rc = step_impl(ctx, s.io.frame_io(nullptr), 0u, st, with_tr);
-        ctx->live_launch = false;
         return rc == RC_OK;
     }, graph, exec);
     if (rc) return rc;                                                 // (step_impl has recorded its message)
@@ -614,14 +612,13 @@ int rc_live_begin(rc_ctx* ctx) {
     s.maybe_pend.assign(ctx->B, 1);
     s.may_reach.assign(ctx->B, 1);
     if (int rc = allocate_and_map(ctx, s)) return rc;
-    struct TimingGuard { rc_ctx* c; bool v; ~TimingGuard() { c->timing = v; } } timing_guard{ctx, ctx->timing};   // restored on every exit path
-    ctx->timing = false;
+    TimingSuspended untimed(ctx);                                      // (no captured launch carries a timing pair; restored on every exit path)
     if (int rc = capture_full(ctx, s, true, s.graph, s.exec)) return rc;
     if (int rc = capture_full(ctx, s, false, s.graph_notr, s.exec_notr)) return rc;
     // (fp32-MFMA contexts only: the lean kernels stream the fp32 weights, a context switched to split products keeps one arithmetic)
     // The lean plan is an OPTION on top of the two captures above: whatever fails in here (an allocation, its capture, the AQL chain) leaves
     // the context on those captures with a note (rc_get_live_backend), and never fails rc_live_begin (round-4 advice).
-    if (!(s.lean && s.io.B <= RC_LIVE_MAXB && !ctx->gemm_split)) return RC_OK;
+    if (!(s.lean && s.io.B <= RC_LIVE_MAXB && !gemm_split(ctx))) return RC_OK;
     s.aql_note.clear();
     std::vector<LiveKernel> plan(RC_LIVE_KERNELS);
     const std::string why = setup_lean(ctx, s, plan);

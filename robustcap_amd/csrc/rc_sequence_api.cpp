@@ -1,7 +1,7 @@
 // The sequence engine behind rc_sequence / rc_sequence_rows: the launch planner (plan_sequence, plan_wave), the per-row-cursor wavefront engine
 // with its three stream schedules (stream_tick) and the resident layer-step segment (run_resident_segment). Host logic only: this file schedules
-// a call over ticks; building and launching the GEMM problems of a tick is rc_api.cpp's, and the declarations under "rc_api.cpp" in rc_ctx.h are
-// all the engine takes from there. Everything it owns is a member of SeqEngine, behind rc_ctx::seq -- except the ring slots' buffers and
+// a call over ticks; building and launching the GEMM problems of a tick is rc_gemm_api.cpp's, and the declarations under "rc_gemm_api.cpp" in
+// rc_ctx.h are all the engine takes from there. Everything it owns is a member of SeqEngine, behind rc_ctx::seq -- except the ring slots' buffers and
 // x1_alt[2], which dev_alloc books with the context's other state (the live self-check saves and restores exactly those).
 #include "../../include/robustcap_hip.h"
 #include "rc_ctx.h"
@@ -391,7 +391,7 @@ WaveEngine pick_wave_engine(const rc_ctx* c) {
 }
 // ... and whether the layer steps of a whole segment go out as ONE launch of the resident kernel (run_resident_segment)
 bool resident_segment(const rc_ctx* c, WaveEngine eng, const WavePlan& P) {
-    return eng == ENG_TRI && c->seq->resident_on && c->B <= 256 && P.n_ticks > 0 && !(c->timing && c->timing_mode != 3);
+    return eng == ENG_TRI && c->seq->resident_on && c->B <= 256 && P.n_ticks > 0 && resident_launch_fits_timing(c);
 }
 // launch group of problem q: in the tri engine rnn6's layer steps and init_net leave the caller's stream to rnn4
 inline int w2_group(int q, bool tri) {
@@ -448,7 +448,7 @@ std::vector<GemmProblem> collect(const rc_ctx* ctx, const WavePlan& P, WaveEngin
             int mr, nc;
             if (lds_problem(ctx, rows_k)) {                                    // the shared-weight kernel (rc_gemm_lds.hip)
                 mr = 16; nc = 8;
-            } else if (ctx->gemm_split && rows_k >= tile64_rows) {               // (split products: the K loop is operand-bound, 64-row tiles)
+            } else if (gemm_split(ctx) && rows_k >= tile64_rows) {              // (split products: the K loop is operand-bound, 64-row tiles)
                 const int* t = n.H == 512 ? tiles.t5 : (n.H == 1024 ? tiles.t6 : tiles.t4);
                 mr = t[0]; nc = t[1];
             } else {
@@ -457,7 +457,7 @@ std::vector<GemmProblem> collect(const rc_ctx* ctx, const WavePlan& P, WaveEngin
             p.mr = mr; p.nc = nc; p.n_tiles = n.H / (4 * nc);
         } else if (kind == 0 || kind == 4) {
             if (rows_k <= 16) { p.mr = 1; p.nc = 1; p.n_tiles = (p.N + 15) / 16; }
-            else if (kind == 0 && ctx->gemm_split && rows_k >= tile64_rows) {
+            else if (kind == 0 && gemm_split(ctx) && rows_k >= tile64_rows) {
                 // linear1 rides in a wide launch behind its 256 LSTM tiles: as 544 tiles of 32 x 64 (K = 128 / 256: two k-blocks, i.e. all
                 // prologue and epilogue) it added two rounds, ~18 us of a 245 us tick; 136 tiles of 64 x 128 add one
                 const int np = round_up(p.N, 64);
@@ -616,13 +616,13 @@ int build_resident_ticks(WaveSeg& S, std::vector<std::vector<GemmProblem>>& init
                 ls.push_back(p);
             }
         ResidentTick& T = ctx->seq->res_ticks_h[k];
-        const size_t region = (size_t)(k & 3);
+        LdsRegion region{};
+        if (int rc = lds_region(ctx, (size_t)(k & 3), &region)) return rc;
         size_t tiles = 0;
         T.B = ctx->B;
-        T.n = build_lds_problems(ctx, ls, nullptr, ctx->lds_slab.get() + region * ctx->lds_region_tiles * RC_LDS_SLAB_FLOATS,
-                                 ctx->lds_tickets.get() + region * ctx->lds_region_tiles, T.p, RC_RES_MAXP, &T.n_items, &tiles, true);
+        T.n = build_lds_problems(ctx, ls, nullptr, region.slab, region.tickets, T.p, RC_RES_MAXP, &T.n_items, &tiles, true);
         if (T.n != (int)ls.size()) return fail(ctx, RC_ERR_INVALID, "resident engine: more problems in a tick than its table holds");
-        if (tiles > ctx->lds_region_tiles) return fail(ctx, RC_ERR_INVALID, "resident engine: more tiles in a tick than a slab region holds");
+        if (tiles > region.tiles) return fail(ctx, RC_ERR_INVALID, "resident engine: more tiles in a tick than a slab region holds");
         const bool tail_wrote = S.rows(S.P.n_reach, k - 1 - kTailStage) > 0;
         for (int i = 0; i < RC_RES_MAXP; ++i) {
             T.dep[i][0] = T.dep[i][1] = -1; T.dep_items[i][0] = T.dep_items[i][1] = 0;
@@ -650,7 +650,8 @@ int run_resident_segment(WaveSeg& S) {
     rc_ctx* ctx = S.ctx;
     hipStream_t st = S.st, aux = S.aux;
     const int res_wgs = std::min(240, std::max(8, ctx->seq->resident_wgs));
-    if (int rc = ensure_lds_pool(ctx)) return rc;
+    LdsRegion pool{};
+    if (int rc = lds_region(ctx, 0, &pool)) return rc;                             // (the pool is allocated in front of everything else the segment needs)
     if (!ctx->seq->res_abort_h) {                                                  // (read by the next rc_sequence call: kept until rc_destroy)
         HIP_TRY(ctx, rc_alloc(ctx->seq->res_abort_h, 1));
         ctx->seq->res_abort_h[0] = 0;
@@ -677,14 +678,8 @@ int run_resident_segment(WaveSeg& S) {
     R.head = W.words; R.done = W.done; R.tick_done = W.tick_done;
     R.flag_tail = W.words + 2; R.abort = W.words + 3;
     R.spin_bound = (unsigned long long)std::max(1, tune_env("RC_SEQ_RESIDENT_BOUND_MS", 2000)) * 100000ull;   // wall_clock64: 100 MHz
-    {
-        hipEvent_t ta = nullptr, tb = nullptr;
-        if (ctx->timing && !timing_pair(ctx, &ta, &tb)) return fail(ctx, RC_ERR_HIP, "hipEventCreate");
-        if (ta) HIP_TRY(ctx, hipEventRecord(ta, st));
-        rc_launch_gemm_resident(R, res_wgs, st);
-        if (tb) HIP_TRY(ctx, hipEventRecord(tb, st));
-    }
-    ctx->stat_lds_launches += 1;
+    if (int rc = timed_launch(ctx, st, LAUNCH_RESIDENT, [&] { rc_launch_gemm_resident(R, res_wgs, st); })) return rc;
+    count_resident_launch(ctx);
     // second stream, tick k: [init_net] -> prep -> [every item of tick k - 1] -> linear2 -> fuse -> tail -> flag_tail = k + 1
     for (int k = 0; k < S.P.n_ticks; ++k) {
         if (int rc = launch_problems(ctx, init_l[k], nullptr, aux, false)) return rc;

@@ -59,7 +59,7 @@ SENTINEL = 7.25                                       # y is prefilled with it: 
 
 
 def lstm_kernel(net, B, split, env=None):
-    """The kernel of rc_lstm_step's LSTM layer launches (the table above, as rc_api.cpp / rc_gemm.hip decide it)."""
+    """The kernel of rc_lstm_step's LSTM layer launches (the table above, as rc_gemm_api.cpp / rc_gemm.hip decide it)."""
     env = env or {}
     H = H_OF[net]
     min_rows = int(env.get("RC_LDS_MIN_ROWS", min(160, max(64, B // 2))))

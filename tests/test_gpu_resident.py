@@ -105,7 +105,7 @@ def test_resident_engine_against_the_oracle():
 
 
 def test_linear1_items_of_the_resident_kernel_equal_the_wide_tile_launch():
-    """RC_DBG_DENSE_ITEMS=1 (rc_api.cpp: dense_items_selftest): every linear1 launch of a frame-stepped run is also computed as one tick
+    """RC_DBG_DENSE_ITEMS=1 (rc_gemm_api.cpp: dense_items_selftest): every linear1 launch of a frame-stepped run is also computed as one tick
     of the resident kernel; the two must agree bit for bit on every element the launch writes (incl. K' = 128, riders' inputs)."""
     code = ("import sys, torch; sys.path.insert(0, %r)\n"
             "from robustcap_amd import synth\nfrom robustcap_amd.net.sig_mp import Net\n"
