@@ -372,6 +372,32 @@ int rc_subnet_backward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* l
  * (a device synchronise at entry) and before anything enqueued later (the call returns when its kernels on `stream` are done).
  * RC_ERR_INVALID on an unknown net, a wrong count or a null tensor; RC_ERR_STATE before rc_finalize_weights. */
 int rc_update_subnet_weights(rc_ctx* ctx, const char* net, const void* const* tensors_dev, int32_t count, void* stream);
+/* The second half of the training iteration (train.py:120-121: clip_grad_norm_(net.parameters(), max_norm), then optimizer.step() with
+ * Adam as in every train_rnnK of net/sig_mp.py) for ONE sub-net, fused with rc_update_subnet_weights's repack and enqueued on `stream`
+ * with no host synchronisation and no read-back. params_dev / grads_dev / exp_avg_dev / exp_avg_sq_dev: HOST arrays of `count` DEVICE
+ * pointers (fp32, contiguous, the tensors' own shapes; the LSTM weight matrices and their gradients and moments 16-byte aligned) in
+ * rc_update_subnet_weights's order, 12 tensors, rnn2 18. A NULL gradient skips
+ * its tensor as torch does for p.grad is None: no share of the norm, parameter and moments untouched (it is still repacked).
+ *  (a) total_norm = the 2-norm over all gradients: squares accumulated in double, per-workgroup partial sums added in index order by one
+ *      workgroup, no floating-point atomics -- the same bits on every run. coef = min(1, max_norm / (total_norm + 1e-6)) in fp32, 1 when
+ *      max_norm <= 0. norm_out_dev DEVICE float[2] receives {total_norm, coef}. The gradients themselves are NOT scaled (clip_grad_norm_
+ *      scales them in place; here only the update sees coef * g).
+ *  (b) per element of each padded packed matrix: g' = coef g + weight_decay p; m = beta1 m + (1 - beta1) g';
+ *      v = beta2 v + (1 - beta2) g'^2; p -= (lr / bias_correction1) m / (sqrt(v) / sqrt(bias_correction2) + eps) in fp32, written back in
+ *      place, and the new p stored into everything rc_update_subnet_weights rewrites (both packings, padded and summed biases, the
+ *      row-major copy of a narrow linear2, rnn2's init_net, the transposed packs that exist) -- bitwise a reload of the stepped values.
+ *      bias_correction1/2 = 1 - beta^step, formed by the caller in double.
+ * Ordering: stream-ordered like every eager entry. Each entry leaves the context's internal streams joined to its caller's stream, so
+ * the step follows everything enqueued on `stream` before it and precedes everything enqueued there later; the next live frame waits
+ * for it. A caller who uses the context from a second stream orders that stream against `stream` itself (the partial sums live in one
+ * context-owned buffer). While a live session is open (rc_live_begin) the call takes rc_update_subnet_weights's order instead: a device
+ * synchronise at entry, and it returns when its kernels are done.
+ * RC_ERR_INVALID on an unknown net, a wrong count, a null parameter / moment pointer or table, a null norm_out_dev, a non-positive
+ * bias correction or a misaligned LSTM matrix; RC_ERR_STATE before rc_finalize_weights -- nothing is enqueued. */
+int rc_subnet_optim_step(rc_ctx* ctx, const char* net, const void* const* params_dev, const void* const* grads_dev,
+                         const void* const* exp_avg_dev, const void* const* exp_avg_sq_dev, int32_t count, double lr, double beta1,
+                         double beta2, double eps, double weight_decay, double bias_correction1, double bias_correction2, double max_norm,
+                         float* norm_out_dev, void* stream);
 /* RNNWithInit.init_net (articulate/utils/torch/rnn.py:195-201, used at :207-219): Linear(69,512) ReLU Linear(512,1024) ReLU
  * Linear(1024,2048) on v DEVICE [n, 69] -> out DEVICE [n, 2048], on the packed weights of rnn2.init_net in the context's gemm mode. */
 int rc_init_net_forward(rc_ctx* ctx, int32_t n, const float* v, float* out, void* stream);

@@ -17,6 +17,7 @@
 #include "rc_ctx.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -498,6 +499,93 @@ int rc_update_subnet_weights(rc_ctx* ctx, const char* net, const void* const* te
     // ... and before anything enqueued later, on whatever stream
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return RC_OK;
+}
+
+// elements of tensor i of sub-net ni, in rc_update_subnet_weights's order
+static long long subnet_tensor_numel(int ni, int i) {
+    const NetSpec& s = kNets[ni];
+    const long long H = s.H;
+    if (i < 8) return (i & 3) < 2 ? 4 * H * H : 4 * H;
+    if (i < 12) return i == 8 ? H * s.in : i == 9 ? H : i == 10 ? (long long)s.out * H : s.out;
+    const int q = (i - 12) / 2;
+    return (i & 1) ? kInit[q][1] : (long long)kInit[q][0] * kInit[q][1];
+}
+
+// One clipped Adam step of ONE sub-net and the repack of rc_update_subnet_weights, fused (kernels: rc_optim.hip). Stream-ordered like any
+// eager entry: every entry leaves the context's internal streams joined to its caller's stream, so work enqueued on `stream` here follows
+// all of it; only an open live session (captured frames on a private stream, perhaps one queued ahead) takes rc_update_subnet_weights's
+// synchronising order.
+int rc_subnet_optim_step(rc_ctx* ctx, const char* net, const void* const* params_dev, const void* const* grads_dev,
+                         const void* const* exp_avg_dev, const void* const* exp_avg_sq_dev, int32_t count, double lr, double beta1,
+                         double beta2, double eps, double weight_decay, double bias_correction1, double bias_correction2, double max_norm,
+                         float* norm_out_dev, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    const char* what = "rc_subnet_optim_step: ";
+    if (!net || !params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev || !norm_out_dev)
+        return fail(ctx, RC_ERR_INVALID, std::string(what) + "null argument");
+    const int ni = net_index(net);
+    if (ni < 0) return fail(ctx, RC_ERR_INVALID, std::string(what) + "unknown net " + net);
+    const int want = ni == N2 ? 18 : 12;
+    if (count != want) return fail(ctx, RC_ERR_INVALID, what + std::string(net) + " has " + std::to_string(want) + " tensors");
+    for (int i = 0; i < count; ++i)
+        if (!params_dev[i] || !exp_avg_dev[i] || !exp_avg_sq_dev[i]) return fail(ctx, RC_ERR_INVALID, std::string(what) + "null parameter or moment tensor");
+    if (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0)) return fail(ctx, RC_ERR_INVALID, std::string(what) + "bias corrections must be positive");
+    if (!ctx->have_weights) return fail(ctx, RC_ERR_STATE, std::string(what) + "weights not finalized");
+    hipStream_t st = (hipStream_t)stream;
+    if (!ctx->optim_partial) {           // once, for the largest sub-net: never regrown, so no later call frees a buffer in use
+        long long most = 0;
+        for (int j = 0; j < 6; ++j) {
+            long long b = 0;
+            for (int i = 0; i < (j == N2 ? 18 : 12); ++i) b += (subnet_tensor_numel(j, i) + RC_OPTIM_CHUNK - 1) / RC_OPTIM_CHUNK;
+            most = std::max(most, b);
+        }
+        HIP_TRY(ctx, rc_alloc(ctx->optim_partial, (size_t)most));
+    }
+    OptimNorm nrm{};
+    nrm.count = count;
+    int blocks = 0;
+    for (int i = 0; i < count; ++i) {
+        nrm.g[i] = static_cast<const float*>(grads_dev[i]);
+        nrm.n[i] = subnet_tensor_numel(ni, i);
+        nrm.block0[i] = blocks;
+        if (nrm.g[i]) blocks += (int)((nrm.n[i] + RC_OPTIM_CHUNK - 1) / RC_OPTIM_CHUNK);
+    }
+    nrm.block0[count] = blocks;
+    OptimScalars a{};
+    a.step_size = (float)(lr / bias_correction1); a.bc2_sqrt = (float)std::sqrt(bias_correction2);
+    a.beta1 = (float)beta1; a.one_m_beta1 = (float)(1.0 - beta1); a.beta2 = (float)beta2; a.one_m_beta2 = (float)(1.0 - beta2);
+    a.eps = (float)eps; a.weight_decay = (float)weight_decay;
+    auto T = [&](int i) {
+        return OptimTensor{static_cast<float*>(const_cast<void*>(params_dev[i])), static_cast<const float*>(grads_dev[i]),
+                           static_cast<float*>(const_cast<void*>(exp_avg_dev[i])), static_cast<float*>(const_cast<void*>(exp_avg_sq_dev[i]))};
+    };
+    for (int i : {0, 1, 4, 5}) {         // the LSTM matrices move as 16-byte pieces
+        const OptimTensor t = T(i);
+        if (((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 15)
+            return fail(ctx, RC_ERR_INVALID, std::string(what) + "the LSTM weight tensors must be 16-byte aligned");
+    }
+    live_forget_last_frame(ctx);
+    const bool live = live_session_open(ctx);
+    if (live) {
+        if (int rc = live_discard_ahead(ctx)) return rc;
+        HIP_TRY(ctx, hipDeviceSynchronize());
+    }
+    rc_launch_optim_norm(nrm, blocks, ctx->optim_partial.get(), (float)max_norm, norm_out_dev, st);
+    NetDev& n = ctx->net[ni];
+    auto dense = [&](Dense& d, int i) { rc_launch_optim_dense(T(i), T(i + 1), d.N, d.K, d.Np, d.Kp, d.W, d.Ws, d.Wrm, d.b, a, norm_out_dev, st); };
+    for (int l = 0; l < 2; ++l)
+        rc_launch_optim_lstm(T(4 * l), T(4 * l + 1), T(4 * l + 2), T(4 * l + 3), n.H, n.Wl[l], n.Wls[l], n.bl[l], a, norm_out_dev, st);
+    dense(n.lin1, 8);
+    dense(n.lin2, 10);
+    if (ni == N2)
+        for (int q = 0; q < 3; ++q) dense(ctx->init[q], 12 + 2 * q);
+    rc_subnet_retranspose(ctx->subnet.get(), ni, n.Wl, n.H, ctx->weights_epoch, st);
+    HIP_TRY(ctx, hipGetLastError());
+    if (live) {
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        return RC_OK;
+    }
+    return mark_eager(ctx, st);
 }
 
 static int finalize_weights_impl(rc_ctx* ctx) {

@@ -74,6 +74,7 @@ struct rc_ctx {
     GemmOwner gemm;                      // the gate-GEMM launcher: arithmetic mode, tile and shared-weight knobs, slab pool, launch timing and counters (rc_gemm_api.cpp)
     SmplifyOwner smplify;                // optimiser work space (rc_smplify_api.cpp)
     SubnetOwner subnet;                  // scratch of rc_subnet_forward (rc_subnet_api.cpp)
+    DevBuf<double> optim_partial;        // rc_subnet_optim_step: per-workgroup sums of squares of the gradient norm, sized once for the largest sub-net
 };
 
 #pragma GCC visibility push(hidden)
@@ -151,4 +152,5 @@ void live_forget_last_frame(rc_ctx* ctx, bool rows_reset = false);   // an eager
                                                               // the last frame (rows_reset: and any row may trigger init_net again)
 int live_discard_ahead(rc_ctx* ctx);                          // what the session computed or queued ahead of the next frame no longer holds
 int mark_eager(rc_ctx* ctx, hipStream_t st);                  // live_discard_ahead + the next live frame waits for the work just enqueued on st
+bool live_session_open(const rc_ctx* ctx);                    // between rc_live_begin and rc_live_end: captured frames and a packet chain read the weights
 #pragma GCC visibility pop

@@ -593,6 +593,25 @@ void rc_launch_repack_dense(const float* Wsrc, int N, int K, int Np, int Kp, flo
 void rc_launch_repack_lstm(const float* wi, const float* wh, const float* bi, const float* bh, int H, float* W, void* Ws, float* bl,
                            hipStream_t s);
 
+// ---- the optimiser step of one sub-net (rc_optim.hip; rc_subnet_optim_step in rc_api.cpp) -----------------------------------------------
+#define RC_OPTIM_CHUNK 16384   // gradient elements per workgroup (and per partial sum) of the norm
+#define RC_OPTIM_MAXT 18       // tensors of a sub-net at most (rnn2)
+struct OptimNorm {             // the gradients in the caller's order; tensor t owns workgroups [block0[t], block0[t + 1]) -- none when skipped
+    const float* g[RC_OPTIM_MAXT];
+    long long n[RC_OPTIM_MAXT];
+    int block0[RC_OPTIM_MAXT + 1];
+    int count;
+};
+struct OptimTensor { float* p; const float* g; float* m; float* v; };   // parameter, gradient (null: the tensor is skipped), first and second moment
+struct OptimScalars { float step_size, bc2_sqrt, beta1, one_m_beta1, beta2, one_m_beta2, eps, weight_decay; };   // step_size = lr / bc1
+// partial [blocks] sums of squares in double, then out2 = {total norm, clip coefficient} (max_norm <= 0: coefficient 1)
+void rc_launch_optim_norm(const OptimNorm& A, int blocks, double* partial, float max_norm, float* out2, hipStream_t s);
+// clip (coefficient read from out2[1]), Adam in place and rc_launch_repack_lstm / rc_launch_repack_dense's stores in one pass
+void rc_launch_optim_lstm(const OptimTensor& wi, const OptimTensor& wh, const OptimTensor& bi, const OptimTensor& bh, int H, float* W, void* Ws,
+                          float* bl, const OptimScalars& a, const float* out2, hipStream_t s);
+void rc_launch_optim_dense(const OptimTensor& Wt, const OptimTensor& bt, int N, int K, int Np, int Kp, float* W, void* Ws, float* Wrm, float* bp,
+                           const OptimScalars& a, const float* out2, hipStream_t s);
+
 // narrow view of the context for rc_subnet_api.cpp
 struct SubnetState;
 struct SubnetDense { const float* W; const void* Ws; const float* b; int K, N, Kp, Np; };

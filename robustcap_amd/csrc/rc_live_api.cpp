@@ -215,6 +215,8 @@ int mark_eager(rc_ctx* ctx, hipStream_t st) {
     return RC_OK;
 }
 
+bool live_session_open(const rc_ctx* ctx) { return (bool)ctx->live->exec; }
+
 struct FrameCall {
     const float* first_tran;
     uint32_t flags;

@@ -13,6 +13,7 @@
 #include "rc_internal.h"
 #include "rc_gates.h"
 #include "rc_mma.h"
+#include "rc_pack.h"
 
 #define RC_SG_STAGE 4         // k-blocks of weights staged in LDS per round
 
@@ -258,22 +259,8 @@ void rc_launch_subnet_bstate(float* a, float* b, long long ls, const float* src_
                        nr, n, H, in);
 }
 
-// ---- packings written on the device: the index arithmetic and the truncation split of pack_weights / pack_weights_split (rc_api.cpp) ----
-// value v of logical element (column n, k) of a matrix packed with Kp: into the fp32 pack W and the three bf16 planes Ws
-__device__ __forceinline__ void rc_pack_store(float* W, unsigned short* Ws, int Kp, int n, int k, float v) {
-    const int cb = n >> 4, j = n & 15;
-    W[((((long long)cb * (Kp / RC_KC) + (k >> 4)) * 64 + ((k >> 2) & 3) * 16 + j) << 2) + (k & 3)] = v;
-    const unsigned u = __float_as_uint(v), uh = u & 0xffff0000u;
-    const float r1 = v - __uint_as_float(uh);
-    const unsigned um = __float_as_uint(r1) & 0xffff0000u;
-    const float r2 = r1 - __uint_as_float(um);
-    const int kb = k >> 5, r = k & 31, lane = ((r & 15) >> 2) * 16 + j, e = (r >> 4) * 4 + (r & 3);
-    const long long base = (((long long)cb * (Kp / 32) + kb) * 3) * 512 + lane * 8 + e;
-    Ws[base] = (unsigned short)(uh >> 16);
-    Ws[base + 512] = (unsigned short)(um >> 16);
-    Ws[base + 1024] = (unsigned short)(__float_as_uint(r2) >> 16);
-}
-
+// ---- packings written on the device: the index arithmetic and the truncation split of pack_weights / pack_weights_split (rc_api.cpp),
+// rc_pack_store in rc_pack.h ----
 __global__ void rc_subnet_transpose_kernel(const float* Wl, int H, float* WT, unsigned short* WTs) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= 8ll * H * H) return;

@@ -42,6 +42,7 @@ class _ModuleView:
 
     def __getattr__(self, name):
         full = self._prefix + "." + name
+        self._net._refresh_host_copy()
         sd = self._net._sd_cpu
         if any(k == full for k, _ in cfg.state_dict_spec()):
             if full not in sd:
@@ -60,6 +61,7 @@ class _ModuleView:
     def state_dict(self):
         from collections import OrderedDict
         n = len(self._prefix) + 1
+        self._net._refresh_host_copy()
         return OrderedDict((k[n:], torch.from_numpy(self._net._sd_cpu[k])) for k in self._keys() if k in self._net._sd_cpu)
 
     def parameters(self):
@@ -132,6 +134,7 @@ class Net:
             self.__dict__["conf_range"] = (0.85, 0.9)
             self.__dict__["tran_filter_num"] = 0.01
         self._sd_cpu = {}
+        self._stale_host_copy = {}                 # sub-net name -> the SubnetTrainer whose device parameters are newer than _sd_cpu's
         self._loaded = False
         self._gravity_key = None
         self.__dict__["_ready"] = True
@@ -213,6 +216,7 @@ class Net:
             new[k] = np.ascontiguousarray(v, dtype=np.float32)      # float32 CPU tensors / arrays: a view of the caller's memory
         # The library packs from the tensors passed since its last finalize and keeps no host copy: a partial (non-strict)
         # load goes on top of the tensors of the previous loads, which are kept here BY REFERENCE (no second copy).
+        self._refresh_host_copy()
         self._sd_cpu.update(new)
         for k, v in self._sd_cpu.items():
             _lib.check(self._ctx, self._lib.rc_load_weight(self._ctx, k.encode(), v.ctypes.data_as(C.c_void_p), v.size), "rc_load_weight")
@@ -228,7 +232,21 @@ class Net:
     # read-only views of the loaded tensors (the weights live packed in device memory; an edit goes through load_state_dict).
     def state_dict(self):
         from collections import OrderedDict
+        self._refresh_host_copy()
         return OrderedDict((k, torch.from_numpy(self._sd_cpu[k])) for k, _ in cfg.state_dict_spec() if k in self._sd_cpu)
+
+    def _mark_host_copy_stale(self, trainer):
+        """``trainer`` stepped its sub-net's packed weights on the device (SubnetAdam.step): ``_sd_cpu`` is behind until it is read."""
+        self._stale_host_copy[trainer.name] = trainer
+
+    def _refresh_host_copy(self):
+        """Called by everything that reads ``_sd_cpu``: the parameters of every sub-net stepped on the device since the last read are
+        downloaded now, once, however many steps were taken."""
+        stale = self.__dict__.get("_stale_host_copy")
+        while stale:
+            name, tr = stale.popitem()
+            for k, p in tr.named_parameters():
+                self._sd_cpu[f"{name}.{k}"] = p.detach().cpu().numpy()
 
     def named_parameters(self, prefix="", recurse=True):
         for k, v in self.state_dict().items():

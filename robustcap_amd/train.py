@@ -9,6 +9,11 @@ with.
     loss = torch.nn.functional.mse_loss(torch.cat(ys), target)
     opt.zero_grad(); loss.backward(); opt.step()  # the next tr(...) commits the stepped parameters first
 
+or, with the second half of the iteration on the device too (``clip_grad_norm_`` + Adam + the repack in one pass, no commit):
+
+    opt = tr.optimizer(lr=1e-3, clip_grad_norm=1.0)
+    loss.backward(); norm = opt.step(); opt.zero_grad()
+
 What runs where. The forward is ``rc_subnet_forward_tape`` (HIP; the values of ``net.rnnK``). Of the backward, the reverse recurrence --
 the only sequential part -- is ``rc_subnet_backward`` (HIP, one launch per step and layer on the transposed weights, in the context's gemm
 mode); everything that is parallel over the frames is plain fp32 ``torch.matmul`` here: ``dH1 = dy @ W2``, the weight gradients
@@ -136,6 +141,121 @@ class _SubnetFunction(torch.autograd.Function):
         return (None, None, dx, d_ih, d_ic) + tuple(g[k] for k in param_names(name) if not k.startswith("init_net."))
 
 
+class AdamState:
+    """The host half of an Adam optimiser over a fixed list of tensors: hyper-parameters, one step count, the two moments per tensor,
+    and ``state_dict()`` / ``load_state_dict()`` in ``torch.optim.Adam``'s layout -- ``state[i] = {"step", "exp_avg", "exp_avg_sq"}`` with
+    ``i`` in the order of ``params``, plus ``param_groups`` -- so a real ``torch.optim.Adam`` over same-shaped tensors loads what this
+    object saves and this object loads what it saves (the reference's ``optimizer_states.pt``). Needs no GPU: the moments live where
+    the parameters live.
+
+    One step count for all tensors: torch counts per parameter, which differs only for a tensor that skipped a step (``grad is None``);
+    a loaded state whose tensors carry different counts is refused."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.0):
+        self._plist = list(params)
+        self.lr = lr
+        self._set_hyper(betas, eps, weight_decay)
+        self.clip_grad_norm = float(clip_grad_norm)
+        self.step_count = 0
+        self.exp_avg = self.exp_avg_sq = None
+
+    def _set_hyper(self, betas, eps, weight_decay):
+        betas = (float(betas[0]), float(betas[1]))
+        if not (float(self.lr) >= 0.0 and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0 and float(eps) >= 0.0 and float(weight_decay) >= 0.0):
+            raise ValueError(f"invalid Adam hyper-parameters: lr {self.lr}, betas {betas}, eps {eps}, weight_decay {weight_decay}")
+        self.betas, self.eps, self.weight_decay = betas, float(eps), float(weight_decay)
+
+    def _ensure_moments(self):
+        if self.exp_avg is None:
+            self.exp_avg = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self._plist]
+            self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self._plist]
+
+    def bias_corrections(self):
+        """(1 - beta1^t, 1 - beta2^t) of the current step count, in double."""
+        return 1.0 - self.betas[0] ** self.step_count, 1.0 - self.betas[1] ** self.step_count
+
+    def state_dict(self):
+        state = {}
+        if self.exp_avg is not None:
+            for i in range(len(self._plist)):
+                state[i] = {"step": torch.tensor(float(self.step_count)), "exp_avg": self.exp_avg[i].clone(),
+                            "exp_avg_sq": self.exp_avg_sq[i].clone()}
+        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "params": list(range(len(self._plist)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(self._plist):
+            raise ValueError(f"expected one parameter group of {len(self._plist)} tensors")
+        g = groups[0]
+        if g.get("amsgrad") or g.get("maximize"):
+            raise ValueError("amsgrad / maximize states are not supported")
+        index = {pid: i for i, pid in enumerate(g["params"])}           # (torch numbers the parameters in order; any ids map back)
+        state = {index[k]: v for k, v in sd["state"].items()}
+        steps = {int(float(v["step"])) for v in state.values()}         # an int, a float or a tensor
+        if len(steps) > 1:
+            raise ValueError(f"the tensors carry different step counts {sorted(steps)}: one count is kept for all")
+        for i, v in state.items():
+            for k in ("exp_avg", "exp_avg_sq"):
+                if tuple(v[k].shape) != tuple(self._plist[i].shape):
+                    raise ValueError(f"{k} of tensor {i} has shape {tuple(v[k].shape)}, expected {tuple(self._plist[i].shape)}")
+        self.lr = g["lr"]
+        self._set_hyper(g["betas"], g["eps"], g["weight_decay"])
+        self.step_count = steps.pop() if steps else 0
+        self.exp_avg = self.exp_avg_sq = None
+        if state:
+            self._ensure_moments()                                      # a tensor without an entry: zero moments
+            for i, v in state.items():
+                self.exp_avg[i].copy_(v["exp_avg"])
+                self.exp_avg_sq[i].copy_(v["exp_avg_sq"])
+
+
+class SubnetAdam(AdamState):
+    """``tr.optimizer(...)``: ``clip_grad_norm_(tr.parameters(), clip_grad_norm)`` + ``torch.optim.Adam.step()`` + ``tr.commit()`` as ONE
+    call, ``rc_subnet_optim_step``, enqueued on the current stream with no host synchronisation: the gradient norm, then per element of
+    the packed weights the clipped Adam update in place and the repack. Unlike ``clip_grad_norm_`` the gradients are NOT modified: only
+    the update sees the clipped values. A parameter whose ``grad`` is None is skipped like torch skips it (but the step count is one
+    for all tensors, see ``AdamState``). The moments are device tensors, zeros from the first step on."""
+
+    def __init__(self, tr, **hyper):
+        super().__init__(tr.parameters(), **hyper)
+        self._tr = tr
+        self.last_norm_and_coef = None          # device [2] of the last step: total norm, clip coefficient
+
+    def zero_grad(self, set_to_none=True):
+        self._tr.zero_grad(set_to_none)
+
+    def step(self):
+        """One optimiser step. Returns the total gradient norm (before clipping) as a 0-d device tensor; nothing waits for the device."""
+        tr = self._tr
+        net = tr._net
+        self._ensure_moments()
+        ps = self._plist
+        gs = [None if p.grad is None else p.grad.detach().to(dtype=torch.float32).contiguous() for p in ps]
+        gs = [g.clone() if g is not None and g.data_ptr() % 16 else g for g in gs]      # (a view into a larger buffer: the kernels move 16-byte pieces)
+        for p, g in zip(ps, gs):
+            if not p.is_contiguous() or (g is not None and (g.shape != p.shape or g.device != p.device)):
+                raise ValueError("parameters and gradients must be contiguous device tensors of the parameters' shapes")
+        self.step_count += 1
+        bc1, bc2 = self.bias_corrections()
+        table = lambda ts: (C.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+        out = torch.empty(2, device=net.device)
+        rc = net._lib.rc_subnet_optim_step(net._ctx, tr.name.encode(), table([p.detach() for p in ps]), table(gs), table(self.exp_avg),
+                                           table(self.exp_avg_sq), len(ps), float(self.lr), self.betas[0], self.betas[1], self.eps,
+                                           self.weight_decay, bc1, bc2, self.clip_grad_norm, _lib.ptr(out), _lib.stream_ptr())
+        if rc != 0:
+            self.step_count -= 1
+        _lib.check(net._ctx, rc, "rc_subnet_optim_step")
+        for p in ps:                                                    # the parameters changed under torch: say so, then record that
+            torch.autograd.graph.increment_version(p)                   # the packed weights already hold these versions (no commit)
+        tr._versions = tr._current_versions()
+        net._mark_host_copy_stale(tr)
+        self.last_norm_and_coef = out
+        return out[0]
+
+
 class SubnetTrainer:
     """``net.trainable(name)``: the sub-net's parameters as ``torch.nn.Parameter`` s on the device (the reference module's names and
     shapes, initialised from the loaded weights) and a differentiable call with the arguments, checks and values of ``net.rnnK``.
@@ -151,6 +271,7 @@ class SubnetTrainer:
         if not net.__dict__.get("_loaded"):
             raise _lib.RobustcapLibraryError("trainable(): load_state_dict first")
         self._net, self.name = net, name
+        net._refresh_host_copy()
         self._params = OrderedDict(
             (k, torch.nn.Parameter(torch.from_numpy(net._sd_cpu[f"{name}.{k}"]).to(net.device).clone())) for k in param_names(name))
         self._versions = self._current_versions()
@@ -182,7 +303,16 @@ class SubnetTrainer:
         _lib.check(net._ctx, rc, "rc_update_subnet_weights")
         for k, t in zip(self._params, ts):                          # what net.state_dict() and the module views return
             net._sd_cpu[f"{self.name}.{k}"] = t.cpu().numpy()
+        net._stale_host_copy.pop(self.name, None)
         self._versions = self._current_versions()
+
+    def optimizer(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_grad_norm=0.0, **other):
+        """Adam with gradient-norm clipping over this sub-net's parameters, stepped on the device in one call (``SubnetAdam``):
+        ``step()``, ``zero_grad()``, a writable ``lr``, ``state_dict()`` / ``load_state_dict()`` in ``torch.optim.Adam``'s layout.
+        ``clip_grad_norm <= 0``: no clipping. ``amsgrad`` or any other argument: ValueError."""
+        if other:
+            raise ValueError(f"unsupported optimiser arguments {sorted(other)} (Adam without amsgrad only)")
+        return SubnetAdam(self, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip_grad_norm=clip_grad_norm)
 
     # ------------------------------------------------------------------------------------------------ the call
     def __call__(self, x, init=None, return_state=False):
