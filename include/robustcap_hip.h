@@ -361,6 +361,33 @@ int rc_subnet_tape_floats(rc_ctx* ctx, const char* net, int32_t n, const int32_t
 int rc_subnet_backward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* tape, const float* d_h1,
                        const float* d_final_h, const float* d_final_c, float* d_gates, float* d_a, float* d_init_h, float* d_init_c,
                        void* stream);
+/* Training with the reference's dropout (articulate/utils/torch/rnn.py:115,130-131: self.dropout = Dropout(p) on relu(linear1), and
+ * torch.nn.LSTM's dropout = p on layer 0's output as layer 1's input, never on the recurrent path; net/sig_mp.py:52-81: p = 0.1 for
+ * rnn7, 0.4 for the others). The mask is counter-based and stored nowhere: Philox4x32-10 (Random123) with key = (seed low 32 bits, seed
+ * high 32 bits) and counter = (row, unit >> 2, site, call); output lane j decides unit 4 (unit >> 2) + j. row: the frame's row in the
+ * CALLER's order (the row of x / acts / d_gates), so the mask does not depend on how a call is cut into chunks; site 0: after linear1,
+ * 1: between the LSTM layers; call: one value per forward and its backward. A unit is kept iff its 32 bits >= (uint32_t)llrint(p * 2^32);
+ * kept: x * (float)(1 / (1 - p)), dropped: +0.0f.
+ *
+ * rc_dropout_apply: dst[j * cols + k] = drop(src[j * cols + k]) for j < rows, with row = j: src, dst DEVICE [rows, cols] row-major,
+ * 16-byte aligned, src == dst allowed; src = ones gives the scaled mask. p == 0 copies. RC_ERR_INVALID on a null pointer, cols % 4 != 0,
+ * rows < 1 or >= 2^32, p outside [0, 1), site outside {0, 1}, or a misaligned or too small buffer (nothing enqueued). */
+int rc_dropout_apply(rc_ctx* ctx, const float* src, float* dst, int64_t rows, int32_t cols, int32_t site, float p, uint64_t seed,
+                     uint32_t call, void* stream);
+/* rc_subnet_forward_tape in train mode (rnn.py:115,130-131 and torch.nn.LSTM's dropout, as above). With p == 0 it IS
+ * rc_subnet_forward_tape: no dropout launch, the same bits. With p > 0, within the same scratch: relu(linear1) is dropped in place at
+ * site 0 before layer 0 reads it, so acts[0] is the DROPPED relu(linear1); layer 1's input half reads h of layer 0 dropped at site 1,
+ * while the recurrent h, acts[1] and the tape stay unmasked. RC_ERR_INVALID also on p outside [0, 1) (nothing enqueued). */
+int rc_subnet_forward_train(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
+                            const float* init_h, const float* init_c, float* final_h, float* final_c, float* acts, float* tape, float p,
+                            uint64_t seed, uint32_t call, void* stream);
+/* rc_subnet_backward of rc_subnet_forward_train(p, seed, call) (rnn.py:115,130-131 and torch.nn.LSTM's dropout): the site-1 mask is
+ * regenerated and applied to dG1 . W_ih1 before layer 0's steps. d_a is the gradient of layer 0's input, i.e. of the DROPPED
+ * relu(linear1): the caller applies site 0 (rc_dropout_apply) and the relu mask; of the weight gradients, layer 1's W_ih takes the
+ * site-1 dropped acts[1] (rc_dropout_apply), W_hh the unmasked h. With p == 0 it IS rc_subnet_backward. */
+int rc_subnet_backward_train(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* tape, const float* d_h1,
+                             const float* d_final_h, const float* d_final_c, float* d_gates, float* d_a, float* d_init_h,
+                             float* d_init_c, float p, uint64_t seed, uint32_t call, void* stream);
 /* The optimiser step's way back (train.py:117-122: optimizer.step()): the tensors of ONE sub-net, already on the device, into every
  * device array rc_finalize_weights derives from them -- both packings of linear1 / linear2 (and the row-major copy of a narrow
  * linear2), the padded biases, both packings and the summed, permuted bias of each LSTM layer, for rnn2 the init_net layers, and the

@@ -40,6 +40,8 @@ NETS = (
     ("rnn8", 141, 512, 2),
 )
 NET_INDEX = {n[0]: i for i, n in enumerate(NETS)}
+# dropout rate each sub-net is built with, net/sig_mp.py:52-81 (after linear1 and between the LSTM layers, rnn.py:112,115)
+DROPOUT = {n[0]: 0.1 if n[0] == "rnn7" else 0.4 for n in NETS}
 # rnn2.init_net: Linear(69,512) ReLU Linear(512,1024) ReLU Linear(1024,2048)  (rnn.py:195-201)
 INIT_NET = ((69, 512), (512, 1024), (1024, 2048))
 

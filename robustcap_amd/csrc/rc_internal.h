@@ -592,6 +592,16 @@ void rc_launch_subnet_state(float* hp, long long hl, long long ps, const int* pa
 void rc_launch_repack_dense(const float* Wsrc, int N, int K, int Np, int Kp, float* W, void* Ws, hipStream_t s);
 void rc_launch_repack_lstm(const float* wi, const float* wh, const float* bi, const float* bh, int H, float* W, void* Ws, float* bl,
                            hipStream_t s);
+// dropout of a trainable sub-net (rc_dropout.hip): kept iff Philox4x32-10(key = seed, counter = (row', k >> 2, site, call))[k & 3] >=
+// round(p 2^32), row' = map ? map[j] : j (the frame's row in the caller's order); kept x / (1 - p), dropped +0. src == dst allowed;
+// both 16-byte aligned, 0 < p < 1.
+struct DropoutKey { float p; unsigned long long seed; unsigned call; };
+// dst[j * cols + k] = drop(src[j * cols + k]) for j < rows, cols % 4 == 0
+void rc_launch_dropout_rows(const float* src, float* dst, long long rows, int cols, const int* map, int site, const DropoutKey& k,
+                            hipStream_t s);
+// dst[rc_pk(j, k, ld)] = drop(src[rc_pk(j, k, ld)]) for j < rows (rows up to the 16-row padding are not touched), ld % 16 == 0
+void rc_launch_dropout_pk(const float* src, float* dst, long long rows, int ld, const int* map, int site, const DropoutKey& k,
+                          hipStream_t s);
 
 // ---- the optimiser step of one sub-net (rc_optim.hip; rc_subnet_optim_step in rc_api.cpp) -----------------------------------------------
 #define RC_OPTIM_CHUNK 16384   // gradient elements per workgroup (and per partial sum) of the norm

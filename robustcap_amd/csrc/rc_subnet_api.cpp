@@ -15,6 +15,11 @@
 // same kernel on the layer's transposed pack (built on the device from the fp32 packing, on first use) with the cell's backward as
 // its epilogue; dG . W_ih of a whole chunk is one tall launch per layer. Weight gradients are reductions over all frames and are left
 // to the caller (robustcap_amd/train.py).
+//
+// Dropout (rnn.py:115,130-131 and torch.nn.LSTM's dropout; the *_train entries with p > 0): rc_dropout.hip's kernel between the launches
+// above, keyed by the caller's row so the plan does not move the mask. Forward: in place on relu(linear1) (site 0), and h of layer 0
+// -> the buffer relu(linear1) has just left, which layer 1's x half then reads (site 1; the recurrent h stays whole). Backward: in
+// place on dG1 . W_ih1 (site 1); d_a leaves unmasked and the caller applies site 0. With p = 0 no such launch is made.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <numeric>
@@ -170,13 +175,17 @@ int upload_plan(rc_ctx* ctx, SubnetState* S, const Plan& P, hipStream_t st) {
     return RC_OK;
 }
 
-// acts, tape: both null (rc_subnet_forward) or both set (rc_subnet_forward_tape)
+bool valid_p(float p) { return p >= 0.0f && p < 1.0f; }
+
+// acts, tape: both null (rc_subnet_forward) or both set (rc_subnet_forward_tape); drop.p > 0: the train-mode forward
 int forward_impl(rc_ctx* ctx, const char* what, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
                  const float* init_h, const float* init_c, float* final_h, float* final_c, float* acts, float* tape, bool record,
-                 hipStream_t st) {
+                 const DropoutKey& drop, hipStream_t st) {
     int ni;
     SubnetNet w;
     if (int rc = check_args(ctx, what, net, n, lengths_host, !x || !y || (record && (!acts || !tape)), &ni, &w)) return rc;
+    if (!valid_p(drop.p)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (std::string(what) + ": p outside [0, 1)").c_str());
+    const bool dropping = drop.p > 0.0f;
     const int split = rc_ctx_gemm_split(ctx);
     SubnetState* S = state(ctx);
     const int H = w.H, Kp1 = w.lin1.Kp;
@@ -226,10 +235,12 @@ int forward_impl(rc_ctx* ctx, const char* what, const char* net, int32_t n, cons
         }
         rc_launch_subnet_pack(x, w.in, map, X, Kp1, (int)M, st);
         rc_launch_subnet_gemm(dense(w.lin1, X, (int)M, A1, H, true, true, nullptr), split, 1, st);
+        if (dropping) rc_launch_dropout_pk(A1, A1, M, H, map, 0, drop, st);
         if (record) rc_launch_subnet_unpack(A1, H, map, acts, H, (int)M, st);
         for (int l = 0; l < 2; ++l) {
             SubGemm half{};
-            half.A = l == 0 ? A1 : H0; half.lda = H; half.a_koff = 0; half.M = (int)M;
+            if (l == 1 && dropping) rc_launch_dropout_pk(H0, A1, M, H, map, 1, drop, st);   // (A1 is dead until layer 1's first step)
+            half.A = l == 0 || dropping ? A1 : H0; half.lda = H; half.a_koff = 0; half.M = (int)M;
             half.W = w.Wl[l]; half.Ws = w.Wls[l]; half.Kp = 2 * H; half.ncb = 4 * H / 16; half.c0 = 0; half.c1 = 2; half.N = 4 * H;
             half.epi = RC_SG_HALF; half.out = PRE; half.ldo = 4 * H;
             rc_launch_subnet_gemm(half, split, 1, st);
@@ -261,54 +272,23 @@ int forward_impl(rc_ctx* ctx, const char* what, const char* net, int32_t n, cons
     return RC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
-                      const float* init_h, const float* init_c, float* final_h, float* final_c, void* stream) {
-    if (!ctx) return RC_ERR_INVALID;
-    return forward_impl(ctx, "rc_subnet_forward", net, n, lengths_host, x, y, init_h, init_c, final_h, final_c, nullptr, nullptr, false,
-                        (hipStream_t)stream);
-}
-
-int rc_subnet_forward_tape(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
-                           const float* init_h, const float* init_c, float* final_h, float* final_c, float* acts, float* tape,
-                           void* stream) {
-    if (!ctx) return RC_ERR_INVALID;
-    return forward_impl(ctx, "rc_subnet_forward_tape", net, n, lengths_host, x, y, init_h, init_c, final_h, final_c, acts, tape, true,
-                        (hipStream_t)stream);
-}
-
-int rc_subnet_tape_floats(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, int64_t* floats) {
-    if (!ctx) return RC_ERR_INVALID;
-    int ni;
-    SubnetNet w;
-    if (int rc = check_args(ctx, "rc_subnet_tape_floats", net, n, lengths_host, !floats, &ni, &w)) return rc;
-    long long total = 0;
-    for (int i = 0; i < n; ++i) total += lengths_host[i];
-    *floats = tape_floats(w, n, total);
-    return RC_OK;
-}
-
-int rc_subnet_backward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* tape, const float* d_h1,
-                       const float* d_final_h, const float* d_final_c, float* d_gates, float* d_a, float* d_init_h, float* d_init_c,
-                       void* stream) {
-    if (!ctx) return RC_ERR_INVALID;
-    const char* what = "rc_subnet_backward";
+// drop.p > 0: the backward of the train-mode forward with the same (p, seed, call)
+int backward_impl(rc_ctx* ctx, const char* what, const char* net, int32_t n, const int32_t* lengths_host, const float* tape,
+                  const float* d_h1, const float* d_final_h, const float* d_final_c, float* d_gates, float* d_a, float* d_init_h,
+                  float* d_init_c, const DropoutKey& drop, hipStream_t st) {
     int ni;
     SubnetNet w;
     if (int rc = check_args(ctx, what, net, n, lengths_host, !tape || !d_h1 || !d_gates || !d_a, &ni, &w)) return rc;
+    if (!valid_p(drop.p)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (std::string(what) + ": p outside [0, 1)").c_str());
     const int split = rc_ctx_gemm_split(ctx);
-    hipStream_t st = (hipStream_t)stream;
     SubnetState* S = state(ctx);
     const int H = w.H;
     Plan P;
-    if (!make_plan(n, lengths_host, plan_rows_max(w), P)) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_subnet_backward: internal plan mismatch");
+    if (!make_plan(n, lengths_host, plan_rows_max(w), P)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (std::string(what) + ": internal plan mismatch").c_str());
     const long long total = P.total;
     if (!dev_holds(tape, 4 * tape_floats(w, n, total)) || !dev_holds(d_h1, 4ll * total * H) || !dev_holds(d_gates, 32ll * total * H) ||
         !dev_holds(d_a, 4ll * total * H))
-        return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_subnet_backward: tape, d_h1, d_gates or d_a smaller than the call needs");
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (std::string(what) + ": tape, d_h1, d_gates or d_a smaller than the call needs").c_str());
 
     if (S->done) HIP_TRY(ctx, hipStreamWaitEvent(st, S->done.get(), 0));
     else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->done), hipEventDisableTiming));
@@ -382,6 +362,7 @@ int rc_subnet_backward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* l
             if (l == 1) tall.out = DH;
             else { tall.out = d_a; tall.out_map = map; }
             rc_launch_subnet_gemm_bwd(tall, split, 1, st);
+            if (l == 1 && drop.p > 0.0f) rc_launch_dropout_rows(DH, DH, M, H, map, 1, drop, st);
         }
         if (c.t0 == 0 && d_init_c)
             rc_launch_subnet_bstate(nullptr, bst + 2 * cps + G * H, ls, nullptr, nullptr, d_init_c, perm, nr, n, H, 0, st);
@@ -391,6 +372,77 @@ int rc_subnet_backward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* l
     HIP_TRY(ctx, hipEventRecord(S->done.get(), st));
     S->calls += 1;
     S->frames += total;
+    return RC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
+                      const float* init_h, const float* init_c, float* final_h, float* final_c, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    return forward_impl(ctx, "rc_subnet_forward", net, n, lengths_host, x, y, init_h, init_c, final_h, final_c, nullptr, nullptr, false,
+                        DropoutKey{0.0f, 0, 0}, (hipStream_t)stream);
+}
+
+int rc_subnet_forward_tape(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
+                           const float* init_h, const float* init_c, float* final_h, float* final_c, float* acts, float* tape,
+                           void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    return forward_impl(ctx, "rc_subnet_forward_tape", net, n, lengths_host, x, y, init_h, init_c, final_h, final_c, acts, tape, true,
+                        DropoutKey{0.0f, 0, 0}, (hipStream_t)stream);
+}
+
+int rc_subnet_forward_train(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
+                            const float* init_h, const float* init_c, float* final_h, float* final_c, float* acts, float* tape, float p,
+                            uint64_t seed, uint32_t call, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    return forward_impl(ctx, "rc_subnet_forward_train", net, n, lengths_host, x, y, init_h, init_c, final_h, final_c, acts, tape, true,
+                        DropoutKey{p, seed, call}, (hipStream_t)stream);
+}
+
+int rc_subnet_tape_floats(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, int64_t* floats) {
+    if (!ctx) return RC_ERR_INVALID;
+    int ni;
+    SubnetNet w;
+    if (int rc = check_args(ctx, "rc_subnet_tape_floats", net, n, lengths_host, !floats, &ni, &w)) return rc;
+    long long total = 0;
+    for (int i = 0; i < n; ++i) total += lengths_host[i];
+    *floats = tape_floats(w, n, total);
+    return RC_OK;
+}
+
+int rc_subnet_backward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* tape, const float* d_h1,
+                       const float* d_final_h, const float* d_final_c, float* d_gates, float* d_a, float* d_init_h, float* d_init_c,
+                       void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    return backward_impl(ctx, "rc_subnet_backward", net, n, lengths_host, tape, d_h1, d_final_h, d_final_c, d_gates, d_a, d_init_h,
+                         d_init_c, DropoutKey{0.0f, 0, 0}, (hipStream_t)stream);
+}
+
+int rc_subnet_backward_train(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* tape, const float* d_h1,
+                             const float* d_final_h, const float* d_final_c, float* d_gates, float* d_a, float* d_init_h,
+                             float* d_init_c, float p, uint64_t seed, uint32_t call, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    return backward_impl(ctx, "rc_subnet_backward_train", net, n, lengths_host, tape, d_h1, d_final_h, d_final_c, d_gates, d_a, d_init_h,
+                         d_init_c, DropoutKey{p, seed, call}, (hipStream_t)stream);
+}
+
+int rc_dropout_apply(rc_ctx* ctx, const float* src, float* dst, int64_t rows, int32_t cols, int32_t site, float p, uint64_t seed,
+                     uint32_t call, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    if (!src || !dst) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_dropout_apply: null argument");
+    if (rows < 1 || rows >= (1ll << 32) || cols < 4 || cols % 4 != 0 || rows > (1ll << 60) / cols)
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_dropout_apply: 1 <= rows < 2^32 and cols a positive multiple of 4");
+    if (!valid_p(p) || (site != 0 && site != 1)) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_dropout_apply: p in [0, 1) and site 0 or 1");
+    const long long bytes = 4ll * rows * cols;
+    if ((((uintptr_t)src | (uintptr_t)dst) & 15) || !dev_holds(src, bytes) || !dev_holds(dst, bytes))
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_dropout_apply: src and dst are 16-byte aligned device buffers of rows * cols floats");
+    hipStream_t st = (hipStream_t)stream;
+    if (p > 0.0f) rc_launch_dropout_rows(src, dst, rows, cols, nullptr, site, DropoutKey{p, seed, call}, st);
+    else if (src != dst) HIP_TRY(ctx, hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, hipGetLastError());
     return RC_OK;
 }
 
