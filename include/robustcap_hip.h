@@ -449,7 +449,7 @@ int rc_mesh_metrics(rc_ctx* ctx, const float* pose, const float* gt_pose, int64_
  * -> imu_ori[T,6,3,3] = global rotations of joint_ids, vert6[T,6,3] = skinned vertices, imu_acc[T,6,3] =
  * _syn_acc(vert6, smooth_n), joint3d[T,24,3] (or NULL). rc_syn_acc is the stencil alone on v[T,width]: second
  * differences * 3600 with zero end frames, interior [n:-n] from the wide stencil / n^2 when smooth_n >= 2 (bit-exact).
- * Like the reference, smooth_n >= 2 needs T >= 2 * smooth_n + 1. */
+ * Like the reference, smooth_n 0 and 1 are the plain stencil and smooth_n >= 2 needs T >= 2 * smooth_n + 1; T = 0 is a no-op. */
 int rc_synth_imu(rc_ctx* ctx, const float* pose, const float* tran, const int32_t* vertex_ids_host,
                  const int32_t* joint_ids_host, int64_t T, int32_t smooth_n, float* imu_ori, float* imu_acc, float* joint3d,
                  float* vert6, void* stream);

@@ -821,7 +821,8 @@ int rc_fk_bone(rc_ctx* ctx, const float* Rg, float* joints, int64_t n, void* str
 }
 int rc_body_fk(rc_ctx* ctx, const float* pose, const float* tran, float* grot, float* joint, float* j33, int64_t n, void* stream) {
     if (!ctx || !ctx->have_body) return ctx ? fail(ctx, RC_ERR_STATE, "rc_body_fk: body not set") : RC_ERR_INVALID;
-    if (!pose || !tran || !joint || !j33) return fail(ctx, RC_ERR_INVALID, "rc_body_fk: null buffer");
+    if (n == 0) return RC_OK;
+    if (n < 0 || !pose || !tran || !joint || !j33) return fail(ctx, RC_ERR_INVALID, "rc_body_fk: null buffer");
     rc_launch_body_fk(ctx->body, pose, tran, grot, joint, j33, n, (hipStream_t)stream);
     HIP_TRY(ctx, hipGetLastError());
     return RC_OK;
@@ -891,7 +892,7 @@ int rc_mesh_metrics(rc_ctx* ctx, const float* pose, const float* gt_pose, int64_
     return RC_OK;
 }
 int rc_syn_acc(const float* v, int64_t T, int64_t width, int32_t smooth_n, float* acc, void* stream) {
-    if (T < 0 || width < 1 || smooth_n < 1) return RC_ERR_INVALID;
+    if (T < 0 || width < 1 || smooth_n < 0) return RC_ERR_INVALID;                       // smooth_n 0 and 1: the plain stencil (n // 2 == 0)
     if (T == 0) return RC_OK;
     if (!v || !acc) return RC_ERR_INVALID;
     if (smooth_n / 2 != 0 && T < 2 * (int64_t)smooth_n + 1) return RC_ERR_INVALID;     // the reference raises here
@@ -901,7 +902,8 @@ int rc_syn_acc(const float* v, int64_t T, int64_t width, int32_t smooth_n, float
 int rc_synth_imu(rc_ctx* ctx, const float* pose, const float* tran, const int32_t* vertex_ids, const int32_t* joint_ids, int64_t T,
                  int32_t smooth_n, float* imu_ori, float* imu_acc, float* joint3d, float* vert6, void* stream) {
     if (!ctx || !ctx->have_body || ctx->mesh_V == 0) return ctx ? fail(ctx, RC_ERR_STATE, "rc_synth_imu: rc_set_body / rc_set_mesh first") : RC_ERR_INVALID;
-    if (T <= 0 || !pose || !tran || !vertex_ids || !joint_ids || !imu_ori || !imu_acc || !vert6 || smooth_n < 1)
+    if (T == 0) return RC_OK;
+    if (T < 0 || !pose || !tran || !vertex_ids || !joint_ids || !imu_ori || !imu_acc || !vert6 || smooth_n < 0)
         return fail(ctx, RC_ERR_INVALID, "rc_synth_imu: bad argument");
     if (smooth_n / 2 != 0 && T < 2 * (int64_t)smooth_n + 1) return fail(ctx, RC_ERR_INVALID, "rc_synth_imu: needs at least 2 * smooth_n + 1 frames");
     for (int i = 0; i < 6; ++i)
@@ -948,7 +950,8 @@ int rc_set_ignored_landmarks(rc_ctx* ctx, const int32_t* ids, int32_t n) {
 int rc_reproj_residual(rc_ctx* ctx, const float* pose, const float* tran, const float* kp, const float* K, float sigma, float* loss,
                        int64_t T, void* stream) {
     if (!ctx || !ctx->have_body) return ctx ? fail(ctx, RC_ERR_STATE, "rc_reproj_residual: body not set") : RC_ERR_INVALID;
-    if (!pose || !tran || !kp || !K || !loss) return fail(ctx, RC_ERR_INVALID, "rc_reproj_residual: null buffer");
+    if (T == 0) return RC_OK;
+    if (T < 0 || !pose || !tran || !kp || !K || !loss) return fail(ctx, RC_ERR_INVALID, "rc_reproj_residual: null buffer");
     rc_launch_residual(ctx->body, pose, tran, kp, K, sigma, ctx->ign_mask, loss, T, (hipStream_t)stream);
     HIP_TRY(ctx, hipGetLastError());
     return RC_OK;

@@ -247,9 +247,10 @@ __global__ void rc_aa2R_kernel(const float* aa, float* R, long long n) {
             R[9 * i + 3 * r + q] = ((r == q ? c : 0.0f) + t * (k[r] * k[q])) + sn * K[3 * r + q];
 }
 
-// art.math.rotation_matrix_to_axis_angle (angular.py:236-246 loops cv2.Rodrigues on the host). Restated from the
-// Rodrigues formula in float64: theta = atan2(|v|, (tr - 1) / 2), v = vee(R - R^T) / 2; near pi the axis comes
-// from the symmetric part. PARITY UNPINNED against OpenCV (absent); validated by round trip.
+// art.math.rotation_matrix_to_axis_angle (angular.py:236-246 loops cv2.Rodrigues on the host): one thread per matrix through
+// rotmat_to_aa, whose steps (range check, Newton polar factor, acos / s < 1e-5 split, sqrt-diagonal branch near pi) are described
+// above it in rc_device.h. PARITY UNPINNED against OpenCV (absent); pinned to the SVD-based oracle within one float32 rounding on
+// every branch by tests/test_gpu_pose_ops_edges.py.
 __global__ void rc_R2aa_kernel(const float* Rm, float* aa, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

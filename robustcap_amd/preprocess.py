@@ -23,7 +23,7 @@ def _syn_acc(v, smooth_n=2, device="cuda"):
     lib = _lib.load()
     rc = lib.rc_syn_acc(_lib.ptr(x), T, width, int(smooth_n), _lib.ptr(out), _lib.stream_ptr())
     if rc != 0:
-        raise _lib.RobustcapLibraryError(f"rc_syn_acc failed ({rc}): needs smooth_n >= 1 and, for smooth_n >= 2, "
+        raise _lib.RobustcapLibraryError(f"rc_syn_acc failed ({rc}): needs smooth_n >= 0 and, for smooth_n >= 2, "
                                          f"at least 2 * smooth_n + 1 frames (got T={T}, smooth_n={smooth_n})")
     return out
 
