@@ -473,7 +473,8 @@ int rc_reproj_residual(rc_ctx* ctx, const float* pose, const float* tran, const 
  * Replaces net/smplify/run.py:6-34 (smplify_runner) -> temporal_smplify.py:97-196 (TemporalSMPLify.__call__):
  * L-BFGS (torch.optim.LBFGS, strong Wolfe) over [body_pose (T*72 axis-angle), tran (T*3)] of the whole sequence on
  * temporal_body_fitting_loss (net/smplify/losses.py:23-87). Loss and analytic gradient run on the device
- * (rc_smplify.hip), the line-search scalars on the host. */
+ * (rc_smplify.hip), the optimiser's vectors stay there too; its scalar logic (csrc/rc_lbfgs_dev.h: two-loop recursion on
+ * coefficients, line search) runs on the host. RC_SMPLIFY_HOST_LBFGS=1 runs csrc/rc_lbfgs.h on host vectors instead (A/B). */
 
 /* GMM pose prior of MaxMixturePrior (net/smplify/prior.py:102-147): HOST means[8,69], precisions[8,69,69]
  * (inverse covariances) and nll_weights[8] (the weights already divided by the determinant term, prior.py:137-141). */
@@ -510,7 +511,7 @@ int rc_smplify_run(rc_ctx* ctx, const float* pose, const float* tran, const floa
                    float* tran_out, uint8_t* update_host, rc_smplify_info* info, void* stream);
 
 /* The same for n_rows independent (sequence, camera) rows at once (evaluate.py:86-90 loops them): every row runs the optimiser
- * of rc_smplify_run as a fiber of the CALLING thread (a stack of its own behind a guard page; RC_SMPLIFY_THREADS=1: a host thread per
+ * of rc_smplify_run (one algorithm, csrc/rc_lbfgs_dev.h, behind a single-row and a batch-row backend) as a fiber of the CALLING thread (a stack of its own behind a guard page; RC_SMPLIFY_THREADS=1: a host thread per
  * row instead), the device work of all rows goes out in lock-step rounds -- one launch per kind
  * of operation over all rows, one read-back and one synchronisation per round -- so 72 rows cost about what the longest row's ~46
  * rounds cost. Per row the arithmetic is that of rc_smplify_run (same n_iter / n_eval / losses). Arrays of n_rows: T, DEVICE

@@ -575,7 +575,8 @@ void rc_launch_smplify_end_rows(const SmplifyRowIO* rows_dev, int n_rows, int T_
 }
 
 // ================================================================= vector kernels of the device-resident L-BFGS
-// (rc_smplify_api.cpp: minimize_on_device). The optimiser's vectors -- parameters, gradients of the bracket points, the
+// (the algorithm: rc_lbfgs_dev.h; rc_smplify_api.cpp holds its two backends, SingleRow on the launches right below and BatchRow on
+// the *_rows launches further down). The optimiser's vectors -- parameters, gradients of the bracket points, the
 // curvature pairs -- never leave the device; what the host reads back per step is a handful of inner products.
 __global__ void rc_vec_axpy_kernel(const float* x, const float* __restrict__ d, float t, float* out, long long n) {   // out may be x
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,13 +1,14 @@
-// Host side of the smplify optimiser: work space, closure evaluation, L-BFGS driver, C ABI.
+// Host side of the smplify optimiser: work space, closure evaluation, the two backends of the device L-BFGS, C ABI.
 //
 // Reference: net/smplify/run.py:6-34 (smplify_runner: pre-check, optimise, per-frame update mask) and
 // net/smplify/temporal_smplify.py:97-196 (parameters, closure, torch.optim.LBFGS). One closure evaluation is
 // H2D of the parameter vector (300 B/frame), two kernels (rc_smplify.hip), D2H of the gradient and the per-frame loss
-// terms (312 B/frame); the L-BFGS vectors stay on the host -- at 20 iterations x 75 T floats they are noise next to
-// the 26 kernel evaluations.
+// terms (312 B/frame) -- so with RC_SMPLIFY_HOST_LBFGS=1, which runs rc_lbfgs.h on host vectors. By default the vectors
+// stay on the device: rc_lbfgs_dev.h holds that optimiser once, and this file gives it a backend for one row at a time
+// (rc_smplify_run) and one for a row of a lock-step batch (rc_smplify_run_batch).
 #include "../../include/robustcap_hip.h"
 #include "rc_internal.h"
-#include "rc_lbfgs.h"
+#include "rc_lbfgs_dev.h"
 
 #include <algorithm>
 #include <chrono>
@@ -40,7 +41,7 @@ struct SmplifyState {
     PinBuf<float> h_x, h_grad, h_terms, h_res;                        // pinned
     HipEvent ev0, ev1;
     double device_ms = 0.0;
-    // device-resident L-BFGS (minimize_on_device): vectors of the optimiser, job table and partial sums of the inner products
+    // device-resident L-BFGS (SingleRow): vectors of the optimiser, job table and partial sums of the inner products
     int64_t lb_cap = 0;                                               // frames the buffers below hold
     int lb_pairs = 0;                                                 // curvature pairs they hold
     DevBuf<float> xt, dir, gslot, Sv, Yv;                             // [n], [n], [6][n], [pairs][n] x 2
@@ -54,8 +55,6 @@ struct SmplifyState {
 };
 
 namespace {
-
-typedef float (*cubic_fn)(float, float, float, float, float, float, bool, float, float);
 
 int state_of(rc_ctx* ctx, SmplifyState** out) {
     SmplifyOwner& s = rc_ctx_smplify(ctx);
@@ -78,17 +77,30 @@ int reserve(rc_ctx* ctx, SmplifyState* s, int64_t T) {
     return RC_OK;
 }
 
-SmplifyArgs make_args(SmplifyState* s, const float* x, const float* kp, const float* ref3d, const float* imu_aa, const float* K,
-                      float* grad, int64_t T, unsigned long long ign_mask) {
+// what one row lends a closure evaluation (SmplifyState and RowBuf both fill it); the prior comes from the context's state
+struct RowPtrs {
+    const float *kp, *ref3d, *imu_aa;
+    float *mj, *proj, *terms, *prior_ll, *prior_g, *fk;               // terms: [3 T] frame | imu | smooth
+    int* argmin;
+    const float* K;
+    int64_t T;
+};
+RowPtrs ptrs_of(SmplifyState* s, const float* kp, const float* ref3d, const float* imu_aa, const float* K, int64_t T) {
+    return RowPtrs{kp, ref3d, imu_aa, s->mj.get(), s->proj.get(), s->terms.get(), s->prior_ll.get(), s->prior_g.get(), s->fk.get(), s->argmin.get(), K, T};
+}
+
+// closure at x (flat [aa | tran]) into grad
+SmplifyArgs make_args(const SmplifyState* prior, const RowPtrs& p, const float* x, float* grad, unsigned long long ign_mask) {
+    const int64_t T = p.T;
     SmplifyArgs A{};
     A.aa = x; A.tran = x + T * 72;
-    A.kp = kp; A.ref3d = ref3d; A.imu_aa = imu_aa;
-    A.means = s->means.get(); A.prec = s->prec.get(); A.prec_sym = s->prec.get() + kPriorMat; A.lognll = s->lognll.get();
-    A.mj = s->mj.get(); A.proj = s->proj.get();
-    A.frame_loss = s->terms.get(); A.imu_loss = s->terms.get() + T; A.smooth_loss = s->terms.get() + 2 * T;
-    A.argmin = s->argmin.get(); A.prior_ll = s->prior_ll.get(); A.prior_g = s->prior_g.get(); A.fk = s->fk.get();
+    A.kp = p.kp; A.ref3d = p.ref3d; A.imu_aa = p.imu_aa;
+    A.means = prior->means.get(); A.prec = prior->prec.get(); A.prec_sym = prior->prec.get() + kPriorMat; A.lognll = prior->lognll.get();
+    A.mj = p.mj; A.proj = p.proj;
+    A.frame_loss = p.terms; A.imu_loss = p.terms + T; A.smooth_loss = p.terms + 2 * T;
+    A.argmin = p.argmin; A.prior_ll = p.prior_ll; A.prior_g = p.prior_g; A.fk = p.fk;
     A.grad_aa = grad; A.grad_tran = grad + T * 72;
-    for (int q = 0; q < 9; ++q) A.K[q] = K[q];
+    for (int q = 0; q < 9; ++q) A.K[q] = p.K[q];
     A.ign_mask = ign_mask;
     A.T = (int)T;
     return A;
@@ -102,21 +114,73 @@ double total_loss(const float* terms, int64_t T) {
     return f + (double)T * imu + sm;
 }
 
+void set_info(rc_smplify_info* info, const rc::Lbfgs<float>::Result& r) {      // of a row that was optimised
+    info->status = 1;
+    info->n_iter = r.n_iter; info->n_eval = r.n_eval;
+    info->first_loss = r.first_loss; info->final_loss = r.loss;
+}
+
+float frame_mean(const float* r) {                                    // torch mean(dim=-1) of 33 fp32 values
+    float acc = 0.0f;
+    for (int v = 0; v < 33; ++v) acc += r[v];
+    return acc / 33.0f;
+}
+
 // ---------------------------------------------------------------------------------- L-BFGS with device-resident vectors
-// The same algorithm object as rc_lbfgs.h (torch.optim.LBFGS(max_iter, strong_wolfe), temporal_smplify.py:141-147) with the
-// vectors left on the device. Per closure evaluation the host reads back the per-frame loss terms and four inner products
-// (g.d, |g|_inf, |g|_1, |d|_inf: one kernel of partial sums); per iteration the inner products of the new curvature pair and of
-// the gradient with the pairs kept so far, from which the two-loop recursion runs in COEFFICIENT space -- the direction is
-// d = sum_i a_i s_i + b_i y_i + c g and only its (2m + 1) coefficients are computed on the host (float64), then one kernel
-// forms d. No parameter or gradient vector crosses PCIe; round 2 moved 2 x 180 KB per evaluation and ran the recursion over
-// 45,000-element host vectors (10 of the 13.8 ms per 600-frame row).
-const int kSlots = 6, kSlotJobs = 4;
+// rc_lbfgs_dev.h holds the algorithm; here are its two backends, which differ only in how a request reaches the device: SingleRow
+// (rc_smplify_run) launches it at once on the SmplifyState buffers, BatchRow (rc_smplify_run_batch) hands it to the batch's executor.
+// Per closure evaluation the host reads back the loss and five inner products (one kernel of partial sums), per iteration the Gram
+// entries of the new curvature pair. No parameter or gradient vector crosses PCIe; round 2 moved 2 x 180 KB per evaluation and ran
+// the recursion over 45,000-element host vectors (10 of the 13.8 ms per 600-frame row).
+using Dev = rc::LbfgsDev<float>;
+const int kSlots = Dev::kSlots, kSlotJobs = 5;
 
 // RC_LBFGS_HISTORY: curvature pairs kept (default: torch's history_size, 100); read per call, by both formulations
 int lbfgs_history_env() {
     const char* v = std::getenv("RC_LBFGS_HISTORY");
     const int h = v && *v ? std::atoi(v) : 100;
     return h < 1 ? 1 : h;
+}
+
+// curvature pairs the device formulation keeps (RC_LBFGS_HISTORY shrinks it for A/B tests); it holds one more physical slot
+int lbfgs_pairs(int max_iter) { return std::max(1, std::min(std::min(max_iter, RC_LBFGS_MAX_PAIRS), lbfgs_history_env())); }
+
+Dev::Options lbfgs_options(float lr, int max_iter) {
+    Dev::Options o;
+    o.lr = lr; o.max_iter = max_iter; o.max_eval = max_iter * 5 / 4; o.history_size = lbfgs_pairs(max_iter);
+    return o;
+}
+
+// a job's partial sums (one per 4,096-element block), added in block order
+double part_sum(const double* p, int nb, bool is_max) {
+    double r = p[0];
+    for (int b = 1; b < nb; ++b) r = is_max ? std::max(r, p[b]) : r + p[b];
+    return r;
+}
+
+// the five inner products of an evaluation into gradient slot g with direction d -- g.d, max |g|, sum |g|, max |d|, g.g -- as jobs
+// (op 0: sum a b, 1: max |a|, 2: sum |a|) and read back into Dev::Eval
+const int kSlotOp[kSlotJobs] = {0, 1, 2, 1, 0};
+template <class Job, class... Tail>
+void slot_jobs(Job* j, const float* g, const float* d, Tail... tail) {
+    const float *a[kSlotJobs] = {g, g, g, d, g}, *b[kSlotJobs] = {d, nullptr, nullptr, nullptr, g};
+    for (int q = 0; q < kSlotJobs; ++q) j[q] = Job{a[q], b[q], kSlotOp[q], 0, tail...};
+}
+void read_slot(Dev::Eval& e, const double* part, int stride, int nb) {
+    float* out[kSlotJobs] = {&e.gtd, &e.gmax, &e.gsum, &e.dmax, &e.gg};
+    for (int q = 0; q < kSlotJobs; ++q) *out[q] = (float)part_sum(part + (size_t)q * stride, nb, kSlotOp[q] == 1);
+}
+
+// both backends: a direction's terms as the kernel's argument, a basis index as an address in the row's Sv / Yv / gslot
+template <class Backend>
+VecComb make_comb(const Backend& be, const Dev::Term* terms, int n_terms) {
+    VecComb comb{};
+    comb.n_vec = n_terms;
+    for (int i = 0; i < n_terms; ++i) { comb.v[i] = be.vec(terms[i].vec); comb.c[i] = terms[i].coef; }
+    return comb;
+}
+float* basis_vec(float* Sv, float* Yv, float* gslot, size_t n, int P, int i) {
+    return i >= 2 * P ? gslot + (size_t)(i - 2 * P) * n : (i >= P ? Yv + (size_t)(i - P) * n : Sv + (size_t)i * n);
 }
 
 int reserve_lbfgs(rc_ctx* ctx, SmplifyState* s, int64_t T, int pairs) {
@@ -130,259 +194,66 @@ int reserve_lbfgs(rc_ctx* ctx, SmplifyState* s, int64_t T, int pairs) {
     return RC_OK;
 }
 
-struct DevResult { int n_iter = 0, n_eval = 0; float first_loss = 0, loss = 0; };
-
-// x (device, s->x.get()) is updated in place. kp / K / ref3d / imu_aa as for the closure.
-int minimize_on_device(rc_ctx* ctx, SmplifyState* s, const BodyConst* body, const float* kp, const float* K, int64_t T, float lr,
-                       int max_iter, hipStream_t st, DevResult& res) {
-    const size_t n = (size_t)T * 75;
-    const int nb = (int)((n + 4095) / 4096);
-    // History: the last M curvature pairs (torch.optim.LBFGS: history_size = 100, old_dirs.pop(0) when full). M + 1 physical slots:
-    // the candidate pair of an iteration goes to the spare one, so that rejecting it (y.s <= 1e-10) leaves the oldest pair alone;
-    // accepting it into a full history makes the oldest pair's slot the next spare. RC_LBFGS_HISTORY shrinks M (A/B tests).
-    const int M = std::max(1, std::min(std::min(max_iter, RC_LBFGS_MAX_PAIRS), lbfgs_history_env()));
-    const int P = M + 1;
-    if (int rc = reserve_lbfgs(ctx, s, T, P)) return rc;
-    const int max_eval = max_iter * 5 / 4;
-    const float tolerance_grad = 1e-7f, tolerance_change = 1e-9f;
-    const unsigned long long ign = rc_ctx_ign_mask(ctx);
-    auto slot = [&](int k) { return s->gslot.get() + (size_t)k * n; };
-    // fixed part of the job table: per gradient slot {g.d, max |g|, sum |g|, max |d|}
-    for (int k = 0; k < kSlots; ++k) {
-        s->jobs_h[k * kSlotJobs + 0] = VecJob{slot(k), s->dir.get(), 0, 0};
-        s->jobs_h[k * kSlotJobs + 1] = VecJob{slot(k), nullptr, 1, 0};
-        s->jobs_h[k * kSlotJobs + 2] = VecJob{slot(k), nullptr, 2, 0};
-        s->jobs_h[k * kSlotJobs + 3] = VecJob{s->dir.get(), nullptr, 1, 0};
-    }
-    const int var0 = kSlots * kSlotJobs;                                // first job of the per-iteration (Gram) part
-    HIP_TRY(ctx, hipMemcpyAsync(s->jobs_d.get(), s->jobs_h.get(), (size_t)var0 * sizeof(VecJob), hipMemcpyHostToDevice, st));
-    auto job_sum = [&](int job, bool is_max) {
-        const double* p = s->part_h.get() + (size_t)job * nb;
-        double r = p[0];
-        for (int b = 1; b < nb; ++b) r = is_max ? std::max(r, p[b]) : r + p[b];
-        return r;
-    };
-    struct Eval { float f, gtd, gmax, gsum, dmax; };
+// backend of rc_smplify_run: the state's buffers, every request launched at once. s->x is updated in place.
+struct SingleRow {
+    SmplifyState* s; const BodyConst* body; RowPtrs ptrs;
+    int P;                                                            // physical pair slots
+    hipStream_t st; unsigned long long ign;
+    size_t n; int nb;                                                 // 75 T, 4,096-element blocks of a vector
     hipError_t herr = hipSuccess;
-    // closure at x + t d into gradient slot k (t == 0: at x itself; the direction-dependent products are then meaningless)
-    auto eval = [&](float t, int k, Eval& e) -> bool {
+    static constexpr int var0 = kSlots * kSlotJobs;                   // first job of the per-iteration (Gram) part of the table
+
+    float* vec(int i) const { return basis_vec(s->Sv.get(), s->Yv.get(), s->gslot.get(), n, P, i); }
+    // fixed part of the job table: the five products of every gradient slot
+    bool begin() {
+        for (int k = 0; k < kSlots; ++k) slot_jobs(s->jobs_h.get() + k * kSlotJobs, vec(2 * P + k), s->dir.get());
+        herr = hipMemcpyAsync(s->jobs_d.get(), s->jobs_h.get(), (size_t)var0 * sizeof(VecJob), hipMemcpyHostToDevice, st);
+        return herr == hipSuccess;
+    }
+    void dots(int job0, int n_jobs) {                                 // launch and read-back of jobs [job0, job0 + n_jobs)
+        rc_launch_vec_dots(s->jobs_d.get() + job0, n_jobs, (long long)n, s->part_d.get() + (size_t)job0 * nb, st);
+        if (herr == hipSuccess) herr = hipMemcpyAsync(s->part_h.get() + (size_t)job0 * nb, s->part_d.get() + (size_t)job0 * nb,
+                                                      (size_t)n_jobs * nb * sizeof(double), hipMemcpyDeviceToHost, st);
+    }
+    bool eval(float t, int k, Dev::Eval& e) {
         const float* xp = s->x.get();
         if (t != 0.0f) { rc_launch_vec_axpy(s->x.get(), s->dir.get(), t, s->xt.get(), (long long)n, st); xp = s->xt.get(); }
-        const SmplifyArgs A = make_args(s, xp, kp, s->ref3d.get(), s->imu_aa.get(), K, slot(k), T, ign);
         herr = hipEventRecord(s->ev0.get(), st);
-        rc_launch_smplify(A, body, st);
+        rc_launch_smplify(make_args(s, ptrs, xp, vec(2 * P + k), ign), body, st);
         if (herr == hipSuccess) herr = hipEventRecord(s->ev1.get(), st);
-        rc_launch_vec_dots(s->jobs_d.get() + k * kSlotJobs, kSlotJobs, (long long)n, s->part_d.get() + (size_t)k * kSlotJobs * nb, st);
-        if (herr == hipSuccess) herr = hipMemcpyAsync(s->part_h.get() + (size_t)k * kSlotJobs * nb, s->part_d.get() + (size_t)k * kSlotJobs * nb,
-                                                      (size_t)kSlotJobs * nb * sizeof(double), hipMemcpyDeviceToHost, st);
-        if (herr == hipSuccess) herr = hipMemcpyAsync(s->h_terms.get(), s->terms.get(), (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
+        dots(k * kSlotJobs, kSlotJobs);
+        if (herr == hipSuccess) herr = hipMemcpyAsync(s->h_terms.get(), s->terms.get(), (size_t)ptrs.T * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
         if (herr == hipSuccess) herr = hipStreamSynchronize(st);
         if (herr == hipSuccess) herr = hipGetLastError();
         if (herr != hipSuccess) return false;
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, s->ev0.get(), s->ev1.get()) == hipSuccess) s->device_ms += ms;
-        e.f = (float)total_loss(s->h_terms.get(), T);
-        e.gtd = (float)job_sum(k * kSlotJobs + 0, false);
-        e.gmax = (float)job_sum(k * kSlotJobs + 1, true);
-        e.gsum = (float)job_sum(k * kSlotJobs + 2, false);
-        e.dmax = (float)job_sum(k * kSlotJobs + 3, true);
+        e.f = (float)total_loss(s->h_terms.get(), ptrs.T);
+        read_slot(e, s->part_h.get() + (size_t)k * kSlotJobs * nb, nb, nb);
         return true;
-    };
-#define LB_FAIL() return rc_ctx_fail(ctx, RC_ERR_HIP, (std::string("smplify L-BFGS: ") + hipGetErrorString(herr)).c_str())
-
-    int base = 0;                                                       // slot of the gradient at x
-    Eval e0;
-    if (!eval(0.0f, base, e0)) LB_FAIL();
-    float loss = e0.f, gmax = e0.gmax, gsum = e0.gsum;
-    res.first_loss = res.loss = loss;
-    int evals = 1;
-    if (gmax <= tolerance_grad) { res.n_eval = evals; return RC_OK; }
-
-    // inner products among the basis {s_0.., y_0.., g} by PHYSICAL slot: index i -> s_i, P + i -> y_i, 2P -> g
-    const int NB = 2 * P + 1, IG = 2 * P;
-    std::vector<double> G((size_t)NB * NB, 0.0), ro(P, 0.0), al(P, 0.0), delta(NB, 0.0);
-    auto Gat = [&](int a, int b) -> double& { return G[(size_t)a * NB + b]; };
-    std::vector<int> order;                                             // physical slots of the pairs kept, oldest first
-    int spare = 0;                                                      // physical slot of the next candidate
-    double H_diag = 1.0;
-    float t = 0.0f, prev_loss = loss, gtd = 0.0f, d_max = 0.0f;
-    int prev_base = base;
-    int n_iter = 0;
-    cubic_fn cubic = rc::Lbfgs<float>::cubic;
-    while (n_iter < max_iter) {
-        ++n_iter;
-        VecComb comb{};
-        if (n_iter == 1) {
-            comb.n_vec = 1; comb.v[0] = slot(base); comb.c[0] = -1.0f;     // d = -g
-        } else {
-            // candidate pair (slot `spare`): y = g - prev_g, s = t d
-            const int c = spare;
-            rc_launch_vec_pair(slot(base), slot(prev_base), s->dir.get(), t, s->Yv.get() + (size_t)c * n, s->Sv.get() + (size_t)c * n, (long long)n, st);
-            // inner products: the candidate against the pairs kept (and itself), the gradient against all of them
-            struct Want { int a, b; };
-            std::vector<Want> want;
-            std::vector<int> with_c(order);
-            with_c.push_back(c);
-            for (int j : with_c) { want.push_back({c, j}); want.push_back({c, P + j}); want.push_back({P + c, P + j}); }
-            for (int j : order) want.push_back({P + c, j});
-            for (int j : with_c) { want.push_back({IG, j}); want.push_back({IG, P + j}); }
-            want.push_back({IG, IG});
-            auto vec_of = [&](int idx) -> const float* {
-                return idx == IG ? slot(base) : (idx >= P ? s->Yv.get() + (size_t)(idx - P) * n : s->Sv.get() + (size_t)idx * n);
-            };
-            for (size_t q = 0; q < want.size(); ++q) s->jobs_h[var0 + q] = VecJob{vec_of(want[q].a), vec_of(want[q].b), 0, 0};
-            herr = hipMemcpyAsync(s->jobs_d.get() + var0, s->jobs_h.get() + var0, want.size() * sizeof(VecJob), hipMemcpyHostToDevice, st);
-            rc_launch_vec_dots(s->jobs_d.get() + var0, (int)want.size(), (long long)n, s->part_d.get() + (size_t)var0 * nb, st);
-            if (herr == hipSuccess) herr = hipMemcpyAsync(s->part_h.get() + (size_t)var0 * nb, s->part_d.get() + (size_t)var0 * nb,
-                                                          want.size() * nb * sizeof(double), hipMemcpyDeviceToHost, st);
-            if (herr == hipSuccess) herr = hipStreamSynchronize(st);
-            if (herr != hipSuccess) LB_FAIL();
-            for (size_t q = 0; q < want.size(); ++q) {
-                const double v = job_sum(var0 + (int)q, false);
-                Gat(want[q].a, want[q].b) = v; Gat(want[q].b, want[q].a) = v;
-            }
-            {
-                const double ys = Gat(c, P + c);
-                if ((float)ys > 1e-10f) {                                 // keep the pair (torch: ys > 1e-10)
-                    H_diag = ys / Gat(P + c, P + c);
-                    ro[c] = 1.0 / ys;
-                    if ((int)order.size() == M) {                         // history full: the oldest pair goes (old_dirs.pop(0)),
-                        spare = order.front();                            // its slot takes the next candidate
-                        order.erase(order.begin());
-                        order.push_back(c);
-                    } else {
-                        order.push_back(c);
-                        spare = (int)order.size();                        // slots are handed out in order until the history is full
-                    }
-                }
-            }
-            const int m = (int)order.size();
-            // two-loop recursion on coefficients: q = sum_k delta[k] basis[k], starting from q = -g
-            std::fill(delta.begin(), delta.end(), 0.0);
-            delta[IG] = -1.0;
-            auto dot_q = [&](int idx) {
-                double r = delta[IG] * Gat(IG, idx);
-                for (int j : order) r += delta[j] * Gat(j, idx) + delta[P + j] * Gat(P + j, idx);
-                return r;
-            };
-            for (int i = m - 1; i >= 0; --i) { const int j = order[i]; al[j] = dot_q(j) * ro[j]; delta[P + j] -= al[j]; }
-            for (double& v : delta) v *= H_diag;
-            for (int i = 0; i < m; ++i) { const int j = order[i]; const double be = dot_q(P + j) * ro[j]; delta[j] += al[j] - be; }
-            comb.n_vec = 0;
-            for (int j : order) {
-                comb.v[comb.n_vec] = s->Sv.get() + (size_t)j * n; comb.c[comb.n_vec++] = (float)delta[j];
-                comb.v[comb.n_vec] = s->Yv.get() + (size_t)j * n; comb.c[comb.n_vec++] = (float)delta[P + j];
-            }
-            comb.v[comb.n_vec] = slot(base); comb.c[comb.n_vec++] = (float)delta[IG];
-            gtd = (float)dot_q(IG);
-        }
-        rc_launch_vec_comb(comb, s->dir.get(), (long long)n, st);
-        prev_base = base;
-        prev_loss = loss;
-        if (n_iter == 1) {
-            t = std::min(1.0f, 1.0f / gsum) * lr;
-            // g.d of d = -g: the base slot's table entry pairs it with d (one more small readback, once per run)
-            rc_launch_vec_dots(s->jobs_d.get() + base * kSlotJobs, 1, (long long)n, s->part_d.get() + (size_t)base * kSlotJobs * nb, st);
-            herr = hipMemcpyAsync(s->part_h.get() + (size_t)base * kSlotJobs * nb, s->part_d.get() + (size_t)base * kSlotJobs * nb, (size_t)nb * sizeof(double),
-                                  hipMemcpyDeviceToHost, st);
-            if (herr == hipSuccess) herr = hipStreamSynchronize(st);
-            if (herr != hipSuccess) LB_FAIL();
-            gtd = (float)job_sum(base * kSlotJobs, false);
-        } else t = lr;
-        if (gtd > -tolerance_change) break;
-
-        // ---- strong-Wolfe line search (rc_lbfgs.h: strong_wolfe) on gradient slots ------------------------------------
-        struct Pt { float t, f, gtd; int k; };
-        const int max_ls = max_eval - evals;
-        auto free_slot = [&](std::initializer_list<int> live) {
-            for (int k = 0; k < kSlots; ++k) { bool used = false; for (int v : live) used = used || v == k; if (!used) return k; }
-            return -1;
-        };
-        const float c1 = 1e-4f, c2 = 0.9f;
-        Pt cur{t, 0, 0, free_slot({base})};
-        Eval ev;
-        if (!eval(cur.t, cur.k, ev)) LB_FAIL();
-        int ls_evals = 1;
-        cur.f = ev.f; cur.gtd = ev.gtd; d_max = ev.dmax;
-        Pt prev{0, loss, gtd, base};
-        Pt br[2] = {prev, prev};
-        int n_br = 0, ls_iter = 0;
-        bool done = false;
-        while (ls_iter < max_ls) {
-            if (cur.f > (loss + c1 * cur.t * gtd) || (ls_iter > 1 && cur.f >= prev.f)) { br[0] = prev; br[1] = cur; n_br = 2; break; }
-            if (std::fabs(cur.gtd) <= -c2 * gtd) { br[0] = cur; n_br = 1; done = true; break; }
-            if (cur.gtd >= 0) { br[0] = prev; br[1] = cur; n_br = 2; break; }
-            const float min_step = cur.t + 0.01f * (cur.t - prev.t), max_step = cur.t * 10;
-            const float tn = cubic(prev.t, prev.f, prev.gtd, cur.t, cur.f, cur.gtd, true, min_step, max_step);
-            prev = cur;
-            cur.t = tn;
-            cur.k = free_slot({base, prev.k});
-            if (!eval(tn, cur.k, ev)) LB_FAIL();
-            cur.f = ev.f; cur.gtd = ev.gtd;
-            ++ls_evals;
-            ++ls_iter;
-        }
-        if (ls_iter == max_ls) { br[0] = Pt{0, loss, gtd, base}; br[1] = cur; n_br = 2; }
-        bool insuf = false;
-        int lo = 0, hi = 1;
-        if (n_br == 2 && !(br[0].f <= br[1].f)) { lo = 1; hi = 0; }
-        while (!done && ls_iter < max_ls) {
-            if (std::fabs(br[1].t - br[0].t) * d_max < tolerance_change) break;
-            float tn = cubic(br[0].t, br[0].f, br[0].gtd, br[1].t, br[1].f, br[1].gtd, false, 0, 0);
-            const float bmax = std::max(br[0].t, br[1].t), bmin = std::min(br[0].t, br[1].t);
-            const float eps = 0.1f * (bmax - bmin);
-            if (std::min(bmax - tn, tn - bmin) < eps) {
-                if (insuf || tn >= bmax || tn <= bmin) {
-                    tn = (std::fabs(tn - bmax) < std::fabs(tn - bmin)) ? bmax - eps : bmin + eps;
-                    insuf = false;
-                } else insuf = true;
-            } else insuf = false;
-            cur.t = tn;
-            cur.k = free_slot({base, br[0].k, br[1].k});
-            if (!eval(tn, cur.k, ev)) LB_FAIL();
-            cur.f = ev.f; cur.gtd = ev.gtd;
-            ++ls_evals;
-            ++ls_iter;
-            if (cur.f > (loss + c1 * tn * gtd) || cur.f >= br[lo].f) {
-                br[hi] = cur;
-                if (br[0].f <= br[1].f) { lo = 0; hi = 1; } else { lo = 1; hi = 0; }
-            } else {
-                if (std::fabs(cur.gtd) <= -c2 * gtd) done = true;
-                else if (cur.gtd * (br[hi].t - br[lo].t) >= 0) br[hi] = br[lo];
-                br[lo] = cur;
-            }
-        }
-        if (n_br == 1) lo = 0;
-        t = br[lo].t;
-        loss = br[lo].f;
-        base = br[lo].k;                                                  // gradient at the accepted point
-        rc_launch_vec_axpy(s->x.get(), s->dir.get(), t, s->x.get(), (long long)n, st);      // x += t d (element-wise, in place)
-        // |g|_inf of the accepted point: its slot's partial sums are still in the pinned table unless the slot is the old base
-        gmax = base == prev_base ? gmax : (float)job_sum(base * kSlotJobs + 1, true);
-        const bool opt_cond = gmax <= tolerance_grad;
-        evals += ls_evals;
-
-        if (n_iter == max_iter) break;
-        if (evals >= max_eval) break;
-        if (opt_cond) break;
-        if (d_max * std::fabs(t) <= tolerance_change) break;
-        if (std::fabs(loss - prev_loss) < tolerance_change) break;
     }
-#undef LB_FAIL
-    res.n_iter = n_iter;
-    res.n_eval = evals;
-    res.loss = loss;
-    return RC_OK;
-}
-
+    void direction(const Dev::Term* terms, int n_terms) { rc_launch_vec_comb(make_comb(*this, terms, n_terms), s->dir.get(), (long long)n, st); }
+    void accept(float t) { rc_launch_vec_axpy(s->x.get(), s->dir.get(), t, s->x.get(), (long long)n, st); }   // (element-wise, in place)
+    bool pair(int c, int g_new, int g_old, float t, const Dev::Want* want, int n_want, double* out) {
+        rc_launch_vec_pair(vec(2 * P + g_new), vec(2 * P + g_old), s->dir.get(), t, vec(P + c), vec(c), (long long)n, st);
+        for (int q = 0; q < n_want; ++q) s->jobs_h[var0 + q] = VecJob{vec(want[q].a), vec(want[q].b), 0, 0};
+        herr = hipMemcpyAsync(s->jobs_d.get() + var0, s->jobs_h.get() + var0, (size_t)n_want * sizeof(VecJob), hipMemcpyHostToDevice, st);
+        dots(var0, n_want);
+        if (herr == hipSuccess) herr = hipStreamSynchronize(st);
+        if (herr != hipSuccess) return false;
+        for (int q = 0; q < n_want; ++q) out[q] = part_sum(s->part_h.get() + (size_t)(var0 + q) * nb, nb, false);
+        return true;
+    }
+    bool flush() { return true; }
+};
 
 // ================================================================== lock-step batch of rows (rc_smplify_run_batch, round 4)
 // evaluate.py:86-90 refines the (sequence, camera) rows of an evaluation one after another; they are independent optimisation
 // problems. Round 3 drove them from host threads, one context and stream each: ~300 HIP calls per row contend for the runtime,
-// 72 rows of 600 frames took 0.19-0.23 s however many threads ran. Here every row's optimiser (the algorithm of
-// minimize_on_device, unchanged, as a fiber of the caller's thread -- a stack of its own, see RowBatch::fibers) hands its next device request -- "evaluate the closure at x + t d
-// into gradient slot k", or "form the curvature pair and these inner products" -- to ONE executor; when every live row has asked,
-// the executor runs all requests with one launch per kind over all rows (descriptor tables in device memory, the row from
+// 72 rows of 600 frames took 0.19-0.23 s however many threads ran. Here every row's optimiser (rc::LbfgsDev on a BatchRow, as a fiber
+// of the caller's thread -- a stack of its own, see RowBatch::fibers) hands its next device request -- "evaluate the closure at
+// x + t d into gradient slot k", or "form the curvature pair and these inner products" -- to ONE executor; when every live row has
+// asked, the executor runs all requests with one launch per kind over all rows (descriptor tables in device memory, the row from
 // blockIdx.y), one read-back, one synchronisation, and resumes the rows. A round costs what its largest kernel costs; per row the
 // arithmetic is the same chain of operations as alone, so n_iter / n_eval / losses are those of the one-row-at-a-time run.
 struct RowBuf {                       // device vectors of one row (carved from the batch's arena)
@@ -454,12 +325,7 @@ class RowBatch {
     ucontext_t sched{};
     std::vector<ucontext_t> fctx;
 
-    double job_sum(const RowReq& q, int j, int nb, bool is_max) const {
-        const double* p = part_h + (size_t)(q.job0 + j) * nb_max;
-        double r = p[0];
-        for (int b = 1; b < nb; ++b) r = is_max ? std::max(r, p[b]) : r + p[b];
-        return r;
-    }
+    const double* part_of(const RowReq& q, int j) const { return part_h + (size_t)(q.job0 + j) * nb_max; }   // partial sums of the request's job j
     // hand in the row's request and sleep until the round it belongs to has run; false = a HIP call failed
     bool submit(int r, RowReq* q) {
         if (fibers) {
@@ -495,19 +361,9 @@ class RowBatch {
             if (q->kind == 1) {
                 const float* xp = b.x;
                 if (q->t != 0.0f) { ops_h[n_ops++] = VecOp{b.x, b.dir, nullptr, b.xt, nullptr, q->t, 0, (long long)b.n}; xp = b.xt; }
-                SmplifyArgs A{};
-                A.aa = xp; A.tran = xp + b.T * 72;
-                A.kp = b.kp; A.ref3d = b.ref3d; A.imu_aa = b.imu_aa;
-                A.means = prior->means.get(); A.prec = prior->prec.get(); A.prec_sym = prior->prec.get() + kPriorMat; A.lognll = prior->lognll.get();
-                A.mj = b.mj; A.proj = b.proj;
-                A.frame_loss = b.terms; A.imu_loss = b.terms + b.T; A.smooth_loss = b.terms + 2 * b.T;
-                A.argmin = b.argmin; A.prior_ll = b.prior_ll; A.prior_g = b.prior_g; A.fk = b.fk;
-                float* g = b.gslot + (size_t)q->k * b.n;
-                A.grad_aa = g; A.grad_tran = g + b.T * 72;
-                for (int e = 0; e < 9; ++e) A.K[e] = b.K[e];
-                A.ign_mask = ign; A.T = (int)b.T;
+                const RowPtrs ptrs{b.kp, b.ref3d, b.imu_aa, b.mj, b.proj, b.terms, b.prior_ll, b.prior_g, b.fk, b.argmin, b.K, b.T};
                 q->arg0 = n_args;
-                args_h[n_args++] = A;
+                args_h[n_args++] = make_args(prior, ptrs, xp, b.gslot + (size_t)q->k * b.n, ign);
             } else if (q->kind == 2) {
                 ops_h[n_ops++] = VecOp{q->g_new, q->g_old, b.dir, q->yv, q->sv, q->pair_t, 1, (long long)b.n};
             }
@@ -564,223 +420,52 @@ class RowBatch {
     }
 };
 
-// minimize_on_device for row r of a batch: the same algorithm, the device work requested from the batch's executor
-void lbfgs_row(RowBatch& B, const int r, const float lr, const int max_iter, DevResult& res, bool& ok) {
-    ok = false;
-    struct Leave { RowBatch& B; int r; ~Leave() { B.leave(r); } } on_exit{B, r};
-    const RowBuf& b = B.row[r];
-    const size_t n = b.n;
-    const int nb = b.nb;
-    const int M = std::max(1, std::min(std::min(max_iter, RC_LBFGS_MAX_PAIRS), lbfgs_history_env()));
-    const int P = M + 1;
-    const int max_eval = max_iter * 5 / 4;
-    const float tolerance_grad = 1e-7f, tolerance_change = 1e-9f;
-    auto slot = [&](int k) { return b.gslot + (size_t)k * n; };
-    // per evaluation five inner products: g.d, max |g|, sum |g|, max |d|, g.g
-    struct Eval { float f, gtd, gmax, gsum, dmax, gg; };
-    float slot_gmax[kSlots] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};           // |g|_inf of the last evaluation into each gradient slot
+// backend of rc_smplify_run_batch for row r: every request goes to the batch's executor. The direction and the accepted step are not
+// requests of their own: they ride in front of the next one (or of the final flush), so that a round is one request per row.
+struct BatchRow {
+    RowBatch& B; const int r; const RowBuf& b;
+    const int P;                                                      // physical pair slots
     RowReq q;
-    bool have_comb = false, have_accept = false;
+    bool have_comb = false, have_accept = false;                      // pending: dir = comb, x += accept_t * dir
     VecComb comb{};
     float accept_t = 0.0f;
-    auto attach = [&]() {
+
+    float* vec(int i) const { return basis_vec(b.Sv, b.Yv, b.gslot, b.n, P, i); }
+    bool submit(int kind) {
+        q.kind = kind;
         q.has_comb = have_comb; if (have_comb) q.comb = comb;
         q.accept = have_accept; q.accept_t = accept_t;
         have_comb = false; have_accept = false;
-    };
-    auto eval = [&](float t, int k, Eval& e) -> bool {
-        q.kind = 1; q.t = t; q.k = k;
-        attach();
-        q.jobs.clear();
-        q.jobs.push_back(VecJobN{slot(k), b.dir, 0, 0, (long long)n});
-        q.jobs.push_back(VecJobN{slot(k), nullptr, 1, 0, (long long)n});
-        q.jobs.push_back(VecJobN{slot(k), nullptr, 2, 0, (long long)n});
-        q.jobs.push_back(VecJobN{b.dir, nullptr, 1, 0, (long long)n});
-        q.jobs.push_back(VecJobN{slot(k), slot(k), 0, 0, (long long)n});
-        if (!B.submit(r, &q)) return false;
+        return B.submit(r, &q);
+    }
+    bool eval(float t, int k, Dev::Eval& e) {
+        q.t = t; q.k = k;
+        q.jobs.resize(kSlotJobs);
+        slot_jobs(q.jobs.data(), vec(2 * P + k), b.dir, (long long)b.n);
+        if (!submit(1)) return false;
         e.f = (float)(B.device_totals ? B.total_h[q.arg0] : total_loss(b.terms_h, b.T));
-        e.gtd = (float)B.job_sum(q, 0, nb, false);
-        e.gmax = (float)B.job_sum(q, 1, nb, true);
-        e.gsum = (float)B.job_sum(q, 2, nb, false);
-        e.dmax = (float)B.job_sum(q, 3, nb, true);
-        e.gg = (float)B.job_sum(q, 4, nb, false);
-        slot_gmax[k] = e.gmax;
+        read_slot(e, B.part_of(q, 0), B.nb_max, b.nb);
         return true;
-    };
-
-    int base = 0;
-    Eval e0;
-    if (!eval(0.0f, base, e0)) return;
-    float loss = e0.f, gmax = e0.gmax, gsum = e0.gsum, gg0 = e0.gg;
-    res.first_loss = res.loss = loss;
-    int evals = 1;
-    ok = true;
-    if (gmax <= tolerance_grad) { res.n_eval = evals; return; }
-
-    const int NB = 2 * P + 1, IG = 2 * P;
-    std::vector<double> G((size_t)NB * NB, 0.0), ro(P, 0.0), al(P, 0.0), delta(NB, 0.0);
-    auto Gat = [&](int a, int c) -> double& { return G[(size_t)a * NB + c]; };
-    std::vector<int> order;
-    int spare = 0;
-    double H_diag = 1.0;
-    float t = 0.0f, prev_loss = loss, gtd = 0.0f, d_max = 0.0f;
-    int prev_base = base;
-    int n_iter = 0;
-    cubic_fn cubic = rc::Lbfgs<float>::cubic;
-    ok = false;
-    while (n_iter < max_iter) {
-        ++n_iter;
-        if (n_iter == 1) {
-            comb = VecComb{};
-            comb.n_vec = 1; comb.v[0] = slot(base); comb.c[0] = -1.0f;     // d = -g
-            gtd = -gg0;                                                     // g.d of d = -g
-        } else {
-            const int c = spare;
-            struct Want { int a, b; };
-            std::vector<Want> want;
-            std::vector<int> with_c(order);
-            with_c.push_back(c);
-            for (int j : with_c) { want.push_back({c, j}); want.push_back({c, P + j}); want.push_back({P + c, P + j}); }
-            for (int j : order) want.push_back({P + c, j});
-            for (int j : with_c) { want.push_back({IG, j}); want.push_back({IG, P + j}); }
-            want.push_back({IG, IG});
-            auto vec_of = [&](int idx) -> const float* {
-                return idx == IG ? slot(base) : (idx >= P ? b.Yv + (size_t)(idx - P) * n : b.Sv + (size_t)idx * n);
-            };
-            q.kind = 2;
-            attach();
-            q.g_new = slot(base); q.g_old = slot(prev_base); q.pair_t = t;
-            q.yv = b.Yv + (size_t)c * n; q.sv = b.Sv + (size_t)c * n;
-            q.jobs.clear();
-            for (const Want& w : want) q.jobs.push_back(VecJobN{vec_of(w.a), vec_of(w.b), 0, 0, (long long)n});
-            if (!B.submit(r, &q)) return;
-            for (size_t i = 0; i < want.size(); ++i) {
-                const double v = B.job_sum(q, (int)i, nb, false);
-                Gat(want[i].a, want[i].b) = v; Gat(want[i].b, want[i].a) = v;
-            }
-            {
-                const double ys = Gat(c, P + c);
-                if ((float)ys > 1e-10f) {
-                    H_diag = ys / Gat(P + c, P + c);
-                    ro[c] = 1.0 / ys;
-                    if ((int)order.size() == M) { spare = order.front(); order.erase(order.begin()); order.push_back(c); }
-                    else { order.push_back(c); spare = (int)order.size(); }
-                }
-            }
-            const int m = (int)order.size();
-            std::fill(delta.begin(), delta.end(), 0.0);
-            delta[IG] = -1.0;
-            auto dot_q = [&](int idx) {
-                double rr = delta[IG] * Gat(IG, idx);
-                for (int j : order) rr += delta[j] * Gat(j, idx) + delta[P + j] * Gat(P + j, idx);
-                return rr;
-            };
-            for (int i = m - 1; i >= 0; --i) { const int j = order[i]; al[j] = dot_q(j) * ro[j]; delta[P + j] -= al[j]; }
-            for (double& v : delta) v *= H_diag;
-            for (int i = 0; i < m; ++i) { const int j = order[i]; const double be = dot_q(P + j) * ro[j]; delta[j] += al[j] - be; }
-            comb = VecComb{};
-            comb.n_vec = 0;
-            for (int j : order) {
-                comb.v[comb.n_vec] = b.Sv + (size_t)j * n; comb.c[comb.n_vec++] = (float)delta[j];
-                comb.v[comb.n_vec] = b.Yv + (size_t)j * n; comb.c[comb.n_vec++] = (float)delta[P + j];
-            }
-            comb.v[comb.n_vec] = slot(base); comb.c[comb.n_vec++] = (float)delta[IG];
-            gtd = (float)dot_q(IG);
-        }
-        have_comb = true;                                                 // formed in front of the line search's first evaluation
-        prev_base = base;
-        prev_loss = loss;
-        t = n_iter == 1 ? std::min(1.0f, 1.0f / gsum) * lr : lr;
-        if (gtd > -tolerance_change) break;
-
-        // ---- strong-Wolfe line search (rc_lbfgs.h: strong_wolfe) on gradient slots: the code of minimize_on_device
-        struct Pt { float t, f, gtd; int k; };
-        const int max_ls = max_eval - evals;
-        auto free_slot = [&](std::initializer_list<int> live) {
-            for (int k = 0; k < kSlots; ++k) { bool used = false; for (int v : live) used = used || v == k; if (!used) return k; }
-            return -1;
-        };
-        const float c1 = 1e-4f, c2 = 0.9f;
-        Pt cur{t, 0, 0, free_slot({base})};
-        Eval ev;
-        if (!eval(cur.t, cur.k, ev)) return;
-        int ls_evals = 1;
-        cur.f = ev.f; cur.gtd = ev.gtd; d_max = ev.dmax;
-        Pt prev{0, loss, gtd, base};
-        Pt br[2] = {prev, prev};
-        int n_br = 0, ls_iter = 0;
-        bool done = false;
-        while (ls_iter < max_ls) {
-            if (cur.f > (loss + c1 * cur.t * gtd) || (ls_iter > 1 && cur.f >= prev.f)) { br[0] = prev; br[1] = cur; n_br = 2; break; }
-            if (std::fabs(cur.gtd) <= -c2 * gtd) { br[0] = cur; n_br = 1; done = true; break; }
-            if (cur.gtd >= 0) { br[0] = prev; br[1] = cur; n_br = 2; break; }
-            const float min_step = cur.t + 0.01f * (cur.t - prev.t), max_step = cur.t * 10;
-            const float tn = cubic(prev.t, prev.f, prev.gtd, cur.t, cur.f, cur.gtd, true, min_step, max_step);
-            prev = cur;
-            cur.t = tn;
-            cur.k = free_slot({base, prev.k});
-            if (!eval(tn, cur.k, ev)) return;
-            cur.f = ev.f; cur.gtd = ev.gtd;
-            ++ls_evals;
-            ++ls_iter;
-        }
-        if (ls_iter == max_ls) { br[0] = Pt{0, loss, gtd, base}; br[1] = cur; n_br = 2; }
-        bool insuf = false;
-        int lo = 0, hi = 1;
-        if (n_br == 2 && !(br[0].f <= br[1].f)) { lo = 1; hi = 0; }
-        while (!done && ls_iter < max_ls) {
-            if (std::fabs(br[1].t - br[0].t) * d_max < tolerance_change) break;
-            float tn = cubic(br[0].t, br[0].f, br[0].gtd, br[1].t, br[1].f, br[1].gtd, false, 0, 0);
-            const float bmax = std::max(br[0].t, br[1].t), bmin = std::min(br[0].t, br[1].t);
-            const float eps = 0.1f * (bmax - bmin);
-            if (std::min(bmax - tn, tn - bmin) < eps) {
-                if (insuf || tn >= bmax || tn <= bmin) {
-                    tn = (std::fabs(tn - bmax) < std::fabs(tn - bmin)) ? bmax - eps : bmin + eps;
-                    insuf = false;
-                } else insuf = true;
-            } else insuf = false;
-            cur.t = tn;
-            cur.k = free_slot({base, br[0].k, br[1].k});
-            if (!eval(tn, cur.k, ev)) return;
-            cur.f = ev.f; cur.gtd = ev.gtd;
-            ++ls_evals;
-            ++ls_iter;
-            if (cur.f > (loss + c1 * tn * gtd) || cur.f >= br[lo].f) {
-                br[hi] = cur;
-                if (br[0].f <= br[1].f) { lo = 0; hi = 1; } else { lo = 1; hi = 0; }
-            } else {
-                if (std::fabs(cur.gtd) <= -c2 * gtd) done = true;
-                else if (cur.gtd * (br[hi].t - br[lo].t) >= 0) br[hi] = br[lo];
-                br[lo] = cur;
-            }
-        }
-        if (n_br == 1) lo = 0;
-        t = br[lo].t;
-        loss = br[lo].f;
-        const int new_base = br[lo].k;
-        have_accept = true; accept_t = t;                                 // x += t d: with the next request (or the final flush)
-        // |g|_inf of the accepted point: from the evaluation that produced it (kept per slot)
-        base = new_base;
-        gmax = base == prev_base ? gmax : slot_gmax[base];
-        const bool opt_cond = gmax <= tolerance_grad;
-        evals += ls_evals;
-        if (n_iter == max_iter) break;
-        if (evals >= max_eval) break;
-        if (opt_cond) break;
-        if (d_max * std::fabs(t) <= tolerance_change) break;
-        if (std::fabs(loss - prev_loss) < tolerance_change) break;
     }
-    if (have_accept) {                                                    // the last accepted step
-        q.kind = 3;
-        have_comb = false;
-        attach();
+    void direction(const Dev::Term* terms, int n_terms) { comb = make_comb(*this, terms, n_terms); have_comb = true; }   // with the next evaluation
+    void accept(float t) { have_accept = true; accept_t = t; }           // x += t d: with the next request (or the final flush)
+    bool pair(int c, int g_new, int g_old, float t, const Dev::Want* want, int n_want, double* out) {
+        q.g_new = vec(2 * P + g_new); q.g_old = vec(2 * P + g_old); q.pair_t = t;
+        q.yv = vec(P + c); q.sv = vec(c);
         q.jobs.clear();
-        if (!B.submit(r, &q)) return;
+        for (int i = 0; i < n_want; ++i) q.jobs.push_back(VecJobN{vec(want[i].a), vec(want[i].b), 0, 0, (long long)b.n});
+        if (!submit(2)) return false;
+        for (int i = 0; i < n_want; ++i) out[i] = part_sum(B.part_of(q, i), b.nb, false);
+        return true;
     }
-    res.n_iter = n_iter;
-    res.n_eval = evals;
-    res.loss = loss;
-    ok = true;
+    bool flush() { have_comb = false; q.jobs.clear(); return !have_accept || submit(3); }   // the last accepted step
+};
+
+void lbfgs_batch_row(RowBatch& B, int r, float lr, int max_iter, Dev::Result& res, char& ok) {
+    struct Leave { RowBatch& B; int r; ~Leave() { B.leave(r); } } on_exit{B, r};
+    const Dev::Options o = lbfgs_options(lr, max_iter);
+    BatchRow be{B, r, B.row[r], o.history_size + 1};
+    ok = Dev::minimize(be, o, res) ? 1 : 0;
 }
 
 }  // namespace
@@ -837,7 +522,7 @@ int rc_smplify_loss_grad(rc_ctx* ctx, const float* x, const float* kp, const flo
     if (!x || !kp || !ref3d || !imu_aa || !K || !grad) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_loss_grad: null buffer");
     if (int rc = reserve(ctx, s, T)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    rc_launch_smplify(make_args(s, x, kp, ref3d, imu_aa, K, grad, T, rc_ctx_ign_mask(ctx)), body, st);
+    rc_launch_smplify(make_args(s, ptrs_of(s, kp, ref3d, imu_aa, K, T), x, grad, rc_ctx_ign_mask(ctx)), body, st);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(s->h_terms.get(), s->terms.get(), (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -870,11 +555,6 @@ int rc_smplify_run(rc_ctx* ctx, const float* pose, const float* tran, const floa
     rc_launch_residual(body, pose, tran, kp, s->Kd.get(), 100.0f, rc_ctx_ign_mask(ctx), s->res0.get(), T, st);
     HIP_TRY(ctx, hipMemcpyAsync(s->h_res.get(), s->res0.get(), (size_t)T * 33 * sizeof(float), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    auto frame_mean = [](const float* r) {                  // torch mean(dim=-1) of 33 fp32 values
-        float acc = 0.0f;
-        for (int v = 0; v < 33; ++v) acc += r[v];
-        return acc / 33.0f;
-    };
     if (frame_mean(s->h_res.get()) > loss_threshold) {
         if (pose_out != pose) HIP_TRY(ctx, hipMemcpyAsync(pose_out, pose, (size_t)T * 216 * sizeof(float), hipMemcpyDeviceToDevice, st));
         if (tran_out != tran) HIP_TRY(ctx, hipMemcpyAsync(tran_out, tran, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -899,63 +579,51 @@ int rc_smplify_run(rc_ctx* ctx, const float* pose, const float* tran, const floa
 
     using L = rc::Lbfgs<float>;
     const size_t n = (size_t)T * 75;
+    const RowPtrs ptrs = ptrs_of(s, kp, s->ref3d.get(), s->imu_aa.get(), K, T);
+    const L::Options opt = lbfgs_options(lr, max_iter);
+    L::Result r;
     const char* hv = std::getenv("RC_SMPLIFY_HOST_LBFGS");            // read per call: tests flip it
-    const bool host_vectors = hv && std::atoi(hv) != 0;
-    if (!host_vectors) {
-        // the optimiser's vectors stay on the device (minimize_on_device); s->x.get() is updated in place
-        DevResult dr;
-        if (int rc = minimize_on_device(ctx, s, body, kp, K, T, lr, max_iter, st, dr)) return rc;
-        rc_launch_aa2R(s->x.get(), pose_out, T * 24, st);
-        HIP_TRY(ctx, hipMemcpyAsync(tran_out, s->x.get() + T * 72, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-        rc_launch_residual(body, pose_out, tran_out, kp, s->Kd.get(), 100.0f, rc_ctx_ign_mask(ctx), s->res1.get(), T, st);
-        HIP_TRY(ctx, hipMemcpyAsync(s->h_res.get() + T * 33, s->res1.get(), (size_t)T * 33 * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        HIP_TRY(ctx, hipGetLastError());
-        for (int64_t t = 0; t < T; ++t) update[t] = frame_mean(s->h_res.get() + (T + t) * 33) < frame_mean(s->h_res.get() + t * 33) ? 1 : 0;
-        info->status = 1;
-        info->n_iter = dr.n_iter;
-        info->n_eval = dr.n_eval;
-        info->first_loss = dr.first_loss;
-        info->final_loss = dr.loss;
-        info->device_ms = s->device_ms;
-        info->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        return RC_OK;
+    if (!(hv && std::atoi(hv) != 0)) {
+        // the optimiser's vectors stay on the device (rc_lbfgs_dev.h on a SingleRow); s->x.get() is updated in place
+        const int P = opt.history_size + 1;
+        if (int rc = reserve_lbfgs(ctx, s, T, P)) return rc;
+        SingleRow be{s, body, ptrs, P, st, rc_ctx_ign_mask(ctx), n, (int)((n + 4095) / 4096)};
+        if (!be.begin() || !Dev::minimize(be, opt, r))
+            return rc_ctx_fail(ctx, RC_ERR_HIP, (std::string("smplify L-BFGS: ") + hipGetErrorString(be.herr)).c_str());
+    } else {
+        // RC_SMPLIFY_HOST_LBFGS=1: round 2's formulation (vectors on the host, rc_lbfgs.h run as is) for A/B runs
+        L::Vec x(s->h_x.get(), s->h_x.get() + n);
+        int hip_rc = RC_OK;
+        const SmplifyArgs A = make_args(s, ptrs, s->x.get(), s->grad.get(), rc_ctx_ign_mask(ctx));
+        L::Objective closure = [&](const L::Vec& xv, L::Vec& g) -> float {
+            std::memcpy(s->h_x.get(), xv.data(), n * sizeof(float));
+            hipError_t e = hipMemcpyAsync(s->x.get(), s->h_x.get(), n * sizeof(float), hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipEventRecord(s->ev0.get(), st);
+            rc_launch_smplify(A, body, st);
+            if (e == hipSuccess) e = hipEventRecord(s->ev1.get(), st);
+            if (e == hipSuccess) e = hipMemcpyAsync(s->h_grad.get(), s->grad.get(), n * sizeof(float), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(s->h_terms.get(), s->terms.get(), (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e == hipSuccess) e = hipGetLastError();
+            if (e != hipSuccess) {
+                if (hip_rc == RC_OK) hip_rc = rc_ctx_fail(ctx, RC_ERR_HIP, (std::string("smplify closure: ") + hipGetErrorString(e)).c_str());
+                std::fill(g.begin(), g.end(), 0.0f);            // zero gradient terminates the search
+                return 0.0f;
+            }
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, s->ev0.get(), s->ev1.get()) == hipSuccess) s->device_ms += ms;
+            std::memcpy(g.data(), s->h_grad.get(), n * sizeof(float));
+            return (float)total_loss(s->h_terms.get(), T);
+        };
+        L::Options host_opt = opt;
+        host_opt.history_size = lbfgs_history_env();
+        r = L::minimize(closure, x, host_opt);
+        if (hip_rc != RC_OK) return hip_rc;
+        std::memcpy(s->h_x.get(), x.data(), n * sizeof(float));
+        HIP_TRY(ctx, hipMemcpyAsync(s->x.get(), s->h_x.get(), n * sizeof(float), hipMemcpyHostToDevice, st));
     }
-    // RC_SMPLIFY_HOST_LBFGS=1: round 2's formulation (vectors on the host, rc_lbfgs.h run as is) for A/B runs
-    L::Vec x(s->h_x.get(), s->h_x.get() + n);
-    int hip_rc = RC_OK;
-    const SmplifyArgs A = make_args(s, s->x.get(), kp, s->ref3d.get(), s->imu_aa.get(), K, s->grad.get(), T, rc_ctx_ign_mask(ctx));
-    L::Objective closure = [&](const L::Vec& xv, L::Vec& g) -> float {
-        std::memcpy(s->h_x.get(), xv.data(), n * sizeof(float));
-        hipError_t e = hipMemcpyAsync(s->x.get(), s->h_x.get(), n * sizeof(float), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipEventRecord(s->ev0.get(), st);
-        rc_launch_smplify(A, body, st);
-        if (e == hipSuccess) e = hipEventRecord(s->ev1.get(), st);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->h_grad.get(), s->grad.get(), n * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->h_terms.get(), s->terms.get(), (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) {
-            if (hip_rc == RC_OK) hip_rc = rc_ctx_fail(ctx, RC_ERR_HIP, (std::string("smplify closure: ") + hipGetErrorString(e)).c_str());
-            std::fill(g.begin(), g.end(), 0.0f);            // zero gradient terminates the search
-            return 0.0f;
-        }
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, s->ev0.get(), s->ev1.get()) == hipSuccess) s->device_ms += ms;
-        std::memcpy(g.data(), s->h_grad.get(), n * sizeof(float));
-        return (float)total_loss(s->h_terms.get(), T);
-    };
-    L::Options opt;
-    opt.lr = lr;
-    opt.max_iter = max_iter;
-    opt.max_eval = max_iter * 5 / 4;
-    opt.history_size = lbfgs_history_env();
-    const L::Result r = L::minimize(closure, x, opt);
-    if (hip_rc != RC_OK) return hip_rc;
 
     // results (temporal_smplify.py:188-196, run.py:31-34): rotation matrices, new residual, per-frame update mask
-    std::memcpy(s->h_x.get(), x.data(), n * sizeof(float));
-    HIP_TRY(ctx, hipMemcpyAsync(s->x.get(), s->h_x.get(), n * sizeof(float), hipMemcpyHostToDevice, st));
     rc_launch_aa2R(s->x.get(), pose_out, T * 24, st);
     HIP_TRY(ctx, hipMemcpyAsync(tran_out, s->x.get() + T * 72, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
     rc_launch_residual(body, pose_out, tran_out, kp, s->Kd.get(), 100.0f, rc_ctx_ign_mask(ctx), s->res1.get(), T, st);
@@ -963,23 +631,17 @@ int rc_smplify_run(rc_ctx* ctx, const float* pose, const float* tran, const floa
     HIP_TRY(ctx, hipStreamSynchronize(st));
     HIP_TRY(ctx, hipGetLastError());
     for (int64_t t = 0; t < T; ++t) update[t] = frame_mean(s->h_res.get() + (T + t) * 33) < frame_mean(s->h_res.get() + t * 33) ? 1 : 0;
-    info->status = 1;
-    info->n_iter = r.n_iter;
-    info->n_eval = r.n_eval;
-    info->first_loss = r.first_loss;
-    info->final_loss = r.loss;
+    set_info(info, r);
     info->device_ms = s->device_ms;
     info->host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return RC_OK;
 }
 
 namespace {
-struct FiberArg { RowBatch* B; int r; float lr; int max_iter; DevResult* res; char* ok; };
+struct FiberArg { RowBatch* B; int r; float lr; int max_iter; Dev::Result* res; char* ok; };
 void fiber_main(unsigned lo, unsigned hi) {
     FiberArg* a = reinterpret_cast<FiberArg*>(((uintptr_t)hi << 32) | (uintptr_t)lo);
-    bool k = false;
-    lbfgs_row(*a->B, a->r, a->lr, a->max_iter, *a->res, k);
-    *a->ok = k ? 1 : 0;
+    lbfgs_batch_row(*a->B, a->r, a->lr, a->max_iter, *a->res, *a->ok);
 }
 bool smplify_threads_env() {            // RC_SMPLIFY_THREADS=1: round 4's first scheme, a host thread per row (A/B runs)
     static const bool v = [] { const char* e = std::getenv("RC_SMPLIFY_THREADS"); return e && std::atoi(e) != 0; }();
@@ -1006,8 +668,7 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
         if (T_rows[r] <= 0 || T_rows[r] > 0x7fffffff / 99 || !pose[r] || !tran[r] || !kp[r] || !imu_ori[r] || !pose_out[r] || !tran_out[r] || !update_host[r])
             return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_run_batch: bad row");
     hipStream_t st = (hipStream_t)stream;
-    const int M = std::max(1, std::min(std::min((int)max_iter, RC_LBFGS_MAX_PAIRS), lbfgs_history_env()));
-    const int P = M + 1;
+    const int P = lbfgs_pairs(max_iter) + 1;
 
     RowBatch B;
     B.ctx = ctx; B.body = body; B.prior = s0; B.st = st; B.ign = rc_ctx_ign_mask(ctx);
@@ -1096,11 +757,6 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
     rc_launch_smplify_begin_rows(io_d, n_rows, B.T_max, body, 100.0f, B.ign, st);
     HIP_TRY(ctx, hipMemcpyAsync(B.pin + p_r0, B.dev + r0_begin, r_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    auto frame_mean = [](const float* v) {
-        float acc = 0.0f;
-        for (int q = 0; q < 33; ++q) acc += v[q];
-        return acc / 33.0f;
-    };
     std::vector<int> live;
     for (int r = 0; r < n_rows; ++r) {
         RowBuf& b = B.row[r];
@@ -1117,13 +773,11 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
     HIP_TRY(ctx, hipGetLastError());
     const auto t_opt = std::chrono::steady_clock::now();
     // ---- the optimisers: a fiber (or, RC_SMPLIFY_THREADS=1, a host thread) per row, the device work in lock-step rounds
-    std::vector<DevResult> res((size_t)n_rows);
+    std::vector<Dev::Result> res((size_t)n_rows);
     std::vector<char> ok((size_t)n_rows, 0);
     B.n_live = (int)live.size();
     if (live.size() == 1) {
-        bool k = false;
-        lbfgs_row(B, live[0], lr, max_iter, res[live[0]], k);
-        ok[live[0]] = k;
+        lbfgs_batch_row(B, live[0], lr, max_iter, res[live[0]], ok[live[0]]);
     } else if (!live.empty() && !smplify_threads_env()) {
         B.fibers = true;
         B.fctx.resize((size_t)n_rows);
@@ -1160,7 +814,7 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
     } else if (!live.empty()) {
         std::vector<std::thread> th;
         th.reserve(live.size());
-        for (int r : live) th.emplace_back([&, r] { bool k = false; lbfgs_row(B, r, lr, max_iter, res[r], k); ok[r] = k; });
+        for (int r : live) th.emplace_back([&, r] { lbfgs_batch_row(B, r, lr, max_iter, res[r], ok[r]); });
         for (std::thread& t : th) t.join();
     }
     if (B.herr != hipSuccess) return rc_ctx_fail(ctx, RC_ERR_HIP, (std::string("smplify batch: ") + hipGetErrorString(B.herr)).c_str());
@@ -1187,11 +841,7 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
     for (int r : live) {
         RowBuf& b = B.row[r];
         for (int64_t t = 0; t < b.T; ++t) update_host[r][t] = frame_mean(b.h_res1 + t * 33) < frame_mean(b.h_res0 + t * 33) ? 1 : 0;
-        infos[r].status = 1;
-        infos[r].n_iter = res[r].n_iter;
-        infos[r].n_eval = res[r].n_eval;
-        infos[r].first_loss = res[r].first_loss;
-        infos[r].final_loss = res[r].loss;
+        set_info(&infos[r], res[r]);
         infos[r].reserved = B.rounds;
     }
     return RC_OK;

@@ -5,7 +5,8 @@ Mirrors ``net/smplify/run.py:smplify_runner`` and ``net/smplify/temporal_smplify
     losses.py:36-37,43-46): one wave-per-frame HIP kernel (rc_reproj_residual);
   * ``__call__`` (temporal_smplify.py:97-196): L-BFGS with a strong-Wolfe line search over the axis-angle pose and the
     translation of the WHOLE sequence. The closure (loss + analytic gradient) is two HIP kernels with one workgroup
-    per frame (csrc/rc_smplify.hip); the optimiser logic is csrc/rc_lbfgs.h, a restatement of torch.optim.LBFGS;
+    per frame (csrc/rc_smplify.hip); the optimiser logic is csrc/rc_lbfgs_dev.h (vectors on the
+    device; csrc/rc_lbfgs.h is the same on host vectors), a restatement of torch.optim.LBFGS;
   * the gate ``mean_k loss[0] > loss_threshold`` and the per-frame ``update`` mask (run.py:24-34).
 Everything numerical is in librobustcap_hip.so; this file prepares constants and marshals pointers.
 """

@@ -240,6 +240,35 @@ def test_batched_rows_equal_one_row_at_a_time(runner, synth_assets):
     assert 20 <= info[0]["rounds"] <= 60                                   # lock-step: rounds of the longest row, not their sum
 
 
+def test_batch_equals_single_at_the_block_edge_with_a_recycling_history(runner, synth_assets, monkeypatch):
+    """The two backends of the device L-BFGS (csrc/rc_lbfgs_dev.h) where their index arithmetic differs most: vectors of 75 T =
+    75, 4,050 (one 4,096-element block of partial sums) and 4,125 elements (two blocks; the batch's table is strided by the longest
+    row's block count, the single row's by its own), T = 1 without temporal terms, and RC_LBFGS_HISTORY=2 with max_iter=12 so that
+    pair and gradient slots are written again and again. The parent of the commit that introduced the shared algorithm gave bitwise
+    equal records, outputs and final losses for batch and single on these inputs, both with the totals added on the device (the
+    default) and with RC_SMPLIFY_DEVICE_TOTALS=0 (both paths add the loss terms on the host): hence bitwise assertions in both."""
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tools"))
+    import smplify_bench as sb
+    body = synth_assets["body"]
+    rows = [sb.make_case(runner, body, T, seed=seed) for seed, T in ((11, 1), (23, 54), (31, 55))]
+    monkeypatch.setenv("RC_LBFGS_HISTORY", "2")
+    for totals in ("1", "0"):
+        monkeypatch.setenv("RC_SMPLIFY_DEVICE_TOTALS", totals)
+        single = []
+        for r in rows:
+            p, tr, upd = runner.run(*r, lr=0.001, max_iter=12)
+            single.append((p.clone(), tr.clone(), upd.clone(), dict(runner.last_info)))
+        out = runner.run_batch(rows, lr=0.001, max_iter=12)
+        for r, (p, tr, upd, a) in enumerate(single):
+            b = runner.last_batch_info[r]
+            print(totals, r, a, b, float((p - out[r][0]).abs().max()), float((tr - out[r][1]).abs().max()))
+            assert a["status"] == 1 and b["status"] == 1 and a["n_iter"] >= 4                    # the history of 2 is full and has evicted
+            assert (a["n_iter"], a["n_eval"], a["first_loss"]) == (b["n_iter"], b["n_eval"], b["first_loss"]), (totals, r, a, b)
+            assert torch.equal(upd, out[r][2])
+            assert a["final_loss"] == b["final_loss"], (totals, r, a, b)
+            assert torch.equal(p, out[r][0]) and torch.equal(tr, out[r][1]), (totals, r)
+
+
 _SCHED_SCRIPT = r"""
 import hashlib, json, os, sys
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tools"))

@@ -1,6 +1,7 @@
 """smplify optimiser timing on one synthetic sequence (frames x 26 closure evaluations), product path only.
 usage: python tools/smplify_bench.py [T]
 (The CPU-oracle comparison of the same workload lives in tests/test_gpu_smplify.py::test_long_sequence_improves.)"""
+import hashlib
 import json
 import sys
 import time
@@ -45,6 +46,10 @@ def main():
     torch.cuda.synchronize()
     out = {"frames": T, "hip": dict(runner.last_info, wall_ms=1e3 * (time.perf_counter() - t0), updated=int(update.sum())),
            "residual": {"before": res(case[0], case[1]), "after": res(pose, tran)}}
+    h = hashlib.sha256()                                           # A/B of numerics-neutral changes (RC_LIB_PATH = the other build)
+    for a in (pose, tran, update):
+        h.update(a.cpu().numpy().tobytes())
+    out["outputs_sha256"] = h.hexdigest()[:16]
     print(json.dumps(out))
 
 
