@@ -40,9 +40,9 @@ COND_FACTOR = 8.0       # every comparison's float64 margin is at least COND_FAC
 CONTACT_KEEP = 1e-3     # distance of every contact probability from the threshold (the two exact cases aside)
 # M: the CPU conditions alone need M > MARGIN for the evaluations that define e32 (their ratio is at most 1 / M), so M = 4, the
 # smallest power of two above 3. Measured (profiles/tail_bound_ratios.txt): the float32 evaluations are at 1 / 4, the weakest
-# mutation at 7.8e3. On an MI355X 13 of the 14 cases have passed every path at this M; the device ratios themselves are not
-# recorded yet (tests/test_gpu_tail_branches.py appends them to the same file through RC_TAIL_RATIOS_OUT). If a path exceeds 1 for
-# an arithmetic reason, M is raised here with that reason, as in smplify_f64.
+# mutation at 7.8e3. On an MI355X all 14 cases pass every path at this M, the translation at 0.25 of the Bound at most and the
+# worst joint at 0.575 (tests/test_gpu_tail_branches.py appends the device ratios to the same file through RC_TAIL_RATIOS_OUT). If a
+# path exceeds 1 for an arithmetic reason, M is raised here with that reason, as in smplify_f64.
 M = 4.0
 
 CORR = ("none", "use1", "use0", "not applied")
@@ -76,6 +76,8 @@ class Params:
         net.smooth = self.smooth
         net.update_vision_freq = self.update_vision_freq
         net.live = self.live
+        net.use_vision_updater = self.use_vision_updater
+        net.use_imu_updater = self.use_imu_updater
 
     def poke_oracle(self, ora):
         ora.conf_range = tuple(self.conf_range)
@@ -88,6 +90,8 @@ class Params:
         ora.smooth = self.smooth
         ora.update_vision_freq = self.update_vision_freq
         ora.live = self.live
+        ora.use_vision_updater = self.use_vision_updater
+        ora.use_imu_updater = self.use_imu_updater
 
 
 class State:
@@ -152,7 +156,8 @@ MUTATIONS = {
 def tail_step(ob, st, bias, Rcr, j2dc, g, first_tran, first_frame, prm, order="plain", mut=None):
     """One frame of B rows. ob: OracleBody of the dtype; st: State (updated in place); bias: dict r6d [144], ct [2], vr [3],
     pc [3]; Rcr [B,3,3], j2dc [B,33,3], g [B,3], first_tran [B,3] or None. Returns (pose [B,24,3,3], tran [B,3], record, margins):
-    record = {name: [B]} of the branches taken, margins = [(name, margin [B], A [B], checked [B])] with A the magnitude behind
+    record = {name: [B]} of the branches taken (+ `upd`, and `joint` [B,24,3] / `j33` [B,33,3]: what the vision updater reads, on
+    the rows with c <= lo, zero elsewhere), margins = [(name, margin [B], A [B], checked [B])] with A the magnitude behind
     the compared quantity (its float32 error is a few eps32 * A)."""
     dt, B = Rcr.dtype, Rcr.shape[0]
     rev = order == "reversed"
@@ -182,7 +187,8 @@ def tail_step(ob, st, bias, Rcr, j2dc, g, first_tran, first_frame, prm, order="p
     c64 = O.conf_mean(j2dc).double() if dt == F32 else j2dc[:, :, 2].mean(dim=1)
     is_hi, gt_lo = c64 >= hi, c64 > lo
     regime = is_hi.long() * 2 + (gt_lo & ~is_hi).long()
-    note("conf vs lo", c64, float(lo), ones, every)
+    # (a mean that EQUALS lo is exact by construction -- 33 equal confidences, oracle/wiring_f64.py -- and exempt like the c0 == c1 tie)
+    note("conf vs lo", c64, float(lo), ones, every & (c64 != float(lo)))
     note("conf vs hi", c64, float(hi), ones, every)
     k64 = (c64 - lo) / (hi - lo)
 
@@ -299,12 +305,17 @@ def tail_step(ob, st, bias, Rcr, j2dc, g, first_tran, first_frame, prm, order="p
     # L228-242
     moves = prm.live and (prm.use_reproj_opt or prm.use_vision_updater)
     refresh = (st.count == 0) if prm.live else every.clone()
-    if prm.use_reproj_opt:
+    upd = ~gt_lo & refresh & bool(prm.use_vision_updater)             # L264: the rows whose vision updater fires on this frame
+    occl = ~gt_lo & bool(prm.use_vision_updater)                      # ... and those the live refresh counter may withhold it from
+    joint_u, j33_u = torch.zeros(B, 24, 3, dtype=dt), torch.zeros(B, 33, 3, dtype=dt)
+    if prm.use_reproj_opt or bool(occl.any()):
         _, joint, vert = ob.forward_kinematics(pose, tran)
         j_new = ob.landmarks(vert, joint)
         j33 = j_new if mut == "cached landmarks ignored in live mode" else torch.where(refresh.view(B, 1, 1), j_new, st.j_temp)
-        if moves:
+        if moves and prm.use_reproj_opt:
             st.j_temp = j33.clone()
+        # what the updater reads (oracle/wiring_f64.py): the refinement below leaves the landmarks of a row with c <= lo alone
+        joint_u, j33_u = torch.where(occl.view(B, 1, 1), joint, joint_u), torch.where(occl.view(B, 1, 1), j33, j33_u)
     if moves:
         st.count = torch.where(refresh, torch.full_like(st.count, prm.update_vision_freq), st.count - 1)
     # L245-261
@@ -336,7 +347,7 @@ def tail_step(ob, st, bias, Rcr, j2dc, g, first_tran, first_frame, prm, order="p
     st.A = A
     rec = dict(regime=regime, use_vel=use_vel.long(), foot=torch.full((B,), foot), far=far.long(), appended=sample.long(),
                corr=corr, refresh=refresh.long(), n_floor=st.n_floor.clone(), reach=reach.long(), start=start.long(),
-               count=st.count.clone())
+               count=st.count.clone(), upd=upd.long(), joint=joint_u, j33=j33_u)
     return pose, tran, rec, margins
 
 
