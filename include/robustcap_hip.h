@@ -388,6 +388,36 @@ int rc_subnet_forward_train(rc_ctx* ctx, const char* net, int32_t n, const int32
 int rc_subnet_backward_train(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* tape, const float* d_h1,
                              const float* d_final_h, const float* d_final_c, float* d_gates, float* d_a, float* d_init_h,
                              float* d_init_c, float p, uint64_t seed, uint32_t call, void* stream);
+/* The weight gradients of one sub-net on the device: what loss.backward() (articulate/utils/torch/train.py:117-122) leaves in the .grad
+ * of linear1, the two LSTM layers and linear2 of an RNN module (articulate/utils/torch/rnn.py:121-133) -- every reduction over the frames
+ * that rc_subnet_backward_train leaves to its caller, in the context's gemm mode (mode 1: both operands split into three bf16 terms
+ * once per element, RC_SPLIT_PRODUCTS partial products on v_mfma_f32_16x16x32_bf16; mode 0: v_mfma_f32_16x16x4_f32), enqueued on
+ * `stream` with no read-back and no host synchronisation (but growing the context's scratch, once per high-water mark).
+ * In, all DEVICE, rows in the caller's order (F = sum T_i): x [F, in]; acts [3, F, H] of rc_subnet_forward_train; init_h [2, n, H] or
+ * NULL (zeros); dy [F, out]; d_gates [2, F, 4H] of rc_subnet_backward_train (torch's columns g * H + u); d_p [F, H], the gradient of
+ * linear1's pre-activation (d_a after the site-0 mask and the relu mask); (p, seed, call) of the forward. outs_dev: HOST array of twelve
+ * DEVICE pointers in rc_update_subnet_weights's order (per LSTM layer weight_ih, weight_hh, bias_ih, bias_hh; linear1.weight, .bias;
+ * linear2.weight, .bias); a NULL entry skips that tensor. For l = 0, 1:
+ *   weight_ih_l = d_gates[l]^T . in_l, in_0 = acts[0] as stored, in_1 = acts[1] dropped at site 1 WHILE it is loaded (the mask of
+ *     rc_dropout_apply(acts[1], site 1, p, seed, call); p == 0: none) -- no masked copy is made;
+ *   weight_hh_l = d_gates[l]^T . h_prev_l, h_prev_l[f] = acts[l + 1][f - 1], at a sequence's first frame init_h[l][sequence] (or zero),
+ *     read through a per-frame index built from lengths_host -- no shifted copy is made;
+ *   bias_ih_l = bias_hh_l = the column sums of d_gates[l];
+ *   linear2.weight = dy^T . acts[2], linear2.bias = column sums of dy; linear1.weight = d_p^T . x, linear1.bias = column sums of d_p.
+ * Summation over the frames is deterministic and on two levels: at most 256 frames in the MFMA accumulators, those blocks into a second
+ * fp32 accumulator; the frames are also cut into at most 16 parts of whole blocks (as many as fill the device, from the tile count),
+ * whose partial sums a second pass adds in index order. No floating-point atomics: two calls give the same bits. Scratch: parts * the
+ * padded output of the largest launch that is cut (grow-only). The column sums take the same blocks and parts in a kernel of their own,
+ * on double accumulators rounded to fp32 once.
+ * RC_ERR_INVALID on an unknown net, n < 1, a length < 1, a null operand or table, p outside [0, 1), or an operand or output whose
+ * allocation ends before its extent; RC_ERR_STATE before rc_finalize_weights -- nothing is enqueued. Ordered with the other sub-net
+ * calls like them; leaves the context's streams joined to `stream` like every eager entry. */
+int rc_subnet_weight_grads(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, const float* acts,
+                           const float* init_h, const float* dy, const float* d_gates, const float* d_p, float p, uint64_t seed,
+                           uint32_t call, void* const* outs_dev, void* stream);
+/* Parts the frames of rc_subnet_weight_grads are cut into: 0 (default) = from the tile count, 1 .. 16 = that many (fewer when the call
+ * has fewer 256-frame blocks). Either way the result is deterministic; the grouping of the sum, and so its rounding, follows the parts. */
+int rc_set_subnet_wgrad_parts(rc_ctx* ctx, int32_t parts);
 /* The optimiser step's way back (train.py:117-122: optimizer.step()): the tensors of ONE sub-net, already on the device, into every
  * device array rc_finalize_weights derives from them -- both packings of linear1 / linear2 (and the row-major copy of a narrow
  * linear2), the padded biases, both packings and the summed, permuted bias of each LSTM layer, for rnn2 the init_net layers, and the

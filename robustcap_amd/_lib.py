@@ -108,6 +108,8 @@ SIGNATURES = {
     "rc_dropout_apply": (_I32, [_P, _P, _P, _I64, _I32, _I32, _F, C.c_uint64, _U32, _P]),
     "rc_subnet_forward_train": (_I32, [_P, C.c_char_p, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, C.c_uint64, _U32, _P]),
     "rc_subnet_backward_train": (_I32, [_P, C.c_char_p, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, C.c_uint64, _U32, _P]),
+    "rc_subnet_weight_grads": (_I32, [_P, C.c_char_p, _I32, _P, _P, _P, _P, _P, _P, _P, _F, C.c_uint64, _U32, _P, _P]),
+    "rc_set_subnet_wgrad_parts": (_I32, [_P, _I32]),
     "rc_update_subnet_weights": (_I32, [_P, C.c_char_p, _P, _I32, _P]),
     "rc_subnet_optim_step": (_I32, [_P, C.c_char_p, _P, _P, _P, _P, _I32] + [C.c_double] * 8 + [_P, _P]),
     "rc_init_net_forward": (_I32, [_P, _I32, _P, _P, _P]),

@@ -14,20 +14,9 @@
 #include <cstdint>
 
 #include "rc_internal.h"
+#include "rc_philox.h"
 
 namespace {
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-        k.x += 0x9E3779B9u;
-        k.y += 0xBB67AE85u;
-    }
-    return c;
-}
 
 // n4: 16-byte pieces of the matrix; c4 = cols / 4 (PK: ld / 4, ld % 16 == 0). PK: piece q of 16-row block q / (16 c4) is
 // [k >> 4][(k >> 2) & 3][row & 15] (rc_pk), and rows from `rows` up to the block's end are left as they are.

@@ -603,6 +603,47 @@ void rc_launch_dropout_rows(const float* src, float* dst, long long rows, int co
 void rc_launch_dropout_pk(const float* src, float* dst, long long rows, int ld, const int* map, int site, const DropoutKey& k,
                           hipStream_t s);
 
+// ---- weight gradients of a trainable sub-net (rc_wgrad.hip; rc_subnet_weight_grads in rc_subnet_api.cpp) --------------------------------
+// C[M, N] = sum over frames f of A[f, m] * B'[f, n]: the contraction runs over the SLOW index of both row-major operands. B' is up to
+// two column segments, each starting a 128-column tile of its own: rows as stored | rows masked at dropout site 1 while they are
+// loaded | the rows of h shifted by one frame within each sequence (init_h, or zero, at a sequence's first frame). Frames are summed on
+// two levels (256 frames in the MFMA accumulators, the blocks into a second set) and cut into `parts` ranges of whole blocks whose
+// partial sums rc_launch_wgrad_reduce adds in index order. The column sums of A (the bias gradients) take the same two levels and
+// parts in a kernel of their own, rc_launch_wgrad_colsum, on double accumulators.
+#define RC_WG_TILE 128         // rows and columns of a workgroup's output tile (four waves, 64 x 64 each)
+#define RC_WG_KB 32            // frames per staged LDS image
+#define RC_WG_BLOCK 256        // frames per first-level sum
+#define RC_WG_MAX_PARTS 16
+enum { RC_WG_ROWS = 0, RC_WG_MASKED = 1, RC_WG_SHIFT = 2 };
+struct WgradSeg {
+    const float* src;        // [F, ld]
+    const float* init;       // SHIFT: [sequences, ld] or null (zeros)
+    float* out;              // [M, ldo]
+    int ld, ncols, ldo, kind;
+    int tile0;               // first column tile of the segment
+    int vec;                 // src (and init) rows may be read as 16-byte pieces
+};
+struct WgradLaunch {
+    const float* A;          // [F, lda], columns [0, M)
+    int lda, M, a_vec;
+    long long F;
+    WgradSeg seg[2];
+    int nseg, ntiles_n, ntiles_m;
+    const int* first;        // [F]: the frame's sequence if it is the sequence's first frame, else -1
+    int parts, blocks_per_part;
+    float* partial;          // parts > 1: [parts][128 ntiles_m][128 ntiles_n]
+    unsigned T;              // MASKED: kept iff bits >= T
+    float scale;
+    uint2 key;
+    unsigned call;
+};
+void rc_launch_wgrad(const WgradLaunch& L, int split, hipStream_t s);           // parts == 1: writes the outputs itself
+void rc_launch_wgrad_reduce(const WgradLaunch& L, hipStream_t s);               // parts > 1: outputs = partial sums added in index order
+// out[m] (and out2[m], either may be null) = sum_f A[f, m], m < M: per part the 256-frame block sums added in frame order, the parts
+// in index order (partial: [parts][M] doubles, used when parts > 1), rounded to fp32 once
+void rc_launch_wgrad_colsum(const float* A, int lda, int M, long long F, int parts, int blocks_per_part, double* partial, float* out,
+                            float* out2, hipStream_t s);
+
 // ---- the optimiser step of one sub-net (rc_optim.hip; rc_subnet_optim_step in rc_api.cpp) -----------------------------------------------
 #define RC_OPTIM_CHUNK 16384   // gradient elements per workgroup (and per partial sum) of the norm
 #define RC_OPTIM_MAXT 18       // tensors of a sub-net at most (rnn2)
@@ -630,6 +671,7 @@ int rc_ctx_subnet_net(rc_ctx* ctx, int net, SubnetNet* out);     // net: kNets i
 int rc_ctx_init_net(rc_ctx* ctx, SubnetDense out[3]);
 int rc_ctx_net_index(const char* name);
 int rc_ctx_gemm_split(rc_ctx* ctx);
+int rc_ctx_mark_eager(rc_ctx* ctx, hipStream_t st);        // mark_eager (rc_ctx.h): eager work was enqueued on st
 long long rc_ctx_weights_epoch(rc_ctx* ctx);               // counts rc_finalize_weights: what was derived from the packed weights is stale
 void rc_subnet_free(SubnetState* s);                       // delete s
 using SubnetOwner = std::unique_ptr<SubnetState, RcRelease<rc_subnet_free>>;

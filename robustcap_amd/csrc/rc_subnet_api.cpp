@@ -22,6 +22,7 @@
 // place on dG1 . W_ih1 (site 1); d_a leaves unmasked and the caller applies site 0. With p = 0 no such launch is made.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cmath>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -45,6 +46,13 @@ struct SubnetState {                 // (grow-only buffers; the context's destru
     DevBuf<float> bst;               // state of a group: per layer two copies of dG [npad, 4H] (rc_pk), d_final_h [npad, H], carried dc [npad, H]
     size_t bst_floats = 0;
     struct TPack { DevBuf<float> W; DevBuf<uint16_t> Ws; long long epoch = -1; } tp[6][2];   // transposed operand per net and layer
+    // weight gradients (rc_subnet_weight_grads)
+    DevBuf<float> wg_part;           // partial sums of a launch cut into parts: [parts][padded M][padded N]
+    size_t wg_part_floats = 0;
+    DevBuf<double> wg_colsum;        // ... and of a bias sum: [parts][M]
+    size_t wg_colsum_doubles = 0;
+    int wg_parts = 0;                // rc_set_subnet_wgrad_parts: 0 = from the tile count
+    int cus = 0;                     // compute units of the device (asked once)
 };
 
 void rc_subnet_free(SubnetState* s) { delete s; }
@@ -375,9 +383,147 @@ int backward_impl(rc_ctx* ctx, const char* what, const char* net, int32_t n, con
     return RC_OK;
 }
 
+// ---- weight gradients: four launches of rc_wgrad.hip's kernel (LSTM layers 0 and 1, linear2, linear1), each followed by the in-order
+// sum of its partial sums when its frames were cut into parts, and by the column sums of its A operand (the bias gradients) ---------------------------------------------------------------
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// appends a segment (its own column tiles) unless its output is null
+void add_seg(WgradLaunch& L, int kind, const float* src, const float* init, int ld, int ncols, float* out, int ldo) {
+    if (!out) return;
+    WgradSeg& s = L.seg[L.nseg++];
+    s = WgradSeg{};
+    s.kind = kind; s.src = src; s.init = init; s.ld = ld; s.ncols = ncols; s.out = out; s.ldo = ldo;
+    s.tile0 = L.ntiles_n;
+    s.vec = ld % 4 == 0 && aligned16(src) && aligned16(init);
+    L.ntiles_n += (ncols + RC_WG_TILE - 1) / RC_WG_TILE;
+}
+
+int weight_grads_impl(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, const float* acts,
+                      const float* init_h, const float* dy, const float* d_gates, const float* d_p, const DropoutKey& drop,
+                      void* const* outs, hipStream_t st) {
+    const std::string what = "rc_subnet_weight_grads";
+    int ni;
+    SubnetNet w;
+    if (int rc = check_args(ctx, what.c_str(), net, n, lengths_host, !x || !acts || !dy || !d_gates || !d_p || !outs, &ni, &w)) return rc;
+    if (!valid_p(drop.p)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (what + ": p outside [0, 1)").c_str());
+    const int H = w.H, in = w.in, out = w.out;
+    long long F = 0;
+    for (int i = 0; i < n; ++i) F += lengths_host[i];
+    if (F >= (1ll << 31)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (what + ": 2^31 frames or more").c_str());
+    if (!dev_holds(x, 4 * F * in) || !dev_holds(acts, 12 * F * H) || !dev_holds(dy, 4 * F * out) || !dev_holds(d_gates, 32 * F * H) ||
+        !dev_holds(d_p, 4 * F * H) || (init_h && !dev_holds(init_h, 8ll * n * H)))
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (what + ": an operand smaller than the call needs").c_str());
+    // the twelve outputs: per LSTM layer weight_ih, weight_hh, bias_ih, bias_hh; linear1.weight, .bias; linear2.weight, .bias
+    const long long numel[12] = {4ll * H * H, 4ll * H * H, 4ll * H, 4ll * H, 4ll * H * H, 4ll * H * H, 4ll * H, 4ll * H,
+                                 (long long)H * in, H, (long long)out * H, out};
+    float* o[12];
+    for (int i = 0; i < 12; ++i) {
+        o[i] = static_cast<float*>(outs[i]);
+        if (o[i] && !dev_holds(o[i], 4 * numel[i])) return rc_ctx_fail(ctx, RC_ERR_INVALID, (what + ": an output smaller than its tensor").c_str());
+    }
+    const int split = rc_ctx_gemm_split(ctx);
+    SubnetState* S = state(ctx);
+    if (!S->cus) {
+        int dev = 0, cus = 0;
+        HIP_TRY(ctx, hipGetDevice(&dev));
+        HIP_TRY(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        S->cus = std::max(1, cus);
+    }
+
+    WgradLaunch L[4];
+    struct ColSum { const float* A; int lda, M; float *out, *out2; int parts, bpp; } cs[4];      // the bias gradients beside each launch
+    auto begin = [&](int q, const float* A, int lda, int M, float* bias, float* bias2) {
+        WgradLaunch& l = L[q];
+        l = WgradLaunch{};
+        l.A = A; l.lda = lda; l.M = M; l.F = F;
+        l.a_vec = lda % 4 == 0 && aligned16(A);
+        l.ntiles_m = (M + RC_WG_TILE - 1) / RC_WG_TILE;
+        l.T = (unsigned)llrint((double)drop.p * 4294967296.0);            // rc_dropout.hip's threshold and scale
+        l.scale = (float)(1.0 / (1.0 - (double)drop.p));
+        l.key = make_uint2((uint32_t)drop.seed, (uint32_t)(drop.seed >> 32));
+        l.call = drop.call;
+        cs[q] = ColSum{A, lda, M, bias, bias2, 1, 1};
+    };
+    for (int l = 0; l < 2; ++l) {        // in_0 = acts[0] as stored; in_1 = acts[1] dropped at site 1 while loaded; h_prev_l from acts[l + 1]
+        begin(l, d_gates + l * F * 4 * H, 4 * H, 4 * H, o[4 * l + 2], o[4 * l + 3]);
+        add_seg(L[l], l == 1 && drop.p > 0.0f ? RC_WG_MASKED : RC_WG_ROWS, acts + l * F * H, nullptr, H, H, o[4 * l], H);
+        add_seg(L[l], RC_WG_SHIFT, acts + (l + 1) * F * H, init_h ? init_h + (long long)l * n * H : nullptr, H, H, o[4 * l + 1], H);
+    }
+    begin(2, dy, out, out, o[11], nullptr);
+    add_seg(L[2], RC_WG_ROWS, acts + 2 * F * H, nullptr, H, H, o[10], H);
+    begin(3, d_p, H, H, o[9], nullptr);
+    add_seg(L[3], RC_WG_ROWS, x, nullptr, in, in, o[8], in);
+
+    // parts: enough workgroups to fill the device, whole 256-frame blocks each, at most RC_WG_MAX_PARTS
+    const long long nblk = (F + RC_WG_BLOCK - 1) / RC_WG_BLOCK;
+    // among 1 .. 16 parts (a forced count: that one) the one whose launch takes the fewest rounds of the device times blocks per part --
+    // more parts both fill a launch of few tiles and trim the last, part-filled round of a launch of many; ties go to fewer parts
+    auto cut = [&](long long workgroups, int* parts, int* bpp) {
+        const long long pmax = std::max(1ll, std::min<long long>(S->wg_parts > 0 ? S->wg_parts : RC_WG_MAX_PARTS, nblk));
+        long long best = -1;
+        for (long long p = S->wg_parts > 0 ? pmax : 1; p <= pmax; ++p) {
+            const long long b = (nblk + p - 1) / p, pe = (nblk + b - 1) / b;
+            const long long cost = (workgroups * pe + S->cus - 1) / S->cus * b;
+            if (best < 0 || cost < best) { best = cost; *parts = (int)pe; *bpp = (int)b; }
+        }
+    };
+    size_t need = 0, need_cs = 0;
+    for (int q = 0; q < 4; ++q) {
+        WgradLaunch& l = L[q];
+        if (l.nseg) {
+            const long long tiles = (long long)l.ntiles_m * l.ntiles_n;
+            cut(tiles, &l.parts, &l.blocks_per_part);
+            if (l.parts > 1) need = std::max(need, (size_t)(l.parts * tiles * RC_WG_TILE * RC_WG_TILE));
+        }
+        if (cs[q].out || cs[q].out2) {
+            cut((cs[q].M + 63) / 64, &cs[q].parts, &cs[q].bpp);
+            if (cs[q].parts > 1) need_cs = std::max(need_cs, (size_t)cs[q].parts * cs[q].M);
+        }
+    }
+
+    if (S->done) HIP_TRY(ctx, hipStreamWaitEvent(st, S->done.get(), 0));
+    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->done), hipEventDisableTiming));
+    HIP_TRY(ctx, rc_grow(S->wg_part_floats, need, need, S->wg_part, need));
+    HIP_TRY(ctx, rc_grow(S->wg_colsum_doubles, need_cs, need_cs, S->wg_colsum, need_cs));
+    Plan P;                              // only its index table: per frame the sequence it opens, or -1
+    P.ih.assign((size_t)F, -1);
+    long long row = 0;
+    for (int i = 0; i < n; ++i) { P.ih[(size_t)row] = i; row += lengths_host[i]; }
+    if (int rc = upload_plan(ctx, S, P, st)) return rc;
+    for (int q = 0; q < 4; ++q) {
+        WgradLaunch& l = L[q];
+        if (l.nseg) {
+            l.first = S->ibuf.get();
+            l.partial = S->wg_part.get();
+            rc_launch_wgrad(l, split, st);
+            if (l.parts > 1) rc_launch_wgrad_reduce(l, st);
+        }
+        if (cs[q].out || cs[q].out2)
+            rc_launch_wgrad_colsum(cs[q].A, cs[q].lda, cs[q].M, F, cs[q].parts, cs[q].bpp, S->wg_colsum.get(), cs[q].out, cs[q].out2, st);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(S->done.get(), st));
+    return rc_ctx_mark_eager(ctx, st);
+}
+
 }  // namespace
 
 extern "C" {
+
+int rc_subnet_weight_grads(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, const float* acts,
+                           const float* init_h, const float* dy, const float* d_gates, const float* d_p, float p, uint64_t seed,
+                           uint32_t call, void* const* outs_dev, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    return weight_grads_impl(ctx, net, n, lengths_host, x, acts, init_h, dy, d_gates, d_p, DropoutKey{p, seed, call}, outs_dev,
+                             (hipStream_t)stream);
+}
+
+int rc_set_subnet_wgrad_parts(rc_ctx* ctx, int32_t parts) {
+    if (!ctx) return RC_ERR_INVALID;
+    if (parts < 0 || parts > RC_WG_MAX_PARTS) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_set_subnet_wgrad_parts: 0 (from the tile count) .. 16");
+    state(ctx)->wg_parts = parts;
+    return RC_OK;
+}
 
 int rc_subnet_forward(rc_ctx* ctx, const char* net, int32_t n, const int32_t* lengths_host, const float* x, float* y,
                       const float* init_h, const float* init_c, float* final_h, float* final_c, void* stream) {

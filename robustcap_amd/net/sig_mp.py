@@ -307,11 +307,12 @@ class Net:
                 raise ValueError(f"rnn2: sequence {i} has shape {tuple(t.shape)}, expected [T >= 1, 72]")
         return xs, v
 
-    def trainable(self, name):
+    def trainable(self, name, weight_grads="torch"):
         """A ``SubnetTrainer`` of sub-net ``name`` ("rnn2" .. "rnn8"): its parameters as torch.nn.Parameters on the device and a
-        differentiable ``tr(xs, init)`` with the values of ``net.rnnK(xs, init)`` (robustcap_amd/train.py)."""
+        differentiable ``tr(xs, init)`` with the values of ``net.rnnK(xs, init)`` (robustcap_amd/train.py). ``weight_grads``: "torch"
+        (fp32 matmuls) or "device" (``rc_subnet_weight_grads``, HIP) for the backward's reductions over the frames."""
         from ..train import SubnetTrainer
-        return SubnetTrainer(self, name)
+        return SubnetTrainer(self, name, weight_grads)
 
     def _subnet_forward(self, name, x, init=None, return_state=False):
         """net.rnnK(x, init): rc_subnet_forward on the current stream. Bad input raises ValueError before anything is enqueued."""
