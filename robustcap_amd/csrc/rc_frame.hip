@@ -103,14 +103,13 @@ __device__ __forceinline__ void fuse_body(const FrameBuffers& fb, const FrameIO&
     } else {
         float v[3];                                                        // j3dc.view(23,3).mm(Rcr), L154
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = (vc[0] * R[c] + vc[1] * R[3 + c]) + vc[2] * R[6 + c];
+        for (int c = 0; c < 3; ++c) v[c] = fuse_rotate(c, vc[0], vc[1], vc[2], R[c], R[3 + c], R[6 + c]);
         if (regime == 2) {
             out[0] = v[0]; out[1] = v[1]; out[2] = v[2];
         } else {                                                           // lerp with a python-double weight, L163-164
             const double k = fb.kconf[row];
-            const float w1 = (float)(1.0 - k), w2 = (float)k;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) out[c] = vi[c] * w1 + v[c] * w2;
+            for (int c = 0; c < 3; ++c) out[c] = fuse_lerp(vi[c], v[c], k);
         }
     }
 #pragma unroll

@@ -4,6 +4,13 @@
 #include "rc_internal.h"
 #include "rc_device.h"
 
+// Everything in this file is compiled into several kernels (rc_prep_kernel / rc_live_k1, the tail kernels of one and of four rows per
+// workgroup / rc_live_k7) that must give the same bits. Under hipcc's default contraction the optimiser decides per kernel which product
+// of "a w1 + b w2" is fused into an FMA -- the translation filter of the tail came out three different ways in one loop, and differently
+// in rc_live_k7 (tests/test_gpu_live_exact.py). contract(on) fuses by the written expression alone (a * b + c -> fma(a, b, c), left operand
+// first, never across statements): the same arithmetic in every kernel that includes this file. Restored at the end of the file.
+#pragma clang fp contract(on)
+
 // -DRC_LIVE_TRACE (tools/live_trace.py; never in the product library): thread 0 of block 0 stamps points inside the lean live
 // frame's kernels with the 100 MHz wall clock -- where a latency-bound kernel spends its microseconds.
 #ifdef RC_LIVE_TRACE
@@ -146,6 +153,25 @@ __device__ __forceinline__ unsigned prep_body(const FrameBuffers& fb, const Fram
     PrepIn in;
     prep_load(in, io, row, lane);
     return prep_compute(fb, in, prm, row, lane, first_frame, pend_in, uv_count, flags2_extra);
+}
+
+// =========================================================================================== fuse (L154-167)
+// The arithmetic of the fuse, ONE definition for fuse_body (rc_frame.hip) and rc_live_k4 (rc_live.hip), every contraction written out
+// and none left to the compiler. As the source expression "(v0 R0c + v1 R1c) + v2 R2c" the two kernels were contracted differently
+// (tests/test_gpu_live_exact.py: rnn7 / rnn8 of the first lean frame off by a last place). The forms below are the ones fuse_body had
+// been compiled to -- packed FMAs for columns 0 and 1, a scalar tail for column 2 -- so the frame-stepped plan keeps its bits.
+// Component c of j3dc.view(23, 3).mm(Rcr): v0..v2 the joint's j3dc, r0 = R[0][c], r1 = R[1][c], r2 = R[2][c].
+__device__ __forceinline__ float fuse_rotate(const int c, const float v0, const float v1, const float v2, const float r0, const float r1, const float r2) {
+#pragma clang fp contract(off)
+    const float p01 = __builtin_fmaf(v0, r0, v1 * r1);                     // columns 0, 1: v1 r1 rounded, then v0 r0 and v2 r2 fused onto it
+    const float q01 = __builtin_fmaf(v1, r1, v0 * r0);                     // column 2: v0 r0 rounded, v1 r1 fused onto it, v2 r2 rounded and added
+    return c == 2 ? q01 + v2 * r2 : __builtin_fmaf(v2, r2, p01);
+}
+// lerp with a python-double weight (L163-164): both weights rounded to float32, vi w1 rounded, vv w2 fused onto it
+__device__ __forceinline__ float fuse_lerp(const float vi, const float vv, const double k) {
+#pragma clang fp contract(off)
+    const float w1 = (float)(1.0 - k), w2 = (float)k;
+    return __builtin_fmaf(vv, w2, vi * w1);
 }
 
 
@@ -522,3 +548,4 @@ __global__ __launch_bounds__(64 * RPB) void rc_tail_kernel(FrameBuffers fb, Fram
     tail_impl<RPB, false>(fb, io, prm, body_g, B, first_frame, io_next, has_next, wt, s_all, s_body, nullptr);
 }
 
+#pragma clang fp contract(fast)      // (hipcc's default for what follows in the including file)

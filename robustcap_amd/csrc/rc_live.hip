@@ -13,8 +13,10 @@
 //   K7 rc_live_tail_kernel   sum of the partials + the tail of the row (L173-273, rc_frame_dev.h: tail_impl)
 // linear2 is computed where h is produced (a tile's 4 or 8 hidden units times their columns of W2) and summed by the consumer
 // behind the launch boundary in a fixed order: no atomics, no fences, nothing that depends on placement. The LSTM tiles are those of
-// rc_gemm.hip's 16-row kernel (same K split over the 4 waves, same MFMA sequence per accumulator, same reduction order and gate
-// functions: layer steps are bitwise those of the frame-stepped plan), with a prologue that requests the weights FIRST and every
+// rc_gemm.hip's 16-row kernel (same K split over the 4 waves, same MFMA sequence per accumulator, same reduction order
+// (p0 + p1) + (p2 + p3) and the one rc_lstm_cell: layer steps are bitwise those of the frame-stepped plan; lin1_tile, K4's fuse
+// (fuse_rotate / fuse_lerp of rc_frame_dev.h) and the tail likewise -- tests/test_gpu_live_exact.py holds all of it to equality
+// over whole sequences), with a prologue that requests the weights FIRST and every
 // per-row word (flags, step parities, cell state, bias) in the same batch -- no row compaction, no dependent read in front of
 // the weight stream. Rows that do not step (rnn4 / rnn6 of an occluded row without a deferred step) are computed and discarded.
 #include "rc_internal.h"
@@ -347,13 +349,9 @@ extern "C" __global__ __launch_bounds__(256) void rc_live_k4(const LiveFrame F) 
                 if (regime == 0) v = vi;
                 else {
                     const float vc0 = s_y4[r][3 * j], vc1 = s_y4[r][3 * j + 1], vc2 = s_y4[r][3 * j + 2];
-                    const float vv = (vc0 * rcr[r][0] + vc1 * rcr[r][1]) + vc2 * rcr[r][2];   // j3dc.view(23,3).mm(Rcr), L154
+                    const float vv = fuse_rotate(e - 3 * j, vc0, vc1, vc2, rcr[r][0], rcr[r][1], rcr[r][2]);   // j3dc.view(23,3).mm(Rcr), L154
                     if (regime == 2) v = vv;
-                    else {                                                 // lerp with a python-double weight, L163-164
-                        const double k = F.fb.kconf[r];
-                        const float w1 = (float)(1.0 - k), w2 = (float)k;
-                        v = vi * w1 + vv * w2;
-                    }
+                    else v = fuse_lerp(vi, vv, F.fb.kconf[r]);             // lerp with a python-double weight, L163-164
                 }
             }
         }
@@ -505,14 +503,14 @@ __device__ __forceinline__ void live_lstm_body(const LiveFrame& F, const LiveGri
     __syncthreads();
     RC_LT(3, 3 + 5 * LAYER);
     if (e_on) {
-        f32x4 g4 = *reinterpret_cast<const f32x4*>(&s_part[er * LD + 4 * eu]);
-#pragma unroll
-        for (int ww = 1; ww < 4; ++ww) g4 += *reinterpret_cast<const f32x4*>(&s_part[(ww * 16 + er) * LD + 4 * eu]);
+        // gemm_tile's order and its cell, to the letter: (p0 + p1) + (p2 + p3) -- the two halves of K summed on their own first -- and
+        // rc_lstm_cell with its contraction written out. (Until tests/test_gpu_live_exact.py compared bits this epilogue added the four
+        // wave sums one after the other and left the contraction of f c + i g to the compiler: a last-place difference in every sixth state.)
+        auto wsum = [&](const int ww) { return *reinterpret_cast<const f32x4*>(&s_part[(ww * 16 + er) * LD + 4 * eu]); };
+        f32x4 g4 = (wsum(0) + wsum(1)) + (wsum(2) + wsum(3));
         g4 += bias4;
-        const float ig = rc_gate_sigmoid(g4[0]), fg = rc_gate_sigmoid(g4[1]);
-        const float gg = rc_gate_tanh(g4[2]), og = rc_gate_sigmoid(g4[3]);
-        const float cn = fg * c_prev + ig * gg;
-        const float hn = og * rc_gate_tanh(cn);
+        float cn, hn;
+        rc_lstm_cell(g4[0], g4[1], g4[2], g4[3], c_prev, cn, hn);
         const bool on = (amask >> er) & 1u;
         if (on) {
             const int unit = n_tile * UT + eu;

@@ -129,6 +129,7 @@ struct LiveSession : LiveKept {
     DevBuf<float> pre_buf;                          // [tiles of the twelve layer steps][2 waves][64 lanes][4]
     PinBuf<unsigned> spin_state_h;                  // pinned + mapped, [4 par]: 3 = the waiting kernel gave up
     LiveFrame frame{};
+    std::string lean_wide;                          // RC_LIVE_LEAN_NC=2: the 16 x 32-tile layer-step kernels of the captured lean plan, by name
     LivePackets aql;
     // nothing below owns anything
     std::vector<unsigned char> maybe_pend;          // host-side, conservative: row may carry a deferred updater step
@@ -492,6 +493,10 @@ std::string setup_lean(rc_ctx* ctx, LiveSession& s, std::vector<LiveKernel>& pla
     if (hipHostGetDevicePointer((void**)&F.status, s.status_h.get(), 0) != hipSuccess) return "lean frame: status word not mapped";
     F.abort = s.abort_d.get();
     if (rc_live_plan(F, plan.data()) != RC_LIVE_KERNELS) return "lean frame: sub-net sizes these kernels are not compiled for";
+    if (F.nc == 2) {                                                   // (what the plan holds, not what the switch asked for: rc_get_live_backend tells)
+        s.lean_wide = "lean LSTM tiles 16 x 32:";
+        for (int i : {1, 2, 4, 5}) s.lean_wide += std::string(" ") + plan[i].name;
+    }
     hipStream_t st = s.stream.get();
     const std::string what = s.io.capture(st, [&] { rc_launch_live_frame(F, st); return true; }, s.graph_lean, s.exec_lean);
     return what.empty() ? what : "lean frame: " + what;
@@ -629,6 +634,7 @@ int rc_live_begin(rc_ctx* ctx) {
         if (hipStreamIsCapturing(s.stream.get(), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) { HipGraph g; (void)hipStreamEndCapture(s.stream.get(), rc_out(g)); }
         (void)hipGetLastError();
         s.exec_lean.reset(); s.graph_lean.reset();
+        s.lean_wide.clear();
         s.aql_note = why;
         return RC_OK;
     }
@@ -692,7 +698,9 @@ int rc_get_live_backend(rc_ctx* ctx, int32_t* lean_captured, int32_t* aql, char*
     if (!ctx) return RC_ERR_INVALID;
     if (lean_captured) *lean_captured = ctx->live->exec_lean ? 1 : 0;
     if (aql) *aql = ctx->live->aql.chain ? 1 : 0;
-    if (note && note_len > 0) std::snprintf(note, (size_t)note_len, "%s", ctx->live->aql_note.c_str());
+    // (the default plan of 16 x 16 tiles adds nothing: an empty note still means "the packet chain is in use")
+    const LiveSession& s = *ctx->live;
+    if (note && note_len > 0) std::snprintf(note, (size_t)note_len, "%s%s%s", s.aql_note.c_str(), (!s.aql_note.empty() && !s.lean_wide.empty()) ? "; " : "", s.lean_wide.c_str());
     return RC_OK;
 }
 

@@ -31,7 +31,9 @@ min(160, max(64, B / 2))), launch_problems, rc_launch_gemm (rc_gemm_is_small / _
   rc_gemm_small_nt_kernel     live frames only (GemmLaunch.live, batch <= 16, fp32): tests/test_gpu_live.py
   rc_gemm_split48_w32_kernel  64 x 128 tiles with one row tile per problem = the wavefront engine of 33-64 row contexts
                               (run_wave2_segment): tests/test_gpu_fixture_in_batch.py, tests/test_gpu_module_surface.py
-  rc_gemm_resident_kernel, live_lstm_body: out of scope here (bitwise against frame-stepped elsewhere)
+  rc_gemm_resident_kernel     out of scope here (bitwise against frame-stepped: tests/test_gpu_resident.py)
+  live_lstm_body (rc_live.hip), both tile widths: bitwise against the frame-stepped plan over whole sequences on a state dict
+                              whose linear2 sums are exact in every order: tests/test_gpu_live_exact.py
 
 linear1 runs on the 2x4 tiles (mid kernels) from 17 rows and on 1x1 tiles below, linear2 on 1x1 tiles (small kernels); in split
 mode both use split products too. launch_stats() counts launches of rc_gemm_lds_kernel and of every kernel but the small ones,
