@@ -456,6 +456,31 @@ int rc_subnet_optim_step(rc_ctx* ctx, const char* net, const void* const* params
                          const void* const* exp_avg_dev, const void* const* exp_avg_sq_dev, int32_t count, double lr, double beta1,
                          double beta2, double eps, double weight_decay, double bias_correction1, double bias_correction2, double max_norm,
                          float* norm_out_dev, void* stream);
+/* The first call of the training iteration (articulate/utils/torch/train.py:117, `loss = loss_fn(net(d), l)`) with the loss function the
+ * reference trains each sub-net with, over the CONCATENATED batch as RNNLossWrapper hands it over (articulate/utils/torch/rnn.py):
+ * x DEVICE [frames, width] (the sub-net's output), y DEVICE [frames, width] (the labels) -> value_dev DEVICE float[1] and, unless NULL,
+ * dx_dev DEVICE [frames, width] = d value / d x, which feeds rc_subnet_backward_train as dy. Enqueued on `stream`, no read-back, no host
+ * synchronisation. kind (rc_loss_kind):
+ *   RC_LOSS_MSE (width 69 or 3; rnn2, rnn4, rnn6: net/sig_mp.py:340,555,683 MSELoss): mean (x - y)^2; dx = 2 (x - y) / (frames width).
+ *   RC_LOSS_BCE_LOGITS (width 2; rnn8: sig_mp.py:829-831 BCEWithLogitsLoss(pos_weight)): aux_dev = pos_weight DEVICE float[2]; with
+ *     L = 1 + (pw - 1) y the mean of (1 - y) x + L (max(-x, 0) + log1p(exp(-|x|))); dx = ((1 - y) - L (1 - sigmoid(x))) / (frames width).
+ *   RC_LOSS_WINDOW_MSE (width 3; rnn3: sig_mp.py:409-415): mse(x, y) + the mse of the sums over windows of 6, 20 and 60 consecutive frames,
+ *     the windows cut from the END of the batch (x[frames % w:].view(-1, w, 3).sum(1)): the first frames % w frames belong to no window
+ *     of width w, and a window runs across sequence boundaries. frames >= 60 (below, the reference's value is the NaN of an empty mean).
+ *   RC_LOSS_POSE_FK (width 144; rnn7: sig_mp.py:749-767): mse(x, y) + 100 mse(J(x), J(y)), J = the 24 joints (root included) from the 24
+ *     r6d rotations (articulate/math/angular.py:249-264, NaN entries set to 0), every rest bone of the context's body (rc_set_body; the
+ *     bones rc_joint_to_bone gives of rc_zero_pose's joints) turned by its PARENT's rotation and summed down the tree. A degenerate joint
+ *     (first vector zero, or the second parallel to it) has R = 0 in the value; its own six entries of dx hold what the formulas give (NaN
+ *     or inf, as the reference's autograd), every other entry and the value are unaffected.
+ * Everything that enters the value is formed in double on the fp32 inputs: per-thread sums in a fixed order, one partial per workgroup in
+ * a context-owned buffer (allocated by the first call), added in index order by one workgroup and rounded to fp32 once. No floating-point
+ * atomics: two calls give the same bits. Calls on one context share that buffer: a caller who uses a second stream orders it itself.
+ * x, y and dx 16-byte aligned (RC_LOSS_WINDOW_MSE: any alignment). RC_ERR_INVALID (nothing enqueued) on a null context, an unknown kind, a
+ * width that does not fit the kind, frames <= 0, frames < 60 for RC_LOSS_WINDOW_MSE, RC_LOSS_POSE_FK before rc_set_body, RC_LOSS_BCE_LOGITS
+ * without aux_dev, a null x, y or value_dev, or a misaligned pointer. */
+typedef enum { RC_LOSS_MSE = 0, RC_LOSS_BCE_LOGITS = 1, RC_LOSS_WINDOW_MSE = 2, RC_LOSS_POSE_FK = 3 } rc_loss_kind;
+int rc_subnet_loss(rc_ctx* ctx, int32_t kind, const float* x, const float* y, int64_t frames, int32_t width, const float* aux_dev,
+                   float* value_dev, float* dx_dev, void* stream);
 /* RNNWithInit.init_net (articulate/utils/torch/rnn.py:195-201, used at :207-219): Linear(69,512) ReLU Linear(512,1024) ReLU
  * Linear(1024,2048) on v DEVICE [n, 69] -> out DEVICE [n, 2048], on the packed weights of rnn2.init_net in the context's gemm mode. */
 int rc_init_net_forward(rc_ctx* ctx, int32_t n, const float* v, float* out, void* stream);

@@ -42,6 +42,8 @@ NETS = (
 NET_INDEX = {n[0]: i for i, n in enumerate(NETS)}
 # dropout rate each sub-net is built with, net/sig_mp.py:52-81 (after linear1 and between the LSTM layers, rnn.py:112,115)
 DROPOUT = {n[0]: 0.1 if n[0] == "rnn7" else 0.4 for n in NETS}
+# loss each sub-net is trained with, net/sig_mp.py:340,409-418,555,683,749-771,829-831 (robustcap_amd/losses.py)
+LOSS = {"rnn2": "mse", "rnn3": "window_mse", "rnn4": "mse", "rnn6": "mse", "rnn7": "pose_fk", "rnn8": "bce_logits"}
 # rnn2.init_net: Linear(69,512) ReLU Linear(512,1024) ReLU Linear(1024,2048)  (rnn.py:195-201)
 INIT_NET = ((69, 512), (512, 1024), (1024, 2048))
 

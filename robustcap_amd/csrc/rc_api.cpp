@@ -589,6 +589,36 @@ int rc_subnet_optim_step(rc_ctx* ctx, const char* net, const void* const* params
     return mark_eager(ctx, st);
 }
 
+// The loss of the training iteration (kernels: rc_loss.hip). Touches nothing of the context but its partial sums, so it is ordered by the
+// caller's stream alone.
+int rc_subnet_loss(rc_ctx* ctx, int32_t kind, const float* x, const float* y, int64_t frames, int32_t width, const float* aux_dev,
+                   float* value_dev, float* dx_dev, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    const std::string what = "rc_subnet_loss: ";
+    bool fits = false;
+    switch (kind) {
+        case RC_LOSS_MSE: fits = width == 69 || width == 3; break;
+        case RC_LOSS_BCE_LOGITS: fits = width == 2; break;
+        case RC_LOSS_WINDOW_MSE: fits = width == 3; break;
+        case RC_LOSS_POSE_FK: fits = width == 144; break;
+        default: return fail(ctx, RC_ERR_INVALID, what + "unknown kind " + std::to_string(kind));
+    }
+    if (!fits) return fail(ctx, RC_ERR_INVALID, what + "width " + std::to_string(width) + " does not fit kind " + std::to_string(kind));
+    if (frames <= 0) return fail(ctx, RC_ERR_INVALID, what + "frames must be positive");
+    if (kind == RC_LOSS_WINDOW_MSE && frames < 60)
+        return fail(ctx, RC_ERR_INVALID, what + "window_mse needs at least 60 frames (" + std::to_string(frames) +
+                                             " given: no window of 60 frames exists and the reference's value is the NaN of an empty mean)");
+    if (kind == RC_LOSS_POSE_FK && !ctx->have_body) return fail(ctx, RC_ERR_INVALID, what + "pose_fk: body not set");
+    if (kind == RC_LOSS_BCE_LOGITS && !aux_dev) return fail(ctx, RC_ERR_INVALID, what + "bce_logits: pos_weight missing");
+    if (!x || !y || !value_dev) return fail(ctx, RC_ERR_INVALID, what + "null argument");
+    if (kind != RC_LOSS_WINDOW_MSE && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)dx_dev) & 15))
+        return fail(ctx, RC_ERR_INVALID, what + "x, y and dx must be 16-byte aligned");
+    if (!ctx->loss_partial) HIP_TRY(ctx, rc_alloc(ctx->loss_partial, (size_t)RC_LOSS_MAX_PARTIALS));     // once: never regrown
+    rc_launch_subnet_loss(kind, ctx->body, x, y, frames, width, aux_dev, ctx->loss_partial.get(), value_dev, dx_dev, (hipStream_t)stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return RC_OK;
+}
+
 static int finalize_weights_impl(rc_ctx* ctx) {
     for (int i = 0; i < 6; ++i) {
         const NetSpec& s = kNets[i];

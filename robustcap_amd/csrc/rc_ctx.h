@@ -75,6 +75,7 @@ struct rc_ctx {
     SmplifyOwner smplify;                // optimiser work space (rc_smplify_api.cpp)
     SubnetOwner subnet;                  // scratch of rc_subnet_forward (rc_subnet_api.cpp)
     DevBuf<double> optim_partial;        // rc_subnet_optim_step: per-workgroup sums of squares of the gradient norm, sized once for the largest sub-net
+    DevBuf<double> loss_partial;         // rc_subnet_loss: RC_LOSS_MAX_PARTIALS per-workgroup sums, allocated by the first call
 };
 
 #pragma GCC visibility push(hidden)

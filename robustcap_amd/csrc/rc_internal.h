@@ -663,6 +663,17 @@ void rc_launch_optim_lstm(const OptimTensor& wi, const OptimTensor& wh, const Op
 void rc_launch_optim_dense(const OptimTensor& Wt, const OptimTensor& bt, int N, int K, int Np, int Kp, float* W, void* Ws, float* Wrm, float* bp,
                            const OptimScalars& a, const float* out2, hipStream_t s);
 
+// ---- the training objectives of the sub-nets (rc_loss.hip; rc_subnet_loss in rc_api.cpp) ---------------------------------------------------
+// (the kinds: rc_loss_kind of the header, which rc_loss.hip and rc_api.cpp include)
+#define RC_LOSS_VEC 4                // elements a thread moves at once (mse, bce_logits): one 16-byte piece
+#define RC_LOSS_CHUNK 4096            // elements per unit of mse and bce_logits: four pieces per thread of a workgroup
+#define RC_LOSS_WINDOW_FRAMES 240     // frames per unit of window_mse, counted from the end of the batch: four blocks of 60
+#define RC_LOSS_POSE_FRAMES 16        // frames per unit of pose_fk: four per wave
+#define RC_LOSS_MAX_PARTIALS 1024     // workgroups (and partial sums) of a call at most: beyond it a workgroup takes several units
+// value = the loss of x, y [F, W] (one device float), dx (may be null) its gradient; partial: RC_LOSS_MAX_PARTIALS doubles
+void rc_launch_subnet_loss(int kind, const BodyConst* body, const float* x, const float* y, long long F, int W, const float* aux,
+                           double* partial, float* value, float* dx, hipStream_t s);
+
 // narrow view of the context for rc_subnet_api.cpp
 struct SubnetState;
 struct SubnetDense { const float* W; const void* Ws; const float* b; int K, N, Kp, Np; };

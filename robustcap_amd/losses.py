@@ -1,0 +1,165 @@
+"""The losses the reference trains its six sub-nets with, on the device: ``loss = tr.loss()`` -- the first call of the iteration of
+``articulate/utils/torch/train.py:117`` (``loss = loss_fn(net(d), l)``), with ``RNNLossWrapper``'s meaning: the sequences of the batch are
+concatenated first, the loss function sees one [F, W] tensor of outputs and one of labels.
+
+    kind          sub-nets            the reference (net/sig_mp.py)
+    mse           rnn2, rnn4, rnn6    :340,555,683  MSELoss
+    window_mse    rnn3                :409-415      mse + the mse of the sums over windows of 6, 20, 60 frames cut from the END of the batch
+    pose_fk       rnn7                :749-767      mse + 100 mse of the joints the 24 r6d rotations give on the rest bones
+    bce_logits    rnn8                :829-831      BCEWithLogitsLoss(pos_weight=(1 - l).sum(0) / l.sum(0))
+
+One HIP entry, ``rc_subnet_loss`` (csrc/rc_loss.hip), forms the value and ``dx = d value / d x`` in the same launch, summed in double in a
+fixed order: no read-back, no host synchronisation, the same bits on every run. ``dx`` is what ``backward()`` hands to
+``rc_subnet_backward_train`` as ``dy``. Labels are constants; there is no double backward.
+"""
+import torch
+
+from . import _lib
+from . import body as _body
+from . import config as cfg
+
+KINDS = {"mse": 0, "bce_logits": 1, "window_mse": 2, "pose_fk": 3}            # rc_loss_kind
+WIDTHS = {"mse": (69, 3), "bce_logits": (2,), "window_mse": (3,), "pose_fk": (144,)}
+WINDOWS = (6, 20, 60)
+# the geometry of csrc/rc_loss.hip (RC_LOSS_* of rc_internal.h), for the tests that stand on its edges
+VEC = 4                  # elements a thread moves at once (mse, bce_logits)
+CHUNK = 4096             # elements a workgroup owns at a time (mse, bce_logits)
+WINDOW_FRAMES = 240      # frames a workgroup owns at a time, counted from the end of the batch (window_mse)
+POSE_FRAMES = 16         # frames a workgroup owns at a time (pose_fk)
+MAX_PARTIALS = 1024      # workgroups of a call at most: beyond it a workgroup takes several such shares
+
+
+def check_frames(kind, frames):
+    """ValueError where the reference's loss has no value: ``window_mse`` below 60 frames is the mean of an empty tensor (NaN)."""
+    if frames <= 0:
+        raise ValueError(f"{kind}: no frames")
+    if kind == "window_mse" and frames < max(WINDOWS):
+        raise ValueError(f"window_mse needs at least {max(WINDOWS)} frames ({frames} given): no window of {max(WINDOWS)} frames exists "
+                         "and the reference's value is the NaN of an empty mean")
+
+
+def _on(t, device):
+    """t lives on `device` ("cuda" names the current device: an index is compared only where both have one)."""
+    return t.device.type == device.type and (t.device.index is None or device.index is None or t.device.index == device.index)
+
+
+def _rows(ts, what, device=None):
+    """(tensors, lengths, width) of ``ys`` / ``labels``: one [F, W] tensor or a list of [T_i, W] tensors, float32."""
+    ts = [ts] if isinstance(ts, torch.Tensor) else list(ts)
+    if not ts or any(not isinstance(t, torch.Tensor) or t.dim() != 2 for t in ts):
+        raise ValueError(f"{what}: one [F, W] tensor or a non-empty list of [T_i, W] tensors")
+    if any(t.dtype != torch.float32 for t in ts):
+        raise ValueError(f"{what}: float32 expected, got {sorted({str(t.dtype) for t in ts})}")
+    if len({int(t.shape[1]) for t in ts}) != 1:
+        raise ValueError(f"{what}: the tensors differ in width")
+    if device is not None and any(not _on(t, device) for t in ts):
+        raise ValueError(f"{what}: expected on {device}")
+    return ts, [int(t.shape[0]) for t in ts], int(ts[0].shape[1])
+
+
+def _flat_view(ts):
+    """The [F, W] tensor whose rows are those of ``ts`` in list order WITHOUT a copy where the list is the split views of one contiguous
+    tensor (what ``tr(...)`` returns: same storage, each view contiguous and starting where the one before ends), else None."""
+    first = ts[0]
+    W = int(first.shape[1])
+    store, at = first.untyped_storage().data_ptr(), first.storage_offset()
+    for t in ts:
+        if not t.is_contiguous() or t.untyped_storage().data_ptr() != store or t.storage_offset() != at:
+            return None
+        at += t.shape[0] * W
+    return first.as_strided((sum(int(t.shape[0]) for t in ts), W), (W, 1), first.storage_offset())
+
+
+def _concat(ts):
+    if len(ts) == 1 and ts[0].is_contiguous():
+        return ts[0]
+    flat = _flat_view(ts)
+    return flat if flat is not None else torch.cat(ts).contiguous()
+
+
+def _aligned(t):
+    return t if t.data_ptr() % 16 == 0 else t.clone()                           # (a view off the 16-byte grid: the kernels move 16-byte pieces)
+
+
+class _LossFunction(torch.autograd.Function):
+    """inputs: the SubnetLoss, the labels [F, W] on the device, whether dx is wanted, then the sequences of ``ys``."""
+
+    @staticmethod
+    def forward(ctx, loss, y, want_dx, *xs):
+        x = _aligned(_concat([t.detach() for t in xs]))
+        value = torch.empty((), device=x.device)
+        dx = torch.empty_like(x) if want_dx else None
+        net = loss._net
+        rc = net._lib.rc_subnet_loss(net._ctx, KINDS[loss.kind], _lib.ptr(x), _lib.ptr(y), x.shape[0], x.shape[1], _lib.ptr(loss.pos_weight),
+                                     _lib.ptr(value), _lib.ptr(dx), _lib.stream_ptr())
+        _lib.check(net._ctx, rc, "rc_subnet_loss")
+        ctx.dx, ctx.lengths = dx, [int(t.shape[0]) for t in xs]
+        return value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if ctx.dx is None:
+            raise RuntimeError("this loss was evaluated without its gradient")
+        return (None, None, None) + tuple(torch.split(ctx.dx * g, ctx.lengths))
+
+
+class SubnetLoss:
+    """``loss(ys, labels)`` -> 0-d device tensor, differentiable with respect to ``ys``. ``kind``: a key of ``KINDS``; ``pos_weight``
+    ([2], ``bce_logits`` only; None: ones); ``width``: the only width accepted (``tr.loss()`` passes the sub-net's), default any the
+    kind has. Each of ``ys`` and ``labels`` is one [F, W] tensor or a list of [T_i, W] tensors, concatenated in list order
+    (``RNNLossWrapper``); only the total number of frames has to agree. ``ys`` on the device; ``labels`` anywhere (moved). Every
+    check raises ValueError before anything is enqueued. Under ``torch.no_grad()``, or when no ``ys`` requires a gradient, only the
+    value is formed."""
+
+    def __init__(self, net, kind, pos_weight=None, width=None):
+        if kind not in KINDS:
+            raise ValueError(f"loss kind {kind!r}: one of {sorted(KINDS)}")
+        if width is not None and width not in WIDTHS[kind]:
+            raise ValueError(f"{kind}: width {width} not in {WIDTHS[kind]}")
+        if pos_weight is not None and kind != "bce_logits":
+            raise ValueError(f"{kind} takes no pos_weight")
+        self._net, self.kind = net, kind
+        self.widths = WIDTHS[kind] if width is None else (int(width),)
+        self.pos_weight = None
+        if kind == "bce_logits":
+            pw = torch.ones(2) if pos_weight is None else torch.as_tensor(pos_weight).detach()
+            if pw.numel() != 2:
+                raise ValueError("pos_weight: two values expected")
+            self.pos_weight = pw.to(device=net.device, dtype=torch.float32).reshape(2).contiguous()
+
+    def __call__(self, ys, labels):
+        net = self._net
+        xs, xl, xw = _rows(ys, "ys", net.device)
+        ls, ll, lw = _rows(labels, "labels")
+        if xw not in self.widths or lw != xw:
+            raise ValueError(f"{self.kind}: width {self.widths} expected, ys have {xw}, labels {lw}")
+        if sum(xl) != sum(ll):
+            raise ValueError(f"ys hold {sum(xl)} frames, labels {sum(ll)}")
+        check_frames(self.kind, sum(xl))
+        y = _aligned(_concat([t.detach().to(net.device) for t in ls]))
+        want_dx = torch.is_grad_enabled() and any(t.requires_grad for t in xs)
+        return _LossFunction.apply(self, y, want_dx, *xs)
+
+
+def pos_weight_from_labels(labels):
+    """``(1 - l).sum(0) / l.sum(0)`` over the concatenated labels (net/sig_mp.py:829-830): rnn8's ``pos_weight``."""
+    ls, _, _ = _rows(labels, "labels")
+    l = torch.cat(ls)
+    return (1 - l).sum(dim=0) / l.sum(dim=0)
+
+
+def position_error(ys, labels, device="cuda"):
+    """The reference's ``rnn_dist_eval_fn = RNNLossWrapper(art.PositionErrorEvaluator())`` of rnn2 and rnn4 (net/sig_mp.py:341,556):
+    the mean Euclidean distance of the 23 predicted joints, on ``body.position_error`` over the concatenated lists. A Python float;
+    no gradient."""
+    xs, xl, xw = _rows(ys, "ys")
+    ls, ll, lw = _rows(labels, "labels")
+    if xw != lw or sum(xl) != sum(ll) or xw % 3:
+        raise ValueError(f"ys [{sum(xl)}, {xw}] and labels [{sum(ll)}, {lw}] must hold the same 3-D points")
+    return _body.position_error(torch.cat([t.detach() for t in xs]), torch.cat([t.detach() for t in ls]), device=device)
+
+
+def for_subnet(tr, pos_weight=None):
+    """``tr.loss(pos_weight)``: the loss the reference trains this trainer's sub-net with (``config.LOSS``)."""
+    return SubnetLoss(tr._net, cfg.LOSS[tr.name], pos_weight=pos_weight, width=dict((n, o) for n, _, _, o in cfg.NETS)[tr.name])
