@@ -587,6 +587,20 @@ int rc_lbfgs_minimize(rc_objective_fn objective, void* user, int64_t n, double* 
                       int32_t max_eval, int32_t history_size, double tolerance_grad, double tolerance_change,
                       int32_t* n_iter_out, int32_t* n_eval_out, double* losses_out, int64_t cap);
 
+/* DIAGNOSTIC (tests only; no reference interface: torch.optim.LBFGS of net/smplify/temporal_smplify.py:141-147 keeps its vectors in
+ * tensors). The device-resident optimiser alone: the backends, vector kernels, job tables and arenas rc_smplify_run (backend 0: each row
+ * through the single-row backend, one after another) and rc_smplify_run_batch (backend 1: all rows in lock-step rounds) run, on a
+ * synthetic closure whose fp32 arithmetic tests/lbfgs_device_emu.cpp restates exactly (csrc/rc_smplify.hip: rc_syn_closure_*). Needs
+ * neither a body nor a prior. Row r has 75 T_r elements; x0 / a / b / x_out are HOST arrays of n_rows DEVICE pointers to [75 T_r]
+ * (start, weights, targets, result). max_eval, history and tolerances are those of rc_smplify_run (RC_LBFGS_HISTORY and
+ * RC_SMPLIFY_DEVICE_TOTALS are read per call). infos[n_rows] receives n_iter / n_eval / first and final loss; losses_out HOST
+ * [n_rows, cap] every closure value of a row in evaluation order (zero-filled); backend 1: *max_jobs_out = the largest job table a
+ * round sent, *rounds_out = the number of rounds (both 0 for backend 0). Synchronises `stream`. */
+int rc_lbfgs_device_probe(rc_ctx* ctx, int32_t backend, int32_t n_rows, const int64_t* T_rows, const float* const* x0,
+                          const float* const* a, const float* const* b, float lr, int32_t max_iter, float* const* x_out,
+                          rc_smplify_info* infos, float* losses_out, int64_t cap, int32_t* max_jobs_out, int32_t* rounds_out,
+                          void* stream);
+
 /* Harness input preparation of evaluate.py:38-51,70-73 for ONE (sequence, camera) of n frames:
  *   j2dc = K^-1 [u, v, 1] with the confidence copied into the last channel, accc = R_cw acc_w, oric = R_cw ori_w,
  *   gravity_out (HOST float[3]) = R_cw [0, -1, 0].

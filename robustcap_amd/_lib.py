@@ -124,6 +124,7 @@ SIGNATURES = {
     "rc_smplify_run_batch": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P, _F, _I32, _F, _P, _P, _P, _P, _P]),
     "rc_lbfgs_minimize": (_I32, [OBJECTIVE_FN, _P, _I64, C.POINTER(C.c_double), C.c_double, _I32, _I32, _I32, C.c_double,
                                  C.c_double, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(C.c_double), _I64]),
+    "rc_lbfgs_device_probe": (_I32, [_P, _I32, _I32, _P, _P, _P, _P, _F, _I32, _P, _P, _P, _I64, C.POINTER(_I32), C.POINTER(_I32), _P]),
     "rc_camera_inputs": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "rc_camera_inputs_rows": (_I32, [_P, _P, _P, _P, _P, _P, _P, _F, _F, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "rc_get_state": (_I32, [_P, C.c_char_p, _P, _P, _P]),

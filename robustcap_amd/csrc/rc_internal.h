@@ -446,6 +446,9 @@ void rc_launch_vec_axpy(const float* x, const float* d, float t, float* out, lon
 void rc_launch_vec_pair(const float* g_new, const float* g_old, const float* d, float t, float* y, float* sv, long long n, hipStream_t s);
 void rc_launch_vec_comb(const VecComb& c, float* out, long long n, hipStream_t s);
 void rc_launch_vec_dots(const VecJob* jobs_dev, int n_jobs, long long n, double* partial, hipStream_t s);
+// synthetic closure of rc_lbfgs_device_probe (rc_smplify.hip): reads aa = x, kp = a, ref3d = b, K[0] = 0.5 / T; fills grad_aa and the [3 T] terms
+void rc_launch_syn_closure(const SmplifyArgs& A, hipStream_t s);
+void rc_launch_syn_closure_rows(const SmplifyArgs* rows_dev, int n_rows, int T_max, hipStream_t s);
 
 // ---- owners of the host code's HIP resources ----------------------------------------------------------------------------------------
 // Move-only; resetting or destroying the owner releases the resource (return code ignored). Never give an owner static storage duration:

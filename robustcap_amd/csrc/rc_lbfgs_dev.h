@@ -15,7 +15,8 @@
 //                                              y_c = g(slot g_new) - g(slot g_old), s_c = t d; out[i] = vec(want[i].a) . vec(want[i].b)
 //     bool flush()                             whatever is still pending at the end
 // (bool: false = the backend failed, minimize returns false at once). rc_smplify_api.cpp holds the two backends of the library;
-// tests/lbfgs_coeff_host.cpp runs the algorithm in double over std::vector against rc::Lbfgs<double>.
+// tests/lbfgs_coeff_host.cpp runs the algorithm in double over std::vector against rc::Lbfgs<double>; tests/lbfgs_device_emu.cpp runs it in
+// float on a backend that restates the library's vector kernels exactly, which the device has to reproduce bit for bit (rc_lbfgs_device_probe).
 #pragma once
 #include "rc_lbfgs.h"
 

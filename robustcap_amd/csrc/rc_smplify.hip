@@ -580,7 +580,7 @@ void rc_launch_smplify_end_rows(const SmplifyRowIO* rows_dev, int n_rows, int T_
 // curvature pairs -- never leave the device; what the host reads back per step is a handful of inner products.
 __global__ void rc_vec_axpy_kernel(const float* x, const float* __restrict__ d, float t, float* out, long long n) {   // out may be x
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = x[i] + t * d[i];
+    if (i < n) out[i] = __fmaf_rn(t, d[i], x[i]);                      // fused, written out: tests/lbfgs_device_emu.cpp restates it
 }
 // curvature pair of an iteration: y = g_new - g_old, s = t d  (torch.optim.LBFGS: y = flat_grad.sub(prev_flat_grad), s = d.mul(t))
 __global__ void rc_vec_pair_kernel(const float* __restrict__ g_new, const float* __restrict__ g_old, const float* __restrict__ d, float t,
@@ -593,7 +593,7 @@ __global__ void rc_vec_comb_kernel(VecComb c, float* __restrict__ out, long long
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float acc = 0.0f;
-    for (int k = 0; k < c.n_vec; ++k) acc += c.c[k] * c.v[k][i];
+    for (int k = 0; k < c.n_vec; ++k) acc = __fmaf_rn(c.c[k], c.v[k][i], acc);
     out[i] = acc;
 }
 // partial[job][block] of job (a, b, op): op 0 sum a_i b_i, 1 max |a_i|, 2 sum |a_i| -- float64 accumulation, one partial per
@@ -608,7 +608,7 @@ __global__ __launch_bounds__(256) void rc_vec_dots_kernel(const VecJob* __restri
         const long long i = lo + q * 256 + threadIdx.x;
         if (i < n) {
             const double a = jb.a[i];
-            if (jb.op == 0) acc += a * (double)jb.b[i];
+            if (jb.op == 0) acc = fma(a, (double)jb.b[i], acc);
             else if (jb.op == 1) acc = fmax(acc, fabs(a));
             else acc += fabs(a);
         }
@@ -632,7 +632,7 @@ __global__ void rc_vec_ops_kernel(const VecOp* __restrict__ ops) {
     const VecOp o = ops[blockIdx.y];
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= o.n) return;
-    if (o.kind == 0) o.out[i] = o.a[i] + o.t * o.b[i];                   // axpy (out may be a)
+    if (o.kind == 0) o.out[i] = __fmaf_rn(o.t, o.b[i], o.a[i]);          // axpy (out may be a)
     else { o.out[i] = o.a[i] - o.b[i]; o.out2[i] = o.c[i] * o.t; }       // curvature pair: y = g_new - g_old, s = t d
 }
 __global__ void rc_vec_comb_rows_kernel(const VecCombRow* __restrict__ rows) {
@@ -641,7 +641,7 @@ __global__ void rc_vec_comb_rows_kernel(const VecCombRow* __restrict__ rows) {
     if (i >= r->n) return;
     const int nv = r->c.n_vec;
     float acc = 0.0f;
-    for (int k = 0; k < nv; ++k) acc += r->c.c[k] * r->c.v[k][i];
+    for (int k = 0; k < nv; ++k) acc = __fmaf_rn(r->c.c[k], r->c.v[k][i], acc);
     r->out[i] = acc;
 }
 __global__ __launch_bounds__(256) void rc_vec_dots_rows_kernel(const VecJobN* __restrict__ jobs, int nb_max, double* __restrict__ partial) {
@@ -655,7 +655,7 @@ __global__ __launch_bounds__(256) void rc_vec_dots_rows_kernel(const VecJobN* __
         const long long i = lo + q * 256 + threadIdx.x;
         if (i < jb.n) {
             const double a = jb.a[i];
-            if (jb.op == 0) acc += a * (double)jb.b[i];
+            if (jb.op == 0) acc = fma(a, (double)jb.b[i], acc);
             else if (jb.op == 1) acc = fmax(acc, fabs(a));
             else acc += fabs(a);
         }
@@ -706,4 +706,71 @@ void rc_launch_vec_dots(const VecJob* jobs_dev, int n_jobs, long long n, double*
     for (int y0 = 0; y0 < n_jobs; y0 += RC_GRID_Y_MAX)
         hipLaunchKernelGGL(rc_vec_dots_kernel, dim3((unsigned)nb, (unsigned)std::min(RC_GRID_Y_MAX, n_jobs - y0)), dim3(256), 0, st, jobs_dev + y0, n, nb,
                            partial + (long long)y0 * nb);
+}
+
+// ================================================================= synthetic closure of rc_lbfgs_device_probe (diagnostic)
+// A closure whose fp32 arithmetic a CPU program restates operation by operation (tests/lbfgs_device_emu.cpp), so that the device
+// L-BFGS -- the vector kernels above and both backends of rc_smplify_api.cpp -- can be pinned bit for bit. Only + - *, no
+// contraction, the order of operations as written. It fills what a smplify evaluation fills: the gradient slot and the [3 T] terms.
+// Of SmplifyArgs it reads aa (the point x[75 T]), kp (a[75 T]), ref3d (b[75 T]), K[0] (0.5 / T, rounded once on the host) and T.
+//   u_i = x_i - b_i,  w_i = x_{i+1} - x_i^2 over the WHOLE vector (the coupling crosses frame and 4,096-block borders)
+//   frame term t  = sum over the frame's 75 elements, in order, of a_i u_i^2 + 0.25 u_i^4
+//   smooth term t = sum over the same elements of 2 w_i^2 (no w at the vector's last element)
+//   IMU term t    = K[0] u_{75 t}^2, which total_loss counts T times
+//   g_i = 2 a_i u_i + u_i^3 - 8 x_i w_i + 4 w_{i-1} + (i at a frame's start: u_i)
+#pragma clang fp contract(off)
+__device__ __forceinline__ void syn_grad_elem(const SmplifyArgs& A, long long i) {
+    const long long n = 75LL * A.T;
+    if (i >= n) return;
+    const float* x = A.aa; const float* a = A.kp; const float* b = A.ref3d;
+    const float xi = x[i], u = xi - b[i];
+    const float uu = u * u;
+    float au = a[i] * u;
+    au = au + au;
+    float g = au + uu * u;
+    if (i + 1 < n) { const float w = x[i + 1] - xi * xi; const float p = xi * w; g = g - 8.0f * p; }
+    if (i > 0) { const float xm = x[i - 1]; const float wm = xi - xm * xm; g = g + 4.0f * wm; }
+    if (i % 75 == 0) g = g + u;
+    A.grad_aa[i] = g;
+}
+__device__ __forceinline__ void syn_terms_frame(const SmplifyArgs& A, int t) {
+    if (t >= A.T) return;
+    const long long n = 75LL * A.T;
+    const float* x = A.aa; const float* a = A.kp; const float* b = A.ref3d;
+    float f = 0.0f, sm = 0.0f;
+    for (int e = 0; e < 75; ++e) {
+        const long long i = 75LL * t + e;
+        const float xi = x[i], u = xi - b[i];
+        const float uu = u * u;
+        const float q = a[i] * uu;
+        float r = uu * uu;
+        r = 0.25f * r;
+        f = f + (q + r);
+        if (i + 1 < n) { const float w = x[i + 1] - xi * xi; const float ww = w * w; sm = sm + (ww + ww); }
+    }
+    const float u0 = x[75LL * t] - b[75LL * t];
+    A.frame_loss[t] = f;
+    A.smooth_loss[t] = sm;
+    A.imu_loss[t] = A.K[0] * (u0 * u0);
+}
+__global__ void rc_syn_closure_grad_kernel(SmplifyArgs A) { syn_grad_elem(A, (long long)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ void rc_syn_closure_terms_kernel(SmplifyArgs A) { syn_terms_frame(A, (int)(blockIdx.x * blockDim.x + threadIdx.x)); }
+__global__ void rc_syn_closure_grad_rows_kernel(const SmplifyArgs* __restrict__ rows) {
+    syn_grad_elem(rows[blockIdx.y], (long long)blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void rc_syn_closure_terms_rows_kernel(const SmplifyArgs* __restrict__ rows) {
+    syn_terms_frame(rows[blockIdx.y], (int)(blockIdx.x * blockDim.x + threadIdx.x));
+}
+void rc_launch_syn_closure(const SmplifyArgs& A, hipStream_t st) {
+    if (A.T <= 0) return;
+    hipLaunchKernelGGL(rc_syn_closure_grad_kernel, dim3((unsigned)((75LL * A.T + 255) / 256)), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(rc_syn_closure_terms_kernel, dim3((unsigned)((A.T + 63) / 64)), dim3(64), 0, st, A);
+}
+void rc_launch_syn_closure_rows(const SmplifyArgs* rows_dev, int n_rows, int T_max, hipStream_t st) {
+    if (n_rows <= 0 || T_max <= 0) return;
+    for (int y0 = 0; y0 < n_rows; y0 += RC_GRID_Y_MAX) {
+        const unsigned ny = (unsigned)std::min(RC_GRID_Y_MAX, n_rows - y0);
+        hipLaunchKernelGGL(rc_syn_closure_grad_rows_kernel, dim3((unsigned)((75LL * T_max + 255) / 256), ny), dim3(256), 0, st, rows_dev + y0);
+        hipLaunchKernelGGL(rc_syn_closure_terms_rows_kernel, dim3((unsigned)((T_max + 63) / 64), ny), dim3(64), 0, st, rows_dev + y0);
+    }
 }

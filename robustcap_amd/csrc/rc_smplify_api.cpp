@@ -5,7 +5,8 @@
 // H2D of the parameter vector (300 B/frame), two kernels (rc_smplify.hip), D2H of the gradient and the per-frame loss
 // terms (312 B/frame) -- so with RC_SMPLIFY_HOST_LBFGS=1, which runs rc_lbfgs.h on host vectors. By default the vectors
 // stay on the device: rc_lbfgs_dev.h holds that optimiser once, and this file gives it a backend for one row at a time
-// (rc_smplify_run) and one for a row of a lock-step batch (rc_smplify_run_batch).
+// (rc_smplify_run) and one for a row of a lock-step batch (rc_smplify_run_batch). rc_lbfgs_device_probe (diagnostic) drives the same two
+// backends through the same helpers (run_single_row, carve_batch, run_batch_rows) on a synthetic closure that tests restate exactly.
 #include "../../include/robustcap_hip.h"
 #include "rc_internal.h"
 #include "rc_lbfgs_dev.h"
@@ -200,6 +201,7 @@ struct SingleRow {
     int P;                                                            // physical pair slots
     hipStream_t st; unsigned long long ign;
     size_t n; int nb;                                                 // 75 T, 4,096-element blocks of a vector
+    bool synthetic = false;                                           // rc_lbfgs_device_probe: the synthetic closure fills the slot and the terms
     hipError_t herr = hipSuccess;
     static constexpr int var0 = kSlots * kSlotJobs;                   // first job of the per-iteration (Gram) part of the table
 
@@ -219,7 +221,8 @@ struct SingleRow {
         const float* xp = s->x.get();
         if (t != 0.0f) { rc_launch_vec_axpy(s->x.get(), s->dir.get(), t, s->xt.get(), (long long)n, st); xp = s->xt.get(); }
         herr = hipEventRecord(s->ev0.get(), st);
-        rc_launch_smplify(make_args(s, ptrs, xp, vec(2 * P + k), ign), body, st);
+        if (synthetic) rc_launch_syn_closure(make_args(s, ptrs, xp, vec(2 * P + k), ign), st);
+        else rc_launch_smplify(make_args(s, ptrs, xp, vec(2 * P + k), ign), body, st);
         if (herr == hipSuccess) herr = hipEventRecord(s->ev1.get(), st);
         dots(k * kSlotJobs, kSlotJobs);
         if (herr == hipSuccess) herr = hipMemcpyAsync(s->h_terms.get(), s->terms.get(), (size_t)ptrs.T * 3 * sizeof(float), hipMemcpyDeviceToHost, st);
@@ -246,6 +249,19 @@ struct SingleRow {
     }
     bool flush() { return true; }
 };
+
+// the optimiser of one row on the state's buffers (rc_smplify_run, and rc_lbfgs_device_probe with backend 0): s->x holds the start
+// and, afterwards, the result
+int run_single_row(rc_ctx* ctx, SmplifyState* s, const BodyConst* body, const RowPtrs& ptrs, bool synthetic, const Dev::Options& opt,
+                   hipStream_t st, Dev::Result& r) {
+    const size_t n = (size_t)ptrs.T * 75;
+    const int P = opt.history_size + 1;
+    if (int rc = reserve_lbfgs(ctx, s, ptrs.T, P)) return rc;
+    SingleRow be{s, body, ptrs, P, st, rc_ctx_ign_mask(ctx), n, (int)((n + 4095) / 4096), synthetic};
+    if (!be.begin() || !Dev::minimize(be, opt, r))
+        return rc_ctx_fail(ctx, RC_ERR_HIP, (std::string("smplify L-BFGS: ") + hipGetErrorString(be.herr)).c_str());
+    return RC_OK;
+}
 
 // ================================================================== lock-step batch of rows (rc_smplify_run_batch, round 4)
 // evaluate.py:86-90 refines the (sequence, camera) rows of an evaluation one after another; they are independent optimisation
@@ -311,6 +327,8 @@ class RowBatch {
     HipEvent ev0, ev1;                                                    // (the arenas belong to the context's SmplifyState)
     double device_ms = 0.0, round_ms = 0.0;                              // closure kernels (events) / wall time inside run_round
     int rounds = 0;
+    int max_round_jobs = 0;                                              // the largest job table a round sent
+    bool synthetic = false;                                              // rc_lbfgs_device_probe: the synthetic closure fills the slots and the terms
     // rendezvous
     std::mutex mu;
     std::condition_variable cv;
@@ -396,7 +414,8 @@ class RowBatch {
         }
         if (n_args > 0) {
             if (herr == hipSuccess) herr = hipEventRecord(ev0.get(), st);
-            rc_launch_smplify_rows(args_d, n_args, T_max, body, st);
+            if (synthetic) rc_launch_syn_closure_rows(args_d, n_args, T_max, st);
+            else rc_launch_smplify_rows(args_d, n_args, T_max, body, st);
             if (herr == hipSuccess) herr = hipEventRecord(ev1.get(), st);
             if (device_totals) rc_launch_smplify_totals(args_d, n_args, total_d, st);
         }
@@ -413,6 +432,7 @@ class RowBatch {
             if (hipEventElapsedTime(&ms, ev0.get(), ev1.get()) == hipSuccess) device_ms += ms;
         }
         ++rounds;
+        max_round_jobs = std::max(max_round_jobs, n_jobs);
         round_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_round).count();
         n_wait = 0;
         ++gen;
@@ -585,11 +605,7 @@ int rc_smplify_run(rc_ctx* ctx, const float* pose, const float* tran, const floa
     const char* hv = std::getenv("RC_SMPLIFY_HOST_LBFGS");            // read per call: tests flip it
     if (!(hv && std::atoi(hv) != 0)) {
         // the optimiser's vectors stay on the device (rc_lbfgs_dev.h on a SingleRow); s->x.get() is updated in place
-        const int P = opt.history_size + 1;
-        if (int rc = reserve_lbfgs(ctx, s, T, P)) return rc;
-        SingleRow be{s, body, ptrs, P, st, rc_ctx_ign_mask(ctx), n, (int)((n + 4095) / 4096)};
-        if (!be.begin() || !Dev::minimize(be, opt, r))
-            return rc_ctx_fail(ctx, RC_ERR_HIP, (std::string("smplify L-BFGS: ") + hipGetErrorString(be.herr)).c_str());
+        if (int rc = run_single_row(ctx, s, body, ptrs, false, opt, st, r)) return rc;
     } else {
         // RC_SMPLIFY_HOST_LBFGS=1: round 2's formulation (vectors on the host, rc_lbfgs.h run as is) for A/B runs
         L::Vec x(s->h_x.get(), s->h_x.get() + n);
@@ -647,31 +663,12 @@ bool smplify_threads_env() {            // RC_SMPLIFY_THREADS=1: round 4's first
     static const bool v = [] { const char* e = std::getenv("RC_SMPLIFY_THREADS"); return e && std::atoi(e) != 0; }();
     return v;
 }
-}  // namespace
 
-int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, const float* const* pose, const float* const* tran,
-                         const float* const* kp, const float* const* imu_ori, const float* K_host, float lr, int32_t max_iter,
-                         float loss_threshold, float* const* pose_out, float* const* tran_out, uint8_t* const* update_host,
-                         rc_smplify_info* infos, void* stream) {
-    if (!ctx) return RC_ERR_INVALID;
-    const auto t_begin = std::chrono::steady_clock::now();
-    const BodyConst* body = rc_ctx_body(ctx);
-    if (!body) return rc_ctx_fail(ctx, RC_ERR_STATE, "rc_smplify_run_batch: body not set");
-    SmplifyState* s0 = nullptr;
-    if (int rc = state_of(ctx, &s0)) return rc;
-    if (!s0->have_prior) return rc_ctx_fail(ctx, RC_ERR_STATE, "rc_smplify_run_batch: prior not set (rc_smplify_set_prior)");
-    if (n_rows < 0 || max_iter < 1 || !(lr >= 0.0f)) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_run_batch: bad arguments");
-    if (n_rows == 0) return RC_OK;
-    if (!T_rows || !pose || !tran || !kp || !imu_ori || !K_host || !pose_out || !tran_out || !update_host || !infos)
-        return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_run_batch: null buffer");
-    for (int r = 0; r < n_rows; ++r)
-        if (T_rows[r] <= 0 || T_rows[r] > 0x7fffffff / 99 || !pose[r] || !tran[r] || !kp[r] || !imu_ori[r] || !pose_out[r] || !tran_out[r] || !update_host[r])
-            return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_run_batch: bad row");
-    hipStream_t st = (hipStream_t)stream;
-    const int P = lbfgs_pairs(max_iter) + 1;
-
-    RowBatch B;
-    B.ctx = ctx; B.body = body; B.prior = s0; B.st = st; B.ign = rc_ctx_ign_mask(ctx);
+// rows and arenas of a batch (rc_smplify_run_batch, and rc_lbfgs_device_probe with backend 1): every row's geometry, then two arenas
+// (device, pinned) carved into the rows' vectors and the round's tables. K_host: [n_rows, 9]; kp: per row, what RowBuf::kp lends the closure.
+struct BatchCarve { size_t r0_begin = 0, r1_begin = 0, r_bytes = 0, p_r0 = 0, p_r1 = 0, o_io = 0, p_io = 0; };
+int carve_batch(rc_ctx* ctx, SmplifyState* s0, RowBatch& B, int n_rows, const int64_t* T_rows, const float* K_host, const float* const* kp,
+                int P, BatchCarve& c) {
     B.row.resize((size_t)n_rows);
     B.pending.assign((size_t)n_rows, nullptr);
     B.max_jobs = 6 * P + 8;
@@ -700,13 +697,13 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
         o.am = dtake(T * 4); o.pl = dtake(T * 4); o.pg = dtake(T * 69 * 4); o.fk = dtake(T * 432 * 4);
     }
     // the residuals of all rows in one span each (one read-back per span; the pinned copies mirror the offsets)
-    const size_t r0_begin = dev_need;
+    const size_t r0_begin = c.r0_begin = dev_need;
     for (int r = 0; r < n_rows; ++r) off[r].r0 = dtake((size_t)B.row[r].T * 33 * 4);
-    const size_t r_bytes = dev_need - r0_begin, r1_begin = dev_need;
+    const size_t r_bytes = c.r_bytes = dev_need - r0_begin, r1_begin = c.r1_begin = dev_need;
     for (int r = 0; r < n_rows; ++r) off[r].r1 = dtake((size_t)B.row[r].T * 33 * 4);
-    const size_t p_r0 = ptake(r_bytes), p_r1 = ptake(r_bytes);
+    const size_t p_r0 = c.p_r0 = ptake(r_bytes), p_r1 = c.p_r1 = ptake(r_bytes);
     const size_t nr = (size_t)n_rows;
-    const size_t o_io = dtake(nr * sizeof(SmplifyRowIO)), p_io = ptake(nr * sizeof(SmplifyRowIO));
+    c.o_io = dtake(nr * sizeof(SmplifyRowIO)); c.p_io = ptake(nr * sizeof(SmplifyRowIO));
     const size_t o_args = dtake(nr * sizeof(SmplifyArgs)), o_ops = dtake(3 * nr * sizeof(VecOp)), o_comb = dtake(nr * sizeof(VecCombRow));
     const size_t o_jobs = dtake(nr * B.max_jobs * sizeof(VecJobN)), o_part = dtake(nr * B.max_jobs * (size_t)B.nb_max * sizeof(double));
     const size_t o_terms = dtake(nr * 3 * (size_t)B.T_max * 4);
@@ -738,42 +735,13 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
         b.terms = B.terms_d + (size_t)r * 3 * B.T_max;
         b.terms_h = B.terms_h + (size_t)r * 3 * B.T_max;
     }
-    // ---- set-up of every row in ONE launch: residual of the initial pose (the pre-check, run.py:24-29, reads its first frame),
-    // optimiser parameters, IMU orientations as axis-angle, joints and preserved landmarks (temporal_smplify.py:111-139)
-    SmplifyRowIO* io_h = (SmplifyRowIO*)(B.pin + p_io);
-    SmplifyRowIO* io_d = (SmplifyRowIO*)(B.dev + o_io);
-    for (int r = 0; r < n_rows; ++r) {
-        RowBuf& b = B.row[r];
-        std::memset(&infos[r], 0, sizeof(infos[r]));
-        std::memset(update_host[r], 0, (size_t)b.T);
-        SmplifyRowIO& io = io_h[r];
-        io.pose = pose[r]; io.tran = tran[r]; io.kp = kp[r]; io.imu_ori = imu_ori[r];
-        io.x = b.x; io.imu_aa = b.imu_aa; io.joint = b.joint; io.ref3d = b.ref3d; io.res0 = b.res0; io.res1 = b.res1;
-        io.pose_out = pose_out[r]; io.tran_out = tran_out[r];
-        for (int e = 0; e < 9; ++e) io.K[e] = b.K[e];
-        io.T = (int)b.T; io.live = 0;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(io_d, io_h, nr * sizeof(SmplifyRowIO), hipMemcpyHostToDevice, st));
-    rc_launch_smplify_begin_rows(io_d, n_rows, B.T_max, body, 100.0f, B.ign, st);
-    HIP_TRY(ctx, hipMemcpyAsync(B.pin + p_r0, B.dev + r0_begin, r_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    std::vector<int> live;
-    for (int r = 0; r < n_rows; ++r) {
-        RowBuf& b = B.row[r];
-        if (frame_mean(b.h_res0) > loss_threshold) {
-            if (pose_out[r] != pose[r]) HIP_TRY(ctx, hipMemcpyAsync(pose_out[r], pose[r], (size_t)b.T * 216 * sizeof(float), hipMemcpyDeviceToDevice, st));
-            if (tran_out[r] != tran[r]) HIP_TRY(ctx, hipMemcpyAsync(tran_out[r], tran[r], (size_t)b.T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-            infos[r].status = 0;
-            continue;
-        }
-        live.push_back(r);
-        io_h[r].live = 1;
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    HIP_TRY(ctx, hipGetLastError());
-    const auto t_opt = std::chrono::steady_clock::now();
-    // ---- the optimisers: a fiber (or, RC_SMPLIFY_THREADS=1, a host thread) per row, the device work in lock-step rounds
-    std::vector<Dev::Result> res((size_t)n_rows);
+    return RC_OK;
+}
+
+// the optimisers of the live rows: a fiber (or, RC_SMPLIFY_THREADS=1, a host thread) per row, the device work in lock-step rounds
+int run_batch_rows(rc_ctx* ctx, RowBatch& B, const std::vector<int>& live, float lr, int max_iter, std::vector<Dev::Result>& res) {
+    const int n_rows = (int)B.row.size();
+    res.assign((size_t)n_rows, Dev::Result());
     std::vector<char> ok((size_t)n_rows, 0);
     B.n_live = (int)live.size();
     if (live.size() == 1) {
@@ -819,6 +787,73 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
     }
     if (B.herr != hipSuccess) return rc_ctx_fail(ctx, RC_ERR_HIP, (std::string("smplify batch: ") + hipGetErrorString(B.herr)).c_str());
     for (int r : live) if (!ok[r]) return rc_ctx_fail(ctx, RC_ERR_HIP, "smplify batch: a row's optimiser did not finish");
+    return RC_OK;
+}
+}  // namespace
+
+int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, const float* const* pose, const float* const* tran,
+                         const float* const* kp, const float* const* imu_ori, const float* K_host, float lr, int32_t max_iter,
+                         float loss_threshold, float* const* pose_out, float* const* tran_out, uint8_t* const* update_host,
+                         rc_smplify_info* infos, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    const auto t_begin = std::chrono::steady_clock::now();
+    const BodyConst* body = rc_ctx_body(ctx);
+    if (!body) return rc_ctx_fail(ctx, RC_ERR_STATE, "rc_smplify_run_batch: body not set");
+    SmplifyState* s0 = nullptr;
+    if (int rc = state_of(ctx, &s0)) return rc;
+    if (!s0->have_prior) return rc_ctx_fail(ctx, RC_ERR_STATE, "rc_smplify_run_batch: prior not set (rc_smplify_set_prior)");
+    if (n_rows < 0 || max_iter < 1 || !(lr >= 0.0f)) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_run_batch: bad arguments");
+    if (n_rows == 0) return RC_OK;
+    if (!T_rows || !pose || !tran || !kp || !imu_ori || !K_host || !pose_out || !tran_out || !update_host || !infos)
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_run_batch: null buffer");
+    for (int r = 0; r < n_rows; ++r)
+        if (T_rows[r] <= 0 || T_rows[r] > 0x7fffffff / 99 || !pose[r] || !tran[r] || !kp[r] || !imu_ori[r] || !pose_out[r] || !tran_out[r] || !update_host[r])
+            return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_run_batch: bad row");
+    hipStream_t st = (hipStream_t)stream;
+    const int P = lbfgs_pairs(max_iter) + 1;
+
+    RowBatch B;
+    B.ctx = ctx; B.body = body; B.prior = s0; B.st = st; B.ign = rc_ctx_ign_mask(ctx);
+    BatchCarve cv;
+    if (int rc = carve_batch(ctx, s0, B, n_rows, T_rows, K_host, kp, P, cv)) return rc;
+    const size_t nr = (size_t)n_rows, r0_begin = cv.r0_begin, r1_begin = cv.r1_begin, r_bytes = cv.r_bytes, p_r0 = cv.p_r0, p_r1 = cv.p_r1,
+                 o_io = cv.o_io, p_io = cv.p_io;
+    // ---- set-up of every row in ONE launch: residual of the initial pose (the pre-check, run.py:24-29, reads its first frame),
+    // optimiser parameters, IMU orientations as axis-angle, joints and preserved landmarks (temporal_smplify.py:111-139)
+    SmplifyRowIO* io_h = (SmplifyRowIO*)(B.pin + p_io);
+    SmplifyRowIO* io_d = (SmplifyRowIO*)(B.dev + o_io);
+    for (int r = 0; r < n_rows; ++r) {
+        RowBuf& b = B.row[r];
+        std::memset(&infos[r], 0, sizeof(infos[r]));
+        std::memset(update_host[r], 0, (size_t)b.T);
+        SmplifyRowIO& io = io_h[r];
+        io.pose = pose[r]; io.tran = tran[r]; io.kp = kp[r]; io.imu_ori = imu_ori[r];
+        io.x = b.x; io.imu_aa = b.imu_aa; io.joint = b.joint; io.ref3d = b.ref3d; io.res0 = b.res0; io.res1 = b.res1;
+        io.pose_out = pose_out[r]; io.tran_out = tran_out[r];
+        for (int e = 0; e < 9; ++e) io.K[e] = b.K[e];
+        io.T = (int)b.T; io.live = 0;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(io_d, io_h, nr * sizeof(SmplifyRowIO), hipMemcpyHostToDevice, st));
+    rc_launch_smplify_begin_rows(io_d, n_rows, B.T_max, body, 100.0f, B.ign, st);
+    HIP_TRY(ctx, hipMemcpyAsync(B.pin + p_r0, B.dev + r0_begin, r_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::vector<int> live;
+    for (int r = 0; r < n_rows; ++r) {
+        RowBuf& b = B.row[r];
+        if (frame_mean(b.h_res0) > loss_threshold) {
+            if (pose_out[r] != pose[r]) HIP_TRY(ctx, hipMemcpyAsync(pose_out[r], pose[r], (size_t)b.T * 216 * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if (tran_out[r] != tran[r]) HIP_TRY(ctx, hipMemcpyAsync(tran_out[r], tran[r], (size_t)b.T * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+            infos[r].status = 0;
+            continue;
+        }
+        live.push_back(r);
+        io_h[r].live = 1;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipGetLastError());
+    const auto t_opt = std::chrono::steady_clock::now();
+    std::vector<Dev::Result> res;
+    if (int rc = run_batch_rows(ctx, B, live, lr, max_iter, res)) return rc;
     const auto t_res = std::chrono::steady_clock::now();
     // ---- results in ONE launch: rotations, translation, residual after; then the per-frame update mask (run.py:31-34)
     if (!live.empty()) {
@@ -843,6 +878,66 @@ int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, con
         for (int64_t t = 0; t < b.T; ++t) update_host[r][t] = frame_mean(b.h_res1 + t * 33) < frame_mean(b.h_res0 + t * 33) ? 1 : 0;
         set_info(&infos[r], res[r]);
         infos[r].reserved = B.rounds;
+    }
+    return RC_OK;
+}
+
+int rc_lbfgs_device_probe(rc_ctx* ctx, int32_t backend, int32_t n_rows, const int64_t* T_rows, const float* const* x0, const float* const* a,
+                          const float* const* b, float lr, int32_t max_iter, float* const* x_out, rc_smplify_info* infos, float* losses,
+                          int64_t cap, int32_t* max_jobs, int32_t* rounds, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    SmplifyState* s = nullptr;
+    if (int rc = state_of(ctx, &s)) return rc;
+    if ((backend != 0 && backend != 1) || n_rows < 0 || max_iter < 1 || !(lr >= 0.0f) || cap < 0)
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_lbfgs_device_probe: bad arguments");
+    if (max_jobs) *max_jobs = 0;
+    if (rounds) *rounds = 0;
+    if (n_rows == 0) return RC_OK;
+    if (!T_rows || !x0 || !a || !b || !x_out || !infos || (cap > 0 && !losses))
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_lbfgs_device_probe: null buffer");
+    for (int r = 0; r < n_rows; ++r)
+        if (T_rows[r] <= 0 || T_rows[r] > 0x7fffffff / 99 || !x0[r] || !a[r] || !b[r] || !x_out[r])
+            return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_lbfgs_device_probe: bad row");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<float> K((size_t)n_rows * 9, 0.0f);                   // K[0] = 0.5 / T: the synthetic closure's IMU weight
+    for (int r = 0; r < n_rows; ++r) K[(size_t)9 * r] = 0.5f / (float)T_rows[r];
+    std::vector<Dev::Result> res((size_t)n_rows);
+    if (backend == 0) {
+        const Dev::Options opt = lbfgs_options(lr, max_iter);
+        for (int r = 0; r < n_rows; ++r) {
+            const int64_t T = T_rows[r];
+            if (int rc = reserve(ctx, s, T)) return rc;
+            HIP_TRY(ctx, hipMemcpyAsync(s->x.get(), x0[r], (size_t)T * 75 * sizeof(float), hipMemcpyDeviceToDevice, st));
+            const RowPtrs ptrs = ptrs_of(s, a[r], b[r], s->imu_aa.get(), K.data() + (size_t)9 * r, T);
+            if (int rc = run_single_row(ctx, s, nullptr, ptrs, true, opt, st, res[r])) return rc;
+            HIP_TRY(ctx, hipMemcpyAsync(x_out[r], s->x.get(), (size_t)T * 75 * sizeof(float), hipMemcpyDeviceToDevice, st));
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+        }
+    } else {
+        RowBatch B;
+        B.ctx = ctx; B.body = nullptr; B.prior = s; B.st = st; B.ign = rc_ctx_ign_mask(ctx); B.synthetic = true;
+        BatchCarve cv;
+        if (int rc = carve_batch(ctx, s, B, n_rows, T_rows, K.data(), a, lbfgs_pairs(max_iter) + 1, cv)) return rc;
+        std::vector<int> live;
+        for (int r = 0; r < n_rows; ++r) {
+            RowBuf& row = B.row[r];
+            row.ref3d = const_cast<float*>(b[r]);                     // (only read)
+            HIP_TRY(ctx, hipMemcpyAsync(row.x, x0[r], row.n * sizeof(float), hipMemcpyDeviceToDevice, st));
+            live.push_back(r);
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (int rc = run_batch_rows(ctx, B, live, lr, max_iter, res)) return rc;
+        for (int r = 0; r < n_rows; ++r)
+            HIP_TRY(ctx, hipMemcpyAsync(x_out[r], B.row[r].x, B.row[r].n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (max_jobs) *max_jobs = B.max_round_jobs;
+        if (rounds) *rounds = B.rounds;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    for (int r = 0; r < n_rows; ++r) {
+        std::memset(&infos[r], 0, sizeof(infos[r]));
+        set_info(&infos[r], res[r]);
+        for (int64_t i = 0; i < cap; ++i) losses[(size_t)r * cap + i] = i < (int64_t)res[r].losses.size() ? res[r].losses[(size_t)i] : 0.0f;
     }
     return RC_OK;
 }

@@ -16,6 +16,9 @@ def test_header_declares_the_documented_surface():
                  "rc_set_gravity", "rc_reset", "rc_step", "rc_sequence", "rc_r6d_to_rotmat", "rc_ik_r", "rc_fk_bone",
                  "rc_body_fk", "rc_lstm_step", "rc_reproj_residual", "rc_get_state", "rc_get_trace"):
         assert name in DECLARED
+    assert "rc_lbfgs_minimize" in DECLARED and "rc_lbfgs_device_probe" in DECLARED        # the optimiser alone: host, and device (diagnostic)
+    probe = HEADER[:HEADER.index("int rc_lbfgs_device_probe")].rsplit("/*", 1)[1]
+    assert "DIAGNOSTIC" in probe and "rc_smplify_run" in probe and "rc_smplify_run_batch" in probe
     # every entry point cites the reference interface it replaces
     assert HEADER.count("net/sig_mp.py") >= 8 and "articulate/model.py" in HEADER and "net/smplify" in HEADER
 
@@ -86,6 +89,8 @@ int main(void) {
     int32_t it = 0, ev = 0;
     if (rc_lbfgs_minimize(quad, NULL, 4, x, 1.0, 20, 25, 100, 1e-7, 1e-9, &it, &ev, losses, 32) != 0) return 4;
     for (int i = 0; i < 4; ++i) if (x[i] < i + 1 - 1e-6 || x[i] > i + 1 + 1e-6) return 5;
+    /* the diagnostic probe of the device optimiser refuses a missing context before it touches the device */
+    if (rc_lbfgs_device_probe(NULL, 0, 0, NULL, NULL, NULL, NULL, 1.0f, 20, NULL, NULL, NULL, 0, NULL, NULL, NULL) != -1) return 6;
     printf("ok %d %d\n", it, ev);
     return 0;
 }
