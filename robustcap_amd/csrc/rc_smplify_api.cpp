@@ -13,9 +13,6 @@
 
 #include <algorithm>
 #include <chrono>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
 #include <cstdio>
 #include <memory>
 #include <sys/mman.h>
@@ -287,6 +284,8 @@ struct RowBuf {                       // device vectors of one row (carved from 
     const float* kp = nullptr;
 };
 
+RowPtrs ptrs_of(const RowBuf& b) { return RowPtrs{b.kp, b.ref3d, b.imu_aa, b.mj, b.proj, b.terms, b.prior_ll, b.prior_g, b.fk, b.argmin, b.K, b.T}; }
+
 struct RowReq {
     int kind = 0;                     // 1: closure evaluation, 2: curvature pair + inner products, 3: pending update of x only
     bool has_comb = false;            // dir = combination, in front of everything else (start of a line search)
@@ -324,50 +323,32 @@ class RowBatch {
     float *terms_d = nullptr, *terms_h = nullptr;
     double *total_d = nullptr, *total_h = nullptr;                       // total loss per closure-table entry of the round
     bool device_totals = true;                                           // RC_SMPLIFY_DEVICE_TOTALS=0: read the per-frame terms back and add them on the host (A/B)
-    HipEvent ev0, ev1;                                                    // (the arenas belong to the context's SmplifyState)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;                              // (the events and the arenas belong to the context's SmplifyState)
     double device_ms = 0.0, round_ms = 0.0;                              // closure kernels (events) / wall time inside run_round
     int rounds = 0;
     int max_round_jobs = 0;                                              // the largest job table a round sent
     bool synthetic = false;                                              // rc_lbfgs_device_probe: the synthetic closure fills the slots and the terms
-    // rendezvous
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<RowReq*> pending;
-    int n_live = 0, n_wait = 0;
-    unsigned long long gen = 0;
+    std::vector<RowReq*> pending;                                        // the live rows' next requests
     hipError_t herr = hipSuccess;
-    // fibers (the default): every row's optimiser runs on a stack of its own inside the CALLER's thread; submit() switches back to the
-    // scheduler in rc_smplify_run_batch, which runs the round when every live row has asked and resumes them one after another. No
-    // thread is created, woken or left spinning (72 condition-variable wake-ups cost 0.27 ms per round, 8.7 of config 3's 40 ms).
+    // Several live rows run as fibers: every row's optimiser on a stack of its own inside the CALLER's thread; submit() switches back to
+    // the scheduler in run_batch_rows, which runs the round when every live row has asked and resumes them one after another. No thread
+    // is created, woken or left spinning (72 condition-variable wake-ups cost 0.27 ms per round, 8.7 of config 3's 40 ms). One live row
+    // runs inline: its request is the round.
     bool fibers = false;
     ucontext_t sched{};
     std::vector<ucontext_t> fctx;
 
     const double* part_of(const RowReq& q, int j) const { return part_h + (size_t)(q.job0 + j) * nb_max; }   // partial sums of the request's job j
-    // hand in the row's request and sleep until the round it belongs to has run; false = a HIP call failed
+    // hand in the row's request and come back when the round it belongs to has run; false = a HIP call failed
     bool submit(int r, RowReq* q) {
-        if (fibers) {
-            pending[r] = q;
-            ++n_wait;
-            swapcontext(&fctx[r], &sched);                                 // back when the round has run
-            return herr == hipSuccess;
-        }
-        std::unique_lock<std::mutex> lk(mu);
         pending[r] = q;
-        ++n_wait;
-        if (n_wait == n_live) run_round();
-        else { const unsigned long long g = gen; cv.wait(lk, [&] { return gen != g; }); }
+        if (fibers) swapcontext(&fctx[r], &sched);
+        else run_round();
         return herr == hipSuccess;
     }
-    void leave(int r) {
-        if (fibers) { pending[r] = nullptr; --n_live; return; }
-        std::unique_lock<std::mutex> lk(mu);
-        pending[r] = nullptr;
-        --n_live;
-        if (n_live > 0 && n_wait == n_live) run_round();
-    }
+    void leave(int r) { pending[r] = nullptr; }
 
-    void run_round() {                                                   // (mu held, or fibers: every live row is waiting)
+    void run_round() {                                                   // (every live row is waiting)
         const auto t_round = std::chrono::steady_clock::now();
         int n_args = 0, n_ops = 0, n_comb = 0, n_jobs = 0;
         for (size_t r = 0; r < row.size(); ++r) {
@@ -379,9 +360,8 @@ class RowBatch {
             if (q->kind == 1) {
                 const float* xp = b.x;
                 if (q->t != 0.0f) { ops_h[n_ops++] = VecOp{b.x, b.dir, nullptr, b.xt, nullptr, q->t, 0, (long long)b.n}; xp = b.xt; }
-                const RowPtrs ptrs{b.kp, b.ref3d, b.imu_aa, b.mj, b.proj, b.terms, b.prior_ll, b.prior_g, b.fk, b.argmin, b.K, b.T};
                 q->arg0 = n_args;
-                args_h[n_args++] = make_args(prior, ptrs, xp, b.gslot + (size_t)q->k * b.n, ign);
+                args_h[n_args++] = make_args(prior, ptrs_of(b), xp, b.gslot + (size_t)q->k * b.n, ign);
             } else if (q->kind == 2) {
                 ops_h[n_ops++] = VecOp{q->g_new, q->g_old, b.dir, q->yv, q->sv, q->pair_t, 1, (long long)b.n};
             }
@@ -413,10 +393,10 @@ class RowBatch {
             } else rc_launch_vec_ops(ops_d, n_ops, (long long)n_max, st);
         }
         if (n_args > 0) {
-            if (herr == hipSuccess) herr = hipEventRecord(ev0.get(), st);
+            if (herr == hipSuccess) herr = hipEventRecord(ev0, st);
             if (synthetic) rc_launch_syn_closure_rows(args_d, n_args, T_max, st);
             else rc_launch_smplify_rows(args_d, n_args, T_max, body, st);
-            if (herr == hipSuccess) herr = hipEventRecord(ev1.get(), st);
+            if (herr == hipSuccess) herr = hipEventRecord(ev1, st);
             if (device_totals) rc_launch_smplify_totals(args_d, n_args, total_d, st);
         }
         rc_launch_vec_dots_rows(jobs_d, n_jobs, nb_max, part_d, st);
@@ -429,14 +409,11 @@ class RowBatch {
         if (herr == hipSuccess) herr = hipGetLastError();
         if (n_args > 0 && herr == hipSuccess) {
             float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, ev0.get(), ev1.get()) == hipSuccess) device_ms += ms;
+            if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) device_ms += ms;
         }
         ++rounds;
         max_round_jobs = std::max(max_round_jobs, n_jobs);
         round_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_round).count();
-        n_wait = 0;
-        ++gen;
-        cv.notify_all();
     }
 };
 
@@ -526,27 +503,6 @@ int rc_smplify_set_ref3d(rc_ctx* ctx, const float* ref3d) {
     SmplifyState* s = nullptr;
     if (int rc = state_of(ctx, &s)) return rc;
     s->ref3d_override = ref3d;
-    return RC_OK;
-}
-
-int rc_smplify_loss_grad(rc_ctx* ctx, const float* x, const float* kp, const float* ref3d, const float* imu_aa, const float* K,
-                         int64_t T, double* loss, float* grad, void* stream) {
-    if (!ctx) return RC_ERR_INVALID;
-    const BodyConst* body = rc_ctx_body(ctx);
-    if (!body) return rc_ctx_fail(ctx, RC_ERR_STATE, "rc_smplify_loss_grad: body not set");
-    SmplifyState* s = nullptr;
-    if (int rc = state_of(ctx, &s)) return rc;
-    if (!s->have_prior) return rc_ctx_fail(ctx, RC_ERR_STATE, "rc_smplify_loss_grad: prior not set (rc_smplify_set_prior)");
-    if (T < 0 || T > 0x7fffffff / 99 || !loss) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_loss_grad: bad arguments");
-    if (T == 0) { *loss = 0.0; return RC_OK; }
-    if (!x || !kp || !ref3d || !imu_aa || !K || !grad) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_loss_grad: null buffer");
-    if (int rc = reserve(ctx, s, T)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    rc_launch_smplify(make_args(s, ptrs_of(s, kp, ref3d, imu_aa, K, T), x, grad, rc_ctx_ign_mask(ctx)), body, st);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(s->h_terms.get(), s->terms.get(), (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    *loss = total_loss(s->h_terms.get(), T);
     return RC_OK;
 }
 
@@ -659,12 +615,9 @@ void fiber_main(unsigned lo, unsigned hi) {
     FiberArg* a = reinterpret_cast<FiberArg*>(((uintptr_t)hi << 32) | (uintptr_t)lo);
     lbfgs_batch_row(*a->B, a->r, a->lr, a->max_iter, *a->res, *a->ok);
 }
-bool smplify_threads_env() {            // RC_SMPLIFY_THREADS=1: round 4's first scheme, a host thread per row (A/B runs)
-    static const bool v = [] { const char* e = std::getenv("RC_SMPLIFY_THREADS"); return e && std::atoi(e) != 0; }();
-    return v;
-}
 
-// rows and arenas of a batch (rc_smplify_run_batch, and rc_lbfgs_device_probe with backend 1): every row's geometry, then two arenas
+// rows and arenas of a batch (rc_smplify_run_batch, rc_lbfgs_device_probe with backend 1, and one row without pairs for
+// rc_smplify_loss_grad): every row's geometry, then two arenas
 // (device, pinned) carved into the rows' vectors and the round's tables. K_host: [n_rows, 9]; kp: per row, what RowBuf::kp lends the closure.
 struct BatchCarve { size_t r0_begin = 0, r1_begin = 0, r_bytes = 0, p_r0 = 0, p_r1 = 0, o_io = 0, p_io = 0; };
 int carve_batch(rc_ctx* ctx, SmplifyState* s0, RowBatch& B, int n_rows, const int64_t* T_rows, const float* K_host, const float* const* kp,
@@ -715,8 +668,7 @@ int carve_batch(rc_ctx* ctx, SmplifyState* s0, RowBatch& B, int n_rows, const in
     HIP_TRY(ctx, rc_grow(s0->batch_pin_cap, pin_need, pin_need, s0->batch_pin, pin_need));
     B.dev = s0->batch_dev.get(); B.pin = s0->batch_pin.get();
     B.dev_bytes = dev_need; B.pin_bytes = pin_need;
-    HIP_TRY(ctx, hipEventCreate(rc_out(B.ev0)));
-    HIP_TRY(ctx, hipEventCreate(rc_out(B.ev1)));
+    B.ev0 = s0->ev0.get(); B.ev1 = s0->ev1.get();
     B.args_d = (SmplifyArgs*)(B.dev + o_args); B.ops_d = (VecOp*)(B.dev + o_ops); B.comb_d = (VecCombRow*)(B.dev + o_comb);
     B.jobs_d = (VecJobN*)(B.dev + o_jobs); B.part_d = (double*)(B.dev + o_part); B.terms_d = (float*)(B.dev + o_terms);
     B.args_h = (SmplifyArgs*)(B.pin + p_args); B.ops_h = (VecOp*)(B.pin + p_ops); B.comb_h = (VecCombRow*)(B.pin + p_comb);
@@ -738,15 +690,14 @@ int carve_batch(rc_ctx* ctx, SmplifyState* s0, RowBatch& B, int n_rows, const in
     return RC_OK;
 }
 
-// the optimisers of the live rows: a fiber (or, RC_SMPLIFY_THREADS=1, a host thread) per row, the device work in lock-step rounds
+// the optimisers of the live rows: one row inline, several as a fiber each, the device work in lock-step rounds
 int run_batch_rows(rc_ctx* ctx, RowBatch& B, const std::vector<int>& live, float lr, int max_iter, std::vector<Dev::Result>& res) {
     const int n_rows = (int)B.row.size();
     res.assign((size_t)n_rows, Dev::Result());
     std::vector<char> ok((size_t)n_rows, 0);
-    B.n_live = (int)live.size();
     if (live.size() == 1) {
         lbfgs_batch_row(B, live[0], lr, max_iter, res[live[0]], ok[live[0]]);
-    } else if (!live.empty() && !smplify_threads_env()) {
+    } else if (!live.empty()) {
         B.fibers = true;
         B.fctx.resize((size_t)n_rows);
         // a stack per row with an inaccessible page below it (round-4 advice: in one plain array an overflow ran silently into the
@@ -779,17 +730,39 @@ int run_batch_rows(rc_ctx* ctx, RowBatch& B, const std::vector<int>& live, float
             for (int r : live) if (B.pending[r]) run.push_back(r);
             if (!run.empty()) B.run_round();                              // every live row is waiting
         }
-    } else if (!live.empty()) {
-        std::vector<std::thread> th;
-        th.reserve(live.size());
-        for (int r : live) th.emplace_back([&, r] { lbfgs_batch_row(B, r, lr, max_iter, res[r], ok[r]); });
-        for (std::thread& t : th) t.join();
     }
     if (B.herr != hipSuccess) return rc_ctx_fail(ctx, RC_ERR_HIP, (std::string("smplify batch: ") + hipGetErrorString(B.herr)).c_str());
     for (int r : live) if (!ok[r]) return rc_ctx_fail(ctx, RC_ERR_HIP, "smplify batch: a row's optimiser did not finish");
     return RC_OK;
 }
 }  // namespace
+
+int rc_smplify_loss_grad(rc_ctx* ctx, const float* x, const float* kp, const float* ref3d, const float* imu_aa, const float* K,
+                         int64_t T, double* loss, float* grad, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    const BodyConst* body = rc_ctx_body(ctx);
+    if (!body) return rc_ctx_fail(ctx, RC_ERR_STATE, "rc_smplify_loss_grad: body not set");
+    SmplifyState* s = nullptr;
+    if (int rc = state_of(ctx, &s)) return rc;
+    if (!s->have_prior) return rc_ctx_fail(ctx, RC_ERR_STATE, "rc_smplify_loss_grad: prior not set (rc_smplify_set_prior)");
+    if (T < 0 || T > 0x7fffffff / 99 || !loss) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_loss_grad: bad arguments");
+    if (T == 0) { *loss = 0.0; return RC_OK; }
+    if (!x || !kp || !ref3d || !imu_aa || !K || !grad) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_smplify_loss_grad: null buffer");
+    hipStream_t st = (hipStream_t)stream;
+    RowBatch B;                                                       // a batch of one row without curvature pairs: the closure's work space
+    BatchCarve cv;
+    if (int rc = carve_batch(ctx, s, B, 1, &T, K, &kp, 0, cv)) return rc;
+    RowBuf& b = B.row[0];
+    b.ref3d = const_cast<float*>(ref3d); b.imu_aa = const_cast<float*>(imu_aa);   // (only read)
+    B.args_h[0] = make_args(s, ptrs_of(b), x, grad, rc_ctx_ign_mask(ctx));
+    HIP_TRY(ctx, hipMemcpyAsync(B.args_d, B.args_h, sizeof(SmplifyArgs), hipMemcpyHostToDevice, st));
+    rc_launch_smplify_rows(B.args_d, 1, (int)T, body, st);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(B.terms_h, B.terms_d, (size_t)T * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    *loss = total_loss(b.terms_h, T);
+    return RC_OK;
+}
 
 int rc_smplify_run_batch(rc_ctx* ctx, int32_t n_rows, const int64_t* T_rows, const float* const* pose, const float* const* tran,
                          const float* const* kp, const float* const* imu_ori, const float* K_host, float lr, int32_t max_iter,

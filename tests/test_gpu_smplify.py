@@ -269,38 +269,40 @@ def test_batch_equals_single_at_the_block_edge_with_a_recycling_history(runner, 
             assert torch.equal(p, out[r][0]) and torch.equal(tr, out[r][1]), (totals, r)
 
 
-_SCHED_SCRIPT = r"""
-import hashlib, json, os, sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tools"))
-import torch
-import smplify_bench as sb
-from robustcap_amd import synth
-from robustcap_amd.smplify import TemporalSMPLify
-body = synth.make_body(1)
-runner = TemporalSMPLify(body=body, gmm=synth.make_gmm(3))
-rows = [sb.make_case(runner, body, T, seed=seed) for seed, T in ((11, 64), (23, 100), (31, 37))]
-out = runner.run_batch(rows, lr=0.001)
-h = hashlib.sha256()
-for p, tr, upd in out:
-    h.update(p.cpu().numpy().tobytes()); h.update(tr.cpu().numpy().tobytes()); h.update(upd.numpy().tobytes())
-print(json.dumps({"sha": h.hexdigest(), "info": [[i["n_iter"], i["n_eval"], i["final_loss"]] for i in runner.last_batch_info]}))
-"""
+def test_ref3d_override_is_used_once(runner, synth_assets, monkeypatch):
+    """rc_smplify_set_ref3d lends the NEXT rc_smplify_run its preserved 3D landmarks and nothing after it. T = 2 (the smallest
+    length with temporal terms), RC_LBFGS_HISTORY=2, max_iter 12. The landmarks the run would form itself give the run's own bits;
+    landmarks 5 cm off give another final loss; the run after that is the plain run again. The 3D term (losses.py:31-33) compares
+    landmarks RELATIVE to landmark 0, so all 33 moved by the same 5 cm are the same landmarks to it (measured: the same final loss,
+    bit for bit); here every landmark but the first moves."""
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tools"))
+    import smplify_bench as sb
+    from robustcap_amd import _lib
+    case = sb.make_case(runner, synth_assets["body"], 2)
+    own = runner.model.forward_kinematics(case[0], tran=case[1], calc_mesh=True)[2].contiguous()
+    monkeypatch.setenv("RC_LBFGS_HISTORY", "2")
 
+    def run(ref3d=None):
+        if ref3d is not None:
+            torch.cuda.synchronize()
+            _lib.check(runner._ctx, runner._lib.rc_smplify_set_ref3d(runner._ctx, _lib.ptr(ref3d)), "rc_smplify_set_ref3d")
+        p, tr, upd = runner.run(*case, lr=0.001, max_iter=12)
+        return p.cpu(), tr.cpu(), upd.clone(), {k: runner.last_info[k] for k in ("status", "n_iter", "n_eval", "first_loss", "final_loss")}
 
-def test_rows_as_fibers_equal_rows_as_threads():
-    """rc_smplify_run_batch drives every row's optimiser as a fiber of the caller's thread (makecontext / swapcontext); RC_SMPLIFY_THREADS=1
-    selects a host thread per row instead. Same requests in the same rounds: outputs and optimiser records bitwise equal."""
-    import json
-    import subprocess
-    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-    res = []
-    for threads in ("0", "1"):
-        env = dict(os.environ, RC_SMPLIFY_THREADS=threads)
-        r = subprocess.run([sys.executable, "-c", _SCHED_SCRIPT, root], capture_output=True, text=True, env=env, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        res.append(json.loads(r.stdout.strip().splitlines()[-1]))
-    assert res[0] == res[1]
-    assert all(i[1] >= 20 for i in res[0]["info"])
+    def same(x, y):
+        return torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]) and torch.equal(x[2], y[2]) and x[3] == y[3]
+
+    a = run()
+    b = run(own)
+    off = own.clone()
+    off[:, 1:] += 0.05
+    c = run(off)
+    d = run()
+    print(a[3], b[3], c[3], d[3])
+    assert a[3]["status"] == 1 and a[3]["n_iter"] >= 1
+    assert same(a, b), (a[3], b[3])                                        # the run's own landmarks, handed in
+    assert c[3]["final_loss"] != a[3]["final_loss"], (a[3], c[3])          # other landmarks: used
+    assert same(a, d), (a[3], d[3])                                        # ... and used once
 
 
 def test_runner_gate_and_errors(g, runner, synth_assets):
