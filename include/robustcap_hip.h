@@ -481,6 +481,40 @@ int rc_subnet_optim_step(rc_ctx* ctx, const char* net, const void* const* params
 typedef enum { RC_LOSS_MSE = 0, RC_LOSS_BCE_LOGITS = 1, RC_LOSS_WINDOW_MSE = 2, RC_LOSS_POSE_FK = 3 } rc_loss_kind;
 int rc_subnet_loss(rc_ctx* ctx, int32_t kind, const float* x, const float* y, int64_t frames, int32_t width, const float* aux_dev,
                    float* value_dev, float* dx_dev, void* stream);
+/* The batch in front of the training iteration (articulate/utils/torch/train.py:117-122 iterates a DataLoader(..., shuffle=True,
+ * collate_fn=RNNDataset.collate_fn) whose every element is one RNNDataset.__getitem__, articulate/utils/torch/rnn.py:64-67, with the
+ * sub-net's augment_fn): n samples gathered out of a corpus that stays on the device and augmented on the way, into ONE [F, W_out] and ONE
+ * [F, W_label] buffer (F = sum of the lengths, sample i's frames from row sum_{j<i} lengths[j]). Enqueued on `stream`; no read-back; the
+ * corpus is only read. data, label: DEVICE, the concatenated sequences; sample i is frames [offsets_host[i], offsets_host[i] +
+ * lengths_host[i]) of both (HOST arrays, any order, repeats allowed; they travel through a ring of four pinned copies, so a call waits on
+ * the host only for the upload made four calls earlier; the device table and the per-sample scratch grow at a new high-water mark of n).
+ * kind (rc_batch_kind):
+ *   RC_BATCH_PLAIN (every sub-net): data [., in], label [., out] of the sub-net (net/sig_mp.py:52-81). x_out = data rows with
+ *     torch.normal(x, sigma) on the last 69 columns (rnn3 sigma 0.04: net/sig_mp.py:360-363; rnn6 0.03: :578-581; rnn8 0.03: :792-795) or
+ *     on all columns (rnn7 0.03: :701-703); every other column, every column of rnn2 and rnn4 (:438-442: the identity) and of a call with
+ *     augment == 0, and the label are copied bit for bit.
+ *   RC_BATCH_WORLD (rnn4, rnn6 -- the AMASS __getitem__ of net/sig_mp.py:520-552 and :649-679): data [., 171] = acc[6,3] | ori[6,3,3] |
+ *     j3dw_mp[33,3], label [., 72] = j3dw[24,3] in the world frame, conf_pool DEVICE [pool_rows, 33] (syn_c.pt). Per sample: Rc0c =
+ *     Ry(yaw) Rx(pitch) Rz(roll) (articulate/math/angular.py:205-218; yaw in +-180 for rnn4, +-90 for rnn6, pitch +-30, roll +-5 degrees),
+ *     formed in double and rounded to fp32 once, Rcw = (diag(-1,-1,1) Rc0c)^T; everything turned by Rcw; t = lerp((-1,-1,3), (1,1,8), u),
+ *     t_z -= min over all frames and joints of j3dc_z; j3dc += t, j3dc_mp += t; j2dc = j3dc_mp / z; per frame a confidence row p of the pool,
+ *     distinct rows within a sample (random.sample); j2dc_xy += 0.003 (1 - p) z; j2dc_conf = p. rnn4: xy / max(bbox width, height), rows
+ *     != 23 relative to row 23 (get_bbox_scale, :277-284, :546-548); x_out = accc | oric | j2dc [F, 171], label_out = j3dc[1:] - j3dc[:1]
+ *     [F, 69]. rnn6: label_out = j3dc[:, 0] [F, 3]; x_out = accc | oric | j2dc | j3dc[1:] - j3dc[:1] [F, 240] with the sigma 0.03 noise on
+ *     the last 69 columns. augment must be non-zero.
+ * Random draws: Philox4x32-10 (Random123), key = (seed low, seed high), counter = (sample i, frame within the sample, site | index << 8,
+ * call); sites 2 (augment_fn noise; index = unit >> 2, unit counted from the first noisy column), 3 (camera: words 0-2 = yaw, pitch, roll),
+ * 4 (translation: words 0-2), 5 (pool rows: a 4-round Feistel permutation of [0, pool_rows) cycle-walked, second counter word = the right
+ * half, index = round), 6 (keypoint noise; index = keypoint >> 1). Uniforms (w >> 8) 2^-24, or ((w >> 9) + 0.5) 2^-23 under the
+ * logarithm; normals by Box-Muller, two per word pair. The stream is not torch's nor Python's: only the distributions, the sites and the
+ * order of the arithmetic are the reference's. No floating-point atomics: the same call gives the same bits.
+ * RC_ERR_INVALID (nothing enqueued) on a null context, net, buffer or table, an unknown net or kind, RC_BATCH_WORLD for another sub-net,
+ * without a pool or with augment == 0, n <= 0, a length < 1, a negative offset, a sample of more frames than the pool has rows, 2^31
+ * frames or more, or a sample, an output or the pool reaching past its allocation. */
+typedef enum { RC_BATCH_PLAIN = 0, RC_BATCH_WORLD = 1 } rc_batch_kind;
+int rc_subnet_batch(rc_ctx* ctx, const char* net, int32_t kind, const float* data, const float* label, int32_t n,
+                    const int64_t* offsets_host, const int32_t* lengths_host, const float* conf_pool, int32_t pool_rows, int32_t augment,
+                    uint64_t seed, uint32_t call, float* x_out, float* label_out, void* stream);
 /* RNNWithInit.init_net (articulate/utils/torch/rnn.py:195-201, used at :207-219): Linear(69,512) ReLU Linear(512,1024) ReLU
  * Linear(1024,2048) on v DEVICE [n, 69] -> out DEVICE [n, 2048], on the packed weights of rnn2.init_net in the context's gemm mode. */
 int rc_init_net_forward(rc_ctx* ctx, int32_t n, const float* v, float* out, void* stream);

@@ -44,6 +44,13 @@ NET_INDEX = {n[0]: i for i, n in enumerate(NETS)}
 DROPOUT = {n[0]: 0.1 if n[0] == "rnn7" else 0.4 for n in NETS}
 # loss each sub-net is trained with, net/sig_mp.py:340,409-418,555,683,749-771,829-831 (robustcap_amd/losses.py)
 LOSS = {"rnn2": "mse", "rnn3": "window_mse", "rnn4": "mse", "rnn6": "mse", "rnn7": "pose_fk", "rnn8": "bce_logits"}
+# augment_fn of each sub-net's datasets, net/sig_mp.py:360-363,438-442,578-581,701-703,792-795: torch.normal(x, sigma) on the last 69
+# columns ("tail") or on every column ("all"); None: the identity (robustcap_amd/batches.py, csrc/rc_augment.hip)
+AUGMENT = {"rnn2": None, "rnn3": ("tail", 69, 0.04), "rnn4": None, "rnn6": ("tail", 69, 0.03), "rnn7": ("all", 0.03), "rnn8": ("tail", 69, 0.03)}
+# the random camera of the AMASS samples, net/sig_mp.py:528,657 (generate_random_rotation_matrix_constrained, degrees), and whether the
+# keypoints are bounding-box normalised afterwards (:546-548; rnn6 keeps them raw)
+CAMERA = {"rnn4": {"yaw": (-180, 180), "pitch": (-30, 30), "roll": (-5, 5), "normalise": True},
+          "rnn6": {"yaw": (-90, 90), "pitch": (-30, 30), "roll": (-5, 5), "normalise": False}}
 # rnn2.init_net: Linear(69,512) ReLU Linear(512,1024) ReLU Linear(1024,2048)  (rnn.py:195-201)
 INIT_NET = ((69, 512), (512, 1024), (1024, 2048))
 

@@ -677,6 +677,20 @@ void rc_launch_optim_dense(const OptimTensor& Wt, const OptimTensor& bt, int N, 
 void rc_launch_subnet_loss(int kind, const BodyConst* body, const float* x, const float* y, long long F, int W, const float* aux,
                            double* partial, float* value, float* dx, hipStream_t s);
 
+// ---- the training batches of one sub-net (rc_augment.hip; rc_subnet_batch in rc_subnet_api.cpp) ------------------------------------------
+// tab (device): [n] first corpus frame of every sample | [n + 1] first output frame of every sample, then the total F. Draws: Philox4x32-10
+// with key = seed and counter = (sample, frame within the sample, site | index << 8, call), sites 2 .. 6 (rc_augment.hip).
+struct BatchKey { unsigned long long seed; unsigned call; };
+struct BatchCamera { float yaw_lo, yaw_hi, pitch_lo, pitch_hi, roll_lo, roll_hi; };   // degrees
+// x_out[f] = data[row of f], columns [c0, W) + sigma * normal (c0 == W: a copy); l_out[f] = label[row of f]. Any alignment.
+void rc_launch_batch_plain(const float* data, const float* label, const long long* tab, int n, long long F, int W, int Wl, int c0,
+                           float sigma, const BatchKey& k, float* x_out, float* l_out, hipStream_t s);
+// the AMASS sample of rnn4 (rnn4 != 0: x [F, 171], label [F, 69]) or rnn6 (x [F, 240], label [F, 3]) from data [., 171], label [., 72] and
+// pool [pool_rows, 33]; cam: [n, 12] scratch (Rcw | t per sample), written by the first of the two launches
+void rc_launch_batch_world(int rnn4, const float* data, const float* label, const long long* tab, int n, long long F,
+                           const BatchCamera& range, float* cam, const float* pool, int pool_rows, float sigma, const BatchKey& k,
+                           float* x_out, float* l_out, hipStream_t s);
+
 // narrow view of the context for rc_subnet_api.cpp
 struct SubnetState;
 struct SubnetDense { const float* W; const void* Ws; const float* b; int K, N, Kp, Np; };

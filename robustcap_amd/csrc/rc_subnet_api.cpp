@@ -52,6 +52,17 @@ struct SubnetState {                 // (grow-only buffers; the context's destru
     DevBuf<double> wg_colsum;        // ... and of a bias sum: [parts][M]
     size_t wg_colsum_doubles = 0;
     int wg_parts = 0;                // rc_set_subnet_wgrad_parts: 0 = from the tile count
+    // training batches (rc_subnet_batch): the sample table, staged through a ring of pinned copies so that a call waits for the upload
+    // made kBatchRing calls earlier, not for the one before it
+    static constexpr int kBatchRing = 4;
+    DevBuf<long long> btab;          // [n] first corpus frame | [n + 1] first output frame of every sample
+    size_t btab_n = 0;
+    PinBuf<long long> btab_h[kBatchRing];
+    size_t btab_hn[kBatchRing] = {};
+    HipEvent btab_ev[kBatchRing];    // the last upload from btab_h[i]
+    int btab_next = 0;
+    DevBuf<float> bcam;              // kind world: Rcw | t of every sample [n, 12]
+    size_t bcam_floats = 0;
     int cus = 0;                     // compute units of the device (asked once)
 };
 
@@ -588,6 +599,89 @@ int rc_dropout_apply(rc_ctx* ctx, const float* src, float* dst, int64_t rows, in
     hipStream_t st = (hipStream_t)stream;
     if (p > 0.0f) rc_launch_dropout_rows(src, dst, rows, cols, nullptr, site, DropoutKey{p, seed, call}, st);
     else if (src != dst) HIP_TRY(ctx, hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, hipGetLastError());
+    return RC_OK;
+}
+
+// (input width, label width) of a "plain" sample: the sub-net's input and output (net/sig_mp.py:52-81), in kNets order
+static const int kBatchWidth[6][2] = {{72, 69}, {141, 3}, {171, 69}, {240, 3}, {141, 144}, {141, 2}};
+// augment_fn: noisy columns counted from the end of the row (0: none) and sigma (net/sig_mp.py:360-363, 438-442, 578-581, 701-703, 792-795)
+static const struct { int cols; float sigma; } kBatchNoise[6] = {{0, 0.f}, {69, 0.04f}, {0, 0.f}, {69, 0.03f}, {141, 0.03f}, {69, 0.03f}};
+// generate_random_rotation_matrix_constrained(y, p, r) of the AMASS samples (net/sig_mp.py:528, :657), degrees
+static const BatchCamera kBatchCamera4 = {-180.f, 180.f, -30.f, 30.f, -5.f, 5.f};
+static const BatchCamera kBatchCamera6 = {-90.f, 90.f, -30.f, 30.f, -5.f, 5.f};
+
+int rc_subnet_batch(rc_ctx* ctx, const char* net, int32_t kind, const float* data, const float* label, int32_t n,
+                    const int64_t* offsets_host, const int32_t* lengths_host, const float* conf_pool, int32_t pool_rows, int32_t augment,
+                    uint64_t seed, uint32_t call, float* x_out, float* label_out, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    const std::string f = "rc_subnet_batch: ";
+    if (!net || !data || !label || !offsets_host || !lengths_host || !x_out || !label_out)
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "null argument").c_str());
+    const int ni = rc_ctx_net_index(net);
+    if (ni < 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "unknown net " + net).c_str());
+    if (kind != RC_BATCH_PLAIN && kind != RC_BATCH_WORLD) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "kind 0 (plain) or 1 (world)").c_str());
+    const bool world = kind == RC_BATCH_WORLD;
+    const bool rnn4 = ni == 2, rnn6 = ni == 3;
+    if (world && !rnn4 && !rnn6) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "kind world is rnn4's and rnn6's, not " + net + "'s").c_str());
+    if (world && !augment) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a world sample has no un-augmented form (the camera is part of it)").c_str());
+    if (n <= 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "no samples").c_str());
+    if (world && (!conf_pool || pool_rows < 1)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "kind world needs a confidence pool").c_str());
+    const int W = world ? 171 : kBatchWidth[ni][0], Wl = world ? 72 : kBatchWidth[ni][1];
+    const int Wo = kBatchWidth[ni][0], Wlo = kBatchWidth[ni][1];
+    // the extents of the caller's allocations, asked once each
+    auto extent = [](const void* p) -> long long {
+        void* base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return -1; }
+        return (long long)((const char*)base + size - (const char*)p);
+    };
+    const long long data_bytes = extent(data), label_bytes = extent(label);
+    long long F = 0;
+    for (int i = 0; i < n; ++i) {
+        const long long off = offsets_host[i], len = lengths_host[i];
+        if (len < 1 || off < 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "every sample needs an offset >= 0 and at least one frame").c_str());
+        if (off + len > (1ll << 40) || (off + len) * 4 * W > data_bytes || (off + len) * 4 * Wl > label_bytes)
+            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sample ends past the corpus buffers").c_str());
+        if (world && len > pool_rows)
+            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sample of " + std::to_string(len) + " frames cannot draw distinct rows from a pool of " +
+                                                     std::to_string(pool_rows)).c_str());
+        F += len;
+    }
+    if (F >= (1ll << 31)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "2^31 frames or more").c_str());
+    if (extent(x_out) < 4 * F * Wo || extent(label_out) < 4 * F * Wlo || (world && extent(conf_pool) < 4ll * pool_rows * 33))
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "an output or the pool ends before its extent").c_str());
+    hipStream_t st = (hipStream_t)stream;
+    SubnetState* S = state(ctx);
+    // ---- the table: pinned slot -> device, on `stream`
+    const size_t nt = 2 * (size_t)n + 1;
+    const int slot = S->btab_next;
+    S->btab_next = (slot + 1) % SubnetState::kBatchRing;
+    if (S->btab_ev[slot]) HIP_TRY(ctx, hipEventSynchronize(S->btab_ev[slot].get()));      // the upload made kBatchRing calls ago has left the slot
+    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->btab_ev[slot]), hipEventDisableTiming));
+    HIP_TRY(ctx, rc_grow(S->btab_hn[slot], nt, 2 * nt, S->btab_h[slot], 2 * nt));
+    if (nt > S->btab_n) {                                                                 // (kernels of earlier calls may still read the old table)
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, rc_grow(S->btab_n, nt, 2 * nt, S->btab, 2 * nt));
+    }
+    if (world && 12 * (size_t)n > S->bcam_floats) {
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, rc_grow(S->bcam_floats, 12 * (size_t)n, 24 * (size_t)n, S->bcam, 24 * (size_t)n));
+    }
+    long long* th = S->btab_h[slot].get();
+    long long at = 0;
+    for (int i = 0; i < n; ++i) { th[i] = offsets_host[i]; th[n + i] = at; at += lengths_host[i]; }
+    th[2 * (size_t)n] = at;
+    HIP_TRY(ctx, hipMemcpyAsync(S->btab.get(), th, nt * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(S->btab_ev[slot].get(), st));
+    const BatchKey key{seed, call};
+    if (world) {
+        rc_launch_batch_world(rnn4 ? 1 : 0, data, label, S->btab.get(), n, F, rnn4 ? kBatchCamera4 : kBatchCamera6, S->bcam.get(), conf_pool,
+                              pool_rows, kBatchNoise[ni].sigma, key, x_out, label_out, st);
+    } else {
+        const int noisy = augment ? kBatchNoise[ni].cols : 0;
+        rc_launch_batch_plain(data, label, S->btab.get(), n, F, W, Wl, W - noisy, kBatchNoise[ni].sigma, key, x_out, label_out, st);
+    }
     HIP_TRY(ctx, hipGetLastError());
     return RC_OK;
 }

@@ -143,9 +143,14 @@ class SubnetLoss:
 
 
 def pos_weight_from_labels(labels):
-    """``(1 - l).sum(0) / l.sum(0)`` over the concatenated labels (net/sig_mp.py:829-830): rnn8's ``pos_weight``."""
-    ls, _, _ = _rows(labels, "labels")
-    l = torch.cat(ls)
+    """``(1 - l).sum(0) / l.sum(0)`` over the concatenated labels (net/sig_mp.py:829-830): rnn8's ``pos_weight``. ``labels``: one tensor,
+    a list of tensors, or a ``tr.dataset(...)`` (its label buffer on the device: every frame of the corpus once, as the reference's
+    ``torch.cat(label)``)."""
+    if hasattr(labels, "label") and hasattr(labels, "samples"):
+        l = labels.label
+    else:
+        ls, _, _ = _rows(labels, "labels")
+        l = torch.cat(ls)
     return (1 - l).sum(dim=0) / l.sum(dim=0)
 
 
