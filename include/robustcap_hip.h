@@ -481,6 +481,30 @@ int rc_subnet_optim_step(rc_ctx* ctx, const char* net, const void* const* params
 typedef enum { RC_LOSS_MSE = 0, RC_LOSS_BCE_LOGITS = 1, RC_LOSS_WINDOW_MSE = 2, RC_LOSS_POSE_FK = 3 } rc_loss_kind;
 int rc_subnet_loss(rc_ctx* ctx, int32_t kind, const float* x, const float* y, int64_t frames, int32_t width, const float* aux_dev,
                    float* value_dev, float* dx_dev, void* stream);
+/* The metric of the validation pass (articulate/utils/torch/train.py:94-101 and :124-131: `vald_loss = sum([eval_fn(net(d), l) for (d, l)
+ * in valid_dataloader]) / num_vald_step`, one value per validation BATCH) for every batch of a concatenated output in one call: x, y DEVICE
+ * [F, width], F = the sum of group_frames_host[0 .. groups) (a HOST array); group g is frames [sum_{j<g} group_frames[j], ... +
+ * group_frames[g]) -- what RNNLossWrapper (articulate/utils/torch/rnn.py) would torch.cat for validation batch g -- and values_dev DEVICE
+ * float[groups] receives its value. Enqueued on `stream`: two launches whatever `groups` is, no read-back; the group table travels through a
+ * ring of four pinned copies, so a call waits on the host only for the upload made four calls earlier (and for the stream where its
+ * context-owned device table or partial sums grow: a new high-water mark of groups or of workgroups). kind:
+ *   the four rc_loss_kind values (widths and aux_dev as for rc_subnet_loss): values_dev[g] has the BITS of rc_subnet_loss(kind, x_g, y_g,
+ *     group_frames[g], width, aux_dev, value, dx = NULL) on a 16-byte aligned copy of the group's slice. By construction: group g runs the
+ *     per-workgroup code of rc_subnet_loss's kernels in min(units of the group, 1024) workgroups of its own, each of which finds its (group,
+ *     index) by bisection of the table, with the double reciprocals the host forms for such a slice; a group's partial sums are added in
+ *     index order. A group that starts off the 16-byte grid (width 69, 3, or 2 after an odd number of frames) loads dwords instead of
+ *     16-byte pieces; which element a thread adds when is the same. RC_LOSS_WINDOW_MSE cuts its windows from the END of the GROUP.
+ *   RC_EVAL_POSITION_ERROR (width a multiple of 3; rnn2 and rnn4, 69: net/sig_mp.py:341,556 PositionErrorEvaluator,
+ *     articulate/evaluator.py:129): the mean over the group's group_frames[g] width / 3 points of the Euclidean norm of x - y; differences,
+ *     squares, square root and sums in double on the fp32 inputs, units of 1024 points, the same fixed-order sums, rounded to fp32 once.
+ * No floating-point atomics: two calls give the same bits. Calls on one context share the table and the partial sums: a caller who uses a
+ * second stream orders it itself. RC_ERR_INVALID (nothing enqueued, values_dev untouched; rc_last_error names this entry and, where one
+ * is at fault, the group) on a null context, a null x, y, values_dev or group_frames_host, an unknown kind, a width that does not fit the
+ * kind, groups < 1 or > 65536, a group of fewer than 1 frame (RC_LOSS_WINDOW_MSE: 60), RC_LOSS_POSE_FK before rc_set_body,
+ * RC_LOSS_BCE_LOGITS without aux_dev, or x or y off the 16-byte grid (RC_LOSS_MSE, RC_LOSS_BCE_LOGITS, RC_LOSS_POSE_FK). */
+typedef enum { RC_EVAL_POSITION_ERROR = 16 } rc_eval_kind;   /* beside the four rc_loss_kind values */
+int rc_subnet_eval(rc_ctx* ctx, int32_t kind, const float* x, const float* y, int32_t groups, const int64_t* group_frames_host,
+                   int32_t width, const float* aux_dev, float* values_dev, void* stream);
 /* The batch in front of the training iteration (articulate/utils/torch/train.py:117-122 iterates a DataLoader(..., shuffle=True,
  * collate_fn=RNNDataset.collate_fn) whose every element is one RNNDataset.__getitem__, articulate/utils/torch/rnn.py:64-67, with the
  * sub-net's augment_fn): n samples gathered out of a corpus that stays on the device and augmented on the way, into ONE [F, W_out] and ONE

@@ -113,6 +113,7 @@ SIGNATURES = {
     "rc_update_subnet_weights": (_I32, [_P, C.c_char_p, _P, _I32, _P]),
     "rc_subnet_optim_step": (_I32, [_P, C.c_char_p, _P, _P, _P, _P, _I32] + [C.c_double] * 8 + [_P, _P]),
     "rc_subnet_loss": (_I32, [_P, _I32, _P, _P, _I64, _I32, _P, _P, _P, _P]),
+    "rc_subnet_eval": (_I32, [_P, _I32, _P, _P, _I32, C.POINTER(_I64), _I32, _P, _P, _P]),
     "rc_subnet_batch": (_I32, [_P, C.c_char_p, _I32, _P, _P, _I32, _P, _P, _P, _I32, _I32, C.c_uint64, _U32, _P, _P, _P]),
     "rc_init_net_forward": (_I32, [_P, _I32, _P, _P, _P]),
     "rc_get_subnet_stats": (_I32, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),

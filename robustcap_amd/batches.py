@@ -4,7 +4,7 @@ the iteration of ``articulate/utils/torch/train.py:117-122`` -- ``len(indices)``
 (``articulate/utils/torch/rnn.py:64-67``) with the sub-net's ``augment_fn`` -- as ONE C call, ``rc_subnet_batch`` (csrc/rc_augment.hip):
 
     ds = tr.dataset(data, label, split_size=200)                  # lists of [T_i, W] tensors, as RNNDataset.__init__ takes them
-    for idx in torch.randperm(len(ds)).split(256):                # the shuffled order, epochs and validation stay the caller's
+    for idx in torch.randperm(len(ds)).split(256):                # (the reference's whole loop around this: robustcap_amd/fit.py)
         xs, labels = ds.batch(idx.tolist())                       # consecutive views of one [F, in] and one [F, out] device buffer
         loss = loss_fn(tr(xs), labels); opt.zero_grad(); loss.backward(); opt.step()
 

@@ -44,6 +44,28 @@ NET_INDEX = {n[0]: i for i, n in enumerate(NETS)}
 DROPOUT = {n[0]: 0.1 if n[0] == "rnn7" else 0.4 for n in NETS}
 # loss each sub-net is trained with, net/sig_mp.py:340,409-418,555,683,749-771,829-831 (robustcap_amd/losses.py)
 LOSS = {"rnn2": "mse", "rnn3": "window_mse", "rnn4": "mse", "rnn6": "mse", "rnn7": "pose_fk", "rnn8": "bce_logits"}
+# eval_fn each sub-net is validated with, net/sig_mp.py:341,556 (rnn2, rnn4: RNNLossWrapper(PositionErrorEvaluator())); the others pass
+# their loss_fn (:431,694,784,836) (robustcap_amd/losses.py: EVAL_KINDS)
+EVAL = dict(LOSS, rnn2="position_error", rnn4="position_error")
+
+
+def _train(num_epoch, between, lr, patience):
+    # shared by all six: clip_grad_norm=1 (:355,432,572,695,785,837), DataLoader(train, 256, shuffle=True) (:348,426,562,689,779,825),
+    # DataLoader(valid, 64) (:352,430,566,693,783,827), split_size=200 for the training sets (:346-347,423-424,560-561,687-688,776-777,825)
+    # and -1 (whole sequences) for the validation sets
+    return {"num_epoch": num_epoch, "num_iter_between_vald": between, "clip_grad_norm": 1.0, "lr": lr, "lr_scheduler_patience": patience,
+            "batch_size": 256, "valid_batch_size": 64, "split_size": 200}
+
+
+# what the reference passes to train() for each sub-net (articulate/utils/torch/train.py:15-18), settings only
+TRAIN = {
+    "rnn2": _train(150, 20, 1e-3, None),       # net/sig_mp.py:354-355; Adam's default lr (train.py:53)
+    "rnn3": _train(200, 20, 1e-3, None),       # :431-432
+    "rnn4": _train(200, 60, 1e-4, None),       # :571-572; optimizer = Adam(lr=1e-4) at :569
+    "rnn6": _train(100, 60, 1e-3, 5),          # :694-697
+    "rnn7": _train(120, 20, 1e-3, 5),          # :784-787
+    "rnn8": _train(80, 20, 1e-3, 10),          # :836-839
+}
 # augment_fn of each sub-net's datasets, net/sig_mp.py:360-363,438-442,578-581,701-703,792-795: torch.normal(x, sigma) on the last 69
 # columns ("tail") or on every column ("all"); None: the identity (robustcap_amd/batches.py, csrc/rc_augment.hip)
 AUGMENT = {"rnn2": None, "rnn3": ("tail", 69, 0.04), "rnn4": None, "rnn6": ("tail", 69, 0.03), "rnn7": ("all", 0.03), "rnn8": ("tail", 69, 0.03)}

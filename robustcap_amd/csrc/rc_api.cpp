@@ -619,6 +619,70 @@ int rc_subnet_loss(rc_ctx* ctx, int32_t kind, const float* x, const float* y, in
     return RC_OK;
 }
 
+// The validation pass's metric (train.py:94-101,124-131: `eval_fn(net(d), l)` per validation batch), for ALL batches of a concatenated
+// output at once (kernels: rc_loss.hip). Like rc_subnet_loss it touches nothing of the context but its own partial sums and group table.
+int rc_subnet_eval(rc_ctx* ctx, int32_t kind, const float* x, const float* y, int32_t groups, const int64_t* group_frames_host,
+                   int32_t width, const float* aux_dev, float* values_dev, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    const std::string what = "rc_subnet_eval: ";
+    bool fits = false;
+    switch (kind) {
+        case RC_LOSS_MSE: fits = width == 69 || width == 3; break;
+        case RC_LOSS_BCE_LOGITS: fits = width == 2; break;
+        case RC_LOSS_WINDOW_MSE: fits = width == 3; break;
+        case RC_LOSS_POSE_FK: fits = width == 144; break;
+        case RC_EVAL_POSITION_ERROR: fits = width >= 3 && width % 3 == 0; break;
+        default: return fail(ctx, RC_ERR_INVALID, what + "unknown kind " + std::to_string(kind));
+    }
+    if (!fits) return fail(ctx, RC_ERR_INVALID, what + "width " + std::to_string(width) + " does not fit kind " + std::to_string(kind));
+    if (groups < 1 || groups > RC_EVAL_MAX_GROUPS)
+        return fail(ctx, RC_ERR_INVALID, what + std::to_string(groups) + " groups: 1 .. " + std::to_string(RC_EVAL_MAX_GROUPS) + " expected");
+    if (!x || !y || !values_dev || !group_frames_host) return fail(ctx, RC_ERR_INVALID, what + "null argument");
+    const int64_t least = kind == RC_LOSS_WINDOW_MSE ? 60 : 1;
+    long long F = 0;
+    for (int g = 0; g < groups; ++g) {
+        const int64_t f = group_frames_host[g];
+        if (f < least || f > (1ll << 40))
+            return fail(ctx, RC_ERR_INVALID, what + "group " + std::to_string(g) + " has " + std::to_string(f) + " frames: at least " +
+                                                 std::to_string(least) + " expected" +
+                                                 (kind == RC_LOSS_WINDOW_MSE ? " (window_mse: below, no window of 60 frames exists)" : ""));
+        F += f;
+        if (F > (1ll << 40)) return fail(ctx, RC_ERR_INVALID, what + "group " + std::to_string(g) + " ends past 2^40 frames");
+    }
+    if (kind == RC_LOSS_POSE_FK && !ctx->have_body) return fail(ctx, RC_ERR_INVALID, what + "pose_fk: body not set");
+    if (kind == RC_LOSS_BCE_LOGITS && !aux_dev) return fail(ctx, RC_ERR_INVALID, what + "bce_logits: pos_weight missing");
+    const bool pieces = kind == RC_LOSS_MSE || kind == RC_LOSS_BCE_LOGITS || kind == RC_LOSS_POSE_FK;
+    if (pieces && (((uintptr_t)x | (uintptr_t)y) & 15)) return fail(ctx, RC_ERR_INVALID, what + "x and y must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    // ---- the group table: pinned slot -> device, on `stream`
+    const size_t G = (size_t)groups;
+    const int slot = ctx->eval_next;
+    ctx->eval_next = (slot + 1) % rc_ctx::kEvalRing;
+    if (ctx->eval_ev[slot]) HIP_TRY(ctx, hipEventSynchronize(ctx->eval_ev[slot].get()));     // the upload made kEvalRing calls ago has left the slot
+    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->eval_ev[slot]), hipEventDisableTiming));
+    HIP_TRY(ctx, rc_grow(ctx->eval_tab_hn[slot], G, 2 * G, ctx->eval_tab_h[slot], 2 * G));
+    EvalGroup* th = ctx->eval_tab_h[slot].get();
+    long long at = 0, blocks = 0;
+    for (int g = 0; g < groups; ++g) {
+        th[g].frame0 = at;
+        th[g].frames = group_frames_host[g];
+        th[g].blk0 = (int)blocks;
+        rc_eval_group(kind, width, &th[g]);
+        at += th[g].frames;
+        blocks += th[g].nblk;
+    }
+    if (G > ctx->eval_tab_n || (size_t)blocks > ctx->eval_partial_n) {                       // (kernels of earlier calls may still use the old buffers)
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, rc_grow(ctx->eval_tab_n, G, 2 * G, ctx->eval_tab, 2 * G));
+        HIP_TRY(ctx, rc_grow(ctx->eval_partial_n, (size_t)blocks, 2 * (size_t)blocks, ctx->eval_partial, 2 * (size_t)blocks));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->eval_tab.get(), th, G * sizeof(EvalGroup), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(ctx->eval_ev[slot].get(), st));
+    rc_launch_subnet_eval(kind, ctx->body, ctx->eval_tab.get(), groups, blocks, x, y, width, aux_dev, ctx->eval_partial.get(), values_dev, st);
+    HIP_TRY(ctx, hipGetLastError());
+    return RC_OK;
+}
+
 static int finalize_weights_impl(rc_ctx* ctx) {
     for (int i = 0; i < 6; ++i) {
         const NetSpec& s = kNets[i];

@@ -76,6 +76,17 @@ struct rc_ctx {
     SubnetOwner subnet;                  // scratch of rc_subnet_forward (rc_subnet_api.cpp)
     DevBuf<double> optim_partial;        // rc_subnet_optim_step: per-workgroup sums of squares of the gradient norm, sized once for the largest sub-net
     DevBuf<double> loss_partial;         // rc_subnet_loss: RC_LOSS_MAX_PARTIALS per-workgroup sums, allocated by the first call
+    // rc_subnet_eval: per-workgroup sums of all groups (grow-only, its own: not loss_partial) and the group table, staged through a ring
+    // of pinned copies like rc_subnet_batch's sample table (a call waits for the upload made kEvalRing calls earlier)
+    static constexpr int kEvalRing = 4;
+    DevBuf<double> eval_partial;
+    size_t eval_partial_n = 0;
+    DevBuf<EvalGroup> eval_tab;
+    size_t eval_tab_n = 0;
+    PinBuf<EvalGroup> eval_tab_h[kEvalRing];
+    size_t eval_tab_hn[kEvalRing] = {};
+    HipEvent eval_ev[kEvalRing];         // the last upload from eval_tab_h[i]
+    int eval_next = 0;
 };
 
 #pragma GCC visibility push(hidden)

@@ -676,6 +676,17 @@ void rc_launch_optim_dense(const OptimTensor& Wt, const OptimTensor& bt, int N, 
 // value = the loss of x, y [F, W] (one device float), dx (may be null) its gradient; partial: RC_LOSS_MAX_PARTIALS doubles
 void rc_launch_subnet_loss(int kind, const BodyConst* body, const float* x, const float* y, long long F, int W, const float* aux,
                            double* partial, float* value, float* dx, hipStream_t s);
+// ---- the validation metrics of the sub-nets, per group of a concatenated batch (rc_loss.hip; rc_subnet_eval in rc_api.cpp) -----------------
+#define RC_EVAL_POINTS 1024           // 3-D points per unit of position_error: four per thread of a workgroup
+#define RC_EVAL_MAX_GROUPS 65536      // groups of a call at most (at most RC_LOSS_MAX_PARTIALS workgroups each: the grid stays below 2^31)
+// One group: frames [frame0, frame0 + frames) of x and y; its workgroups are [blk0, blk0 + nblk) of the launch, nblk = what rc_subnet_loss
+// launches for such a slice; c: the double reciprocals rc_launch_subnet_loss hands its kernels for such a slice (element kinds and
+// position_error: 1 / count | window_mse: 1 / (3 F), 1 / (3 (F / 6)), 1 / (3 (F / 20)), 1 / (3 (F / 60)) | pose_fk: 1 / (144 F), 100 / (72 F))
+struct EvalGroup { long long frame0, frames; int blk0, nblk; double c[4]; };
+void rc_eval_group(int kind, int W, EvalGroup* g);         // frames set by the caller -> nblk and c, by the code rc_launch_subnet_loss uses
+// values[g] = the value of group g; tab DEVICE [groups]; blocks = sum of nblk; partial: `blocks` doubles. Two launches whatever `groups` is.
+void rc_launch_subnet_eval(int kind, const BodyConst* body, const EvalGroup* tab, int groups, long long blocks, const float* x, const float* y,
+                           int W, const float* aux, double* partial, float* values, hipStream_t s);
 
 // ---- the training batches of one sub-net (rc_augment.hip; rc_subnet_batch in rc_subnet_api.cpp) ------------------------------------------
 // tab (device): [n] first corpus frame of every sample | [n + 1] first output frame of every sample, then the total F. Draws: Philox4x32-10

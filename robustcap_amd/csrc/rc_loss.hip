@@ -11,6 +11,12 @@
 // counted from the END of the batch | RC_LOSS_POSE_FRAMES frames), every thread adds its terms into one double in a fixed order, the 256
 // doubles are added in a fixed tree and stored as one partial; rc_loss_finish_kernel adds the at most RC_LOSS_MAX_PARTIALS partials in
 // index order. No atomics: two runs give the same bits.
+//
+// The validation metric (rc_subnet_eval; train.py:94-101,124-131, `sum([eval_fn(net(d), l) for d, l in vald_dataloader]) / num_vald_step`
+// with the eval_fn of net/sig_mp.py:341,431,556,694,784,836): the same sums for every validation BATCH (group) of a concatenated output in
+// one launch. What a workgroup does with its units is one __device__ function per kind (rc_loss_*_units), shared by the kernels above and
+// by rc_eval_kernel, where workgroup B finds its group and its index within the group in a table; so a group's value has the bits of
+// rc_subnet_loss on the group's slice. position_error (articulate/evaluator.py:129, rnn2's and rnn4's eval_fn) exists here only.
 #include "../../include/robustcap_hip.h"
 #include "rc_internal.h"
 #include "rc_device.h"
@@ -59,23 +65,32 @@ __device__ __forceinline__ double rc_loss_element(float xf, float yf, double pw,
 
 // Unit u = elements [u RC_LOSS_CHUNK, (u + 1) RC_LOSS_CHUNK): four 16-byte pieces per thread, piece i of thread t at element
 // 4 (256 i + t) of the unit -- a wave's load is 1 KiB of consecutive bytes. The piece that crosses n is done element by element.
+// al == false (a group of rc_subnet_eval that starts off the 16-byte grid): the piece comes in as four dwords; which element a thread adds
+// when is the same.
+__device__ __forceinline__ f32x4 rc_loss_piece(const float* p, bool al) {
+    if (al) return *reinterpret_cast<const f32x4*>(p);
+    f32x4 v;
+    v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
+    return v;
+}
+
+// the sum of workgroup b of nb over its units b, b + nb, ... of x, y [n] (before the division by n)
 template <int KIND>
-__global__ __launch_bounds__(256) void rc_loss_elem_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ pwt,
-                                                           long long n, long long units, double inv_n, double* partial, float* dx) {
-    __shared__ double s[256];
+__device__ __forceinline__ double rc_loss_elem_units(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ pwt,
+                                                     long long n, long long units, double inv_n, int b, int nb, bool al, float* dx) {
     const int tid = threadIdx.x;
     double pw0 = 1.0, pw1 = 1.0;
     if constexpr (KIND == RC_LOSS_BCE_LOGITS) { pw0 = (double)pwt[0]; pw1 = (double)pwt[1]; }   // W = 2: an element's column is its parity
     // bce_logits is bound by exp and log1p in double: one copy of their code, not sixteen
     constexpr int UP = KIND == RC_LOSS_MSE ? RC_LOSS_CHUNK / 1024 : 1, UE = KIND == RC_LOSS_MSE ? 4 : 1;
     double acc = 0.0;
-    for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+    for (long long u = b; u < units; u += nb) {
         const long long e0 = u * RC_LOSS_CHUNK + 4 * tid;
 #pragma unroll UP                                                         // (mse: four loads in flight)
         for (int i = 0; i < RC_LOSS_CHUNK / 1024; ++i) {
             const long long e = e0 + 1024 * i;
             if (e + 3 < n) {
-                const f32x4 xv = *reinterpret_cast<const f32x4*>(x + e), yv = *reinterpret_cast<const f32x4*>(y + e);
+                const f32x4 xv = rc_loss_piece(x + e, al), yv = rc_loss_piece(y + e, al);
                 f32x4 gv;
 #pragma unroll UE
                 for (int k = 0; k < 4; ++k) {
@@ -93,7 +108,15 @@ __global__ __launch_bounds__(256) void rc_loss_elem_kernel(const float* __restri
             }
         }
     }
-    rc_loss_store_partial(acc * inv_n, s, partial);
+    return acc * inv_n;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void rc_loss_elem_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ pwt,
+                                                           long long n, long long units, double inv_n, double* partial, float* dx) {
+    __shared__ double s[256];
+    const double acc = rc_loss_elem_units<KIND>(x, y, pwt, n, units, inv_n, (int)blockIdx.x, (int)gridDim.x, true, dx);
+    rc_loss_store_partial(acc, s, partial);
 }
 
 // ---- window_mse (W = 3): mse + the mse of the sums over windows of 6, 20 and 60 frames cut from the END of the batch -----------------------
@@ -106,15 +129,15 @@ struct LossWindow {
 };
 #define RC_LOSS_WINDOW_SUMS (RC_LOSS_WINDOW_FRAMES / 6 + RC_LOSS_WINDOW_FRAMES / 20 + RC_LOSS_WINDOW_FRAMES / 60)
 
-__global__ __launch_bounds__(256) void rc_loss_window_kernel(const float* __restrict__ x, const float* __restrict__ y, const LossWindow A,
-                                                             long long units, double* partial, float* dx) {
-    __shared__ double s[256];
+// the sum of workgroup b of nb over its units b, b + nb, ... of x, y [A.F, 3]
+__device__ __forceinline__ double rc_loss_window_units(const float* __restrict__ x, const float* __restrict__ y, const LossWindow A,
+                                                       long long units, int b, int nb, float* dx) {
     __shared__ double sd[RC_LOSS_WINDOW_FRAMES * 3];
     __shared__ double sS[RC_LOSS_WINDOW_SUMS * 3];
     constexpr int N6 = RC_LOSS_WINDOW_FRAMES / 6, N20 = RC_LOSS_WINDOW_FRAMES / 20;
     const int tid = threadIdx.x;
     double acc = 0.0;
-    for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+    for (long long u = b; u < units; u += nb) {
         const long long elo = u * RC_LOSS_WINDOW_FRAMES;
         const long long ehi = elo + RC_LOSS_WINDOW_FRAMES < A.F ? elo + RC_LOSS_WINDOW_FRAMES : A.F;
         const int nf = (int)(ehi - elo);                                  // frames of the unit: f0 .. f0 + nf - 1, e descending
@@ -149,6 +172,13 @@ __global__ __launch_bounds__(256) void rc_loss_window_kernel(const float* __rest
             }
         }
     }
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void rc_loss_window_kernel(const float* __restrict__ x, const float* __restrict__ y, const LossWindow A,
+                                                             long long units, double* partial, float* dx) {
+    __shared__ double s[256];
+    const double acc = rc_loss_window_units(x, y, A, units, (int)blockIdx.x, (int)gridDim.x, dx);
     rc_loss_store_partial(acc, s, partial);
 }
 
@@ -167,10 +197,9 @@ struct alignas(16) LossPoseWave {
     double J[2][24][3];         // joints of x | of y; the reverse sweep keeps the subtree sums in [1]
 };
 
-__global__ __launch_bounds__(256) void rc_loss_pose_kernel(const BodyConst* __restrict__ body, const float* __restrict__ x,
-                                                           const float* __restrict__ y, long long F, long long units, double cm, double cj,
-                                                           double* partial, float* dx) {
-    __shared__ double s[256];
+// the sum of workgroup b of nb over its units b, b + nb, ... of x, y [F, 144]
+__device__ __forceinline__ double rc_loss_pose_units(const BodyConst* __restrict__ body, const float* __restrict__ x, const float* __restrict__ y,
+                                                     long long F, long long units, double cm, double cj, int b, int nb, float* dx) {
     __shared__ LossPoseWave sw[4];
     __shared__ double sbone[24][3];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, side = lane >> 5;
@@ -187,7 +216,7 @@ __global__ __launch_bounds__(256) void rc_loss_pose_kernel(const BodyConst* __re
     if (tid < 72) sbone[tid / 3][tid % 3] = (double)body->bone[tid / 3][tid % 3];
     __syncthreads();
     double acc = 0.0;
-    for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+    for (long long u = b; u < units; u += nb) {
         for (int k = 0; k < RC_LOSS_POSE_FRAMES / 4; ++k) {
             const long long f = u * RC_LOSS_POSE_FRAMES + 4 * k + wave;
             if (f >= F) break;                                            // (wave-uniform)
@@ -309,31 +338,143 @@ __global__ __launch_bounds__(256) void rc_loss_pose_kernel(const BodyConst* __re
             }
         }
     }
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void rc_loss_pose_kernel(const BodyConst* __restrict__ body, const float* __restrict__ x,
+                                                           const float* __restrict__ y, long long F, long long units, double cm, double cj,
+                                                           double* partial, float* dx) {
+    __shared__ double s[256];
+    const double acc = rc_loss_pose_units(body, x, y, F, units, cm, cj, (int)blockIdx.x, (int)gridDim.x, dx);
     rc_loss_store_partial(acc, s, partial);
 }
 
+// ---- position_error (rc_subnet_eval only): the mean Euclidean distance of the F W / 3 points (articulate/evaluator.py:129) ----------------
+// Unit u = points [u RC_EVAL_POINTS, (u + 1) RC_EVAL_POINTS): point 256 i + t of the unit is thread t's i-th. Three dwords of x and of y per
+// point (a wave's three loads cover 768 consecutive bytes; any alignment); differences, squares, the square root and the sum in double.
+__device__ __forceinline__ double rc_eval_point_units(const float* __restrict__ x, const float* __restrict__ y, long long P, long long units,
+                                                      double inv_p, int b, int nb) {
+    const int tid = threadIdx.x;
+    double acc = 0.0;
+    for (long long u = b; u < units; u += nb) {
+#pragma unroll
+        for (int i = 0; i < RC_EVAL_POINTS / 256; ++i) {
+            const long long p = u * RC_EVAL_POINTS + 256 * i + tid;
+            if (p < P) {
+                const double d0 = (double)x[3 * p] - (double)y[3 * p], d1 = (double)x[3 * p + 1] - (double)y[3 * p + 1],
+                             d2 = (double)x[3 * p + 2] - (double)y[3 * p + 2];
+                acc += sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+            }
+        }
+    }
+    return acc * inv_p;
+}
+
+// ---- the geometry of a call, shared by rc_subnet_loss and rc_subnet_eval: units, workgroups and the double reciprocals ----------------------
 static inline long long units_of(long long n, long long per) { return (n + per - 1) / per; }
+
+// g.frames, g.frame0 and g.blk0 set by the caller; fills g.nblk and g.c, returns the units
+static long long rc_loss_geometry(int kind, int W, EvalGroup& g) {
+    const long long F = g.frames, n = F * W;
+    long long units = 0;
+    g.c[0] = g.c[1] = g.c[2] = g.c[3] = 0.0;
+    if (kind == RC_LOSS_MSE || kind == RC_LOSS_BCE_LOGITS) {
+        units = units_of(n, RC_LOSS_CHUNK);
+        g.c[0] = 1.0 / (double)n;
+    } else if (kind == RC_LOSS_WINDOW_MSE) {
+        units = units_of(F, RC_LOSS_WINDOW_FRAMES);
+        g.c[0] = 1.0 / (3.0 * (double)F); g.c[1] = 1.0 / (3.0 * (double)(F / 6)); g.c[2] = 1.0 / (3.0 * (double)(F / 20));
+        g.c[3] = 1.0 / (3.0 * (double)(F / 60));
+    } else if (kind == RC_LOSS_POSE_FK) {
+        units = units_of(F, RC_LOSS_POSE_FRAMES);
+        g.c[0] = 1.0 / (144.0 * (double)F); g.c[1] = 100.0 / (72.0 * (double)F);
+    } else {                                                              // RC_EVAL_POSITION_ERROR
+        units = units_of(n / 3, RC_EVAL_POINTS);
+        g.c[0] = 1.0 / (double)(n / 3);
+    }
+    g.nblk = (int)(units < RC_LOSS_MAX_PARTIALS ? units : RC_LOSS_MAX_PARTIALS);
+    return units;
+}
+
+void rc_eval_group(int kind, int W, EvalGroup* g) { rc_loss_geometry(kind, W, *g); }
 
 // x, y (and dx) 16-byte aligned for every kind but window_mse; width and F checked by the caller (rc_subnet_loss)
 void rc_launch_subnet_loss(int kind, const BodyConst* body, const float* x, const float* y, long long F, int W, const float* aux,
                            double* partial, float* value, float* dx, hipStream_t st) {
     const long long n = F * W;
-    long long units = 0;
-    if (kind == RC_LOSS_MSE || kind == RC_LOSS_BCE_LOGITS) units = units_of(n, RC_LOSS_CHUNK);
-    else if (kind == RC_LOSS_WINDOW_MSE) units = units_of(F, RC_LOSS_WINDOW_FRAMES);
-    else units = units_of(F, RC_LOSS_POSE_FRAMES);
-    const int blocks = (int)(units < RC_LOSS_MAX_PARTIALS ? units : RC_LOSS_MAX_PARTIALS);
+    EvalGroup g{0, F, 0, 0, {0.0, 0.0, 0.0, 0.0}};
+    const long long units = rc_loss_geometry(kind, W, g);
+    const int blocks = g.nblk;
     const dim3 grid((unsigned)blocks), wg(256);
     if (kind == RC_LOSS_MSE) {
-        hipLaunchKernelGGL(rc_loss_elem_kernel<RC_LOSS_MSE>, grid, wg, 0, st, x, y, aux, n, units, 1.0 / (double)n, partial, dx);
+        hipLaunchKernelGGL(rc_loss_elem_kernel<RC_LOSS_MSE>, grid, wg, 0, st, x, y, aux, n, units, g.c[0], partial, dx);
     } else if (kind == RC_LOSS_BCE_LOGITS) {
-        hipLaunchKernelGGL(rc_loss_elem_kernel<RC_LOSS_BCE_LOGITS>, grid, wg, 0, st, x, y, aux, n, units, 1.0 / (double)n, partial, dx);
+        hipLaunchKernelGGL(rc_loss_elem_kernel<RC_LOSS_BCE_LOGITS>, grid, wg, 0, st, x, y, aux, n, units, g.c[0], partial, dx);
     } else if (kind == RC_LOSS_WINDOW_MSE) {
-        const LossWindow A{F, 1.0 / (3.0 * (double)F), 1.0 / (3.0 * (double)(F / 6)), 1.0 / (3.0 * (double)(F / 20)), 1.0 / (3.0 * (double)(F / 60))};
+        const LossWindow A{F, g.c[0], g.c[1], g.c[2], g.c[3]};
         hipLaunchKernelGGL(rc_loss_window_kernel, grid, wg, 0, st, x, y, A, units, partial, dx);
     } else {
-        hipLaunchKernelGGL(rc_loss_pose_kernel, grid, wg, 0, st, body, x, y, F, units, 1.0 / (144.0 * (double)F), 100.0 / (72.0 * (double)F),
-                           partial, dx);
+        hipLaunchKernelGGL(rc_loss_pose_kernel, grid, wg, 0, st, body, x, y, F, units, g.c[0], g.c[1], partial, dx);
     }
     hipLaunchKernelGGL(rc_loss_finish_kernel, dim3(1), dim3(256), 0, st, (const double*)partial, blocks, value);
 }
+
+// ---- rc_subnet_eval: the same sums per GROUP of a concatenated batch, one launch for all groups -----------------------------------------------
+// Workgroup B of the launch is workgroup B - tab[g].blk0 of group g's own tab[g].nblk (= what rc_subnet_loss would launch for the group's
+// slice): g is the last group with blk0 <= B, found by bisection. It runs the per-workgroup code above on the slice with the slice's
+// geometry, value only, and stores partial[B]; rc_eval_finish_kernel, one workgroup per group, adds the group's partials in index order.
+template <int KIND>
+__global__ __launch_bounds__(256) void rc_eval_kernel(const EvalGroup* __restrict__ tab, int groups, const BodyConst* __restrict__ body,
+                                                      const float* __restrict__ x, const float* __restrict__ y, int W,
+                                                      const float* __restrict__ aux, double* partial) {
+    __shared__ double s[256];
+    const int B = (int)blockIdx.x;
+    int lo = 0, hi = groups - 1;                                          // (uniform: every thread walks the same way)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].blk0 <= B) lo = mid; else hi = mid - 1;
+    }
+    const EvalGroup G = tab[lo];
+    const int b = B - G.blk0, nb = G.nblk;
+    const float* xg = x + G.frame0 * W;
+    const float* yg = y + G.frame0 * W;
+    const long long F = G.frames, n = F * W;
+    double acc;
+    if constexpr (KIND == RC_LOSS_MSE || KIND == RC_LOSS_BCE_LOGITS) {
+        const bool al = ((((unsigned long long)xg) | ((unsigned long long)yg)) & 15ull) == 0;
+        acc = rc_loss_elem_units<KIND>(xg, yg, aux, n, (n + RC_LOSS_CHUNK - 1) / RC_LOSS_CHUNK, G.c[0], b, nb, al, nullptr);
+    } else if constexpr (KIND == RC_LOSS_WINDOW_MSE) {
+        const LossWindow A{F, G.c[0], G.c[1], G.c[2], G.c[3]};
+        acc = rc_loss_window_units(xg, yg, A, (F + RC_LOSS_WINDOW_FRAMES - 1) / RC_LOSS_WINDOW_FRAMES, b, nb, nullptr);
+    } else if constexpr (KIND == RC_LOSS_POSE_FK) {                       // (576 bytes a frame: every group starts on the 16-byte grid)
+        acc = rc_loss_pose_units(body, xg, yg, F, (F + RC_LOSS_POSE_FRAMES - 1) / RC_LOSS_POSE_FRAMES, G.c[0], G.c[1], b, nb, nullptr);
+    } else {
+        const long long P = n / 3;
+        acc = rc_eval_point_units(xg, yg, P, (P + RC_EVAL_POINTS - 1) / RC_EVAL_POINTS, G.c[0], b, nb);
+    }
+    rc_loss_store_partial(acc, s, partial);
+}
+
+__global__ __launch_bounds__(256) void rc_eval_finish_kernel(const EvalGroup* __restrict__ tab, const double* partial, float* values) {
+    __shared__ double s[RC_LOSS_MAX_PARTIALS];
+    const EvalGroup G = tab[blockIdx.x];
+    for (int i = threadIdx.x; i < G.nblk; i += 256) s[i] = partial[G.blk0 + i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double sum = 0.0;
+    for (int i = 0; i < G.nblk; ++i) sum += s[i];                         // index order
+    values[blockIdx.x] = (float)sum;
+}
+
+// tab: DEVICE [groups], filled by rc_eval_group; blocks = sum of nblk; partial: `blocks` doubles. Two launches whatever `groups` is.
+void rc_launch_subnet_eval(int kind, const BodyConst* body, const EvalGroup* tab, int groups, long long blocks, const float* x, const float* y,
+                           int W, const float* aux, double* partial, float* values, hipStream_t st) {
+    const dim3 grid((unsigned)blocks), wg(256);
+    if (kind == RC_LOSS_MSE) hipLaunchKernelGGL(rc_eval_kernel<RC_LOSS_MSE>, grid, wg, 0, st, tab, groups, body, x, y, W, aux, partial);
+    else if (kind == RC_LOSS_BCE_LOGITS) hipLaunchKernelGGL(rc_eval_kernel<RC_LOSS_BCE_LOGITS>, grid, wg, 0, st, tab, groups, body, x, y, W, aux, partial);
+    else if (kind == RC_LOSS_WINDOW_MSE) hipLaunchKernelGGL(rc_eval_kernel<RC_LOSS_WINDOW_MSE>, grid, wg, 0, st, tab, groups, body, x, y, W, aux, partial);
+    else if (kind == RC_LOSS_POSE_FK) hipLaunchKernelGGL(rc_eval_kernel<RC_LOSS_POSE_FK>, grid, wg, 0, st, tab, groups, body, x, y, W, aux, partial);
+    else hipLaunchKernelGGL(rc_eval_kernel<RC_EVAL_POSITION_ERROR>, grid, wg, 0, st, tab, groups, body, x, y, W, aux, partial);
+    hipLaunchKernelGGL(rc_eval_finish_kernel, dim3((unsigned)groups), dim3(256), 0, st, tab, (const double*)partial, values);
+}
+

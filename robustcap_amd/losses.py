@@ -11,7 +11,14 @@ concatenated first, the loss function sees one [F, W] tensor of outputs and one 
 One HIP entry, ``rc_subnet_loss`` (csrc/rc_loss.hip), forms the value and ``dx = d value / d x`` in the same launch, summed in double in a
 fixed order: no read-back, no host synchronisation, the same bits on every run. ``dx`` is what ``backward()`` hands to
 ``rc_subnet_backward_train`` as ``dy``. Labels are constants; there is no double backward.
+
+The validation pass (train.py:101,131: ``sum([eval_fn(net(d), l) for d, l in vald_dataloader]) / num_vald_step``) takes its per-batch
+values from a second entry, ``rc_subnet_eval``: ``SubnetEval`` returns one value per validation batch of a concatenated output in one
+call -- the four kinds above, each group with the bits of ``SubnetLoss`` on its slice, and ``position_error``, the ``eval_fn`` of rnn2
+and rnn4 (net/sig_mp.py:341,556) -- and ``reference_mean`` is the reference's fp32 mean of them.
 """
+import ctypes as C
+
 import torch
 
 from . import _lib
@@ -27,6 +34,10 @@ CHUNK = 4096             # elements a workgroup owns at a time (mse, bce_logits)
 WINDOW_FRAMES = 240      # frames a workgroup owns at a time, counted from the end of the batch (window_mse)
 POSE_FRAMES = 16         # frames a workgroup owns at a time (pose_fk)
 MAX_PARTIALS = 1024      # workgroups of a call at most: beyond it a workgroup takes several such shares
+# the validation metrics (rc_subnet_eval): the four losses plus the reference's eval_fn of rnn2 and rnn4 (rc_eval_kind)
+EVAL_KINDS = dict(KINDS, position_error=16)
+EVAL_POINTS = 1024       # 3-D points a workgroup owns at a time (position_error; RC_EVAL_POINTS)
+EVAL_MAX_GROUPS = 65536  # groups of a call at most (RC_EVAL_MAX_GROUPS)
 
 
 def check_frames(kind, frames):
@@ -140,6 +151,84 @@ class SubnetLoss:
         y = _aligned(_concat([t.detach().to(net.device) for t in ls]))
         want_dx = torch.is_grad_enabled() and any(t.requires_grad for t in xs)
         return _LossFunction.apply(self, y, want_dx, *xs)
+
+
+class SubnetEval:
+    """``ev(ys, labels, group_rows=k)`` or ``ev(ys, labels, group_sizes=[...])`` -> device tensor [G]: the validation metric of every
+    validation batch of a concatenated output in ONE call (``rc_subnet_eval``), never differentiable. ``kind``: a key of
+    ``EVAL_KINDS`` -- a loss kind (value g has the bits of ``SubnetLoss(kind)`` on group g's slice) or ``"position_error"`` (rnn2's and
+    rnn4's ``eval_fn``, net/sig_mp.py:341,556: the mean distance of the group's 3-D points); ``pos_weight`` and ``width`` as
+    ``SubnetLoss``. ``ys`` / ``labels``: one [F, W] tensor or a list of [T_i, W] tensors each, as ``SubnetLoss`` takes them.
+    ``group_sizes``: the FRAMES of every group, in order, summing to F; ``group_rows=k``: consecutive groups of k of the sequences of
+    ``ys``, the last one smaller -- the batches of ``DataLoader(dataset, k)``. Every check raises ValueError before anything is
+    enqueued; consecutive views of one buffer are taken without a copy."""
+
+    def __init__(self, net, kind, pos_weight=None, width=None):
+        if kind not in EVAL_KINDS:
+            raise ValueError(f"evaluation kind {kind!r}: one of {sorted(EVAL_KINDS)}")
+        if kind == "position_error":
+            if pos_weight is not None:
+                raise ValueError("position_error takes no pos_weight")
+            if width is not None and (width < 3 or width % 3):
+                raise ValueError(f"position_error: width {width} is no multiple of 3")
+            self._net, self.kind, self.pos_weight = net, kind, None
+            self.widths = None if width is None else (int(width),)
+        else:
+            base = SubnetLoss(net, kind, pos_weight=pos_weight, width=width)
+            self._net, self.kind, self.pos_weight, self.widths = net, kind, base.pos_weight, base.widths
+
+    def _fits(self, w):
+        return (w >= 3 and w % 3 == 0) if self.widths is None else w in self.widths
+
+    def __call__(self, ys, labels, group_rows=None, group_sizes=None):
+        net = self._net
+        xs, xl, xw = _rows(ys, "ys", net.device)
+        ls, ll, lw = _rows(labels, "labels")
+        if not self._fits(xw) or lw != xw:
+            raise ValueError(f"{self.kind}: width {self.widths or 'a multiple of 3'} expected, ys have {xw}, labels {lw}")
+        if sum(xl) != sum(ll):
+            raise ValueError(f"ys hold {sum(xl)} frames, labels {sum(ll)}")
+        if (group_rows is None) == (group_sizes is None):
+            raise ValueError("exactly one of group_rows and group_sizes")
+        if group_rows is not None:
+            k = int(group_rows)
+            if k < 1:
+                raise ValueError(f"group_rows {group_rows}: at least 1")
+            sizes = [sum(xl[i:i + k]) for i in range(0, len(xl), k)]
+        else:
+            sizes = [int(s) for s in group_sizes]
+            if sum(sizes) != sum(xl):
+                raise ValueError(f"group_sizes sum to {sum(sizes)} frames, ys hold {sum(xl)}")
+        if not 1 <= len(sizes) <= EVAL_MAX_GROUPS:
+            raise ValueError(f"{len(sizes)} groups: 1 .. {EVAL_MAX_GROUPS} expected")
+        for g, s in enumerate(sizes):
+            try:
+                check_frames(self.kind, s)
+            except ValueError as e:
+                raise ValueError(f"group {g}: {e}") from None
+        needs_grid = self.kind in ("mse", "bce_logits", "pose_fk")
+        fit = _aligned if needs_grid else (lambda t: t)
+        x = fit(_concat([t.detach() for t in xs]))
+        y = fit(_concat([t.detach().to(net.device) for t in ls]))
+        G = len(sizes)
+        values = torch.empty(G, device=x.device)
+        rc = net._lib.rc_subnet_eval(net._ctx, EVAL_KINDS[self.kind], _lib.ptr(x), _lib.ptr(y), G, (C.c_int64 * G)(*sizes), xw,
+                                     _lib.ptr(self.pos_weight), _lib.ptr(values), _lib.stream_ptr())
+        _lib.check(net._ctx, rc, "rc_subnet_eval")
+        return values
+
+
+def reference_mean(values):
+    """The reference's ``sum([eval_fn(net(d), l) for (d, l) in valid_dataloader]) / num_vald_step`` (articulate/utils/torch/train.py:
+    101,131) of the per-batch ``values`` [G] as a Python float: Python's ``sum`` over fp32 0-d tensors is a sequential fp32 sum
+    starting from the int 0, in order, and the division by the int G stays in fp32. Reads ``values`` back (the one wait of a validation)."""
+    v = torch.as_tensor(values).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+    if v.numel() == 0:
+        raise ValueError("reference_mean: no values")
+    total = v[0].clone()
+    for i in range(1, v.numel()):
+        total = total + v[i]
+    return float(total / v.numel())
 
 
 def pos_weight_from_labels(labels):

@@ -314,13 +314,25 @@ class Net:
         from ..train import SubnetTrainer
         return SubnetTrainer(self, name, weight_grads)
 
+    def _flat_input(self, xs):
+        """``xs`` as one [F, in] tensor WITHOUT the copy of ``torch.cat`` where they are consecutive views of one contiguous, 16-byte
+        aligned fp32 buffer on this device (what ``ds.batch`` returns; ``losses._flat_view``), else None: the same bits either way, and
+        over a whole validation set that copy is the size of the corpus."""
+        from ..losses import _flat_view, _on
+        if any(t.dtype != torch.float32 or not _on(t, self.device) for t in xs):
+            return None
+        flat = _flat_view([t.detach() for t in xs])
+        return flat if flat is not None and flat.data_ptr() % 16 == 0 else None
+
     def _subnet_forward(self, name, x, init=None, return_state=False):
         """net.rnnK(x, init): rc_subnet_forward on the current stream. Bad input raises ValueError before anything is enqueued."""
         nin, H, nout = _SUBNETS[name]
         xs, h0, c0 = self._subnet_check(name, x, init)
         N = len(xs)
         lengths = [int(t.shape[0]) for t in xs]
-        xcat = torch.cat([t.to(device=self.device, dtype=torch.float32) for t in xs]).contiguous()
+        xcat = self._flat_input(xs)
+        if xcat is None:
+            xcat = torch.cat([t.to(device=self.device, dtype=torch.float32) for t in xs]).contiguous()
         y = torch.empty(sum(lengths), nout, device=self.device)
         fh = torch.empty(2, N, H, device=self.device) if return_state else None
         fc = torch.empty(2, N, H, device=self.device) if return_state else None
