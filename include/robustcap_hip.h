@@ -143,12 +143,30 @@ int rc_get_sequence_row_frames(rc_ctx* ctx, int64_t* body_frames);
  *           of the partial products down to 2^-16 of it (what is dropped is below 2^-23 of a product, i.e. below the
  *           rounding of the running fp32 sum); operands, accumulators, gates and state stay fp32. Same accuracy class as
  *           mode 0 (parity with the reference: tests), 2.7x fewer MFMA cycles per product.
+ *   mode 2: the fast mode, a REDUCED-precision one, for offline batches that can spend part of the 1e-4 m / 0.1 deg budget. Every fp32
+ *           operand a becomes TWO bf16 terms by rounding -- hi = RN_bf16(a) (round to nearest, ties to even), mid = RN_bf16(a - hi);
+ *           the subtraction is exact, nothing below mid is kept -- and a 16x16x32 block pair is three products with fp32
+ *           accumulation, small terms first: a_mid.w_hi, a_hi.w_mid, a_hi.w_hi. Half the MFMAs of mode 1 and 4 B per weight
+ *           instead of 6. Two finite operands' product is off by at most about 3 x 2^-16 |a w| (mode 1: 2^-23); |a| within half a
+ *           bf16 ulp of FLT_MAX rounds to inf where the truncation of mode 1 did not. Everything outside the products -- the order of
+ *           k-blocks, K quarters and halves, bias, epilogues, dispatch -- is mode 1's. The weight planes of this mode are built on the
+ *           device from the fp32 packing the first time a context is in mode 2 with finalized weights (a context that never is
+ *           allocates nothing) and follow every later weight change (rc_finalize_weights, rc_update_subnet_weights,
+ *           rc_subnet_optim_step). Against oracle/lstm_f64.py a step stays within G = 8 times the bound modes 0 and 1 are held to
+ *           (tests/test_gemm_mode2_cpu.py: where 8 comes from); the reference fixtures are reproduced to 5e-6 m / 1e-4 deg on the
+ *           seeded synthetic weights they use -- trained weights have not been tried. Never a default: rc_default_gemm_mode returns
+ *           0 or 1; RC_GEMM_SPLIT=2 in the environment makes new contexts start in it. The sub-net entries (rc_subnet_forward* /
+ *           _backward* / _weight_grads, rc_init_net_forward) return RC_ERR_INVALID in mode 2; the resident kernel (rc_set_resident) is
+ *           not used, a mode-2 context runs its segments on the streams; the lean live frame is fp32-only as before.
  * Default: mode 1 for contexts of batch >= 48, mode 0 below (weight-streaming bound: 6 B instead of 4 B per weight would
  * slow them). Within one mode a row's result does not depend on the batch, the tile shape or the engine
- * (bitwise); between the two modes results differ by fp32 rounding noise. rc_get_gemm_mode returns the mode. */
+ * (bitwise); between modes 0 and 1 results differ by fp32 rounding noise, mode 2 by the figures above. Any change of mode ends
+ * a live session. rc_get_gemm_mode returns the mode. */
 int rc_set_gemm_mode(rc_ctx* ctx, int32_t mode);
 int rc_get_gemm_mode(const rc_ctx* ctx);
-int rc_default_gemm_mode(int32_t total_rows);   /* the default of a context of that many rows: sharded runs pin every shard to the TOTAL's */
+int rc_default_gemm_mode(int32_t total_rows);   /* the default of a context of that many rows (0 or 1, never 2) */
+int rc_initial_gemm_mode(int32_t total_rows);   /* the mode rc_create gives a context of that many rows: the default, or 2 under RC_GEMM_SPLIT=2
+                                                   (the one reading of that variable). Sharded runs pin every shard to the TOTAL's */
 
 /* Sequence mode of rc_sequence (on by default). With mode >= 1 every rc_sequence call of T >= 2 frames first classifies
  * each (frame, row) on the device (the arithmetic of the per-frame prep kernel), reads the codes back -- ONE

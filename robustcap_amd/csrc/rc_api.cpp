@@ -454,11 +454,13 @@ int rc_finalize_weights(rc_ctx* ctx) {
     rc_live_end(ctx);
     HIP_TRY(ctx, hipDeviceSynchronize());
     ctx->weight_allocs.clear();
+    gemm_planes2_released(ctx);
     ctx->have_weights = false;
     seq_weights_changed(ctx);
     ctx->weights_epoch += 1;
     ctx->alloc_weights = true;
-    const int rc = finalize_weights_impl(ctx);
+    int rc = finalize_weights_impl(ctx);
+    if (rc == RC_OK) rc = gemm_planes2_ensure(ctx);          // a context in gemm mode 2: its planes, from the new packings
     ctx->alloc_weights = false;
     return rc;
 }
@@ -496,6 +498,7 @@ int rc_update_subnet_weights(rc_ctx* ctx, const char* net, const void* const* te
         for (int q = 0; q < 3; ++q)
             if (int rc = dense(ctx->init[q], T(12 + 2 * q), T(13 + 2 * q))) return rc;
     rc_subnet_retranspose(ctx->subnet.get(), ni, n.Wl, n.H, ctx->weights_epoch, st);
+    gemm_planes2_refresh(ctx, ni, st);
     HIP_TRY(ctx, hipGetLastError());
     // ... and before anything enqueued later, on whatever stream
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -581,6 +584,7 @@ int rc_subnet_optim_step(rc_ctx* ctx, const char* net, const void* const* params
     if (ni == N2)
         for (int q = 0; q < 3; ++q) dense(ctx->init[q], 12 + 2 * q);
     rc_subnet_retranspose(ctx->subnet.get(), ni, n.Wl, n.H, ctx->weights_epoch, st);
+    gemm_planes2_refresh(ctx, ni, st);
     HIP_TRY(ctx, hipGetLastError());
     if (live) {
         HIP_TRY(ctx, hipStreamSynchronize(st));

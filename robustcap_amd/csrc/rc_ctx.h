@@ -127,7 +127,14 @@ GemmProblem lstm_problem(const rc_ctx* c, const Stage& s, int layer);
 GemmProblem lin2_problem(const rc_ctx* c, const Stage& s);
 bool tile_env(const char* name, int* mr, int* nc);
 void pick_tile(int H, int rows, int* mr, int* nc);
-bool gemm_split(const rc_ctx* c);                             // the context's products are split-bf16 partial products (rc_set_gemm_mode)
+bool gemm_split(const rc_ctx* c);                             // the context's products are NOT fp32: split-bf16 partial products (rc_set_gemm_mode 1 or 2)
+int gemm_mode(const rc_ctx* c);                               // rc_get_gemm_mode: 0 fp32 MFMA, 1 six products of three truncated planes, 2 three products of two rounded planes
+// Mode 2's weight planes (two round-to-nearest bf16 planes per matrix, 4 B per weight), built on the device from the fp32 packings.
+// A context that never enters mode 2 has none. They live with the packed weights (rc_finalize_weights releases both) and are rewritten
+// in place, on the caller's stream, by whatever rewrites a sub-net's packings in place.
+void gemm_planes2_released(rc_ctx* ctx);                      // rc_finalize_weights freed the packed weights, the planes with them
+int gemm_planes2_ensure(rc_ctx* ctx);                         // mode 2 and finalized weights: allocate and build what is missing (synchronises the device)
+void gemm_planes2_refresh(rc_ctx* ctx, int net, hipStream_t st);   // sub-net `net`'s packings were rewritten on st: its planes follow, where the context has any
 // "This problem runs on the shared-weight kernel (rc_gemm_lds.hip)": a CONTEXT takes it (and the tri engine) in split-product mode from
 // RC_LDS_MIN_BATCH rows, a PROBLEM inside such a context from RC_LDS_MIN_ROWS rows.
 bool lds_context(const rc_ctx* c);

@@ -62,7 +62,8 @@ __device__ __forceinline__ float tanhf_(float x) { return rc_gate_tanh(x); }
 // v_mfma_f32_16x16x4_f32 instead of 32x32x2: same rate, half the accumulator traffic, measured -14 % time.
 // PIPE pins a software pipeline (loads of chunk q+1 issued before the MFMAs of chunk q) with sched_barrier;
 // without it hipcc issues both chunks' loads at the top of an iteration and drains them inside it.
-template <int MR, int NC, int D, bool PIPE, bool SPLIT = false, bool DEEPOK = true, bool NTW = false, bool W32 = (RC_SPLIT_W32 != 0)>
+// NP: planes per operand of the split products -- 3 (mode 1: six products per block pair) or 2 (mode 2: three, rc_mma.h: split2_rn)
+template <int MR, int NC, int D, bool PIPE, bool SPLIT = false, bool DEEPOK = true, bool NTW = false, bool W32 = (RC_SPLIT_W32 != 0), int NP = 3>
 __device__ __forceinline__ void gemm_tile(const GemmProblem& P, const int B, const int m_tile0, const int n_tile, float* s_mem) {
     constexpr int MT = 16 * MR, NT = 16 * NC, UT = 4 * NC, LD = NT + (MR >= 8 ? 4 : LDS_PAD);   // 128-row tiles: 140 KB with pad 4
 #ifdef RC_TRACE_TILES
@@ -130,9 +131,9 @@ __device__ __forceinline__ void gemm_tile(const GemmProblem& P, const int B, con
     // split products: the first k-blocks' weight planes depend on nothing the prologue computes -- requested here, behind the
     // step-counter reads (vmcnt completes in order) and in front of everything that waits for those, they travel while the
     // activation pointers are formed (a tile waits ~3 us for its first weights: profiles/r02_kloop_ablation.txt)
-    FragS<MR, NC, W32> fa = {}, fb = {};
+    FragS<MR, NC, W32, NP> fa = {}, fb = {};
     const int Qs = P.Kp / 32, Qws = Qs / RC_NW;                     // k-blocks per wave (K' % 128 == 0 -> >= 1)
-    constexpr int WPL = W32 ? 2 : 3;
+    constexpr int WPL = FragS<MR, NC, W32, NP>::WPL;
     constexpr int KBU = WPL * 64;                                   // uint4 per column block and k-block (planes, or fp32 chunks, x 64 lanes)
     const long long bs = (long long)Qs * KBU;                       // uint4 between consecutive 16-column blocks
     const u32x4* pbs = reinterpret_cast<const u32x4*>(W32 ? (const void*)P.W : P.Ws) + ((long long)(n_tile * NC) * Qs + (long long)wave * Qws) * KBU + lane;
@@ -205,7 +206,7 @@ __device__ __forceinline__ void gemm_tile(const GemmProblem& P, const int B, con
         // every row block's MFMAs -- was measured at -2 % / +-1 %: profiles/r02_kloop_ablation.txt.)
 #define STEP(FL, QL, FM) do { LOADS(FL, QL); SB(); mma_kblock(FM, acc); SB(); } while (0)
         if constexpr (DEEP) {
-            FragS<MR, NC, W32> fc = {};
+            FragS<MR, NC, W32, NP> fc = {};
             LOADS_A(fa, 0);
             LOADS_A(fb, min(1, Qws - 1));
             for (; q + 3 <= Qws; q += 3) {  // prefetch indices past the end are clamped: a redundant, valid load, no branch
@@ -410,21 +411,21 @@ __device__ __forceinline__ bool locate_tile(const GemmLaunch& L, int& pi, int& m
     return n_tile < P.n_tiles;
 }
 
-template <bool SPLIT>
+template <bool SPLIT, int NP = 3>
 __device__ __forceinline__ void wide_tiles(const GemmLaunch& L, float* s_mem) {
     int pi, m_tile, n_tile;
     if (!locate_tile(L, pi, m_tile, n_tile)) return;
     const GemmProblem& P = L.p[pi];
     switch (P.mr * 16 + P.nc) {
-        case 8 * 16 + 4: gemm_tile<8, 4, 2, true, SPLIT>(P, L.B, m_tile, n_tile, s_mem); break;
-        case 4 * 16 + 8: gemm_tile<4, 8, 2, true, SPLIT>(P, L.B, m_tile, n_tile, s_mem); break;
-        case 4 * 16 + 5: gemm_tile<4, 5, 2, true, SPLIT>(P, L.B, m_tile, n_tile, s_mem); break;
-        case 4 * 16 + 4: gemm_tile<4, 4, 2, true, SPLIT>(P, L.B, m_tile, n_tile, s_mem); break;
-        case 2 * 16 + 10: gemm_tile<2, 10, 2, true, SPLIT>(P, L.B, m_tile, n_tile, s_mem); break;
-        case 2 * 16 + 8: gemm_tile<2, 8, 2, true, SPLIT>(P, L.B, m_tile, n_tile, s_mem); break;
-        case 1 * 16 + 2: gemm_tile<1, 2, 8, true, SPLIT>(P, L.B, m_tile, n_tile, s_mem); break;
-        case 1 * 16 + 1: gemm_tile<1, 1, 8, true, SPLIT>(P, L.B, m_tile, n_tile, s_mem); break;
-        default: gemm_tile<2, 4, 2, true, SPLIT>(P, L.B, m_tile, n_tile, s_mem); break;
+        case 8 * 16 + 4: gemm_tile<8, 4, 2, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;
+        case 4 * 16 + 8: gemm_tile<4, 8, 2, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;
+        case 4 * 16 + 5: gemm_tile<4, 5, 2, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;
+        case 4 * 16 + 4: gemm_tile<4, 4, 2, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;
+        case 2 * 16 + 10: gemm_tile<2, 10, 2, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;
+        case 2 * 16 + 8: gemm_tile<2, 8, 2, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;
+        case 1 * 16 + 2: gemm_tile<1, 2, 8, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;
+        case 1 * 16 + 1: gemm_tile<1, 1, 8, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;
+        default: gemm_tile<2, 4, 2, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;
     }
 }
 
@@ -437,6 +438,11 @@ __global__ __launch_bounds__(RC_NW * 64, RC_WPS) void rc_gemm_split_kernel(const
     __shared__ __attribute__((aligned(16))) float s_mem[RC_LDS_FLOATS];
     wide_tiles<true>(L, s_mem);
 }
+// ... and with the three products of mode 2 (two round-to-nearest planes per operand: P.Ws points at the context's mode-2 planes)
+__global__ __launch_bounds__(RC_NW * 64, RC_WPS) void rc_gemm_split2_kernel(const GemmLaunch L) {
+    __shared__ __attribute__((aligned(16))) float s_mem[RC_LDS_FLOATS];
+    wide_tiles<true, 2>(L, s_mem);
+}
 
 // Split-product launches of 64 x 128 tiles in which every weight slice has ONE reader (a single row tile per problem: contexts of 33-64
 // rows on the wavefront engine): the weights stream as fp32 and are split in the K loop (W32, above).
@@ -446,20 +452,23 @@ __global__ __launch_bounds__(RC_NW * 64, RC_WPS) void rc_gemm_split48_w32_kernel
     if (!locate_tile(L, pi, m_tile, n_tile)) return;
     gemm_tile<4, 8, 2, true, true, true, false, true>(L.p[pi], L.B, m_tile, n_tile, s_mem);
 }
+// (Mode 2 has no such variant: its planes are 4 B per weight already, and the same launches measured faster reading them than rounding the
+// fp32 stream in the loop -- batch 64 mixed 726-730k against 707-709k body-frames/s, batch 48 556-603k against 550-559k,
+// profiles/gemm_mode2_bench.txt. They run on rc_gemm_split2_kernel.)
 
 // Launches whose tiles are all at most 32 x 64 (the linear1 launches; LSTM stages of batches below 128) do not need the
 // 148 KB of the wide kernel: with 41 KB of LDS and a register budget for two waves per SIMD three of these workgroups
 // share a CU, so the 328 short tiles of a linear1 launch no longer take two rounds of 256.
 #define RC_MID_LDS_FLOATS (RC_LDS_HEAD + RC_NW * 32 * (16 * 4 + LDS_PAD))
-template <bool SPLIT>
+template <bool SPLIT, int NP = 3>
 __device__ __forceinline__ void mid_tiles(const GemmLaunch& L, float* s_mem) {
     int pi, m_tile, n_tile;
     if (!locate_tile(L, pi, m_tile, n_tile)) return;
     const GemmProblem& P = L.p[pi];
     switch (P.mr * 16 + P.nc) {
-        case 1 * 16 + 2: gemm_tile<1, 2, 8, true, SPLIT>(P, L.B, m_tile, n_tile, s_mem); break;
-        case 1 * 16 + 1: gemm_tile<1, 1, 8, true, SPLIT>(P, L.B, m_tile, n_tile, s_mem); break;
-        default: gemm_tile<2, 4, 2, true, SPLIT, false>(P, L.B, m_tile, n_tile, s_mem); break;   // two buffers: 256-register budget
+        case 1 * 16 + 2: gemm_tile<1, 2, 8, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;
+        case 1 * 16 + 1: gemm_tile<1, 1, 8, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;
+        default: gemm_tile<2, 4, 2, true, SPLIT, false, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem); break;   // two buffers: 256-register budget
     }
 }
 __global__ __launch_bounds__(RC_NW * 64, 2) void rc_gemm_mid_kernel(const GemmLaunch L) {
@@ -470,6 +479,10 @@ __global__ __launch_bounds__(RC_NW * 64, 2) void rc_gemm_mid_split_kernel(const 
     __shared__ __attribute__((aligned(16))) float s_mem[RC_MID_LDS_FLOATS];
     mid_tiles<true>(L, s_mem);
 }
+__global__ __launch_bounds__(RC_NW * 64, 2) void rc_gemm_mid_split2_kernel(const GemmLaunch L) {
+    __shared__ __attribute__((aligned(16))) float s_mem[RC_MID_LDS_FLOATS];
+    mid_tiles<true, 2>(L, s_mem);
+}
 
 // Launches whose problems all use 16-row tiles (batch <= 16: live mode, transition rows) are weight-streaming, not
 // MFMA-bound: their own kernel with a 12 KB LDS footprint and a register budget for 4 waves per SIMD keeps four
@@ -478,7 +491,7 @@ __global__ __launch_bounds__(RC_NW * 64, 2) void rc_gemm_mid_split_kernel(const 
 // workgroups fill a CU's register file and lock the wide tiles' 300-register waves out; a variant with its LDS padded to
 // 60 KB, so that only one fits beside a wide-tile workgroup, still stretched a 116 us rnn4 launch to 150-220 us.)
 #define RC_SMALL_LDS_FLOATS (RC_LDS_HEAD + RC_NW * 16 * (16 * 2 + LDS_PAD))
-template <bool SPLIT, bool NTW = false>
+template <bool SPLIT, bool NTW = false, int NP = 3>
 __device__ __forceinline__ void small_tiles(const GemmLaunch& L, float* s_mem) {
     int pi, m_tile, n_tile;
     if (!locate_tile(L, pi, m_tile, n_tile)) return;
@@ -488,8 +501,8 @@ __device__ __forceinline__ void small_tiles(const GemmLaunch& L, float* s_mem) {
         else if (P.nt) gemm_tile<1, 1, 8, true, SPLIT, true, true>(P, L.B, m_tile, n_tile, s_mem);
         else gemm_tile<1, 1, 8, true, SPLIT, true, false>(P, L.B, m_tile, n_tile, s_mem);
     } else {
-        if (P.nc == 2) gemm_tile<1, 2, 4, true, SPLIT, true, false>(P, L.B, m_tile, n_tile, s_mem);
-        else gemm_tile<1, 1, 8, true, SPLIT, true, false>(P, L.B, m_tile, n_tile, s_mem);
+        if (P.nc == 2) gemm_tile<1, 2, 4, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem);
+        else gemm_tile<1, 1, 8, true, SPLIT, true, false, (RC_SPLIT_W32 != 0 && NP == 3), NP>(P, L.B, m_tile, n_tile, s_mem);
     }
 }
 __global__ __launch_bounds__(RC_NW * 64, 4) void rc_gemm_small_kernel(const GemmLaunch L) {
@@ -506,6 +519,30 @@ __global__ __launch_bounds__(RC_NW * 64, 4) void rc_gemm_small_nt_kernel(const G
 __global__ __launch_bounds__(RC_NW * 64, 4) void rc_gemm_small_split_kernel(const GemmLaunch L) {
     __shared__ __attribute__((aligned(16))) float s_mem[RC_SMALL_LDS_FLOATS];
     small_tiles<true>(L, s_mem);
+}
+__global__ __launch_bounds__(RC_NW * 64, 4) void rc_gemm_small_split2_kernel(const GemmLaunch L) {
+    __shared__ __attribute__((aligned(16))) float s_mem[RC_SMALL_LDS_FLOATS];
+    small_tiles<true, false, 2>(L, s_mem);
+}
+
+// Mode 2's weight planes, built on the device from the fp32 packing (the host copy is gone after rc_finalize_weights). A lane of the fp32
+// packing [cb][chunk of 16 k][lane][4] holds, in chunks 2 kb and 2 kb + 1, the very eight k that lane holds of k-block kb in the plane layout
+// [cb][kb][plane][lane][8] (rc_pack.h: rc_pack_store has the element map) -- so thread (cb, kb, lane) reads two float4 and stores two uint4,
+// split by the function the K loops split activations with.
+__global__ __launch_bounds__(256) void rc_planes2_kernel(const f32x4* __restrict__ W, u32x4* __restrict__ Ws2, long long n) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;     // (cb * Qs + kb) * 64 + lane
+    if (t >= n) return;
+    const long long blk = t >> 6;
+    const int lane = (int)(t & 63);
+    u32x4 h, m;
+    split2_rn(W[(2 * blk) * 64 + lane], W[(2 * blk + 1) * 64 + lane], h, m);
+    Ws2[(2 * blk) * 64 + lane] = h;
+    Ws2[(2 * blk + 1) * 64 + lane] = m;
+}
+void rc_launch_planes2(const float* W, void* Ws2, int Np, int Kp, hipStream_t s) {
+    const long long n = (long long)(Np / 16) * (Kp / 32) * 64;
+    hipLaunchKernelGGL(rc_planes2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(W),
+                       reinterpret_cast<u32x4*>(Ws2), n);
 }
 
 bool rc_gemm_is_small(const GemmLaunch& L) {
@@ -524,7 +561,7 @@ bool rc_gemm_is_mid(const GemmLaunch& L) {
 // true: a wide-tile split-product launch that rc_launch_gemm puts on rc_gemm_split48_w32_kernel (every problem 64 x 128 tiles, one row tile)
 bool rc_gemm_is_w32(const GemmLaunch& L) {
     if (rc_gemm_is_small(L) || rc_gemm_is_mid(L)) return false;
-    bool one_reader = L.split != 0;
+    bool one_reader = L.split == 1;
     for (int q = 0; q < L.n; ++q) one_reader = one_reader && L.p[q].mr == 4 && L.p[q].nc == 8 && L.p[q].m_tiles == 1;
     static const bool w32 = !std::getenv("RC_GEMM_W32") || std::atoi(std::getenv("RC_GEMM_W32")) != 0;
     return one_reader && w32;
@@ -536,14 +573,17 @@ void rc_launch_gemm(const GemmLaunch& L, int total_wg, hipStream_t s, hipEvent_t
     if (rc_gemm_is_small(L)) {
         bool single_reader = L.live != 0;      // a live frame's launch (rc_gemm_api.cpp: launch_problems)
         for (int q = 0; q < L.n; ++q) single_reader = single_reader && L.p[q].m_tiles == 1;
-        if (L.split) RC_GO(rc_gemm_small_split_kernel);
+        if (L.split == 2) RC_GO(rc_gemm_small_split2_kernel);
+        else if (L.split) RC_GO(rc_gemm_small_split_kernel);
         else if (single_reader) RC_GO(rc_gemm_small_nt_kernel);
         else RC_GO(rc_gemm_small_kernel);
     } else if (rc_gemm_is_mid(L)) {
-        if (L.split) RC_GO(rc_gemm_mid_split_kernel);
+        if (L.split == 2) RC_GO(rc_gemm_mid_split2_kernel);
+        else if (L.split) RC_GO(rc_gemm_mid_split_kernel);
         else RC_GO(rc_gemm_mid_kernel);
     } else {
         if (rc_gemm_is_w32(L)) RC_GO(rc_gemm_split48_w32_kernel);
+        else if (L.split == 2) RC_GO(rc_gemm_split2_kernel);
         else if (L.split) RC_GO(rc_gemm_split_kernel);
         else RC_GO(rc_gemm_kernel);
     }

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -30,7 +31,10 @@ const int kLdsRegions = 12;               // launches whose half sums can be in 
 
 // The event pool stands behind nothing that outlives it: default destruction is fine. (rc_destroy has synchronised the device.)
 struct GemmLauncher {
-    bool split = false;                  // products of every GEMM as split-bf16 partial products (rc_set_gemm_mode)
+    int mode = 0;                        // rc_set_gemm_mode: 0 fp32 MFMA, 1 split-bf16 products (three truncated planes, six products), 2 two rounded planes, three products
+    // mode 2: a matrix's three-plane packing (the Ws of every problem builder) -> its two-plane packing, swapped in where a launch is laid out.
+    // Empty until the context first enters mode 2 with finalized weights; the buffers are booked with the packed weights.
+    std::map<const void*, void*> planes2;
     bool live_launch = false;            // set while a live frame is captured / launched (GemmLaunch.live)
     unsigned live_nt_mask = 63u;         // RC_LIVE_NT_MASK: sub-nets (bit = kNets index) whose weights a live frame streams with non-temporal loads
     // LSTM tile shapes of full-batch stages (0 = pick_tile), RC_TILE_RNN4 / _RNN6 / _S2H512 / _RNN2. Full-batch LSTM stages (batch >= 128),
@@ -71,13 +75,16 @@ struct GemmLauncher {
 
 void rc_gemm_free(GemmLauncher* g) { delete g; }
 
-static int default_gemm_mode(int rows) { return tune_env("RC_GEMM_SPLIT", rows >= RC_SPLIT_MIN_BATCH ? 1 : 0) != 0 ? 1 : 0; }
+static int default_gemm_mode(int rows) { return tune_env("RC_GEMM_SPLIT", rows >= RC_SPLIT_MIN_BATCH ? 1 : 0) != 0 ? 1 : 0; }   // (never 2: mode 2 is asked for, not defaulted to)
+
+// the mode a new context of that many rows starts in: the default, or 2 where RC_GEMM_SPLIT=2 asks for it (rc_initial_gemm_mode)
+static int initial_gemm_mode(int rows) { return tune_env("RC_GEMM_SPLIT", -1) == 2 ? 2 : default_gemm_mode(rows); }
 
 int gemm_create(rc_ctx* ctx) {
     ctx->gemm.reset(new GemmLauncher());
     GemmLauncher& g = *ctx->gemm;
     const int batch = ctx->B;
-    g.split = default_gemm_mode(batch) != 0;
+    g.mode = initial_gemm_mode(batch);                      // RC_GEMM_SPLIT=2: the context starts in mode 2 (planes: rc_finalize_weights)
     g.live_nt_mask = (unsigned)tune_env("RC_LIVE_NT_MASK", 63);
     g.lds_min_rows = tune_env("RC_LDS_MIN_ROWS", std::min(160, std::max(64, batch / 2)));
     g.lds_min_batch = tune_env("RC_LDS_MIN_BATCH", g.lds_min_batch);
@@ -99,8 +106,9 @@ int gemm_create(rc_ctx* ctx) {
     return RC_OK;
 }
 
-bool gemm_split(const rc_ctx* c) { return c->gemm->split; }
-bool lds_context(const rc_ctx* c) { return c->gemm->split && c->gemm->lds_min_rows > 0 && c->B >= c->gemm->lds_min_batch; }
+bool gemm_split(const rc_ctx* c) { return c->gemm->mode != 0; }
+int gemm_mode(const rc_ctx* c) { return c->gemm->mode; }
+bool lds_context(const rc_ctx* c) { return c->gemm->mode != 0 && c->gemm->lds_min_rows > 0 && c->B >= c->gemm->lds_min_batch; }
 bool lds_problem(const rc_ctx* c, int rows) { return lds_context(c) && rows >= c->gemm->lds_min_rows; }
 
 LiveLaunchScope::LiveLaunchScope(rc_ctx* c) : ctx(c) { ctx->gemm->live_launch = true; }
@@ -204,6 +212,67 @@ GemmProblem lin2_problem(const rc_ctx* c, const Stage& s) {
     p.out_flags = c->fb.flags; p.out_bit = s.out_bit;
     p.nt = 1;
     return p;
+}
+
+// ------------------------------------------------------------------------------------------ mode 2's weight planes
+namespace {
+struct PackedMatrix { const float* W; const void* Ws; int Np, Kp; };
+// every matrix a gate-GEMM problem can name (net < 0: all of them; init_net travels with rnn2)
+std::vector<PackedMatrix> packed_matrices(const rc_ctx* ctx, int net) {
+    std::vector<PackedMatrix> m;
+    for (int i = 0; i < 6; ++i) {
+        if (net >= 0 && i != net) continue;
+        const NetDev& n = ctx->net[i];
+        m.push_back({n.lin1.W, n.lin1.Ws, n.lin1.Np, n.lin1.Kp});
+        m.push_back({n.lin2.W, n.lin2.Ws, n.lin2.Np, n.lin2.Kp});
+        for (int l = 0; l < 2; ++l) m.push_back({n.Wl[l], n.Wls[l], 4 * n.H, 2 * n.H});
+        if (i == N2)
+            for (int q = 0; q < 3; ++q) m.push_back({ctx->init[q].W, ctx->init[q].Ws, ctx->init[q].Np, ctx->init[q].Kp});
+    }
+    return m;
+}
+}  // namespace
+
+void gemm_planes2_released(rc_ctx* ctx) { ctx->gemm->planes2.clear(); }
+
+int gemm_planes2_ensure(rc_ctx* ctx) {
+    GemmLauncher& g = *ctx->gemm;
+    if (g.mode != 2 || !ctx->have_weights || !g.planes2.empty()) return RC_OK;
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    const bool booked = ctx->alloc_weights;
+    ctx->alloc_weights = true;                                   // freed with the packings they were made from
+    int rc = RC_OK;
+    for (const PackedMatrix& m : packed_matrices(ctx, -1)) {
+        uint16_t* q = nullptr;
+        if ((rc = dev_alloc(ctx, &q, (size_t)m.Np * m.Kp * 2, false)) != RC_OK) break;
+        rc_launch_planes2(m.W, q, m.Np, m.Kp, nullptr);
+        g.planes2[m.Ws] = q;
+    }
+    ctx->alloc_weights = booked;
+    if (rc == RC_OK && hipGetLastError() != hipSuccess) rc = fail(ctx, RC_ERR_HIP, "mode-2 weight planes: launch failed");
+    if (rc == RC_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(ctx, RC_ERR_HIP, "mode-2 weight planes: build failed");
+    if (rc != RC_OK) g.planes2.clear();                          // (what was allocated stays booked with the weights; nothing points at it)
+    return rc;
+}
+
+void gemm_planes2_refresh(rc_ctx* ctx, int net, hipStream_t st) {
+    GemmLauncher& g = *ctx->gemm;
+    if (g.planes2.empty()) return;
+    for (const PackedMatrix& m : packed_matrices(ctx, net)) {
+        const auto it = g.planes2.find(m.Ws);
+        if (it != g.planes2.end()) rc_launch_planes2(m.W, it->second, m.Np, m.Kp, st);
+    }
+}
+
+// mode 2: the problems of a launch read the two-plane packings. false: a matrix without planes (the launch must not go out)
+template <class P>
+static bool to_planes2(const GemmLauncher& g, P* p, int n) {
+    for (int i = 0; i < n; ++i) {
+        const auto it = g.planes2.find(p[i].Ws);
+        if (it == g.planes2.end()) return false;
+        p[i].Ws = it->second;
+    }
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------ slab pool, timing
@@ -329,8 +398,10 @@ static int launch_lds(rc_ctx* ctx, const std::vector<GemmProblem>& ps_in, const 
     size_t tiles = 0;
     build_lds_launch(ctx, ps, flags_override, region, L, &base, &tiles);
     if (tiles > region.tiles) return fail(ctx, RC_ERR_INVALID, "shared-weight launch: more tiles than its slab region holds");
+    const int planes = ctx->gemm->mode == 2 ? 2 : 3;
+    if (planes == 2 && !to_planes2(*ctx->gemm, L.p, L.n)) return fail(ctx, RC_ERR_STATE, "gemm mode 2: a matrix has no weight planes");
     ctx->gemm->stat_lds_launches += 1;
-    if (int rc = timed_launch(ctx, st, LAUNCH_SHARED, [&] { rc_launch_gemm_lds(L, base, st, stop); })) return rc;
+    if (int rc = timed_launch(ctx, st, LAUNCH_SHARED, [&] { rc_launch_gemm_lds(L, base, st, stop, planes); })) return rc;
     if (launched && stop) *launched = true;
     HIP_TRY(ctx, hipGetLastError());
     return RC_OK;
@@ -339,11 +410,11 @@ static int launch_lds(rc_ctx* ctx, const std::vector<GemmProblem>& ps_in, const 
 // ------------------------------------------------------------------------------------------ wide and small launches
 // The problems of one launch of the wide-tile / small-tile kernels, laid out: XCD-aligned problems first so that (block id % 8) is the XCD
 // for them, every problem's workgroups from a multiple of 8, the caller's row flags where it overrides them, the tile-trace slot.
-// Returns the workgroups of the launch; -1: more problems than a launch holds.
-static int lay_out_launch(const rc_ctx* ctx, const std::vector<GemmProblem>& ps, const unsigned char* flags_override, bool split, GemmLaunch& L) {
+// Returns the workgroups of the launch; -1: more problems than a launch holds, -2: mode 2 and a matrix without planes.
+static int lay_out_launch(const rc_ctx* ctx, const std::vector<GemmProblem>& ps, const unsigned char* flags_override, int mode, GemmLaunch& L) {
     L = GemmLaunch{};
     L.B = ctx->B;
-    L.split = split ? 1 : 0;
+    L.split = mode;
     L.live = ctx->gemm->live_launch ? 1 : 0;
     if ((int)ps.size() > RC_MAX_PROB) return -1;
     int base = 0;
@@ -357,6 +428,7 @@ static int lay_out_launch(const rc_ctx* ctx, const std::vector<GemmProblem>& ps,
             base += round_up(p.n_tiles * p.m_tiles, 8);
             p.trace_base = ctx->gemm->trace_next;
         }
+    if (mode == 2 && !to_planes2(*ctx->gemm, L.p, L.n)) return -2;
     return base;
 }
 
@@ -365,7 +437,7 @@ static int lay_out_launch(const rc_ctx* ctx, const std::vector<GemmProblem>& ps,
 // must agree bit for bit wherever the launch wrote (stderr: one line per problem).
 static bool dense_items_selftest_wanted(rc_ctx* ctx, const std::vector<GemmProblem>& ps, hipStream_t st, bool fp32) {
     static const int on = std::getenv("RC_DBG_DENSE_ITEMS") ? std::atoi(std::getenv("RC_DBG_DENSE_ITEMS")) : 0;
-    if (!on || !ctx->gemm->split || fp32 || ctx->B > 256 || seq_is_engine_stream(ctx, st) || (int)ps.size() > RC_RES_MAXP) return false;
+    if (!on || ctx->gemm->mode != 1 || fp32 || ctx->B > 256 || seq_is_engine_stream(ctx, st) || (int)ps.size() > RC_RES_MAXP) return false;
     for (const GemmProblem& p : ps)
         if (!(p.epi == RC_EPI_RELU && p.out_packed && p.N % 128 == 0 && p.Kp % 128 == 0 && p.out_bit == 0 && p.out_col0 == 0 && p.seg[0].par_mode == 0)) return false;
     return true;
@@ -405,7 +477,7 @@ static int dense_items_selftest(rc_ctx* ctx, const std::vector<GemmProblem>& ps,
     }
     {   // the launch itself (it also opens the step)
         GemmLaunch L{};
-        const int wg = lay_out_launch(ctx, ps, flags_override, true, L);
+        const int wg = lay_out_launch(ctx, ps, flags_override, 1, L);
         if (wg < 0) return fail(ctx, RC_ERR_INVALID, "too many fused problems");
         rc_launch_gemm(L, wg, st, nullptr);
         HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -439,7 +511,7 @@ int launch_problems(rc_ctx* ctx, std::vector<GemmProblem> ps, const unsigned cha
         std::vector<GemmProblem> lds, rest;
         for (GemmProblem& p : ps) {
             if (p.mr == 16) {
-                if (g.split && !fp32 && p.epi == RC_EPI_LSTM && (int)lds.size() < RC_LDS_MAXP) { lds.push_back(p); continue; }
+                if (g.mode != 0 && !fp32 && p.epi == RC_EPI_LSTM && (int)lds.size() < RC_LDS_MAXP) { lds.push_back(p); continue; }
                 p.mr = 4; p.nc = 8; p.m_tiles *= 4;
             }
             rest.push_back(p);
@@ -455,7 +527,8 @@ int launch_problems(rc_ctx* ctx, std::vector<GemmProblem> ps, const unsigned cha
         return launch_problems(ctx, tail, flags_override, st, fp32, stop, launched);
     }
     GemmLaunch L{};
-    const int base = lay_out_launch(ctx, ps, flags_override, g.split && !fp32, L);
+    const int base = lay_out_launch(ctx, ps, flags_override, fp32 ? 0 : g.mode, L);
+    if (base == -2) return fail(ctx, RC_ERR_STATE, "gemm mode 2: a matrix has no weight planes");
     if (base < 0) return fail(ctx, RC_ERR_INVALID, "too many fused problems");
     g.trace_next = (g.trace_next + base) & 0x3fffffff;
     const bool small = rc_gemm_is_small(L);
@@ -470,19 +543,25 @@ int launch_problems(rc_ctx* ctx, std::vector<GemmProblem> ps, const unsigned cha
 #pragma GCC visibility pop
 
 // =============================================================================================== C ABI
-int rc_ctx_gemm_split(rc_ctx* ctx) { return ctx->gemm->split ? 1 : 0; }
+int rc_ctx_gemm_split(rc_ctx* ctx) { return ctx->gemm->mode != 0 ? 1 : 0; }
+int rc_ctx_gemm_mode(rc_ctx* ctx) { return ctx->gemm->mode; }
 
 extern "C" {
 
 int rc_set_gemm_mode(rc_ctx* ctx, int32_t mode) {
-    if (!ctx || mode < 0 || mode > 1) return ctx ? fail(ctx, RC_ERR_INVALID, "rc_set_gemm_mode: 0 (fp32 MFMA) or 1 (split-bf16 products)") : RC_ERR_INVALID;
-    if ((mode != 0) != ctx->gemm->split) rc_live_end(ctx);      // a captured frame has the kernel choice baked in
-    ctx->gemm->split = mode != 0;
+    if (!ctx || mode < 0 || mode > 2)
+        return ctx ? fail(ctx, RC_ERR_INVALID, "rc_set_gemm_mode: 0 (fp32 MFMA), 1 (split-bf16, six products) or 2 (two rounded bf16 terms, three products)") : RC_ERR_INVALID;
+    if (mode == ctx->gemm->mode) return RC_OK;
+    rc_live_end(ctx);                                           // a captured frame has the kernel choice baked in
+    const int was = ctx->gemm->mode;
+    ctx->gemm->mode = mode;
+    if (int rc = gemm_planes2_ensure(ctx)) { ctx->gemm->mode = was; return rc; }   // (before rc_finalize_weights: built there)
     return RC_OK;
 }
-int rc_get_gemm_mode(const rc_ctx* ctx) { return ctx ? (ctx->gemm->split ? 1 : 0) : RC_ERR_INVALID; }
+int rc_get_gemm_mode(const rc_ctx* ctx) { return ctx ? ctx->gemm->mode : RC_ERR_INVALID; }
 // (honours RC_GEMM_SPLIT like rc_create does: a sharded run pins every shard to this value)
 int rc_default_gemm_mode(int32_t total_rows) { return default_gemm_mode(total_rows); }
+int rc_initial_gemm_mode(int32_t total_rows) { return initial_gemm_mode(total_rows); }
 
 int rc_get_launch_stats_w32(rc_ctx* ctx, int64_t* w32_launches) {
     if (!ctx || !w32_launches) return RC_ERR_INVALID;

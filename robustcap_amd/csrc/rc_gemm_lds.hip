@@ -38,6 +38,7 @@
 #include "rc_internal.h"
 #include <hip/hip_ext.h>
 #include "rc_gates.h"
+#include "rc_mma.h"             // split2_rn: mode 2 rounds activations with the function that built its weight planes
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -76,9 +77,11 @@ extern "C" int rc_trace_lds_set(unsigned long long* buf, unsigned long long cap_
 namespace {
 
 constexpr int kWaves = 8;                     // waves per workgroup
-constexpr int kStage = 8 * 3 * 1024;          // bytes of one k-block of weight planes in the ring: [column block][plane][lane] x 16 B
-constexpr int kRing = 4;                      // stages (a power of two; three are in use at any time)
-constexpr int kPW = 3;                        // LDS-DMA pieces per wave and k-block (one column block's three planes)
+// NP = planes per operand: 3 (mode 1: six products per block pair) or 2 (mode 2: three products of two round-to-nearest terms). The plane
+// count is a template parameter of the kernel, of lds_item and of k_half; with it go the stage size, the pieces a wave moves per k-block
+// (and so every counted vmcnt / lgkmcnt wait of the loop) and the products of a slot.
+template <int NP> constexpr int kStageOf = 8 * NP * 1024;   // bytes of one k-block of weight planes in the ring: [column block][plane][lane] x 16 B
+constexpr int kRing = 4;                      // stages (a power of two; three are in use at any time): 96 KiB with three planes, 64 KiB with two
 constexpr int kCnt = 3 * kWaves;              // ints of the row scan's scratch: per wave its count (+ active-block bits), then its ballot (two words)
 constexpr int kRowIdle = (int)0x80000000u;    // s_rows entry in block mode: a row of an active storage block that does not step (multiplied, never stored)
 constexpr int kRowMask = 0x7fffffff;
@@ -119,6 +122,16 @@ __device__ __forceinline__ void glds(const u32x4* g, unsigned lds_) {
 }
 template <int OFF>
 __device__ __forceinline__ void dsread(u32x4& d, unsigned addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory"); }
+template <int N>
+__device__ __forceinline__ void wait_lgkm_tie(u32x4 (&b)[N]) {      // all but the N youngest LDS reads have landed: the planes in b are there
+    if constexpr (N == 3) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]) :: "memory");
+    else asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(b[0]), "+v"(b[1]) :: "memory");
+}
+template <int N>
+__device__ __forceinline__ void tie_planes(u32x4 (&b)[N]) {
+    if constexpr (N == 3) asm volatile("" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]));
+    else asm volatile("" : "+v"(b[0]), "+v"(b[1]));
+}
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
@@ -166,14 +179,16 @@ struct HalfArgs {
 // One half of K for a wave that multiplies NR of its two row blocks (0: the wave only moves its share of the weight planes).
 // k-block Q: [activations of Q (requested two k-blocks ago) are split | the buffer and the ring stage go to k-block Q + 2 |
 // 8 slots: one column block each, its planes requested a slot earlier | at slot 7: B(Q + 1) landed, barrier].
-// Vector-memory operations complete in order, so with the issue order A(Q + 1), B(Q + 1), A(Q + 2), B(Q + 2) "all but the NA + 3
+// Vector-memory operations complete in order, so with the issue order A(Q + 1), B(Q + 1), A(Q + 2), B(Q + 2) "all but the NA + NP
 // youngest" is exactly "A(Q + 1) and B(Q + 1) have landed".
-template <int NR, bool SHORT_OK>
+template <int NR, bool SHORT_OK, int NP>
 __device__ __forceinline__ void k_half(const HalfArgs& c, f32x4 (&acc0)[2][8], f32x4 (&acc1)[2][8]) {
+    constexpr int kStage = kStageOf<NP>;
+    constexpr int kPW = NP;                   // LDS-DMA pieces per wave and k-block (one column block's planes)
     constexpr int NA = 2 * NR;                // activation loads per k-block
     f32x4 raw[2][2][2];                       // [buffer][row block][chunk of 16 k]
-    u32x4 pl[2][3];                           // [row block][plane] of the k-block being multiplied
-    u32x4 bf[2][3];                           // [buffer][plane] of one column block's weights
+    u32x4 pl[2][NP];                           // [row block][plane] of the k-block being multiplied
+    u32x4 bf[2][NP];                           // [buffer][plane] of one column block's weights
     const int Qh = c.Qh;
 #define ISSUE_A(BUF, QI)                                                                                                    \
     do {                                                                                                                    \
@@ -183,9 +198,9 @@ __device__ __forceinline__ void k_half(const HalfArgs& c, f32x4 (&acc0)[2][8], f
     } while (0)
 #define ISSUE_B(QI)                                                                                                         \
     do {                                                                                                                    \
-        const u32x4* g_ = c.pw + (long long)min((QI), Qh - 1) * 192;                                                        \
+        const u32x4* g_ = c.pw + (long long)min((QI), Qh - 1) * (64 * NP);                                                        \
         const unsigned dst_ = c.my_lds + (unsigned)((QI) & (kRing - 1)) * kStage;                                           \
-        glds<0>(g_, dst_); glds<1024>(g_, dst_); glds<2048>(g_, dst_);                                                      \
+        glds<0>(g_, dst_); glds<1024>(g_, dst_); if constexpr (NP == 3) glds<2048>(g_, dst_);                                                    \
     } while (0)
 #define TIE_RAW(BUF)                                                                                                        \
     do {                                                                                                                    \
@@ -202,17 +217,20 @@ __device__ __forceinline__ void k_half(const HalfArgs& c, f32x4 (&acc0)[2][8], f
         if constexpr (NR > 0) {                                                                                             \
             if ((J) == 7) {                                                                                                 \
                 const unsigned a_ = c.rd0 + (unsigned)(((Q) + 1) & (kRing - 1)) * kStage;                                   \
-                dsread<0>(bf[bi_ ^ 1][0], a_); dsread<1024>(bf[bi_ ^ 1][1], a_); dsread<2048>(bf[bi_ ^ 1][2], a_);          \
+                dsread<0>(bf[bi_ ^ 1][0], a_); dsread<1024>(bf[bi_ ^ 1][1], a_);                                            \
+                if constexpr (NP == 3) dsread<2048>(bf[bi_ ^ 1][NP - 1], a_);                                               \
             } else {                                                                                                        \
                 const unsigned a_ = c.rd0 + (unsigned)((Q) & (kRing - 1)) * kStage;                                         \
-                dsread<((J) + 1) * 3072>(bf[bi_ ^ 1][0], a_); dsread<((J) + 1) * 3072 + 1024>(bf[bi_ ^ 1][1], a_);          \
-                dsread<((J) + 1) * 3072 + 2048>(bf[bi_ ^ 1][2], a_);                                                        \
+                dsread<((J) + 1) * NP * 1024>(bf[bi_ ^ 1][0], a_); dsread<((J) + 1) * NP * 1024 + 1024>(bf[bi_ ^ 1][1], a_); \
+                if constexpr (NP == 3) dsread<((J) + 1) * NP * 1024 + 2048>(bf[bi_ ^ 1][NP - 1], a_);                       \
             }                                                                                                               \
-            asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(bf[bi_][0]), "+v"(bf[bi_][1]), "+v"(bf[bi_][2]) :: "memory");        \
+            wait_lgkm_tie<NP>(bf[bi_]);                                                                                     \
             /* gemm_tile's products in its order (mma_kblock): small terms first */                                         \
-            RC_MFMA(pl[0][2], bf[bi_][0], ACC[0][J]); if constexpr (NR > 1) RC_MFMA(pl[1][2], bf[bi_][0], ACC[1][J]);       \
-            RC_MFMA(pl[0][0], bf[bi_][2], ACC[0][J]); if constexpr (NR > 1) RC_MFMA(pl[1][0], bf[bi_][2], ACC[1][J]);       \
+            if constexpr (NP == 3) {                                                                                        \
+            RC_MFMA(pl[0][NP - 1], bf[bi_][0], ACC[0][J]); if constexpr (NR > 1) RC_MFMA(pl[1][NP - 1], bf[bi_][0], ACC[1][J]); \
+            RC_MFMA(pl[0][0], bf[bi_][NP - 1], ACC[0][J]); if constexpr (NR > 1) RC_MFMA(pl[1][0], bf[bi_][NP - 1], ACC[1][J]); \
             RC_MFMA(pl[0][1], bf[bi_][1], ACC[0][J]); if constexpr (NR > 1) RC_MFMA(pl[1][1], bf[bi_][1], ACC[1][J]);       \
+            }       /* (two planes: a_mid . w_hi, a_hi . w_mid, a_hi . w_hi -- the last three of the six) */                   \
             RC_MFMA(pl[0][1], bf[bi_][0], ACC[0][J]); if constexpr (NR > 1) RC_MFMA(pl[1][1], bf[bi_][0], ACC[1][J]);       \
             RC_MFMA(pl[0][0], bf[bi_][1], ACC[0][J]); if constexpr (NR > 1) RC_MFMA(pl[1][0], bf[bi_][1], ACC[1][J]);       \
             RC_MFMA(pl[0][0], bf[bi_][0], ACC[0][J]); if constexpr (NR > 1) RC_MFMA(pl[1][0], bf[bi_][0], ACC[1][J]);       \
@@ -224,12 +242,14 @@ __device__ __forceinline__ void k_half(const HalfArgs& c, f32x4 (&acc0)[2][8], f
         if constexpr (NR > 0) {                                                                                             \
             wait_vm<NA + kPW>();                                                                                            \
             TIE_RAW(CUR);                                                                                                   \
-            split_block(raw[CUR][0][0], raw[CUR][0][1], pl[0][0], pl[0][1], pl[0][2]);                                      \
-            asm volatile("" : "+v"(pl[0][0]), "+v"(pl[0][1]), "+v"(pl[0][2]));                                              \
+            if constexpr (NP == 3) split_block(raw[CUR][0][0], raw[CUR][0][1], pl[0][0], pl[0][1], pl[0][NP - 1]);          \
+            else split2_rn(raw[CUR][0][0], raw[CUR][0][1], pl[0][0], pl[0][1]);                                            \
+            tie_planes<NP>(pl[0]);                                                                                          \
         }                                                                                                                   \
         if constexpr (NR > 1) {                                                                                             \
-            split_block(raw[CUR][1][0], raw[CUR][1][1], pl[1][0], pl[1][1], pl[1][2]);                                      \
-            asm volatile("" : "+v"(pl[1][0]), "+v"(pl[1][1]), "+v"(pl[1][2]));                                              \
+            if constexpr (NP == 3) split_block(raw[CUR][1][0], raw[CUR][1][1], pl[1][0], pl[1][1], pl[1][NP - 1]);          \
+            else split2_rn(raw[CUR][1][0], raw[CUR][1][1], pl[1][0], pl[1][1]);                                            \
+            tie_planes<NP>(pl[1]);                                                                                          \
         }                                                                                                                   \
         ISSUE_A(CUR, (Q) + 2);                                                                                              \
         ISSUE_B((Q) + 2);                                                                                                   \
@@ -246,7 +266,7 @@ __device__ __forceinline__ void k_half(const HalfArgs& c, f32x4 (&acc0)[2][8], f
         wait_vm<NA + kPW>();
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if constexpr (NR > 0) { dsread<0>(bf[0][0], c.rd0); dsread<1024>(bf[0][1], c.rd0); dsread<2048>(bf[0][2], c.rd0); }
+    if constexpr (NR > 0) { dsread<0>(bf[0][0], c.rd0); dsread<1024>(bf[0][1], c.rd0); if constexpr (NP == 3) dsread<2048>(bf[0][NP - 1], c.rd0); }
     // Resident kernel (SHORT_OK). The loads of this loop are asm the compiler only sees REQUESTING a register (raw[]: two k-blocks ahead,
     // bf[]: one column block ahead); it is free to copy or spill that register the next instruction. The launch-per-tick kernel never gave
     // it a reason to; the resident kernel's longer-lived state does, and its register allocation spills in front of the loop headers -- a
@@ -258,7 +278,7 @@ __device__ __forceinline__ void k_half(const HalfArgs& c, f32x4 (&acc0)[2][8], f
         if constexpr (SHORT_OK && RC_LAND) {                                                                                \
             asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");                                        \
             TIE_RAW(0); TIE_RAW(1);                                                                                         \
-            if constexpr (NR > 0) asm volatile("" : "+v"(bf[0][0]), "+v"(bf[0][1]), "+v"(bf[0][2]), "+v"(bf[1][0]), "+v"(bf[1][1]), "+v"(bf[1][2])); \
+            if constexpr (NR > 0) { tie_planes<NP>(bf[0]); tie_planes<NP>(bf[1]); }                                         \
         }                                                                                                                   \
     } while (0)
     LAND_ALL();
@@ -274,7 +294,7 @@ __device__ __forceinline__ void k_half(const HalfArgs& c, f32x4 (&acc0)[2][8], f
     // the wait above. (Without this the straight-line short-K path reused them -- for addresses -- while the loads were in flight: a memory
     // fault two instructions later. The loop form kept them alive as loop-carried values by luck of structure, not by contract.)
     TIE_RAW(0); TIE_RAW(1);
-    if constexpr (NR > 0) asm volatile("" : "+v"(bf[0][0]), "+v"(bf[0][1]), "+v"(bf[0][2]), "+v"(bf[1][0]), "+v"(bf[1][1]), "+v"(bf[1][2]));
+    if constexpr (NR > 0) { tie_planes<NP>(bf[0]); tie_planes<NP>(bf[1]); }
 #undef LAND_ALL
 #undef ITER
 #undef SLOT
@@ -288,7 +308,7 @@ __device__ __forceinline__ void k_half(const HalfArgs& c, f32x4 (&acc0)[2][8], f
 // One work item (a half tile, or a whole one with ksplit = 1; the padding of a problem's item range to a multiple of 8 included) of a launch:
 // the body of rc_gemm_lds_kernel, and of every turn of the resident kernel's loop. Returns 1 when the item wrote the tile's h / c (a
 // finisher), 0 otherwise; *pi_out = the item's problem.
-template <int MAXP, bool WITH_DENSE, typename PP>   // PP: pointer to the launch's problems -- kernel arguments, or the resident kernel's table in the constant address space
+template <int MAXP, bool WITH_DENSE, int NP, typename PP>   // NP: planes per operand (3: mode 1, 2: mode 2); PP: pointer to the launch's problems -- kernel arguments, or the resident kernel's table in the constant address space
 __device__ __forceinline__ int lds_item(const PP Lp, const int Ln, const int LB, const int item, unsigned char* ring, int* s_rows, int* s_cnt, int* pi_out) {
 #ifdef RC_TRACE_TILES
     unsigned long long trace_t[4] = {0, 0, 0, 0};
@@ -313,6 +333,7 @@ __device__ __forceinline__ int lds_item(const PP Lp, const int Ln, const int LB,
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, kq = lane >> 4;
     const unsigned ring0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)ring;
+    constexpr int kStage = kStageOf<NP>;
 
     // The first two k-blocks of weight planes depend on nothing the prologue computes: requested here, they travel (from HBM: every
     // slice has one reader per launch) while the rows are selected and their step numbers read -- three dependent memory round trips.
@@ -320,11 +341,11 @@ __device__ __forceinline__ int lds_item(const PP Lp, const int Ln, const int LB,
     HalfArgs hc;
     hc.Qh = Qh; hc.Qq = Qh >> 1;
     hc.rd0 = ring0 + lane * 16;
-    hc.my_lds = ring0 + (unsigned)wave * 3072u;
+    hc.my_lds = ring0 + (unsigned)wave * (NP * 1024u);
     {
-        const u32x4* g_ = reinterpret_cast<const u32x4*>(P.Ws) + ((long long)(n_tile * 8 + wave) * Qs + (long long)kh0 * Qh) * 192 + lane;
-        glds<0>(g_, hc.my_lds); glds<1024>(g_, hc.my_lds); glds<2048>(g_, hc.my_lds);
-        glds<0>(g_ + 192, hc.my_lds + kStage); glds<1024>(g_ + 192, hc.my_lds + kStage); glds<2048>(g_ + 192, hc.my_lds + kStage);
+        const u32x4* g_ = reinterpret_cast<const u32x4*>(P.Ws) + ((long long)(n_tile * 8 + wave) * Qs + (long long)kh0 * Qh) * (64 * NP) + lane;
+        glds<0>(g_, hc.my_lds); glds<1024>(g_, hc.my_lds); if constexpr (NP == 3) glds<2048>(g_, hc.my_lds);
+        glds<0>(g_ + 64 * NP, hc.my_lds + kStage); glds<1024>(g_ + 64 * NP, hc.my_lds + kStage); if constexpr (NP == 3) glds<2048>(g_ + 64 * NP, hc.my_lds + kStage);
     }
     // ---- active rows of this row tile (gemm_tile's stateless compaction, 256 rows per tile) ------------------------------------
     const int lo = m_tile * 256;
@@ -425,16 +446,16 @@ __device__ __forceinline__ int lds_item(const PP Lp, const int Ln, const int LB,
             if (WITH_DENSE && P.sel_bit != 0 && !(P.sel_flags[row_c[r]] & P.sel_bit)) a_base = P.alt[kh];      // a rider's row: its deferred input
             hc.pa[r] = a_base + (long long)par * sg.par_stride + rc_pk(row_r[r], 4 * kq, sg.ld);
         }
-        hc.pw = reinterpret_cast<const u32x4*>(P.Ws) + ((long long)(n_tile * 8 + wave) * Qs + (long long)kh * Qh) * 192 + lane;
+        hc.pw = reinterpret_cast<const u32x4*>(P.Ws) + ((long long)(n_tile * 8 + wave) * Qs + (long long)kh * Qh) * (64 * NP) + lane;
         hc.primed = kh == kh0;
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
             for (int j = 0; j < 8; ++j) { acc0[r][j] = f32x4{0.f, 0.f, 0.f, 0.f}; acc1[r][j] = acc0[r][j]; }
         if (kh == kh0) LDS_T(1);
-        if (nr == 2) k_half<2, WITH_DENSE>(hc, acc0, acc1);
-        else if (nr == 1) k_half<1, WITH_DENSE>(hc, acc0, acc1);
-        else k_half<0, WITH_DENSE>(hc, acc0, acc1);
+        if (nr == 2) k_half<2, WITH_DENSE, NP>(hc, acc0, acc1);
+        else if (nr == 1) k_half<1, WITH_DENSE, NP>(hc, acc0, acc1);
+        else k_half<0, WITH_DENSE, NP>(hc, acc0, acc1);
         if (dense && kh == 1) {
             // a dense layer sums its quarters in sequence, ((p0 + p1) + p2) + p3 as gemm_tile's dense epilogue does: the parked p0 + p1 (this
             // workgroup's own stores: ksplit = 1) comes back here and the epilogue finds the finished sum in acc0
@@ -576,11 +597,21 @@ __device__ __forceinline__ int lds_item(const PP Lp, const int Ln, const int LB,
 }
 
 __global__ __launch_bounds__(kWaves * 64, 1) void rc_gemm_lds_kernel(const LdsLaunch L) {
-    __shared__ __attribute__((aligned(1024))) unsigned char ring[kRing * kStage];
+    __shared__ __attribute__((aligned(1024))) unsigned char ring[kRing * kStageOf<3>];
     __shared__ int s_rows[256];
     __shared__ int s_cnt[kCnt];
     int pi;
-    (void)lds_item<RC_LDS_MAXP, false, const LdsProblem*>(L.p, L.n, L.B, (int)blockIdx.x, ring, s_rows, s_cnt, &pi);
+    (void)lds_item<RC_LDS_MAXP, false, 3, const LdsProblem*>(L.p, L.n, L.B, (int)blockIdx.x, ring, s_rows, s_cnt, &pi);
+}
+// Mode 2: the same item on two planes per operand (P.Ws: the context's mode-2 planes) -- 16 KiB stages, two DMA pieces per wave and k-block,
+// three MFMAs per block pair and slot. LDS: 4 x 16 KiB of ring + 1.1 KiB; a second workgroup per CU would fit the LDS but not the register
+// file (the two quarter chains alone are 128 accumulator registers per lane: one 8-wave workgroup per CU either way).
+__global__ __launch_bounds__(kWaves * 64, 1) void rc_gemm_lds2_kernel(const LdsLaunch L) {
+    __shared__ __attribute__((aligned(1024))) unsigned char ring[kRing * kStageOf<2>];
+    __shared__ int s_rows[256];
+    __shared__ int s_cnt[kCnt];
+    int pi;
+    (void)lds_item<RC_LDS_MAXP, false, 2, const LdsProblem*>(L.p, L.n, L.B, (int)blockIdx.x, ring, s_rows, s_cnt, &pi);
 }
 
 // ================================================================================================ resident kernel
@@ -620,7 +651,7 @@ __device__ __forceinline__ void resident_wait(const ResidentArgs& R, const __att
 }
 
 __global__ __launch_bounds__(kWaves * 64, 1) void rc_gemm_resident_kernel(const ResidentArgs R) {
-    __shared__ __attribute__((aligned(1024))) unsigned char ring[kRing * kStage];
+    __shared__ __attribute__((aligned(1024))) unsigned char ring[kRing * kStageOf<3>];
     __shared__ int s_rows[256];
     __shared__ int s_cnt[kCnt];
     __shared__ int s_item;
@@ -662,7 +693,7 @@ __global__ __launch_bounds__(kWaves * 64, 1) void rc_gemm_resident_kernel(const 
         resident_wait(R, T, k, pi);
         RES_STAMP(p_wait);
         typedef const __attribute__((address_space(4))) LdsProblem* ProbC;
-        (void)lds_item<RC_RES_MAXP, true, ProbC>(T->p, T->n, T->B, item, ring, s_rows, s_cnt, &pi);
+        (void)lds_item<RC_RES_MAXP, true, 3, ProbC>(T->p, T->n, T->B, item, ring, s_rows, s_cnt, &pi);
         RES_STAMP(p_item);
 #ifdef RC_RES_PROF
         if (threadIdx.x == 0) s_prof[p_n] += 1;
@@ -704,8 +735,13 @@ void rc_launch_flag_wait(const int* counter, int target, int* abort, unsigned lo
     hipLaunchKernelGGL(rc_flag_wait_kernel, dim3(1), dim3(1), 0, s, counter, target, abort, spin_bound);
 }
 
-void rc_launch_gemm_lds(const LdsLaunch& L, int total_wg, hipStream_t s, hipEvent_t stop) {
+void rc_launch_gemm_lds(const LdsLaunch& L, int total_wg, hipStream_t s, hipEvent_t stop, int planes) {
     const dim3 g(total_wg), b(kWaves * 64);
+    if (planes == 2) {
+        if (stop) hipExtLaunchKernelGGL(rc_gemm_lds2_kernel, g, b, 0, s, nullptr, stop, 0, L);
+        else hipLaunchKernelGGL(rc_gemm_lds2_kernel, g, b, 0, s, L);
+        return;
+    }
     if (stop) hipExtLaunchKernelGGL(rc_gemm_lds_kernel, g, b, 0, s, nullptr, stop, 0, L);
     else hipLaunchKernelGGL(rc_gemm_lds_kernel, g, b, 0, s, L);
 }

@@ -92,7 +92,8 @@ struct GemmProblem {
 struct GemmLaunch {
     int n;                  // problems
     int B;                  // rows in the batch
-    int split;              // 1: products as split-bf16 partial products on the bf16 MFMA (rc_gemm.hip: mma_kblock), W -> Ws
+    int split;              // the gemm mode. 1: products as split-bf16 partial products on the bf16 MFMA (rc_gemm.hip: mma_kblock), W -> Ws;
+                            // 2: three products of two round-to-nearest planes, every p.Ws then a mode-2 packing (rc_launch_planes2)
     int live;               // 1: launch of a live frame (16-row launches then stream their weights with non-temporal loads)
     GemmProblem p[RC_MAX_PROB];
 };
@@ -128,7 +129,9 @@ struct LdsLaunch {
     LdsProblem p[RC_LDS_MAXP];
 };
 #define RC_RES_MAXP 20    // problems of a tick of the resident kernel: twelve layer steps + six linear1
-void rc_launch_gemm_lds(const LdsLaunch& L, int total_wg, hipStream_t s, hipEvent_t stop = nullptr);
+void rc_launch_gemm_lds(const LdsLaunch& L, int total_wg, hipStream_t s, hipEvent_t stop = nullptr, int planes = 3);   // planes 2: mode 2 (every p.Ws a two-plane packing)
+// mode 2's two round-to-nearest bf16 planes [cb][kb][2][lane][8] of a matrix, from its fp32 packing W (rc_gemm.hip: rc_planes2_kernel)
+void rc_launch_planes2(const float* W, void* Ws2, int Np, int Kp, hipStream_t s);
 
 // ---- resident layer-step kernel (rc_gemm_lds.hip: rc_gemm_resident_kernel) ----------------------------------
 // One launch carries the LSTM layer steps of EVERY tick of a wavefront-engine segment: its workgroups stay on their CUs and take work
@@ -709,7 +712,8 @@ struct SubnetNet { SubnetDense lin1, lin2; const float* Wl[2]; const void* Wls[2
 int rc_ctx_subnet_net(rc_ctx* ctx, int net, SubnetNet* out);     // net: kNets index (rnn2 .. rnn8); RC_ERR_STATE before weights
 int rc_ctx_init_net(rc_ctx* ctx, SubnetDense out[3]);
 int rc_ctx_net_index(const char* name);
-int rc_ctx_gemm_split(rc_ctx* ctx);
+int rc_ctx_gemm_split(rc_ctx* ctx);                        // 1: the context's products are not fp32 (gemm mode 1 or 2)
+int rc_ctx_gemm_mode(rc_ctx* ctx);                         // rc_get_gemm_mode
 int rc_ctx_mark_eager(rc_ctx* ctx, hipStream_t st);        // mark_eager (rc_ctx.h): eager work was enqueued on st
 long long rc_ctx_weights_epoch(rc_ctx* ctx);               // counts rc_finalize_weights: what was derived from the packed weights is stale
 void rc_subnet_free(SubnetState* s);                       // delete s

@@ -62,15 +62,16 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // W32 (round 5: a template parameter as well as the build macro): the launches whose weight slices have ONE reader -- every problem a single
 // 64-row tile per slice, i.e. contexts of 48-64 rows -- are pure weight streams, and 4 B per weight beat 6 B + no split (measured in round 4 with
 // the macro: batch 48 +13 %, 64 +7 %; at 256 rows, four readers per slice through the L2, -7 %). Bitwise the same products either way.
-template <int MR, int NC, bool W32 = (RC_SPLIT_W32 != 0)>
-struct FragS {                // one k-block (32 k): fp32 activations (two float4 per row block), three weight planes per column block
-    static constexpr int WPL = W32 ? 2 : 3;
+// NP = planes per operand: 3 (mode 1, the truncation split above) or 2 (mode 2, split2_rn below: two round-to-nearest terms)
+template <int MR, int NC, bool W32 = (RC_SPLIT_W32 != 0), int NP = 3>
+struct FragS {                // one k-block (32 k): fp32 activations (two float4 per row block), NP weight planes per column block
+    static constexpr int WPL = (W32 || NP == 2) ? 2 : 3;      // 1-KiB pieces per column block: two fp32 chunks (W32, mode 1 only), or NP planes
     f32x4 a0[MR], a1[MR];
     u32x4 b[NC][WPL];
 };
 
-template <int MR, int NC, bool W32>
-__device__ __forceinline__ void load_kblock(FragS<MR, NC, W32>& f, const float* const (&pa)[MR], long long aoff, const u32x4* pb,
+template <int MR, int NC, bool W32, int NP>
+__device__ __forceinline__ void load_kblock(FragS<MR, NC, W32, NP>& f, const float* const (&pa)[MR], long long aoff, const u32x4* pb,
                                             long long bstride) {
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
@@ -80,7 +81,7 @@ __device__ __forceinline__ void load_kblock(FragS<MR, NC, W32>& f, const float* 
 #pragma unroll
     for (int j = 0; j < NC; ++j)
 #pragma unroll
-        for (int p = 0; p < (W32 ? 2 : 3); ++p) f.b[j][p] = pb[j * bstride + p * 64];
+        for (int p = 0; p < FragS<MR, NC, W32, NP>::WPL; ++p) f.b[j][p] = pb[j * bstride + p * 64];
 }
 
 // a = hi + mid + lo exactly; each output packs 8 bf16 (element e in the low / high half of dword e / 2).
@@ -104,15 +105,33 @@ __device__ __forceinline__ void split3(const f32x4& x0, const f32x4& x1, u32x4& 
     }
 }
 
-template <int MR, int NC, bool W32>
-__device__ __forceinline__ void load_kblock_b(FragS<MR, NC, W32>& f, const u32x4* pb, long long bstride) {
+// Mode 2 (rc_set_gemm_mode): a ~ hi + mid, two bf16 terms by ROUNDING -- hi = RN_bf16(a) (round to nearest, ties to even: v_cvt_pk_bf16_f32),
+// mid = RN_bf16(a - hi); the subtraction is exact in fp32 and nothing below mid is kept: |a - hi - mid| <= 2^-17 |a| (hi within 2^-9 |a|
+// of a, mid within 2^-9 of that remainder). A block pair is then THREE products (mma_kblock: a_mid.w_hi, a_hi.w_mid, a_hi.w_hi) and
+// a . w is off by at most about 3 x 2^-16 |a . w| for finite operands (a_mid.w_mid, <= 2^-16, is not formed; each operand's own
+// remainder adds <= 2^-17). |a| within half a bf16 ulp of FLT_MAX rounds to inf where the truncation of mode 1 did not; a NaN stays a NaN.
+// The device builds the weight planes of this mode with this very function (rc_planes2_kernel, rc_gemm.hip).
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void split2_rn(const f32x4& x0, const f32x4& x1, u32x4& h, u32x4& m) {
+    const f32x2 a[4] = {f32x2{x0[0], x0[1]}, f32x2{x0[2], x0[3]}, f32x2{x1[0], x1[1]}, f32x2{x1[2], x1[3]}};
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const unsigned uh = __builtin_bit_cast(unsigned, __builtin_convertvector(a[d], bf16x2));     // element e in the low / high half
+        const f32x2 r = a[d] - __builtin_bit_cast(f32x2, u32x2{uh << 16, uh & 0xffff0000u});         // a - hi, exact
+        h[d] = uh;
+        m[d] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
+    }
+}
+
+template <int MR, int NC, bool W32, int NP>
+__device__ __forceinline__ void load_kblock_b(FragS<MR, NC, W32, NP>& f, const u32x4* pb, long long bstride) {
 #pragma unroll
     for (int j = 0; j < NC; ++j)
 #pragma unroll
-        for (int p = 0; p < (W32 ? 2 : 3); ++p) f.b[j][p] = pb[j * bstride + p * 64];
+        for (int p = 0; p < FragS<MR, NC, W32, NP>::WPL; ++p) f.b[j][p] = pb[j * bstride + p * 64];
 }
-template <int MR, int NC, bool W32>
-__device__ __forceinline__ void load_kblock_a(FragS<MR, NC, W32>& f, const float* const (&pa)[MR], long long aoff) {
+template <int MR, int NC, bool W32, int NP>
+__device__ __forceinline__ void load_kblock_a(FragS<MR, NC, W32, NP>& f, const float* const (&pa)[MR], long long aoff) {
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
         f.a0[r] = *reinterpret_cast<const f32x4*>(pa[r] + aoff);
@@ -120,27 +139,39 @@ __device__ __forceinline__ void load_kblock_a(FragS<MR, NC, W32>& f, const float
     }
 }
 
-template <int MR, int NC, bool W32>
-__device__ __forceinline__ void mma_kblock(const FragS<MR, NC, W32>& f, f32x4 (&acc)[MR][NC]) {
-    u32x4 wp[3][NC];              // the column blocks' planes: hi, mid, lo
+template <int MR, int NC, bool W32, int NP>
+__device__ __forceinline__ void mma_kblock(const FragS<MR, NC, W32, NP>& f, f32x4 (&acc)[MR][NC]) {
+    u32x4 wp[NP][NC];             // the column blocks' planes: hi, mid(, lo)
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
-        if constexpr (W32) split3(__builtin_bit_cast(f32x4, f.b[j][0]), __builtin_bit_cast(f32x4, f.b[j][1]), wp[0][j], wp[1][j], wp[2][j]);
-        else { wp[0][j] = f.b[j][0]; wp[1][j] = f.b[j][1]; wp[2][j] = f.b[j][2]; }
+        if constexpr (NP == 2) {
+            static_assert(!W32, "mode 2 reads its planes: 4 B per weight as they are");
+            wp[0][j] = f.b[j][0]; wp[1][j] = f.b[j][1];
+        } else {
+            if constexpr (W32) split3(__builtin_bit_cast(f32x4, f.b[j][0]), __builtin_bit_cast(f32x4, f.b[j][1]), wp[0][j], wp[1][j], wp[2][j]);
+            else { wp[0][j] = f.b[j][0]; wp[1][j] = f.b[j][1]; wp[2][j] = f.b[j][2]; }
+        }
     }
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
-        u32x4 uh, um, ul;
-        split3(f.a0[r], f.a1[r], uh, um, ul);
-        const bf16x8 ah = __builtin_bit_cast(bf16x8, uh), am = __builtin_bit_cast(bf16x8, um), al = __builtin_bit_cast(bf16x8, ul);
         // small terms first; consecutive MFMAs go to different accumulators (NC of them between two uses of one)
 #define RC_PROD(AV, PL)                                                                                                  \
     _Pragma("unroll") for (int j = 0; j < NC; ++j)                                                                        \
         acc[r][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AV, __builtin_bit_cast(bf16x8, wp[PL][j]), acc[r][j], 0, 0, 0);
+        if constexpr (NP == 2) {
+            u32x4 uh, um;
+            split2_rn(f.a0[r], f.a1[r], uh, um);
+            const bf16x8 ah = __builtin_bit_cast(bf16x8, uh), am = __builtin_bit_cast(bf16x8, um);
+            RC_PROD(am, 0) RC_PROD(ah, 1) RC_PROD(ah, 0)
+        } else {
+            u32x4 uh, um, ul;
+            split3(f.a0[r], f.a1[r], uh, um, ul);
+            const bf16x8 ah = __builtin_bit_cast(bf16x8, uh), am = __builtin_bit_cast(bf16x8, um), al = __builtin_bit_cast(bf16x8, ul);
 #if RC_SPLIT_PRODUCTS == 9
-        RC_PROD(al, 2) RC_PROD(am, 2) RC_PROD(al, 1)
+            RC_PROD(al, 2) RC_PROD(am, 2) RC_PROD(al, 1)
 #endif
-        RC_PROD(al, 0) RC_PROD(ah, 2) RC_PROD(am, 1) RC_PROD(am, 0) RC_PROD(ah, 1) RC_PROD(ah, 0)
+            RC_PROD(al, 0) RC_PROD(ah, 2) RC_PROD(am, 1) RC_PROD(am, 0) RC_PROD(ah, 1) RC_PROD(ah, 0)
+        }
 #undef RC_PROD
     }
 }

@@ -391,7 +391,8 @@ WaveEngine pick_wave_engine(const rc_ctx* c) {
 }
 // ... and whether the layer steps of a whole segment go out as ONE launch of the resident kernel (run_resident_segment)
 bool resident_segment(const rc_ctx* c, WaveEngine eng, const WavePlan& P) {
-    return eng == ENG_TRI && c->seq->resident_on && c->B <= 256 && P.n_ticks > 0 && resident_launch_fits_timing(c);
+    // (gemm mode 2 has no resident instantiation: such a context ignores the setting and runs its segments on the three streams)
+    return eng == ENG_TRI && c->seq->resident_on && gemm_mode(c) != 2 && c->B <= 256 && P.n_ticks > 0 && resident_launch_fits_timing(c);
 }
 // launch group of problem q: in the tri engine rnn6's layer steps and init_net leave the caller's stream to rnn4
 inline int w2_group(int q, bool tri) {

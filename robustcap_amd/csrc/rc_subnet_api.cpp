@@ -168,6 +168,13 @@ bool dev_holds(const void* p, long long bytes) {
     return (long long)((const char*)base + size - (const char*)p) >= bytes;
 }
 
+// The sub-net entries run the six-product kernels of rc_subnet.hip; gemm mode 2 (two rounded bf16 terms, three products) has no
+// instantiation of them: refused, not run in another arithmetic than the context's.
+int refuse_mode2(rc_ctx* ctx, const std::string& what) {
+    if (rc_ctx_gemm_mode(ctx) != 2) return RC_OK;
+    return rc_ctx_fail(ctx, RC_ERR_INVALID, (what + ": not available in gemm mode 2 (rc_set_gemm_mode 0 or 1 for the sub-net entries)").c_str());
+}
+
 // validates what every entry takes; on RC_OK: *ni, *w
 int check_args(rc_ctx* ctx, const char* what, const char* net, int32_t n, const int32_t* lengths_host, bool others_null, int* ni, SubnetNet* w) {
     const std::string f(what);
@@ -205,6 +212,7 @@ int forward_impl(rc_ctx* ctx, const char* what, const char* net, int32_t n, cons
     if (int rc = check_args(ctx, what, net, n, lengths_host, !x || !y || (record && (!acts || !tape)), &ni, &w)) return rc;
     if (!valid_p(drop.p)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (std::string(what) + ": p outside [0, 1)").c_str());
     const bool dropping = drop.p > 0.0f;
+    if (int rc = refuse_mode2(ctx, what)) return rc;
     const int split = rc_ctx_gemm_split(ctx);
     SubnetState* S = state(ctx);
     const int H = w.H, Kp1 = w.lin1.Kp;
@@ -299,6 +307,7 @@ int backward_impl(rc_ctx* ctx, const char* what, const char* net, int32_t n, con
     SubnetNet w;
     if (int rc = check_args(ctx, what, net, n, lengths_host, !tape || !d_h1 || !d_gates || !d_a, &ni, &w)) return rc;
     if (!valid_p(drop.p)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (std::string(what) + ": p outside [0, 1)").c_str());
+    if (int rc = refuse_mode2(ctx, what)) return rc;
     const int split = rc_ctx_gemm_split(ctx);
     SubnetState* S = state(ctx);
     const int H = w.H;
@@ -432,6 +441,7 @@ int weight_grads_impl(rc_ctx* ctx, const char* net, int32_t n, const int32_t* le
         o[i] = static_cast<float*>(outs[i]);
         if (o[i] && !dev_holds(o[i], 4 * numel[i])) return rc_ctx_fail(ctx, RC_ERR_INVALID, (what + ": an output smaller than its tensor").c_str());
     }
+    if (int rc = refuse_mode2(ctx, what)) return rc;
     const int split = rc_ctx_gemm_split(ctx);
     SubnetState* S = state(ctx);
     if (!S->cus) {
@@ -691,6 +701,7 @@ int rc_init_net_forward(rc_ctx* ctx, int32_t n, const float* v, float* out, void
     if (n < 1 || !v || !out) return rc_ctx_fail(ctx, RC_ERR_INVALID, "rc_init_net_forward: n >= 1 rows and non-null buffers");
     SubnetDense d[3];
     if (rc_ctx_init_net(ctx, d)) return rc_ctx_fail(ctx, RC_ERR_STATE, "rc_init_net_forward: weights not finalized");
+    if (int rc = refuse_mode2(ctx, "rc_init_net_forward")) return rc;
     const int split = rc_ctx_gemm_split(ctx);
     hipStream_t st = (hipStream_t)stream;
     SubnetState* S = state(ctx);

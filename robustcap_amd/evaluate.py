@@ -130,13 +130,14 @@ def run_dataset(dataset, state_dict, body, use_first_tran=True, use_flat_floor=T
     prior (dict means/covars/weights); ``smplify_info`` (a dict) receives the per-row optimiser records. ``nets``: an optional
     dict the caller keeps between calls -- the ``Net`` of a given row count is then built (weights re-packed and uploaded,
     ~0.4 s) once and only reset for the next dataset (an entry is reused only for the very same ``state_dict`` object).
-    ``gemm_mode``: product arithmetic of the GEMMs (False fp32 MFMA, True split-bf16 products); None picks the library's
+    ``gemm_mode``: product arithmetic of the GEMMs (False / 0 fp32 MFMA, True / 1 split-bf16 products, 2 the fast three-product
+    mode of ``Net.set_gemm_mode``), pinned on every shard; None picks the library's
     default for the TOTAL number of rows of the run, not for this rank's shard, so a row's result does not depend on
     the number of ranks (``Net.default_gemm_mode``). ``ragged=True`` hands every row's own length to ``forward_sequence``: the
     padding frames behind a short row are neither computed nor read; the frames returned are bitwise those of the padded run."""
     all_rows = rows_of(dataset) if rows is None else list(rows)
     Tmax = max(len(dataset["pose"][i]) for i, _ in all_rows)
-    split = Net.default_gemm_mode(len(all_rows)) if gemm_mode is None else bool(gemm_mode)
+    split = int(Net.default_gemm_mode(len(all_rows))) if gemm_mode is None else (2 if gemm_mode == 2 else int(bool(gemm_mode)))
 
     def compute(mine):
         n = len(mine)
@@ -151,7 +152,7 @@ def run_dataset(dataset, state_dict, body, use_first_tran=True, use_flat_floor=T
                 nets[n] = (net, state_dict)
         else:
             net.reset_states()
-        if bool(net.gemm_mode) != bool(split):                  # (only when it differs: a switch drops a captured live frame)
+        if net.gemm_mode != split:                              # (only when it differs: a switch drops a captured live frame)
             net.set_gemm_mode(split)
         net.use_flat_floor = use_flat_floor
         net.gravityc = grav

@@ -310,8 +310,12 @@ class Net:
     def trainable(self, name, weight_grads="torch"):
         """A ``SubnetTrainer`` of sub-net ``name`` ("rnn2" .. "rnn8"): its parameters as torch.nn.Parameters on the device and a
         differentiable ``tr(xs, init)`` with the values of ``net.rnnK(xs, init)`` (robustcap_amd/train.py). ``weight_grads``: "torch"
-        (fp32 matmuls) or "device" (``rc_subnet_weight_grads``, HIP) for the backward's reductions over the frames."""
+        (fp32 matmuls) or "device" (``rc_subnet_weight_grads``, HIP) for the backward's reductions over the frames. Not in gemm mode 2:
+        this raises, and a trainer made in mode 0 or 1 raises from the library, with a message naming mode 2, at its next forward,
+        backward or weight-gradient call once the context has been switched with ``set_gemm_mode(2)``."""
         from ..train import SubnetTrainer
+        if self.gemm_mode == 2:
+            raise RuntimeError(f"trainable({name!r}): not available in gemm mode 2 (set_gemm_mode(0) or (1) for the sub-net entries)")
         return SubnetTrainer(self, name, weight_grads)
 
     def _flat_input(self, xs):
@@ -539,16 +543,30 @@ class Net:
 
     @staticmethod
     def default_gemm_mode(total_rows):
-        """The library's default product arithmetic for a workload of ``total_rows`` bodies (rc_default_gemm_mode: split-bf16
+        """The mode (int 0, 1 or 2) a new context gets for a workload of ``total_rows`` bodies (rc_initial_gemm_mode: split-bf16
         products from 48 rows). Sharded runs pass their TOTAL row count here and pin every shard's context with
-        ``set_gemm_mode``, so that a row's bits do not depend on the number of ranks it was split over."""
-        return bool(_lib.load().rc_default_gemm_mode(int(total_rows)))
+        ``set_gemm_mode``, so that a row's bits do not depend on the number of ranks it was split over. With RC_GEMM_SPLIT=2 in the
+        environment -- new contexts then start in the fast mode 2, which the library itself never defaults to -- this is 2, so that
+        a run pinned this way stays in the mode its contexts started in (the library reads the variable, nothing here does)."""
+        lib = _lib.load()
+        try:
+            return int(lib.rc_initial_gemm_mode(int(total_rows)))
+        except AttributeError:                                              # (an older build of the library under RC_LIB_PATH: A/B runs)
+            return int(lib.rc_default_gemm_mode(int(total_rows)))
 
     def set_gemm_mode(self, split):
-        """Product arithmetic of every GEMM of this context (rc_set_gemm_mode): False = fp32 MFMA (fma chains), True =
-        split-bf16 partial products with fp32 accumulation (default for batch >= 48). Results are bitwise reproducible
-        across batch sizes and shards WITHIN one mode."""
-        _lib.check(self._ctx, self._lib.rc_set_gemm_mode(self._ctx, int(bool(split))), "rc_set_gemm_mode")
+        """Product arithmetic of every GEMM of this context (rc_set_gemm_mode): False / 0 = fp32 MFMA (fma chains), True / 1 =
+        split-bf16 partial products with fp32 accumulation (six per block pair; default for batch >= 48), 2 = the fast mode: two
+        round-to-nearest bf16 terms per operand, three products -- about 2^-16 per product instead of 2^-23, for offline batches
+        that can spend part of the 1e-4 m budget (include/robustcap_hip.h; the sub-net entries ``net.rnnK(x)`` / ``trainable``
+        refuse it). Results are bitwise reproducible across batch sizes and shards WITHIN one mode. Any other value: ValueError."""
+        if isinstance(split, bool):
+            mode = int(split)
+        elif isinstance(split, int) and split in (0, 1, 2):
+            mode = split
+        else:
+            raise ValueError(f"set_gemm_mode: False / True / 0 / 1 / 2, not {split!r}")
+        _lib.check(self._ctx, self._lib.rc_set_gemm_mode(self._ctx, mode), "rc_set_gemm_mode")
         self.__dict__["_live_on"] = False
 
     @property
@@ -601,7 +619,7 @@ class Net:
         except AttributeError:                                              # (an older build of the library under RC_LIB_PATH: A/B runs)
             lds, other = 0, 0
         if lds > 0:
-            return "rc_gemm_lds_kernel"
+            return "rc_gemm_lds2_kernel" if self.gemm_mode == 2 else "rc_gemm_lds_kernel"
         try:
             w = C.c_int64()
             _lib.check(self._ctx, self._lib.rc_get_launch_stats_w32(self._ctx, C.byref(w)), "rc_get_launch_stats_w32")
@@ -609,7 +627,7 @@ class Net:
                 return "rc_gemm_split48_w32_kernel"
         except AttributeError:
             pass
-        return "rc_gemm_split_kernel" if self.gemm_mode else "rc_gemm_kernel"
+        return {0: "rc_gemm_kernel", 1: "rc_gemm_split_kernel", 2: "rc_gemm_split2_kernel"}[self.gemm_mode]
 
     def launch_stats(self):
         """(launches of the shared-weight kernel rc_gemm_lds_kernel, launches of the other wide-tile kernels) since construction."""
