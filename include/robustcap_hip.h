@@ -680,7 +680,14 @@ int rc_lbfgs_device_probe(rc_ctx* ctx, int32_t backend, int32_t n_rows, const in
 /* Harness input preparation of evaluate.py:38-51,70-73 for ONE (sequence, camera) of n frames:
  *   j2dc = K^-1 [u, v, 1] with the confidence copied into the last channel, accc = R_cw acc_w, oric = R_cw ori_w,
  *   gravity_out (HOST float[3]) = R_cw [0, -1, 0].
- * kp_pix[n,33,3] = (u, v, conf) in pixels, imu_acc_w[n,6,3], imu_ori_w[n,6,3,3] DEVICE; K[3,3], Tcw[4,4] HOST. */
+ * kp_pix[n,33,3] = (u, v, conf) in pixels, imu_acc_w[n,6,3], imu_ori_w[n,6,3,3] DEVICE; K[3,3], Tcw[4,4] HOST (the last row of Tcw
+ * is not read). K^-1 is the float64 adjugate rounded once to float; only its rows 0 and 1 are used, with the homogeneous 1 as it
+ * stands (no division by the third row), so a K with skew, K[2][2] != 1 or a general third row gives what the reference's
+ * K.inverse() gives. The confidence is copied bit for bit.
+ * RC_ERR_INVALID, with nothing launched and neither the outputs nor gravity_out written: a null buffer (the device buffers may be
+ * null when n == 0), n < 0, a NaN or an infinity in K or in the upper 3 x 4 of Tcw, det K == 0, an entry of K^-1 that is not
+ * finite as a float. n == 0 writes gravity_out and launches nothing.
+ * Pinned to a float64 restatement by tests/test_gpu_harness_inputs.py (bounds: oracle/harness_f64.py). */
 int rc_camera_inputs(const float* kp_pix, const float* imu_acc_w, const float* imu_ori_w, const float* K_host,
                      const float* Tcw_host, float* j2dc, float* accc, float* oric, float* gravity_out_host, int64_t n,
                      void* stream);
@@ -692,7 +699,11 @@ int rc_camera_inputs(const float* kp_pix, const float* imu_acc_w, const float* i
  * the row; later frames are written as padding: zero keypoints and accelerations, identity orientations) -- all DEVICE;
  * K[n_rows,3,3], Tcw[n_rows,4,4] HOST. Outputs j2dc[n_rows,Tmax,33,3], accc[n_rows,Tmax,6,3], oric[n_rows,Tmax,6,3,3] DEVICE,
  * gravity_out[n_rows,3] HOST. cam_scratch: caller-owned DEVICE buffer of n_rows * 72 bytes (camera constants).
- * Synchronises `stream` once (upload of the camera constants). */
+ * Padding frames of the inputs are not used (they may hold anything, NaN included); valid frames are bitwise those of
+ * rc_camera_inputs on the same row. Synchronises `stream` once (upload of the camera constants).
+ * RC_ERR_INVALID as for rc_camera_inputs, whichever row holds the bad camera: every row's constants are computed on the host
+ * first, and gravity_out, cam_scratch and the outputs are written only when all rows passed. n_rows == 0 or Tmax == 0 returns RC_OK
+ * and writes nothing. One launch carries at most 65535 rows (grid y); that limit and frame counts beyond 2^31 are not tested. */
 int rc_camera_inputs_rows(const float* kp_norm, const float* imu_acc_w, const float* imu_ori_w, const int32_t* seq_of_row,
                           const int32_t* len, const float* K_host, const float* Tcw_host, float image_w, float image_h,
                           int32_t n_rows, int32_t Tmax, float* j2dc, float* accc, float* oric, float* gravity_out_host,

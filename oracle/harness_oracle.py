@@ -1,7 +1,10 @@
 """TEST INFRASTRUCTURE ONLY (see oracle/sig_mp_oracle.py): torch-CPU restatement of the reference's evaluation-loop input
 preparation, evaluate.py:38-51,70-73 (evaluate_aist_ours). Imported by tests only; the product path (robustcap_amd.evaluate)
-runs rc_camera_inputs_rows on the device and never touches this module. Parity: pinned by
-tests/test_gpu_evaluate.py::test_camera_inputs_match_reference_formulas (same formulas, HIP kernel vs this arithmetic)."""
+runs rc_camera_inputs_rows on the device and never touches this module. Parity: this module is one of the honest float32
+evaluations of oracle/harness_f64.py's float64 restatement -- tests/test_harness_bound_cpu.py
+::test_harness_oracle_and_host_torch_stay_within_a_third_of_the_bound holds it to a third of the Bound on every case (cameras far
+from the identity, K with skew, four image sizes) -- and tests/test_gpu_harness_inputs.py holds both HIP kernels to the same Bound
+and to this module's NaN pattern (::test_a_nan_keypoint_poisons_what_it_poisons_in_the_float32_oracle)."""
 import torch
 
 

@@ -1075,14 +1075,19 @@ int rc_lstm_step(rc_ctx* ctx, const char* net, const float* x, const uint8_t* ro
 }
 
 namespace {
-// K^-1 by the adjugate in double (the reference uses torch's float32 LU inverse, evaluate.py:34,70), R_cw, gravity
+// K^-1 by the adjugate in double (the reference uses torch's float32 LU inverse, evaluate.py:34,70), R_cw, gravity.
+// Refused (false, nothing written): a non-finite entry of K or of the upper 3 x 4 of T_cw, det K == 0, an entry of K^-1 that is
+// not finite once rounded to float -- each would turn every frame of the row into NaN.
 bool camera_constants(const float* K, const float* Tcw, CamConst* cam, float* g_out) {
+    for (int q = 0; q < 9; ++q) if (!std::isfinite(K[q])) return false;
+    for (int q = 0; q < 12; ++q) if (!std::isfinite(Tcw[q])) return false;
     const double a = K[0], b = K[1], c = K[2], d = K[3], e = K[4], f = K[5], g = K[6], h = K[7], i = K[8];
     const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
     if (det == 0.0) return false;
     const double inv[9] = {(e * i - f * h) / det, (c * h - b * i) / det, (b * f - c * e) / det,
                            (f * g - d * i) / det, (a * i - c * g) / det, (c * d - a * f) / det,
                            (d * h - e * g) / det, (b * g - a * h) / det, (a * e - b * d) / det};
+    for (int q = 0; q < 9; ++q) if (!std::isfinite((float)inv[q])) return false;
     for (int q = 0; q < 9; ++q) cam->Kinv[q] = (float)inv[q];
     for (int r = 0; r < 3; ++r)
         for (int q = 0; q < 3; ++q) cam->R[3 * r + q] = Tcw[4 * r + q];
@@ -1094,10 +1099,10 @@ bool camera_constants(const float* K, const float* Tcw, CamConst* cam, float* g_
 int rc_camera_inputs(const float* kp, const float* acc, const float* ori, const float* K, const float* Tcw, float* j2dc,
                      float* accc, float* oric, float* g_out, int64_t n, void* stream) {
     if (!K || !Tcw || !g_out || n < 0) return RC_ERR_INVALID;
+    if (n > 0 && (!kp || !acc || !ori || !j2dc || !accc || !oric)) return RC_ERR_INVALID;    // before g_out is written
     CamConst cam;
     if (!camera_constants(K, Tcw, &cam, g_out)) return RC_ERR_INVALID;
     if (n == 0) return RC_OK;
-    if (!kp || !acc || !ori || !j2dc || !accc || !oric) return RC_ERR_INVALID;
     rc_launch_camera_inputs(kp, acc, ori, cam, j2dc, accc, oric, n, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? RC_OK : RC_ERR_HIP;
 }
@@ -1110,8 +1115,10 @@ int rc_camera_inputs_rows(const float* kp_norm, const float* imu_acc_w, const fl
     if (n_rows == 0 || Tmax == 0) return RC_OK;
     if (!kp_norm || !imu_acc_w || !imu_ori_w || !seq_of_row || !len || !j2dc || !accc || !oric) return RC_ERR_INVALID;
     std::vector<CamConst> cams((size_t)n_rows);
+    std::vector<float> grav(3 * (size_t)n_rows);                          // handed out only once every row has passed
     for (int r = 0; r < n_rows; ++r)
-        if (!camera_constants(K_host + 9 * (size_t)r, Tcw_host + 16 * (size_t)r, &cams[r], gravity_out_host + 3 * (size_t)r)) return RC_ERR_INVALID;
+        if (!camera_constants(K_host + 9 * (size_t)r, Tcw_host + 16 * (size_t)r, &cams[r], grav.data() + 3 * (size_t)r)) return RC_ERR_INVALID;
+    std::copy(grav.begin(), grav.end(), gravity_out_host);
     hipStream_t st = (hipStream_t)stream;
     // cam_scratch: DEVICE buffer of n_rows * 72 bytes owned by the caller (the library allocates nothing here)
     if (hipMemcpyAsync(cam_scratch, cams.data(), cams.size() * sizeof(CamConst), hipMemcpyHostToDevice, st) != hipSuccess) return RC_ERR_HIP;

@@ -256,6 +256,21 @@ __global__ void rc_R2aa_kernel(const float* Rm, float* aa, long long n) {
     rotmat_to_aa(Rm + 9 * i, aa + 3 * i);
 }
 
+// One arithmetic for both camera-input kernels, written out and none left to the compiler. As the source expression
+// "(Kinv0 u + Kinv1 v) + Kinv2" the two kernels were contracted differently -- the single-row one fused Kinv0 u onto a rounded
+// Kinv1 v, the batched one rounded both products -- so under a K with skew or K[1][0] != 0 a row of the batched run was not bitwise
+// that row run alone (tests/test_gpu_harness_inputs.py; with Kinv1 = Kinv3 = 0, every camera run before, the two forms agree).
+// The forms below are the ones the BATCHED kernel, the evaluation's path, had been compiled to, so that path keeps its bits.
+__device__ __forceinline__ float cam_unproject(const float k0, const float k1, const float k2, const float u, const float v) {
+#pragma clang fp contract(off)
+    return (k0 * u + k1 * v) + k2;                                         // both products rounded
+}
+// row r of R_cw times a column: r1 x1 and r2 x2 rounded, r0 x0 fused onto the first, the second added (both kernels, as compiled)
+__device__ __forceinline__ float cam_rotate(const float* r, const float x0, const float x1, const float x2) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(r[0], x0, r[1] * x1) + r[2] * x2;
+}
+
 // evaluate.py:38-51,70-72: per-frame camera-frame inputs from pixel keypoints and world-frame IMU readings
 __global__ void rc_camera_inputs_kernel(const float* kp, const float* acc, const float* ori, CamConst cam, float* j2dc,
                                         float* accc, float* oric, long long n) {
@@ -264,17 +279,17 @@ __global__ void rc_camera_inputs_kernel(const float* kp, const float* acc, const
     if (t < 33) {
         const float u = kp[(f * 33 + t) * 3], v = kp[(f * 33 + t) * 3 + 1], cf = kp[(f * 33 + t) * 3 + 2];
         float* o = j2dc + (f * 33 + t) * 3;
-        o[0] = (cam.Kinv[0] * u + cam.Kinv[1] * v) + cam.Kinv[2];
-        o[1] = (cam.Kinv[3] * u + cam.Kinv[4] * v) + cam.Kinv[5];
+        o[0] = cam_unproject(cam.Kinv[0], cam.Kinv[1], cam.Kinv[2], u, v);
+        o[1] = cam_unproject(cam.Kinv[3], cam.Kinv[4], cam.Kinv[5], u, v);
         o[2] = cf;
     } else if (t < 33 + 18) {
         const int e = t - 33, i = e / 3, r = e % 3;
         const float* a = acc + (f * 6 + i) * 3;
-        accc[f * 18 + e] = (cam.R[3 * r] * a[0] + cam.R[3 * r + 1] * a[1]) + cam.R[3 * r + 2] * a[2];
+        accc[f * 18 + e] = cam_rotate(cam.R + 3 * r, a[0], a[1], a[2]);
     } else if (t < 33 + 18 + 54) {
         const int e = t - 51, i = e / 9, r = (e % 9) / 3, c = e % 3;
         const float* o = ori + (f * 6 + i) * 9;
-        oric[f * 54 + e] = (cam.R[3 * r] * o[c] + cam.R[3 * r + 1] * o[3 + c]) + cam.R[3 * r + 2] * o[6 + c];
+        oric[f * 54 + e] = cam_rotate(cam.R + 3 * r, o[c], o[3 + c], o[6 + c]);
     }
 }
 
@@ -294,17 +309,17 @@ __global__ __launch_bounds__(128) void rc_camera_inputs_rows_kernel(const float*
         const float* k = kp + (o * 33 + t) * 3;
         float* d = j2dc + (o * 33 + t) * 3;
         const float u = pad ? 0.f : k[0] * sx, v = pad ? 0.f : k[1] * sy;           // evaluate.py:43-44: pixels from the image-size normalisation
-        d[0] = pad ? 0.f : (cam.Kinv[0] * u + cam.Kinv[1] * v) + cam.Kinv[2];
-        d[1] = pad ? 0.f : (cam.Kinv[3] * u + cam.Kinv[4] * v) + cam.Kinv[5];
+        d[0] = pad ? 0.f : cam_unproject(cam.Kinv[0], cam.Kinv[1], cam.Kinv[2], u, v);
+        d[1] = pad ? 0.f : cam_unproject(cam.Kinv[3], cam.Kinv[4], cam.Kinv[5], u, v);
         d[2] = pad ? 0.f : k[2];
     } else if (t < 33 + 18) {
         const int e = t - 33, i = e / 3, q = e % 3;
         const float* a = acc + (in * 6 + i) * 3;
-        accc[o * 18 + e] = pad ? 0.f : (cam.R[3 * q] * a[0] + cam.R[3 * q + 1] * a[1]) + cam.R[3 * q + 2] * a[2];
+        accc[o * 18 + e] = pad ? 0.f : cam_rotate(cam.R + 3 * q, a[0], a[1], a[2]);
     } else if (t < 33 + 18 + 54) {
         const int e = t - 51, i = e / 9, q = (e % 9) / 3, c = e % 3;
         const float* m = ori + (in * 6 + i) * 9;
-        oric[o * 54 + e] = pad ? (q == c ? 1.f : 0.f) : (cam.R[3 * q] * m[c] + cam.R[3 * q + 1] * m[3 + c]) + cam.R[3 * q + 2] * m[6 + c];
+        oric[o * 54 + e] = pad ? (q == c ? 1.f : 0.f) : cam_rotate(cam.R + 3 * q, m[c], m[3 + c], m[6 + c]);
     }
 }
 
