@@ -576,6 +576,32 @@ int rc_body_mesh(rc_ctx* ctx, const float* pose, const float* tran, float* vert,
 int rc_set_regressor(rc_ctx* ctx, const float* j_regressor_host, int32_t n_rows, int32_t n_used);
 int rc_mesh_metrics(rc_ctx* ctx, const float* pose, const float* gt_pose, int64_t n, float* per_frame, double* mean_host,
                     void* stream);
+/* art.FullMotionEvaluator (articulate/evaluator.py:317-394) for every motion of a concatenated batch in one call, and the column means
+ * behind PerJointErrorEvaluator (:155-215) and MeshErrorEvaluator (:256-314). pose_p, pose_t DEVICE [n,24,3,3] local rotations, tran_p,
+ * tran_t DEVICE [n,3] or NULL (zeros, evaluator.py:361-362). Group g ("one motion") is frames [sum_{j<g} group_frames_host[j], ... +
+ * group_frames_host[g]) (a HOST array, every entry >= 1, summing to n). Both motions run on the context's current body (rc_set_body; a
+ * body shaped by rc_shape_body serves both) and, for the vertex error, on the full mesh of rc_set_mesh. Per group, exactly as
+ * evaluator.py:365-382: offset = joint_t[align_joint] - joint_p[align_joint]; je, tre [N,24]; ve [N,V]; lae, gae [N,24] in degrees with the
+ * angle of rc_angle_between on R_p^T R_t; jkp, jkt [N-3,24] = |x(t+3) - 3 x(t+2) + 3 x(t+1) - x(t)| fps^3 on the translated joints; te
+ * [N-fps,1] on joint 0; the masked je / lae / gae over the joints of joint_mask (bit j = joint j). The stencils never reach across a
+ * group boundary. out DEVICE [groups,11,2], rows in the order of evaluator.py:384-394 (je, ve, lae, gae, jkp, jkt, te, masked je, masked
+ * lae, masked gae, tre): column 0 the mean over all elements, column 1 the mean over columns of the UNBIASED standard deviation over
+ * frames (`x.std(dim=0).mean()`). Where the reference's expression is the mean or std of an empty or one-sample set the entry is torch's
+ * value: NaN for the std of N = 1, the jerk rows of N <= 3 and the te row of N <= fps; joint_mask == 0 gives the reference's torch.zeros(1)
+ * rows (0, NaN). per_joint DEVICE [groups,4,24] or NULL: the column means of je, lae, gae, tre. flags: RC_MOTION_NO_MESH skips the vertex
+ * sweep and leaves row 1 NaN (every other entry keeps its bits); without it a context with no mesh returns RC_ERR_STATE.
+ * Enqueued on `stream`: no read-back, no synchronisation; the group table travels through a ring of four pinned copies like
+ * rc_subnet_eval's (a call waits on the host for the upload made four calls earlier, and for the stream where its context-owned scratch
+ * grows). Column statistics are (mean, sum of squared deviations) pairs in double per block of 32 frames of ONE group, shifted by the
+ * block's first value and merged in index order (Chan's update): no floating-point atomics, two calls give the same bits, and a group's
+ * entries are those of a call with that group alone. Calls on one context share the scratch: a caller who uses a second stream orders it
+ * itself. RC_ERR_INVALID (nothing written, nothing enqueued) on a null context, pose_p, pose_t, out or group_frames_host, n < 0 or >=
+ * 2^31, groups < 1, an entry < 1, a sum of the entries != n, fps < 1, align_joint outside 0..23, mask bits >= 24 or an unknown flag;
+ * n == 0 with groups == 0 is a no-op. */
+#define RC_MOTION_NO_MESH 1u
+int rc_motion_metrics(rc_ctx* ctx, const float* pose_p, const float* tran_p, const float* pose_t, const float* tran_t, int64_t n,
+                      int32_t groups, const int64_t* group_frames_host, int32_t fps, int32_t align_joint, uint32_t joint_mask,
+                      uint32_t flags, float* out, float* per_joint, void* stream);
 /* IMU synthesis of the dataset preparation (preprocess.py:22-33 `_syn_acc`, :206-214): pose[T,24,3,3] local rotations,
  * tran[T,3] DEVICE; vertex_ids[6] (config.vi_mask) and joint_ids[6] (config.ji_mask) HOST; needs rc_set_mesh.
  * -> imu_ori[T,6,3,3] = global rotations of joint_ids, vert6[T,6,3] = skinned vertices, imu_acc[T,6,3] =

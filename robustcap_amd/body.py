@@ -240,6 +240,32 @@ class ParametricModel:
                    "rc_mesh_metrics")
         return per_frame, [float(v) for v in mean]
 
+    def motion_metrics(self, pose_p, pose_t, tran_p=None, tran_t=None, group_frames=None, fps=60, align_joint=0, joint_mask=0,
+                       mesh=True, per_joint=True):
+        """art.FullMotionEvaluator (articulate/evaluator.py:317-394) of every motion of a concatenated batch in one call
+        (rc_motion_metrics): poses [n,24,3,3] local, translations [n,3] or None (zeros), ``group_frames`` the lengths of the motions
+        (None: one motion of n frames), ``joint_mask`` a bit mask (bit j = joint j). Returns device tensors (out [groups,11,2],
+        per-joint column means of je / lae / gae / tre [groups,4,24] or None); nothing is read back. ``mesh=False`` skips the vertex
+        sweep (row 1 is NaN)."""
+        pose_p = _f32c(pose_p, self.device).view(-1, 24, 3, 3)
+        pose_t = _f32c(pose_t, self.device).view(-1, 24, 3, 3)
+        if pose_t.shape != pose_p.shape:
+            raise ValueError("pose_p and pose_t must have the same number of frames")
+        n = pose_p.shape[0]
+        tran_p = None if tran_p is None else _f32c(tran_p, self.device).view(n, 3)
+        tran_t = None if tran_t is None else _f32c(tran_t, self.device).view(n, 3)
+        sizes = [n] if group_frames is None else [int(f) for f in group_frames]
+        G = len(sizes)
+        if mesh:
+            self._ensure_mesh()
+        out = torch.empty(G, 11, 2, device=self.device)
+        pj = torch.empty(G, 4, 24, device=self.device) if per_joint else None
+        rc = self._lib.rc_motion_metrics(self._ctx, _lib.ptr(pose_p), _lib.ptr(tran_p), _lib.ptr(pose_t), _lib.ptr(tran_t), n, G,
+                                         (C.c_int64 * G)(*sizes), int(fps), int(align_joint), int(joint_mask), 0 if mesh else 1,
+                                         _lib.ptr(out), _lib.ptr(pj), _lib.stream_ptr())
+        _lib.check(self._ctx, rc, "rc_motion_metrics")
+        return out, pj
+
     def reprojection_residual(self, pose, tran, keypoints_2d, cam_k, sigma=100.0):
         """``TemporalSMPLify.get_fitting_loss`` (temporal_smplify.py:198-220): [T,33] robust reprojection loss."""
         pose = _f32c(pose, self.device).view(-1, 24, 3, 3)

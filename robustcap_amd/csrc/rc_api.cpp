@@ -990,6 +990,64 @@ int rc_mesh_metrics(rc_ctx* ctx, const float* pose, const float* gt_pose, int64_
     }
     return RC_OK;
 }
+// FullMotionEvaluator (articulate/evaluator.py:317-394) of every group of a concatenated batch (kernels: rc_motion.hip). It touches nothing
+// of the context but its own scratch, partial sums and group table.
+int rc_motion_metrics(rc_ctx* ctx, const float* pose_p, const float* tran_p, const float* pose_t, const float* tran_t, int64_t n,
+                      int32_t groups, const int64_t* group_frames_host, int32_t fps, int32_t align_joint, uint32_t joint_mask, uint32_t flags,
+                      float* out, float* per_joint, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    const std::string what = "rc_motion_metrics: ";
+    if (n == 0 && groups == 0) return RC_OK;
+    if (n < 0 || n >= (1ll << 31)) return fail(ctx, RC_ERR_INVALID, what + "n must be in 0 .. 2^31 - 1");
+    if (groups < 1) return fail(ctx, RC_ERR_INVALID, what + "groups must be positive");
+    if (!pose_p || !pose_t || !out || !group_frames_host) return fail(ctx, RC_ERR_INVALID, what + "null argument");
+    if (fps < 1) return fail(ctx, RC_ERR_INVALID, what + "fps must be positive");
+    if (align_joint < 0 || align_joint > 23) return fail(ctx, RC_ERR_INVALID, what + "align_joint must be in 0 .. 23");
+    if (joint_mask >> 24) return fail(ctx, RC_ERR_INVALID, what + "joint_mask has bits past joint 23");
+    if (flags & ~(uint32_t)RC_MOTION_NO_MESH) return fail(ctx, RC_ERR_INVALID, what + "unknown flag");
+    long long F = 0, blocks = 0;
+    for (int g = 0; g < groups; ++g) {
+        const int64_t f = group_frames_host[g];
+        if (f < 1 || f > n) return fail(ctx, RC_ERR_INVALID, what + "group " + std::to_string(g) + " has " + std::to_string(f) + " frames: 1 .. n expected");
+        F += f;
+        blocks += (f + RC_MOTION_FG - 1) / RC_MOTION_FG;
+    }
+    if (F != n) return fail(ctx, RC_ERR_INVALID, what + "the groups hold " + std::to_string(F) + " frames, n is " + std::to_string(n));
+    const bool mesh = !(flags & RC_MOTION_NO_MESH);
+    if (!ctx->have_body) return fail(ctx, RC_ERR_STATE, what + "rc_set_body first");
+    if (mesh && ctx->mesh_V == 0) return fail(ctx, RC_ERR_STATE, what + "rc_set_mesh first (or pass RC_MOTION_NO_MESH)");
+    hipStream_t st = (hipStream_t)stream;
+    // ---- the group table: pinned slot -> device, on `stream`
+    const size_t G = (size_t)groups;
+    const int slot = ctx->motion_next;
+    ctx->motion_next = (slot + 1) % rc_ctx::kEvalRing;
+    if (ctx->motion_ev[slot]) HIP_TRY(ctx, hipEventSynchronize(ctx->motion_ev[slot].get()));   // the upload made kEvalRing calls ago has left the slot
+    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->motion_ev[slot]), hipEventDisableTiming));
+    HIP_TRY(ctx, rc_grow(ctx->motion_tab_hn[slot], G, 2 * G, ctx->motion_tab_h[slot], 2 * G));
+    MotionGroup* th = ctx->motion_tab_h[slot].get();
+    long long at = 0, blk = 0;
+    for (int g = 0; g < groups; ++g) {
+        th[g].frame0 = at;
+        th[g].frames = group_frames_host[g];
+        th[g].blk0 = (int)blk;
+        th[g].nblk = (int)((th[g].frames + RC_MOTION_FG - 1) / RC_MOTION_FG);
+        at += th[g].frames;
+        blk += th[g].nblk;
+    }
+    const size_t need_s = (size_t)rc_motion_scratch_floats(n), need_p = (size_t)rc_motion_partial_doubles(ctx->mesh_V, blocks, groups, mesh);
+    if (G > ctx->motion_tab_n || need_s > ctx->motion_scratch_n || need_p > ctx->motion_partial_n) {   // (kernels of earlier calls may still use the old buffers)
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, rc_grow(ctx->motion_tab_n, G, 2 * G, ctx->motion_tab, 2 * G));
+        HIP_TRY(ctx, rc_grow(ctx->motion_scratch_n, need_s, need_s, ctx->motion_scratch, need_s));
+        HIP_TRY(ctx, rc_grow(ctx->motion_partial_n, need_p, need_p, ctx->motion_partial, need_p));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->motion_tab.get(), th, G * sizeof(MotionGroup), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(ctx->motion_ev[slot].get(), st));
+    rc_launch_motion_metrics(ctx->body, ctx->mesh_vt, ctx->mesh_w, ctx->mesh_V, ctx->motion_tab.get(), groups, blocks, pose_p, tran_p, pose_t,
+                             tran_t, n, fps, align_joint, joint_mask, mesh, ctx->motion_scratch.get(), ctx->motion_partial.get(), out, per_joint, st);
+    HIP_TRY(ctx, hipGetLastError());
+    return RC_OK;
+}
 int rc_syn_acc(const float* v, int64_t T, int64_t width, int32_t smooth_n, float* acc, void* stream) {
     if (T < 0 || width < 1 || smooth_n < 0) return RC_ERR_INVALID;                       // smooth_n 0 and 1: the plain stencil (n // 2 == 0)
     if (T == 0) return RC_OK;

@@ -87,6 +87,18 @@ struct rc_ctx {
     size_t eval_tab_hn[kEvalRing] = {};
     HipEvent eval_ev[kEvalRing];         // the last upload from eval_tab_h[i]
     int eval_next = 0;
+    // rc_motion_metrics: per-frame scratch, per-block (mean, M2) pairs and the group table (all grow-only), the table staged through a ring
+    // of pinned copies like rc_subnet_eval's
+    DevBuf<float> motion_scratch;
+    size_t motion_scratch_n = 0;
+    DevBuf<double> motion_partial;
+    size_t motion_partial_n = 0;
+    DevBuf<MotionGroup> motion_tab;
+    size_t motion_tab_n = 0;
+    PinBuf<MotionGroup> motion_tab_h[kEvalRing];
+    size_t motion_tab_hn[kEvalRing] = {};
+    HipEvent motion_ev[kEvalRing];       // the last upload from motion_tab_h[i]
+    int motion_next = 0;
 };
 
 #pragma GCC visibility push(hidden)

@@ -381,6 +381,17 @@ void rc_launch_imu_frames(const BodyConst* body, const float* vt, const float* w
 void rc_launch_syn_acc(const float* v, float* acc, long long T, long long width, int n, hipStream_t s);
 void rc_launch_procrustes(const float* S1, const float* S2, int nk, float* err, long long n, hipStream_t s);
 void rc_launch_point_distance(const float* a, const float* b, float* d, long long n, hipStream_t s);
+// ---- FullMotionEvaluator per group of a concatenated batch (rc_motion.hip; rc_motion_metrics in rc_api.cpp) -----------------------------
+#define RC_MOTION_FG 32                // frames per workgroup of the column and vertex sweeps; a block holds frames of ONE group
+// One group: frames [frame0, frame0 + frames) of the call; its frame blocks are [blk0, blk0 + nblk) of the launch, nblk = ceil(frames / FG)
+struct MotionGroup { long long frame0, frames; int blk0, nblk; };
+long long rc_motion_scratch_floats(long long n);                                          // per-frame columns, joints and difference transforms
+long long rc_motion_partial_doubles(int V, long long blocks, int groups, bool mesh);      // per-block (mean, M2) pairs and the slab sums
+// out [groups,11,2], per_joint [groups,4,24] or nullptr; tab DEVICE [groups]; blocks = sum of nblk; mesh == false: no vertex sweep, row 1 NaN
+void rc_launch_motion_metrics(const BodyConst* body, const float* vt, const float* w, int V, const MotionGroup* tab, int groups,
+                              long long blocks, const float* pose_p, const float* tran_p, const float* pose_t, const float* tran_t, long long n,
+                              int fps, int align, unsigned mask, bool mesh, float* scratch, double* partial, float* out, float* per_joint,
+                              hipStream_t s);
 
 // smplify optimiser (rc_smplify.hip): one evaluation = loss terms + analytic gradient of all T frames
 struct SmplifyArgs {

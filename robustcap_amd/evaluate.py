@@ -312,6 +312,29 @@ def dataset_metrics(model, dataset, results, device="cuda"):
     return out, [float(v) for v in np.mean(list(out.values()), axis=0)]
 
 
+def motion_metrics(model, dataset, results, fps=60, joint_mask=None, device="cuda"):
+    """``art.FullMotionEvaluator`` (articulate/evaluator.py:317-394: joint, vertex and angle errors, jerk, the one-second translation
+    error, the masked errors and the tracking error, each as mean and mean per-column std) of EVERY (sequence, camera) row of
+    ``results`` = {(i, j): (pose [T,24,3,3], tran [T,3])} against the camera-frame labels, in ONE ``rc_motion_metrics`` call: every row is
+    one group of the concatenated frames, as ``dataset_metrics`` concatenates them. Returns ({(i, j): tensor [11,2]}, their mean over
+    the rows [11,2]), on the CPU."""
+    from .evaluator import _mask_bits
+    dev = torch.device(device)
+    rows = list(results)
+    if not rows:
+        return {}, torch.full((11, 2), float("nan"))
+    P, G, TP, TG, lens = [], [], [], [], []
+    for (i, j) in rows:
+        pt, tt = labels(dataset, i, j, device)
+        pose, tran = results[(i, j)]
+        n = min(pose.shape[0], pt.shape[0])
+        P.append(pose[:n].to(dev)), G.append(pt[:n].to(dev)), TP.append(tran[:n].to(dev)), TG.append(tt[:n].to(dev)), lens.append(n)
+    out, _ = model.motion_metrics(torch.cat(P), torch.cat(G), torch.cat(TP), torch.cat(TG), group_frames=lens, fps=fps,
+                                  joint_mask=_mask_bits(joint_mask), per_joint=False)
+    out = out.cpu()
+    return {r: out[k] for k, r in enumerate(rows)}, out.mean(dim=0)
+
+
 def evaluate(dataset, state_dict, body, device="cuda", **kw):
     """Full loop: run all rows, return per-row metrics and their mean (rank-local when not distributed)."""
     res = run_dataset(dataset, state_dict, body, device=device, **kw)
