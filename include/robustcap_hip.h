@@ -557,6 +557,46 @@ typedef enum { RC_BATCH_PLAIN = 0, RC_BATCH_WORLD = 1 } rc_batch_kind;
 int rc_subnet_batch(rc_ctx* ctx, const char* net, int32_t kind, const float* data, const float* label, int32_t n,
                     const int64_t* offsets_host, const int32_t* lengths_host, const float* conf_pool, int32_t pool_rows, int32_t augment,
                     uint64_t seed, uint32_t call, float* x_out, float* label_out, void* stream);
+/* rc_subnet_batch over a concatenation of corpora of one sub-net (torch.utils.data.ConcatDataset([AISTDataset, AMASSDataset]) of
+ * net/sig_mp.py:559-566, :686-693: plain and world samples shuffled into one batch) in ONE call: one table upload, one launch per kind
+ * present. Part p has kinds_host[p] and the DEVICE buffers data_parts[p] / label_parts[p] (HOST arrays of n_parts device addresses);
+ * sample i is lengths_host[i] frames from frame offsets_host[i] of part part_host[i]; every world part draws from the same conf_pool.
+ * x_out / label_out as in rc_subnet_batch, the samples in the order given. The Philox `sample` word is the sample's position i in the
+ * whole batch, so sample i has the bits it has at position i of a single-kind rc_subnet_batch of equal lengths, seed and call.
+ * RC_ERR_INVALID (nothing enqueued) as rc_subnet_batch, and on n_parts <= 0, a null part or a part index outside [0, n_parts). */
+int rc_subnet_batch_parts(rc_ctx* ctx, const char* net, int32_t n_parts, const int32_t* kinds_host, const float* const* data_parts,
+                          const float* const* label_parts, const float* conf_pool, int32_t pool_rows, int32_t n, const int32_t* part_host,
+                          const int64_t* offsets_host, const int32_t* lengths_host, int32_t augment, uint64_t seed, uint32_t call,
+                          float* x_out, float* label_out, void* stream);
+/* The training corpus of one sub-net from the fields of a preprocessed dictionary: the dataset builders inside train_rnn2 .. train_rnn8
+ * (net/sig_mp.py:302-336, :365-405, :444-518, :583-647, :705-747, :797-821), one call per sub-net and source, enqueued on `stream` with no
+ * read-back. The fields are DEVICE fp32 buffers concatenated over the n_seq sequences (seq_frames_host[i] frames each, `frames` in all):
+ * pose [frames, 72] axis-angle, imu_acc [frames, 6, 3], imu_ori [frames, 6, 3, 3], joint3d [frames, 24, 3], tran [frames, 3],
+ * sync_3d_mp [frames, 33, 3]; a field the corpus does not read may be NULL. Every builder ends in [1:-1]: a sample of T frames gives T - 2
+ * rows, row r is frame r + 1, and the velocity / contact stencils read frames r and r + 2 of the same sample; x_out DEVICE [R, in],
+ * label_out DEVICE [R, out], R the sum over the samples, in sample order.
+ *   rnn2, rnn3, rnn7, rnn8 (samples = sequences; n_samples 0 or n_seq, the sample arguments NULL): Rrw = R(root axis-angle)^T;
+ *     x = Rrw acc | Rrw ori (rnn7: sensor 5 left as it is) and, but for rnn2, the root-frame joints 1 .. 23 relative to joint 0 (AIST:
+ *     Rrw.matmul(j), then the difference; AMASS: (j - j0).bmm(R)), which are rnn2's label. Labels: rnn3 Rrw (j0[f + 1] - j0[f - 1]) 30 /
+ *     vel_scale; rnn7 r6d of forward_kinematics_R(pose with root := I) (needs rc_set_body); rnn8 (AMASS only) 1.0 where
+ *     |(j[f + 1] - j[f - 1]) 30| < 0.25 for joints 10 and 11, else 0.0.
+ *   rnn4, rnn6 from AIST: sample s is sequence sample_seq_host[s] seen by the camera cam_K_host[s] (HOST [9]) / cam_T_host[s] (HOST [16],
+ *     T_cw) with the keypoints kp DEVICE [kp_frames, 33, 3] = (u / image_w, v / image_h, confidence), concatenated over the samples;
+ *     x = T_cw (acc; 0) | R_cw ori | K^-1 (u image_w, v image_h, 1) with the confidence last; rnn4: xy / get_bbox_scale and rows != 23
+ *     relative to row 23 -- for sample_occ_host[s] != 0 (the joint2d_occ sample) WITHOUT the division, as :480 divides the other tensor --
+ *     label T_cw (j; 1), joints 1 .. 23 minus joint 0; rnn6: raw xy, then those joints; label T_cw (tran; 1). K^-1 and the refusal of a
+ *     camera are rc_camera_inputs_rows'.
+ *   rnn4, rnn6 from AMASS: the world corpus of RC_BATCH_WORLD: x = acc | ori | sync_3d_mp - root with sync_mp3d's twelve joint
+ *     overrides [., 171], label = joint3d - root [., 72], root = joint3d[0, 0] of the sequence.
+ * No atomics: the same call gives the same bits. RC_ERR_INVALID (nothing enqueued or written) on a null context, net or field the corpus
+ * reads, an unknown net or source, rnn8 from AIST, a sequence of fewer than 3 frames (the reference would form an empty tensor), a table
+ * that does not sum to `frames` / `kp_frames`, 2^31 rows or more, a non-finite or singular camera, or a buffer shorter than its extent. */
+typedef enum { RC_CORPUS_AIST = 0, RC_CORPUS_AMASS = 1 } rc_corpus_source;
+int rc_subnet_corpus(rc_ctx* ctx, const char* net, int32_t source, int32_t n_seq, const int32_t* seq_frames_host, int64_t frames,
+                     const float* pose, const float* imu_acc, const float* imu_ori, const float* joint3d, const float* tran,
+                     const float* sync_3d_mp, int32_t n_samples, const int32_t* sample_seq_host, const int32_t* sample_occ_host,
+                     const float* cam_K_host, const float* cam_T_host, const float* kp, int64_t kp_frames, float image_w, float image_h,
+                     float* x_out, float* label_out, void* stream);
 /* RNNWithInit.init_net (articulate/utils/torch/rnn.py:195-201, used at :207-219): Linear(69,512) ReLU Linear(512,1024) ReLU
  * Linear(1024,2048) on v DEVICE [n, 69] -> out DEVICE [n, 2048], on the packed weights of rnn2.init_net in the context's gemm mode. */
 int rc_init_net_forward(rc_ctx* ctx, int32_t n, const float* v, float* out, void* stream);

@@ -117,6 +117,9 @@ SIGNATURES = {
     "rc_subnet_loss": (_I32, [_P, _I32, _P, _P, _I64, _I32, _P, _P, _P, _P]),
     "rc_subnet_eval": (_I32, [_P, _I32, _P, _P, _I32, C.POINTER(_I64), _I32, _P, _P, _P]),
     "rc_subnet_batch": (_I32, [_P, C.c_char_p, _I32, _P, _P, _I32, _P, _P, _P, _I32, _I32, C.c_uint64, _U32, _P, _P, _P]),
+    "rc_subnet_batch_parts": (_I32, [_P, C.c_char_p, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _I32, C.c_uint64, _U32, _P, _P, _P]),
+    "rc_subnet_corpus": (_I32, [_P, C.c_char_p, _I32, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _I64, _F, _F,
+                                _P, _P, _P]),
     "rc_init_net_forward": (_I32, [_P, _I32, _P, _P, _P]),
     "rc_get_subnet_stats": (_I32, [_P, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     "rc_set_ignored_landmarks": (_I32, [_P, _P, _I32]),

@@ -1,0 +1,154 @@
+"""The training corpus of a sub-net, formed on the device from a preprocessed dictionary: what the dataset builders inside
+``train_rnn2 .. train_rnn8`` (``net/sig_mp.py:302-336, 365-405, 444-518, 583-647, 705-747, 797-821``) compute on the host from the
+``{train,val}.pt`` files of ``preprocess.py`` -- as ONE C call per sub-net and source, ``rc_subnet_corpus`` (csrc/rc_corpus.hip):
+
+    tr = net.trainable("rnn4")
+    data, label, lengths = corpus.build(tr, "aist", torch.load("aist/train.pt"))          # two device buffers, rows per sample
+    ds = batches.SubnetDataset.from_buffers(tr, data, label, lengths, split_size=200)     # adopts them, no copy
+    wd, wl, wn = corpus.build(tr, "amass", torch.load("amass/train.pt"))
+    both = tr.concat([ds, batches.SubnetDataset.from_buffers(tr, wd, wl, wn, 200, "world", conf_pool)])
+
+The only host work is reading the dictionary: every field is concatenated over the sequences and uploaded once as fp32. Every builder
+ends in ``[1:-1]``, so a sequence of T frames gives T - 2 rows. Sample order is the reference's: sequence-major, then view, a plain
+sample before its occlusion sample (rnn4). ``"amass"`` for rnn4 / rnn6 gives the ``world`` corpus of ``batches.WORLD_WIDTHS``.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import batches
+from . import config as cfg
+
+SOURCES = {"aist": 0, "amass": 1}                # rc_corpus_source
+_SPEC = {n: (i, o) for n, i, _, o in cfg.NETS}
+
+
+def kind_of(name, source):
+    """The batch kind of the corpus ``build`` forms: "world" for the AMASS part of rnn4 / rnn6, else "plain"."""
+    return "world" if source == "amass" and name in cfg.CAMERA else "plain"
+
+
+def _f32(a):
+    return a.detach().to(dtype=torch.float32, device="cpu") if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a), dtype=torch.float32)
+
+
+def _field(dataset, key, tail, frames, device):
+    """dataset[key] (one array per sequence, [T_i, *tail]) as one device buffer [sum T_i, prod tail]."""
+    if key not in dataset:
+        raise ValueError(f"the dictionary has no {key!r}")
+    seqs = [_f32(a) for a in dataset[key]]
+    if len(seqs) != len(frames):
+        raise ValueError(f"{key}: {len(seqs)} sequences, {len(frames)} expected")
+    width = int(np.prod(tail))
+    for i, (a, T) in enumerate(zip(seqs, frames)):
+        if a.shape[0] != T or a.numel() != T * width:
+            if key == "joint3d":
+                raise ValueError(f"joint3d[{i}]: [T, 24, 3] expected, got {tuple(a.shape)} (the 33 of preprocess.py:233's comment is stale)")
+            raise ValueError(f"{key}[{i}]: [{T}, {', '.join(map(str, tail))}] expected, got {tuple(a.shape)}")
+    return torch.cat([a.reshape(a.shape[0], width) for a in seqs]).to(device).contiguous()
+
+
+class Prepared:
+    """The arguments of one ``rc_subnet_corpus`` call, uploaded: ``fields`` (device buffers by name, None where the corpus does not
+    read one), the host tables, ``lengths`` (rows of every sample), ``rows`` and ``widths`` of the outputs. ``call(x, y)`` enqueues the
+    build into two device buffers and returns the C entry's code; ``args`` may be edited first (the tests of the refusals do)."""
+
+    def __init__(self, net, name, source, frames, fields, seq_of, occ_of, Ks, Ts, kp, lengths, widths, image_size):
+        self.net, self.name, self.source, self.fields, self.lengths, self.widths = net, name, source, fields, lengths, widths
+        self.rows = sum(lengths)
+        n_seq, ns = len(frames), len(seq_of)
+        self.kp, self.K, self.T = kp, Ks, Ts
+        self.args = {
+            "ctx": net._ctx, "net": name.encode(), "source": SOURCES[source], "n_seq": n_seq, "seq_frames": (C.c_int32 * n_seq)(*frames),
+            "frames": sum(frames), "pose": _lib.ptr(fields["pose"]), "imu_acc": _lib.ptr(fields["imu_acc"]),
+            "imu_ori": _lib.ptr(fields["imu_ori"]), "joint3d": _lib.ptr(fields["joint3d"]), "tran": _lib.ptr(fields["tran"]),
+            "sync_3d_mp": _lib.ptr(fields["sync_3d_mp"]), "n_samples": ns, "sample_seq": (C.c_int32 * ns)(*seq_of) if ns else None,
+            "sample_occ": (C.c_int32 * ns)(*occ_of) if ns else None, "cam_K": _lib.ptr(Ks), "cam_T": _lib.ptr(Ts), "kp": _lib.ptr(kp),
+            "kp_frames": 0 if kp is None else int(kp.shape[0]), "image_w": float(image_size[0]), "image_h": float(image_size[1])}
+
+    def call(self, x, y):
+        rc = self.net._lib.rc_subnet_corpus(*self.args.values(), _lib.ptr(x), _lib.ptr(y), _lib.stream_ptr())
+        for t in list(self.fields.values()) + [self.kp]:                   # the fields outlive the asynchronous launch
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream())
+        return rc
+
+
+def prepare(tr, source, dataset, image_size=(1920, 1080)):
+    """``build`` up to the call: the checks, the uploads and the tables, as a ``Prepared``. Bad input raises ValueError."""
+    if source not in SOURCES:
+        raise ValueError(f"source {source!r}: one of {sorted(SOURCES)}")
+    net, name = tr._net, tr.name
+    if name == "rnn8" and source == "aist":
+        raise ValueError("rnn8 trains on AMASS only (net/sig_mp.py:825-827)")
+    dev = net.device
+    world = kind_of(name, source) == "world"
+    views = source == "aist" and name in cfg.CAMERA
+    frames = [int(np.shape(a)[0]) for a in dataset["imu_acc"]]
+    if not frames:
+        raise ValueError("the dictionary holds no sequence")
+    if min(frames) < 3:
+        raise ValueError(f"a sequence of {min(frames)} frames has no row: [1:-1] of it is empty (the reference would form an empty tensor)")
+    f = {k: None for k in ("pose", "imu_acc", "imu_ori", "joint3d", "tran", "sync_3d_mp")}
+    f["imu_acc"], f["imu_ori"] = _field(dataset, "imu_acc", (6, 3), frames, dev), _field(dataset, "imu_ori", (6, 3, 3), frames, dev)
+    f["joint3d"] = _field(dataset, "joint3d", (24, 3), frames, dev)
+    if not views and not world:
+        f["pose"] = _field(dataset, "pose", (72,) if source == "aist" else (24, 3), frames, dev)
+    if views and name == "rnn6":
+        f["tran"] = _field(dataset, "tran", (3,), frames, dev)
+    if world:
+        f["sync_3d_mp"] = _field(dataset, "sync_3d_mp", (33, 3), frames, dev)
+    seq_of, occ_of, Ks, Ts, kps = [], [], [], [], []
+    if views:
+        occ = dataset.get("joint2d_occ") if name == "rnn4" else None
+        for i in range(len(frames)):
+            for j in range(len(dataset["cam_K"][i])):
+                kp = dataset["joint2d_mp"][i][j]
+                if kp is None:
+                    continue
+                kp = _f32(kp)
+                if tuple(kp.shape) != (frames[i], 33, 3):
+                    raise ValueError(f"joint2d_mp[{i}][{j}]: [{frames[i]}, 33, 3] expected, got {tuple(kp.shape)}")
+                K, T = _f32(dataset["cam_K"][i][j]).reshape(9), _f32(dataset["cam_T"][i][j]).reshape(16)
+                seq_of.append(i), occ_of.append(0), Ks.append(K), Ts.append(T), kps.append(kp)
+                ko = None if occ is None else occ[i][j]
+                if ko is None or len(ko) != frames[i]:
+                    continue
+                ko = _f32(ko)
+                if tuple(ko.shape) != (frames[i], 33, 3):
+                    raise ValueError(f"joint2d_occ[{i}][{j}]: [{frames[i]}, 33, 3] expected, got {tuple(ko.shape)}")
+                seq_of.append(i), occ_of.append(1), Ks.append(K), Ts.append(T), kps.append(ko)
+        if not seq_of:
+            raise ValueError("no view of the dictionary has keypoints")
+        lengths = [frames[i] - 2 for i in seq_of]
+    else:
+        lengths = [T - 2 for T in frames]
+    if sum(lengths) >= 1 << 31:
+        raise ValueError(f"{sum(lengths)} rows: 2^31 or more")
+    widths = batches.WORLD_WIDTHS if world else _SPEC[name]
+    kp_d = torch.cat(kps).reshape(-1, 99).to(dev).contiguous() if views else None
+    Kh = torch.stack(Ks).contiguous() if views else None
+    Th = torch.stack(Ts).contiguous() if views else None
+    return Prepared(net, name, source, frames, f, seq_of, occ_of, Kh, Th, kp_d, lengths, widths, image_size)
+
+
+def build(tr, source, dataset, image_size=(1920, 1080)):
+    """``(data [R, in], label [R, out], lengths)`` of ``tr``'s sub-net from ``dataset`` (the dictionary as ``torch.load`` returns it,
+    tensors or numpy arrays): two device buffers and the rows of every sample. ``source``: "aist" (``pose`` [T, 72]) or "amass"
+    (``pose`` [T, 24, 3]). For the AIST corpora of rnn4 / rnn6 the views of sequence i are ``range(len(cam_K[i]))``; a view whose
+    ``joint2d_mp[i][j]`` is None is skipped, and rnn4's occlusion sample where the dictionary has no ``joint2d_occ``, the entry is None
+    or its length differs. Enqueued on the current stream, nothing is read back. Bad input raises ValueError before the call."""
+    p = prepare(tr, source, dataset, image_size)
+    x = torch.empty(p.rows, p.widths[0], device=p.net.device)
+    y = torch.empty(p.rows, p.widths[1], device=p.net.device)
+    _lib.check(p.net._ctx, p.call(x, y), "rc_subnet_corpus")
+    return x, y, p.lengths
+
+
+def dataset(tr, source, dictionary, split_size=-1, conf_pool=None, image_size=(1920, 1080)):
+    """``build`` and ``SubnetDataset.from_buffers`` in one step; ``conf_pool`` ([P, 33], ``syn_c.pt``) for the world corpora."""
+    x, y, lengths = build(tr, source, dictionary, image_size)
+    kind = kind_of(tr.name, source)
+    return batches.SubnetDataset.from_buffers(tr, x, y, lengths, split_size, kind, conf_pool if kind == "world" else None)

@@ -1232,3 +1232,6 @@ int rc_get_trace(rc_ctx* ctx, int32_t* trace_host, void* stream) {
 }
 
 }  // extern "C"
+
+// camera_constants for rc_subnet_corpus (rc_subnet_api.cpp): one inverse, one refusal
+bool rc_camera_constants(const float* K, const float* Tcw, CamConst* cam, float* g_out) { return camera_constants(K, Tcw, cam, g_out); }

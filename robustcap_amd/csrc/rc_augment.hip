@@ -16,6 +16,10 @@
 // four words of one call -- units 4q, 4q + 1 = r cos(t), r sin(t) with r = sqrt(-2 ln u((w0 >> 9) + 0.5)), t = 2 pi u(w1 >> 8); units
 // 4q + 2, 4q + 3 the same from (w2, w3). perm(f): a 4-round balanced Feistel network on m bits (m the smallest even number with 2^m >= P),
 // (L, R) <- (R, L ^ (word 0 & (2^(m/2) - 1))), cycle-walked from f until the value is < P: a permutation of [0, P) by construction.
+//
+// A mixed batch (rc_subnet_batch_parts: plain and world samples of several corpora in one batch) runs the same kernels once per kind with
+// a table `ext` (rc_internal.h) that gives every sample of the launch its position in the WHOLE batch -- the `sample` word above -- its
+// first output frame there and its own corpus buffers; rc_subnet_batch passes none and keeps its bits.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -74,7 +78,8 @@ __device__ __forceinline__ void copy4(const float* __restrict__ src, float* __re
 // kind "plain": per output frame nc pieces of copied columns [0, c0), nq Philox calls of noisy columns [c0, W), nl pieces of the label
 __global__ __launch_bounds__(256) void rc_batch_plain_kernel(const float* __restrict__ data, const float* __restrict__ label,
                                                              const long long* __restrict__ tab, int n, long long F, int W, int Wl, int c0,
-                                                             float sigma, Key key, float* __restrict__ x_out, float* __restrict__ l_out) {
+                                                             float sigma, Key key, float* __restrict__ x_out, float* __restrict__ l_out,
+                                                             const long long* __restrict__ ext) {
     const long long* out_off = tab + n;
     const int nc = (c0 + 3) >> 2, nq = (W - c0 + 3) >> 2, nl = (Wl + 3) >> 2;
     const int ipr = nc + nq + nl;
@@ -85,14 +90,18 @@ __global__ __launch_bounds__(256) void rc_batch_plain_kernel(const float* __rest
         const int s = find_sample(out_off, n, f);
         const long long t = f - out_off[s];
         const long long sf = tab[s] + t;
+        const long long fo = ext ? ext[n + s] + t : f;                       // a mixed batch: the frame, the draws and the corpus of the
+        const uint32_t pos = ext ? (uint32_t)ext[s] : (uint32_t)s;          // sample's place in the whole batch
+        const float* data_s = ext ? reinterpret_cast<const float*>(ext[2 * (long long)n + s]) : data;
+        const float* label_s = ext ? reinterpret_cast<const float*>(ext[3 * (long long)n + s]) : label;
         if (j < nc) {
-            copy4(data + sf * W + 4 * j, x_out + f * W + 4 * j, min(4, c0 - 4 * j));
+            copy4(data_s + sf * W + 4 * j, x_out + fo * W + 4 * j, min(4, c0 - 4 * j));
         } else if (j < nc + nq) {
             const int q = j - nc, col = c0 + 4 * q, cnt = min(4, W - col);
-            const float* src = data + sf * W + col;
-            float* dst = x_out + f * W + col;
+            const float* src = data_s + sf * W + col;
+            float* dst = x_out + fo * W + col;
             float z[4];
-            normals4((uint32_t)s, (uint32_t)t, SITE_NOISE, (uint32_t)q, key, z);
+            normals4(pos, (uint32_t)t, SITE_NOISE, (uint32_t)q, key, z);
             if (cnt == 4 && both16(src, dst)) {
                 float4 v = *reinterpret_cast<const float4*>(src);
                 v.x += sigma * z[0]; v.y += sigma * z[1]; v.z += sigma * z[2]; v.w += sigma * z[3];
@@ -104,7 +113,7 @@ __global__ __launch_bounds__(256) void rc_batch_plain_kernel(const float* __rest
             }
         } else {
             const int jl = j - nc - nq;
-            copy4(label + sf * Wl + 4 * jl, l_out + f * Wl + 4 * jl, min(4, Wl - 4 * jl));
+            copy4(label_s + sf * Wl + 4 * jl, l_out + fo * Wl + 4 * jl, min(4, Wl - 4 * jl));
         }
     }
 }
@@ -118,14 +127,16 @@ __device__ __forceinline__ void rot(const float* R, float x, float y, float z, f
 // double and rounded to fp32 once, Rcw = (diag(-1, -1, 1) Rc0c)^T; t = lerp((-1, -1, 3), (1, 1, 8), u) with t_z lowered by the minimum of
 // the camera-frame z over every frame and all 24 joints of the sample (a wave tree, then the four waves in order: min is exact).
 __global__ __launch_bounds__(256) void rc_batch_camera_kernel(const float* __restrict__ label, const long long* __restrict__ tab, int n,
-                                                              BatchCamera range, Key key, float* __restrict__ cam) {
+                                                              BatchCamera range, Key key, float* __restrict__ cam,
+                                                              const long long* __restrict__ ext) {
     __shared__ float Rs[9];
     __shared__ float red[4];
     const int s = blockIdx.x;
     const long long* out_off = tab + n;
     const long long T = out_off[s + 1] - out_off[s];
+    const uint32_t pos = ext ? (uint32_t)ext[s] : (uint32_t)s;
     if (threadIdx.x == 0) {
-        const uint4 w = philox4x32_10(make_uint4((uint32_t)s, 0u, SITE_CAMERA, key.call), key.key);
+        const uint4 w = philox4x32_10(make_uint4(pos, 0u, SITE_CAMERA, key.call), key.key);
         const double rad = 3.14159265358979323846 / 180.0;
         const double uy = (double)u_closed0(w.x), up = (double)u_closed0(w.y), ur = (double)u_closed0(w.z);
         const double ay = ((double)range.yaw_lo * (1.0 - uy) + (double)range.yaw_hi * uy) * rad;
@@ -144,7 +155,7 @@ __global__ __launch_bounds__(256) void rc_batch_camera_kernel(const float* __res
     float R[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) R[q] = Rs[q];
-    const float* joints = label + tab[s] * 72;
+    const float* joints = (ext ? reinterpret_cast<const float*>(ext[3 * (long long)n + s]) : label) + tab[s] * 72;
     float zmin = __builtin_inff();
     for (long long g = threadIdx.x; g < T * 24; g += 256) {
         float o[3];
@@ -156,7 +167,7 @@ __global__ __launch_bounds__(256) void rc_batch_camera_kernel(const float* __res
     __syncthreads();
     if (threadIdx.x == 0) {
         zmin = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
-        const uint4 w = philox4x32_10(make_uint4((uint32_t)s, 0u, SITE_TRAN, key.call), key.key);
+        const uint4 w = philox4x32_10(make_uint4(pos, 0u, SITE_TRAN, key.call), key.key);
         const float u0 = u_closed0(w.x), u1 = u_closed0(w.y), u2 = u_closed0(w.z);
         float* c = cam + 12ll * s;
 #pragma unroll
@@ -192,7 +203,8 @@ template <bool RNN4>
 __global__ __launch_bounds__(256) void rc_batch_world_kernel(const float* __restrict__ data, const float* __restrict__ label,
                                                              const long long* __restrict__ tab, int n, long long F,
                                                              const float* __restrict__ cam, const float* __restrict__ pool, uint32_t P, int h,
-                                                             float sigma, Key key, float* __restrict__ x_out, float* __restrict__ l_out) {
+                                                             float sigma, Key key, float* __restrict__ x_out, float* __restrict__ l_out,
+                                                             const long long* __restrict__ ext) {
     constexpr int WOUT = RNN4 ? 171 : 240, WL = RNN4 ? 69 : 3;
     __shared__ float rel[4][72];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -208,10 +220,12 @@ __global__ __launch_bounds__(256) void rc_batch_world_kernel(const float* __rest
     for (int q = 0; q < 9; ++q) R[q] = cam[12ll * s + q];
 #pragma unroll
     for (int q = 0; q < 3; ++q) tr[q] = cam[12ll * s + 9 + q];
-    const float* row = data + sf * 171;
-    const float* lab = label + sf * 72;
-    float* xo = x_out + f * WOUT;
-    float* lo = l_out + f * WL;
+    const long long fo = ext ? ext[n + s] + t : f;
+    const uint32_t pos = ext ? (uint32_t)ext[s] : (uint32_t)s;
+    const float* row = (ext ? reinterpret_cast<const float*>(ext[2 * (long long)n + s]) : data) + sf * 171;
+    const float* lab = (ext ? reinterpret_cast<const float*>(ext[3 * (long long)n + s]) : label) + sf * 72;
+    float* xo = x_out + fo * WOUT;
+    float* lo = l_out + fo * WL;
     float o[3];
     if (lane < 6) {                                             // accc = Rcw acc
         rot(R, row[3 * lane], row[3 * lane + 1], row[3 * lane + 2], o);
@@ -230,7 +244,7 @@ __global__ __launch_bounds__(256) void rc_batch_world_kernel(const float* __rest
     }
     const float r0 = __shfl(j[0], 0), r1 = __shfl(j[1], 0), r2 = __shfl(j[2], 0);
     float x = 0.f, y = 0.f, p = 0.f;
-    const uint32_t prow = pool_row((uint32_t)s, (uint32_t)t, P, h, key);
+    const uint32_t prow = pool_row(pos, (uint32_t)t, P, h, key);
     if (lane < 33) {                                            // j2dc = (Rcw j3dw_mp + t) / z, then the confidence row and its noise
         rot(R, row[72 + 3 * lane], row[72 + 3 * lane + 1], row[72 + 3 * lane + 2], o);
         o[0] += tr[0]; o[1] += tr[1]; o[2] += tr[2];
@@ -238,7 +252,7 @@ __global__ __launch_bounds__(256) void rc_batch_world_kernel(const float* __rest
         y = o[1] / o[2];
         p = pool[(long long)prow * 33 + lane];
         float z[4];
-        normals4((uint32_t)s, (uint32_t)t, SITE_KP, (uint32_t)(lane >> 1), key, z);
+        normals4(pos, (uint32_t)t, SITE_KP, (uint32_t)(lane >> 1), key, z);
         const float sd = 0.003f * (1.0f - p);
         x += sd * ((lane & 1) ? z[2] : z[0]);
         y += sd * ((lane & 1) ? z[3] : z[1]);
@@ -259,7 +273,7 @@ __global__ __launch_bounds__(256) void rc_batch_world_kernel(const float* __rest
         __syncthreads();
         if (lane < 18) {                                        // the ("tail", 69) noise of augment_fn: lane q owns units 4q .. 4q + 3
             float z[4];
-            normals4((uint32_t)s, (uint32_t)t, SITE_NOISE, (uint32_t)lane, key, z);
+            normals4(pos, (uint32_t)t, SITE_NOISE, (uint32_t)lane, key, z);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int u = 4 * lane + k;
@@ -272,28 +286,29 @@ __global__ __launch_bounds__(256) void rc_batch_world_kernel(const float* __rest
 }  // namespace
 
 void rc_launch_batch_plain(const float* data, const float* label, const long long* tab, int n, long long F, int W, int Wl, int c0,
-                           float sigma, const BatchKey& k, float* x_out, float* l_out, hipStream_t s) {
+                           float sigma, const BatchKey& k, float* x_out, float* l_out, hipStream_t s, const long long* ext) {
     const int ipr = (c0 + 3) / 4 + (W - c0 + 3) / 4 + (Wl + 3) / 4;
     const long long total = F * ipr;
     if (total <= 0) return;
     const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 4096);   // 16 blocks per CU, the rest by stride
     const Key key{make_uint2((uint32_t)k.seed, (uint32_t)(k.seed >> 32)), k.call};
-    hipLaunchKernelGGL(rc_batch_plain_kernel, dim3(grid), dim3(256), 0, s, data, label, tab, n, F, W, Wl, c0, sigma, key, x_out, l_out);
+    hipLaunchKernelGGL(rc_batch_plain_kernel, dim3(grid), dim3(256), 0, s, data, label, tab, n, F, W, Wl, c0, sigma, key, x_out, l_out,
+                       ext);
 }
 
 void rc_launch_batch_world(int rnn4, const float* data, const float* label, const long long* tab, int n, long long F,
                            const BatchCamera& range, float* cam, const float* pool, int pool_rows, float sigma, const BatchKey& k,
-                           float* x_out, float* l_out, hipStream_t s) {
+                           float* x_out, float* l_out, hipStream_t s, const long long* ext) {
     if (F <= 0 || n <= 0) return;
     const Key key{make_uint2((uint32_t)k.seed, (uint32_t)(k.seed >> 32)), k.call};
     int m = 0;
     while ((1ll << m) < pool_rows) m += 2;
-    hipLaunchKernelGGL(rc_batch_camera_kernel, dim3((unsigned)n), dim3(256), 0, s, label, tab, n, range, key, cam);
+    hipLaunchKernelGGL(rc_batch_camera_kernel, dim3((unsigned)n), dim3(256), 0, s, label, tab, n, range, key, cam, ext);
     const unsigned grid = (unsigned)((F + 3) / 4);
     if (rnn4)
         hipLaunchKernelGGL(rc_batch_world_kernel<true>, dim3(grid), dim3(256), 0, s, data, label, tab, n, F, cam, pool, (uint32_t)pool_rows,
-                           m / 2, sigma, key, x_out, l_out);
+                           m / 2, sigma, key, x_out, l_out, ext);
     else
         hipLaunchKernelGGL(rc_batch_world_kernel<false>, dim3(grid), dim3(256), 0, s, data, label, tab, n, F, cam, pool, (uint32_t)pool_rows,
-                           m / 2, sigma, key, x_out, l_out);
+                           m / 2, sigma, key, x_out, l_out, ext);
 }

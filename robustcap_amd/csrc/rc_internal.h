@@ -708,13 +708,33 @@ void rc_launch_subnet_eval(int kind, const BodyConst* body, const EvalGroup* tab
 struct BatchKey { unsigned long long seed; unsigned call; };
 struct BatchCamera { float yaw_lo, yaw_hi, pitch_lo, pitch_hi, roll_lo, roll_hi; };   // degrees
 // x_out[f] = data[row of f], columns [c0, W) + sigma * normal (c0 == W: a copy); l_out[f] = label[row of f]. Any alignment.
+// ext (device, or nullptr: rc_subnet_batch): the launch is one kind's share of a mixed batch (rc_subnet_batch_parts) -- [n] the sample's
+// position in the whole batch (the Philox `sample` word) | [n] its first output frame in the whole batch | [n] its part's data | [n] its
+// part's label (device addresses); tab's output frames then only enumerate the launch's own frames.
 void rc_launch_batch_plain(const float* data, const float* label, const long long* tab, int n, long long F, int W, int Wl, int c0,
-                           float sigma, const BatchKey& k, float* x_out, float* l_out, hipStream_t s);
+                           float sigma, const BatchKey& k, float* x_out, float* l_out, hipStream_t s, const long long* ext = nullptr);
 // the AMASS sample of rnn4 (rnn4 != 0: x [F, 171], label [F, 69]) or rnn6 (x [F, 240], label [F, 3]) from data [., 171], label [., 72] and
 // pool [pool_rows, 33]; cam: [n, 12] scratch (Rcw | t per sample), written by the first of the two launches
 void rc_launch_batch_world(int rnn4, const float* data, const float* label, const long long* tab, int n, long long F,
                            const BatchCamera& range, float* cam, const float* pool, int pool_rows, float sigma, const BatchKey& k,
-                           float* x_out, float* l_out, hipStream_t s);
+                           float* x_out, float* l_out, hipStream_t s, const long long* ext = nullptr);
+
+// ---- the training corpus of one sub-net (rc_corpus.hip; rc_subnet_corpus in rc_subnet_api.cpp) -------------------------------------------
+// tab (device): [n] first field frame of every sample's sequence | [n] first keypoint frame of every sample | [n + 1] first output row of
+// every sample, then the total R. cams (device, camera mode): per sample K^-1 [9] | rows 0 .. 2 of T_cw [12] | 1.0 for an occlusion sample.
+struct CorpusArgs {
+    const float *pose, *acc, *ori, *joint, *tran, *mp, *kp;   // the fields, concatenated over the sequences (kp: over the samples)
+    const long long* tab;
+    const float* cams;
+    const BodyConst* body;                                    // rnn7: the parent table
+    int n, net, amass, W, Wl;                                 // samples, kNets index, the AMASS spelling, row widths
+    long long R;
+    float sx, sy;                                             // image size: keypoints are stored divided by it
+    float *x, *y;
+};
+void rc_launch_subnet_corpus(int mode, const CorpusArgs& a, hipStream_t s);   // mode 0: root frame, 1: camera frame, 2: world
+// K^-1, R_cw and gravity of one camera by rc_camera_inputs_rows' routine (rc_api.cpp); false, nothing written: unusable
+bool rc_camera_constants(const float* K, const float* Tcw, CamConst* cam, float* g_out);
 
 // narrow view of the context for rc_subnet_api.cpp
 struct SubnetState;

@@ -63,6 +63,13 @@ struct SubnetState {                 // (grow-only buffers; the context's destru
     int btab_next = 0;
     DevBuf<float> bcam;              // kind world: Rcw | t of every sample [n, 12]
     size_t bcam_floats = 0;
+    // the corpus builders (rc_subnet_corpus): sample table and cameras; a call waits for the one before it (ctab_ev: its last kernel)
+    DevBuf<long long> ctab;          // [n] field frame | [n] keypoint frame | [n + 1] output row of every sample
+    DevBuf<float> ccam;              // [n, 22] K^-1 | rows 0 .. 2 of T_cw | occlusion flag
+    PinBuf<long long> ctab_h;
+    PinBuf<float> ccam_h;
+    size_t ctab_n = 0, ccam_n = 0;
+    HipEvent ctab_ev;
     int cus = 0;                     // compute units of the device (asked once)
 };
 
@@ -621,6 +628,39 @@ static const struct { int cols; float sigma; } kBatchNoise[6] = {{0, 0.f}, {69, 
 static const BatchCamera kBatchCamera4 = {-180.f, 180.f, -30.f, 30.f, -5.f, 5.f};
 static const BatchCamera kBatchCamera6 = {-90.f, 90.f, -30.f, 30.f, -5.f, 5.f};
 
+// the next pinned slot of the batch-table ring with room for nt entries (*th), the device table grown to hold them (and, for nw world
+// samples, the camera scratch): rc_subnet_batch and rc_subnet_batch_parts fill *th, then upload_batch_table
+static int batch_table_slot(rc_ctx* ctx, SubnetState* S, size_t nt, size_t nw, hipStream_t st, int* slot_out, long long** th) {
+    const int slot = S->btab_next;
+    S->btab_next = (slot + 1) % SubnetState::kBatchRing;
+    if (S->btab_ev[slot]) HIP_TRY(ctx, hipEventSynchronize(S->btab_ev[slot].get()));      // the upload made kBatchRing calls ago has left the slot
+    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->btab_ev[slot]), hipEventDisableTiming));
+    HIP_TRY(ctx, rc_grow(S->btab_hn[slot], nt, 2 * nt, S->btab_h[slot], 2 * nt));
+    if (nt > S->btab_n) {                                                                 // (kernels of earlier calls may still read the old table)
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, rc_grow(S->btab_n, nt, 2 * nt, S->btab, 2 * nt));
+    }
+    if (12 * nw > S->bcam_floats) {
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, rc_grow(S->bcam_floats, 12 * nw, 24 * nw, S->bcam, 24 * nw));
+    }
+    *slot_out = slot;
+    *th = S->btab_h[slot].get();
+    return RC_OK;
+}
+static int upload_batch_table(rc_ctx* ctx, SubnetState* S, int slot, size_t nt, hipStream_t st) {
+    HIP_TRY(ctx, hipMemcpyAsync(S->btab.get(), S->btab_h[slot].get(), nt * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(S->btab_ev[slot].get(), st));
+    return RC_OK;
+}
+// the bytes from p to the end of its allocation (-1: not a device allocation)
+static long long device_extent(const void* p) {
+    void* base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return (long long)((const char*)base + size - (const char*)p);
+}
+
 int rc_subnet_batch(rc_ctx* ctx, const char* net, int32_t kind, const float* data, const float* label, int32_t n,
                     const int64_t* offsets_host, const int32_t* lengths_host, const float* conf_pool, int32_t pool_rows, int32_t augment,
                     uint64_t seed, uint32_t call, float* x_out, float* label_out, void* stream) {
@@ -640,12 +680,7 @@ int rc_subnet_batch(rc_ctx* ctx, const char* net, int32_t kind, const float* dat
     const int W = world ? 171 : kBatchWidth[ni][0], Wl = world ? 72 : kBatchWidth[ni][1];
     const int Wo = kBatchWidth[ni][0], Wlo = kBatchWidth[ni][1];
     // the extents of the caller's allocations, asked once each
-    auto extent = [](const void* p) -> long long {
-        void* base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return -1; }
-        return (long long)((const char*)base + size - (const char*)p);
-    };
+    auto extent = device_extent;
     const long long data_bytes = extent(data), label_bytes = extent(label);
     long long F = 0;
     for (int i = 0; i < n; ++i) {
@@ -665,25 +700,13 @@ int rc_subnet_batch(rc_ctx* ctx, const char* net, int32_t kind, const float* dat
     SubnetState* S = state(ctx);
     // ---- the table: pinned slot -> device, on `stream`
     const size_t nt = 2 * (size_t)n + 1;
-    const int slot = S->btab_next;
-    S->btab_next = (slot + 1) % SubnetState::kBatchRing;
-    if (S->btab_ev[slot]) HIP_TRY(ctx, hipEventSynchronize(S->btab_ev[slot].get()));      // the upload made kBatchRing calls ago has left the slot
-    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->btab_ev[slot]), hipEventDisableTiming));
-    HIP_TRY(ctx, rc_grow(S->btab_hn[slot], nt, 2 * nt, S->btab_h[slot], 2 * nt));
-    if (nt > S->btab_n) {                                                                 // (kernels of earlier calls may still read the old table)
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        HIP_TRY(ctx, rc_grow(S->btab_n, nt, 2 * nt, S->btab, 2 * nt));
-    }
-    if (world && 12 * (size_t)n > S->bcam_floats) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        HIP_TRY(ctx, rc_grow(S->bcam_floats, 12 * (size_t)n, 24 * (size_t)n, S->bcam, 24 * (size_t)n));
-    }
-    long long* th = S->btab_h[slot].get();
+    int slot = 0;
+    long long* th = nullptr;
+    if (int rc = batch_table_slot(ctx, S, nt, world ? (size_t)n : 0, st, &slot, &th)) return rc;
     long long at = 0;
     for (int i = 0; i < n; ++i) { th[i] = offsets_host[i]; th[n + i] = at; at += lengths_host[i]; }
     th[2 * (size_t)n] = at;
-    HIP_TRY(ctx, hipMemcpyAsync(S->btab.get(), th, nt * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(S->btab_ev[slot].get(), st));
+    if (int rc = upload_batch_table(ctx, S, slot, nt, st)) return rc;
     const BatchKey key{seed, call};
     if (world) {
         rc_launch_batch_world(rnn4 ? 1 : 0, data, label, S->btab.get(), n, F, rnn4 ? kBatchCamera4 : kBatchCamera6, S->bcam.get(), conf_pool,
@@ -693,6 +716,197 @@ int rc_subnet_batch(rc_ctx* ctx, const char* net, int32_t kind, const float* dat
         rc_launch_batch_plain(data, label, S->btab.get(), n, F, W, Wl, W - noisy, kBatchNoise[ni].sigma, key, x_out, label_out, st);
     }
     HIP_TRY(ctx, hipGetLastError());
+    return RC_OK;
+}
+
+int rc_subnet_batch_parts(rc_ctx* ctx, const char* net, int32_t n_parts, const int32_t* kinds_host, const float* const* data_parts,
+                          const float* const* label_parts, const float* conf_pool, int32_t pool_rows, int32_t n, const int32_t* part_host,
+                          const int64_t* offsets_host, const int32_t* lengths_host, int32_t augment, uint64_t seed, uint32_t call,
+                          float* x_out, float* label_out, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    const std::string f = "rc_subnet_batch_parts: ";
+    if (!net || !kinds_host || !data_parts || !label_parts || !part_host || !offsets_host || !lengths_host || !x_out || !label_out)
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "null argument").c_str());
+    const int ni = rc_ctx_net_index(net);
+    if (ni < 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "unknown net " + net).c_str());
+    if (n_parts <= 0 || n <= 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "no parts or no samples").c_str());
+    const bool rnn4 = ni == 2, rnn6 = ni == 3;
+    const int Wo = kBatchWidth[ni][0], Wlo = kBatchWidth[ni][1];
+    std::vector<long long> data_bytes((size_t)n_parts), label_bytes((size_t)n_parts);
+    for (int p = 0; p < n_parts; ++p) {
+        if (kinds_host[p] != RC_BATCH_PLAIN && kinds_host[p] != RC_BATCH_WORLD)
+            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "kind 0 (plain) or 1 (world)").c_str());
+        if (kinds_host[p] == RC_BATCH_WORLD && !rnn4 && !rnn6)
+            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "kind world is rnn4's and rnn6's, not " + net + "'s").c_str());
+        if (!data_parts[p] || !label_parts[p]) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "null part").c_str());
+        data_bytes[p] = device_extent(data_parts[p]);
+        label_bytes[p] = device_extent(label_parts[p]);
+    }
+    long long F = 0;
+    int nw = 0;
+    for (int i = 0; i < n; ++i) {
+        const int p = part_host[i];
+        if (p < 0 || p >= n_parts) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sample of a part that is not there").c_str());
+        const bool world = kinds_host[p] == RC_BATCH_WORLD;
+        const int W = world ? 171 : Wo, Wl = world ? 72 : Wlo;
+        const long long off = offsets_host[i], len = lengths_host[i];
+        if (len < 1 || off < 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "every sample needs an offset >= 0 and at least one frame").c_str());
+        if (off + len > (1ll << 40) || (off + len) * 4 * W > data_bytes[p] || (off + len) * 4 * Wl > label_bytes[p])
+            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sample ends past the corpus buffers").c_str());
+        if (world && !augment)
+            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a world sample has no un-augmented form (the camera is part of it)").c_str());
+        if (world && (!conf_pool || pool_rows < 1)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "kind world needs a confidence pool").c_str());
+        if (world && len > pool_rows)
+            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sample of " + std::to_string(len) + " frames cannot draw distinct rows from a pool of " +
+                                                     std::to_string(pool_rows)).c_str());
+        nw += world ? 1 : 0;
+        F += len;
+    }
+    if (F >= (1ll << 31)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "2^31 frames or more").c_str());
+    if (device_extent(x_out) < 4 * F * Wo || device_extent(label_out) < 4 * F * Wlo || (nw && device_extent(conf_pool) < 4ll * pool_rows * 33))
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "an output or the pool ends before its extent").c_str());
+    hipStream_t st = (hipStream_t)stream;
+    SubnetState* S = state(ctx);
+    // ---- one table for both launches: per kind [m] corpus frame | [m + 1] the launch's own output frames | ext [4 m] (rc_internal.h)
+    const int np = n - nw;
+    const size_t nt = 6 * (size_t)n + 2;
+    int slot = 0;
+    long long* th = nullptr;
+    if (int rc = batch_table_slot(ctx, S, nt, (size_t)nw, st, &slot, &th)) return rc;
+    long long* tab_k[2] = {th, th + (6 * (size_t)np + 1)};
+    const int m_k[2] = {np, nw};
+    int at_k[2] = {0, 0};
+    long long F_k[2] = {0, 0}, at = 0;
+    for (int i = 0; i < n; ++i) {
+        const int p = part_host[i], k = kinds_host[p] == RC_BATCH_WORLD ? 1 : 0, m = m_k[k], j = at_k[k]++;
+        long long* t = tab_k[k];
+        long long* ext = t + 2 * (size_t)m + 1;
+        t[j] = offsets_host[i];
+        t[m + j] = F_k[k];
+        ext[j] = i;
+        ext[m + j] = at;
+        ext[2 * (size_t)m + j] = (long long)(uintptr_t)data_parts[p];
+        ext[3 * (size_t)m + j] = (long long)(uintptr_t)label_parts[p];
+        F_k[k] += lengths_host[i];
+        at += lengths_host[i];
+    }
+    tab_k[0][2 * (size_t)np] = F_k[0];
+    tab_k[1][2 * (size_t)nw] = F_k[1];
+    if (int rc = upload_batch_table(ctx, S, slot, nt, st)) return rc;
+    const long long* dev_k[2] = {S->btab.get(), S->btab.get() + (6 * (size_t)np + 1)};
+    const BatchKey key{seed, call};
+    if (np) {
+        const int noisy = augment ? kBatchNoise[ni].cols : 0;
+        rc_launch_batch_plain(nullptr, nullptr, dev_k[0], np, F_k[0], Wo, Wlo, Wo - noisy, kBatchNoise[ni].sigma, key, x_out, label_out, st,
+                              dev_k[0] + 2 * (size_t)np + 1);
+    }
+    if (nw)
+        rc_launch_batch_world(rnn4 ? 1 : 0, nullptr, nullptr, dev_k[1], nw, F_k[1], rnn4 ? kBatchCamera4 : kBatchCamera6, S->bcam.get(),
+                              conf_pool, pool_rows, kBatchNoise[ni].sigma, key, x_out, label_out, st, dev_k[1] + 2 * (size_t)nw + 1);
+    HIP_TRY(ctx, hipGetLastError());
+    return RC_OK;
+}
+
+int rc_subnet_corpus(rc_ctx* ctx, const char* net, int32_t source, int32_t n_seq, const int32_t* seq_frames_host, int64_t frames,
+                     const float* pose, const float* imu_acc, const float* imu_ori, const float* joint3d, const float* tran,
+                     const float* sync_3d_mp, int32_t n_samples, const int32_t* sample_seq_host, const int32_t* sample_occ_host,
+                     const float* cam_K_host, const float* cam_T_host, const float* kp, int64_t kp_frames, float image_w, float image_h,
+                     float* x_out, float* label_out, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    const std::string f = "rc_subnet_corpus: ";
+    if (!net || !seq_frames_host || !x_out || !label_out) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "null argument").c_str());
+    const int ni = rc_ctx_net_index(net);
+    if (ni < 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "unknown net " + net).c_str());
+    if (source != RC_CORPUS_AIST && source != RC_CORPUS_AMASS)
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "source 0 (AIST) or 1 (AMASS)").c_str());
+    const bool amass = source == RC_CORPUS_AMASS, cam_net = ni == 2 || ni == 3;
+    if (ni == 5 && !amass) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "the reference has no AIST corpus for rnn8").c_str());
+    const int mode = !cam_net ? 0 : (amass ? 2 : 1);
+    if (!imu_acc || !imu_ori || !joint3d || (mode == 0 && !pose) || (mode == 1 && ni == 3 && !tran) || (mode == 2 && !sync_3d_mp) ||
+        (mode == 1 && (!sample_seq_host || !cam_K_host || !cam_T_host || !kp)))
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a field this corpus reads is null").c_str());
+    const BodyConst* body = rc_ctx_body(ctx);
+    if (ni == 4 && !body) return rc_ctx_fail(ctx, RC_ERR_STATE, (f + "rnn7's labels need the body (rc_set_body)").c_str());
+    if (n_seq <= 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "no sequences").c_str());
+    std::vector<long long> first((size_t)n_seq);
+    long long total = 0;
+    for (int i = 0; i < n_seq; ++i) {
+        if (seq_frames_host[i] < 3)
+            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sequence of fewer than 3 frames has no row ([1:-1] of it is empty)").c_str());
+        first[i] = total;
+        total += seq_frames_host[i];
+    }
+    if (total != frames) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "the sequence table does not sum to the buffers' frames").c_str());
+    if (mode != 1) {
+        if (sample_seq_host || (n_samples != 0 && n_samples != n_seq))
+            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "only the AIST corpora of rnn4 and rnn6 have view samples").c_str());
+        n_samples = n_seq;
+    }
+    if (n_samples <= 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "no samples").c_str());
+    const int n = n_samples;
+    long long R = 0, kp_total = 0;
+    for (int s = 0; s < n; ++s) {
+        const int q = mode == 1 ? sample_seq_host[s] : s;
+        if (q < 0 || q >= n_seq) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sample of a sequence that is not there").c_str());
+        R += seq_frames_host[q] - 2;
+        kp_total += seq_frames_host[q];
+    }
+    if (mode == 1 && kp_total != kp_frames)
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "the sample table does not sum to the keypoint buffer's frames").c_str());
+    if (R >= (1ll << 31)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "2^31 rows or more").c_str());
+    if (mode == 1 && !(std::isfinite(image_w) && std::isfinite(image_h)))
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "image size not finite").c_str());
+    std::vector<CamConst> cams;
+    if (mode == 1) {
+        cams.resize((size_t)n);
+        float g[3];
+        for (int s = 0; s < n; ++s)
+            if (!rc_camera_constants(cam_K_host + 9 * (size_t)s, cam_T_host + 16 * (size_t)s, &cams[s], g))
+                return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "camera of sample " + std::to_string(s) + " is not finite or K is singular").c_str());
+    }
+    const int W = mode == 2 ? 171 : kBatchWidth[ni][0], Wl = mode == 2 ? 72 : kBatchWidth[ni][1];
+    auto holds = [](const float* p, long long rows, int width) { return !p || device_extent(p) >= 4 * rows * width; };
+    if (!holds(pose, total, 72) || !holds(imu_acc, total, 18) || !holds(imu_ori, total, 54) || !holds(joint3d, total, 72) ||
+        !holds(tran, total, 3) || !holds(sync_3d_mp, total, 99) || (mode == 1 && !holds(kp, kp_total, 99)) || !holds(x_out, R, W) ||
+        !holds(label_out, R, Wl))
+        return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a field or an output ends before its extent").c_str());
+    hipStream_t st = (hipStream_t)stream;
+    SubnetState* S = state(ctx);
+    if (S->ctab_ev) HIP_TRY(ctx, hipEventSynchronize(S->ctab_ev.get()));                   // the call before this one has left the tables
+    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->ctab_ev), hipEventDisableTiming));
+    const size_t nt = 3 * (size_t)n + 1, nc = 22 * (size_t)n;
+    HIP_TRY(ctx, rc_grow(S->ctab_n, nt, 2 * nt, S->ctab, 2 * nt, S->ctab_h, 2 * nt));
+    if (mode == 1) HIP_TRY(ctx, rc_grow(S->ccam_n, nc, 2 * nc, S->ccam, 2 * nc, S->ccam_h, 2 * nc));
+    long long* th = S->ctab_h.get();
+    long long row = 0, kf = 0;
+    for (int s = 0; s < n; ++s) {
+        const int q = mode == 1 ? sample_seq_host[s] : s;
+        th[s] = first[q];
+        th[n + s] = kf;
+        th[2 * (size_t)n + s] = row;
+        row += seq_frames_host[q] - 2;
+        kf += seq_frames_host[q];
+    }
+    th[3 * (size_t)n] = row;
+    HIP_TRY(ctx, hipMemcpyAsync(S->ctab.get(), th, nt * sizeof(long long), hipMemcpyHostToDevice, st));
+    if (mode == 1) {
+        float* ch = S->ccam_h.get();
+        for (int s = 0; s < n; ++s) {
+            float* c = ch + 22 * (size_t)s;
+            for (int q = 0; q < 9; ++q) c[q] = cams[s].Kinv[q];
+            for (int q = 0; q < 12; ++q) c[9 + q] = cam_T_host[16 * (size_t)s + q];
+            c[21] = (sample_occ_host && sample_occ_host[s]) ? 1.0f : 0.0f;
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(S->ccam.get(), ch, nc * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    CorpusArgs a{};
+    a.pose = pose; a.acc = imu_acc; a.ori = imu_ori; a.joint = joint3d; a.tran = tran; a.mp = sync_3d_mp; a.kp = kp;
+    a.tab = S->ctab.get(); a.cams = S->ccam.get(); a.body = body;
+    a.n = n; a.net = ni; a.amass = amass ? 1 : 0; a.W = W; a.Wl = Wl; a.R = R;
+    a.sx = image_w; a.sy = image_h; a.x = x_out; a.y = label_out;
+    rc_launch_subnet_corpus(mode, a, st);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(S->ctab_ev.get(), st));
     return RC_OK;
 }
 

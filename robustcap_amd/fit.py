@@ -302,3 +302,31 @@ def train(tr, train_ds, valid_ds=None, save_dir="weights", loss_fn=None, eval_fn
         if epoch_callback_fn is not None:
             epoch_callback_fn()
     return history
+
+
+# ---- from the dictionaries ------------------------------------------------------------------------------------------------------------------
+def train_subnet(net, name, aist=None, amass=None, aist_val=None, amass_val=None, conf_pool=None, save_dir="weights",
+                 image_size=(1920, 1080), **overrides):
+    """The reference's ``train_rnnK()`` (net/sig_mp.py:301-839) from the preprocessed dictionaries to ``best_weights.pt``:
+    ``aist`` / ``amass`` are the ``train.pt`` dictionaries, ``aist_val`` / ``amass_val`` the ``val.pt`` ones, as ``torch.load`` returns
+    them (the only host work is reading them). Each present dictionary becomes a corpus on the device (``corpus.build``), the training
+    parts cut with ``config.TRAIN[name]["split_size"]``, the validation parts whole; the parts are concatenated in the reference's order
+    (AIST, then AMASS; rnn8 trains on AMASS only and refuses ``aist``); rnn8's ``pos_weight`` comes from the training labels; then
+    ``tr.fit``. ``conf_pool`` ([P, 33], ``syn_c.pt``): the AMASS parts of rnn4 / rnn6. ``overrides``: any argument of ``fit.train``, and
+    ``split_size`` for the training parts. Returns ``tr.fit``'s records."""
+    from . import corpus
+    if name == "rnn8" and (aist is not None or aist_val is not None):
+        raise ValueError("rnn8 trains on AMASS only (net/sig_mp.py:825-827)")
+    if aist is None and amass is None:
+        raise ValueError("train_subnet: no training dictionary")
+    tr = net.trainable(name)
+    split = overrides.pop("split_size", cfg.TRAIN[name]["split_size"])
+
+    def parts(a, b, split_size):
+        ps = [corpus.dataset(tr, source, d, split_size, conf_pool, image_size) for source, d in (("aist", a), ("amass", b)) if d is not None]
+        return tr.concat(ps) if ps else None
+
+    train_ds, valid_ds = parts(aist, amass, split), parts(aist_val, amass_val, -1)
+    if name == "rnn8" and "pos_weight" not in overrides:
+        overrides["pos_weight"] = losses.pos_weight_from_labels(train_ds)
+    return tr.fit(train_ds, valid_ds, save_dir, **overrides)

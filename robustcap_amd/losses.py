@@ -233,10 +233,12 @@ def reference_mean(values):
 
 def pos_weight_from_labels(labels):
     """``(1 - l).sum(0) / l.sum(0)`` over the concatenated labels (net/sig_mp.py:829-830): rnn8's ``pos_weight``. ``labels``: one tensor,
-    a list of tensors, or a ``tr.dataset(...)`` (its label buffer on the device: every frame of the corpus once, as the reference's
-    ``torch.cat(label)``)."""
+    a list of tensors, a ``tr.dataset(...)`` (its label buffer on the device: every frame of the corpus once, as the reference's
+    ``torch.cat(label)``) or a ``tr.concat(...)`` of such (its parts' buffers, concatenated)."""
     if hasattr(labels, "label") and hasattr(labels, "samples"):
         l = labels.label
+        if isinstance(l, (list, tuple)):
+            l = torch.cat(list(l))
     else:
         ls, _, _ = _rows(labels, "labels")
         l = torch.cat(ls)

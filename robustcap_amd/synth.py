@@ -331,6 +331,84 @@ def make_dataset(seed, n_seq, T, body, n_cam=3, conf="mixed", image_size=(1920, 
     return ds
 
 
+def make_training_dicts(seed, lengths, body, n_cam=3, image_size=(1920, 1080)):
+    """Synthetic ``train.pt`` / ``val.pt`` dictionaries in the two layouts the dataset builders of net/sig_mp.py:301-839 read, one
+    sequence per entry of ``lengths``: ``(aist, amass)``.
+
+    Both: ``tran`` [T,3], ``imu_ori`` [T,6,3,3], ``imu_acc`` [T,6,3], ``joint3d`` [T,24,3], ``sync_3d_mp`` [T,33,3] (sync_mp3d of the
+    posed body), ``shape`` [10], all world-frame float32. ``aist``: ``pose`` [T,72] axis-angle, per sequence ``cam_K`` [n_cam,3,3],
+    ``cam_T`` [n_cam,4,4] and the lists ``joint2d_mp`` / ``joint2d_occ`` of n_cam entries [T,33,3] = (u / width, v / height,
+    confidence); sequence i has the view (i + 1) % n_cam missing (None) and, at view (i + 2) % n_cam, a None occlusion entry (even i) or
+    one a frame short (odd i). ``amass``: ``pose`` [T,24,3] and other motions (its seeds differ).
+
+    Every sequence moves slowly in its first half and fast in its second (the per-frame increments are scaled by 0.02), so that both
+    feet are in contact (central-difference speed < 0.25 m/s, net/sig_mp.py:812-815) and out of it within one sequence of >= 6 frames."""
+    W, H = image_size
+    ids = list(C.mp_mask) + list(C.vi_mask)
+
+    def motion(s, T):
+        sp = np.where(np.arange(T) < T // 2, 0.02, 1.0)
+        aa = np.cumsum(0.03 * normal(s, 1, T * 72).reshape(T, 24, 3).astype(np.float64) * sp[:, None, None], 0)
+        aa = 0.7 * np.tanh(aa / 0.7)
+        R = _rodrigues(aa)
+        yaw = np.cumsum(0.03 * normal(s, 2, T).astype(np.float64) * sp) + 6.28 * uniform01(s, 3, 1)[0]
+        Rtilt = _rodrigues(0.15 * (uniform01(s, 4, 3).astype(np.float64) - 0.5))
+        R[:, 0] = Rtilt @ np.diag([1.0, -1.0, -1.0]) @ _rodrigues(np.stack([np.zeros(T), yaw, np.zeros(T)], -1)) @ R[:, 0]
+        u0 = uniform01(s, 5, 3).astype(np.float64)
+        start = np.array([-0.8 + 1.6 * u0[0], -0.5 + 1.0 * u0[1], 3.5 + 3.5 * u0[2]])
+        tr = start + np.cumsum(0.012 * normal(s, 6, T * 3).reshape(T, 3).astype(np.float64) * sp[:, None], 0)
+        G, joint, vert = body_fk_numpy(body, R, tr, ids)
+        v33, v6 = vert[:, :33].copy(), vert[:, 33:]
+        for row, j in C.mp_joint_override.items():
+            v33[:, row] = joint[:, j]
+        acc = np.zeros((T, 6, 3))
+        if T > 2:
+            acc[1:-1] = (v6[:-2] + v6[2:] - 2 * v6[1:-1]) * 3600
+        return {"R": R, "tran": tr, "imu_ori": G[:, list(C.ji_mask)], "imu_acc": acc, "joint3d": joint, "sync_3d_mp": v33}
+
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    keys = ("pose", "tran", "imu_ori", "imu_acc", "joint3d", "sync_3d_mp", "shape")
+    aist = {k: [] for k in keys + ("cam_K", "cam_T", "joint2d_mp", "joint2d_occ")}
+    amass = {k: [] for k in keys}
+    for i, T in enumerate(lengths):
+        for ds, s in ((aist, seed * 131 + i), (amass, seed * 137 + 7919 + i)):
+            m = motion(s, T)
+            ds["pose"].append(f32(_log_map(m["R"]).reshape(T, 72) if ds is aist else _log_map(m["R"])))
+            for k in ("tran", "imu_ori", "imu_acc", "joint3d", "sync_3d_mp"):
+                ds[k].append(f32(m[k]))
+            ds["shape"].append(np.zeros(10, np.float32))
+            if ds is amass:
+                continue
+            Ks, Ts, kps, occs = [], [], [], []
+            for c in range(n_cam):
+                u = uniform01(seed * 977 + i, 50 + c, 8).astype(np.float64)
+                Rcw = np.eye(3) if c == 0 else _rodrigues(np.array([0.05 * (u[1] - 0.5), 0.5 * (u[0] - 0.5), 0.03 * (u[2] - 0.5)]))
+                centre = m["tran"].mean(0)
+                t = np.zeros(3) if c == 0 else centre - Rcw @ centre + np.array([0.4 * (u[3] - 0.5), 0.2 * (u[4] - 0.5), 0.6 * u[5]])
+                Tcw = np.eye(4)
+                Tcw[:3, :3], Tcw[:3, 3] = Rcw, t
+                fl = 1400.0 + 200.0 * u[6]
+                K = np.array([[fl, 0.0, W / 2 + 20 * (u[7] - 0.5)], [0.0, fl * 1.002, H / 2], [0.0, 0.0, 1.0]])
+                Xc = m["sync_3d_mp"] @ Rcw.T + t
+                uv = ((Xc / Xc[..., 2:]) @ K.T)[..., :2]
+                conf = 0.5 + 0.49 * uniform01(seed * 31 + i, 80 + c, T * 33).reshape(T, 33).astype(np.float64)
+                kp = np.concatenate([uv / np.array([W, H]), conf[..., None]], -1)
+                hid = uniform01(seed * 37 + i, 120 + c, T * 33).reshape(T, 33) < 0.3          # occluded landmarks: displaced, low confidence
+                shift = 0.05 * (uniform01(seed * 41 + i, 160 + c, T * 66).reshape(T, 33, 2).astype(np.float64) - 0.5)
+                occ = kp.copy()
+                occ[..., :2] += np.where(hid[..., None], shift, 0.0)
+                occ[..., 2] = np.where(hid, 0.2 * conf, conf)
+                Ks.append(K), Ts.append(Tcw), kps.append(f32(kp)), occs.append(f32(occ))
+            kps[(i + 1) % n_cam] = None
+            j = (i + 2) % n_cam
+            occs[j] = None if i % 2 == 0 else occs[j][:-1]
+            aist["cam_K"].append(f32(np.stack(Ks)))
+            aist["cam_T"].append(f32(np.stack(Ts)))
+            aist["joint2d_mp"].append(kps)
+            aist["joint2d_occ"].append(occs)
+    return aist, amass
+
+
 # ------------------------------------------------------------------------------------------------- smplify prior
 def make_gmm(seed=3, n=8, dim=69):
     """Synthetic stand-in for the SMPLify pose prior ``gmm_08.pkl`` (external asset; net/smplify/prior.py:102-111 reads
