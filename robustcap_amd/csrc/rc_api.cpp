@@ -660,12 +660,8 @@ int rc_subnet_eval(rc_ctx* ctx, int32_t kind, const float* x, const float* y, in
     hipStream_t st = (hipStream_t)stream;
     // ---- the group table: pinned slot -> device, on `stream`
     const size_t G = (size_t)groups;
-    const int slot = ctx->eval_next;
-    ctx->eval_next = (slot + 1) % rc_ctx::kEvalRing;
-    if (ctx->eval_ev[slot]) HIP_TRY(ctx, hipEventSynchronize(ctx->eval_ev[slot].get()));     // the upload made kEvalRing calls ago has left the slot
-    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->eval_ev[slot]), hipEventDisableTiming));
-    HIP_TRY(ctx, rc_grow(ctx->eval_tab_hn[slot], G, 2 * G, ctx->eval_tab_h[slot], 2 * G));
-    EvalGroup* th = ctx->eval_tab_h[slot].get();
+    EvalGroup* th = nullptr;
+    HIP_TRY(ctx, ctx->eval_tab.stage(G, &th));
     long long at = 0, blocks = 0;
     for (int g = 0; g < groups; ++g) {
         th[g].frame0 = at;
@@ -675,13 +671,13 @@ int rc_subnet_eval(rc_ctx* ctx, int32_t kind, const float* x, const float* y, in
         at += th[g].frames;
         blocks += th[g].nblk;
     }
-    if (G > ctx->eval_tab_n || (size_t)blocks > ctx->eval_partial_n) {                       // (kernels of earlier calls may still use the old buffers)
+    if (!ctx->eval_tab.holds(G) || (size_t)blocks > ctx->eval_partial_n) {                   // (kernels of earlier calls may still use the old buffers)
         HIP_TRY(ctx, hipStreamSynchronize(st));
-        HIP_TRY(ctx, rc_grow(ctx->eval_tab_n, G, 2 * G, ctx->eval_tab, 2 * G));
+        HIP_TRY(ctx, ctx->eval_tab.grow(G));
         HIP_TRY(ctx, rc_grow(ctx->eval_partial_n, (size_t)blocks, 2 * (size_t)blocks, ctx->eval_partial, 2 * (size_t)blocks));
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->eval_tab.get(), th, G * sizeof(EvalGroup), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(ctx->eval_ev[slot].get(), st));
+    HIP_TRY(ctx, ctx->eval_tab.upload(G, st));
+    HIP_TRY(ctx, ctx->eval_tab.record(st));
     rc_launch_subnet_eval(kind, ctx->body, ctx->eval_tab.get(), groups, blocks, x, y, width, aux_dev, ctx->eval_partial.get(), values_dev, st);
     HIP_TRY(ctx, hipGetLastError());
     return RC_OK;
@@ -1019,12 +1015,8 @@ int rc_motion_metrics(rc_ctx* ctx, const float* pose_p, const float* tran_p, con
     hipStream_t st = (hipStream_t)stream;
     // ---- the group table: pinned slot -> device, on `stream`
     const size_t G = (size_t)groups;
-    const int slot = ctx->motion_next;
-    ctx->motion_next = (slot + 1) % rc_ctx::kEvalRing;
-    if (ctx->motion_ev[slot]) HIP_TRY(ctx, hipEventSynchronize(ctx->motion_ev[slot].get()));   // the upload made kEvalRing calls ago has left the slot
-    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->motion_ev[slot]), hipEventDisableTiming));
-    HIP_TRY(ctx, rc_grow(ctx->motion_tab_hn[slot], G, 2 * G, ctx->motion_tab_h[slot], 2 * G));
-    MotionGroup* th = ctx->motion_tab_h[slot].get();
+    MotionGroup* th = nullptr;
+    HIP_TRY(ctx, ctx->motion_tab.stage(G, &th));
     long long at = 0, blk = 0;
     for (int g = 0; g < groups; ++g) {
         th[g].frame0 = at;
@@ -1035,14 +1027,14 @@ int rc_motion_metrics(rc_ctx* ctx, const float* pose_p, const float* tran_p, con
         blk += th[g].nblk;
     }
     const size_t need_s = (size_t)rc_motion_scratch_floats(n), need_p = (size_t)rc_motion_partial_doubles(ctx->mesh_V, blocks, groups, mesh);
-    if (G > ctx->motion_tab_n || need_s > ctx->motion_scratch_n || need_p > ctx->motion_partial_n) {   // (kernels of earlier calls may still use the old buffers)
+    if (!ctx->motion_tab.holds(G) || need_s > ctx->motion_scratch_n || need_p > ctx->motion_partial_n) {   // (kernels of earlier calls may still use the old buffers)
         HIP_TRY(ctx, hipStreamSynchronize(st));
-        HIP_TRY(ctx, rc_grow(ctx->motion_tab_n, G, 2 * G, ctx->motion_tab, 2 * G));
+        HIP_TRY(ctx, ctx->motion_tab.grow(G));
         HIP_TRY(ctx, rc_grow(ctx->motion_scratch_n, need_s, need_s, ctx->motion_scratch, need_s));
         HIP_TRY(ctx, rc_grow(ctx->motion_partial_n, need_p, need_p, ctx->motion_partial, need_p));
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->motion_tab.get(), th, G * sizeof(MotionGroup), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(ctx->motion_ev[slot].get(), st));
+    HIP_TRY(ctx, ctx->motion_tab.upload(G, st));
+    HIP_TRY(ctx, ctx->motion_tab.record(st));
     rc_launch_motion_metrics(ctx->body, ctx->mesh_vt, ctx->mesh_w, ctx->mesh_V, ctx->motion_tab.get(), groups, blocks, pose_p, tran_p, pose_t,
                              tran_t, n, fps, align_joint, joint_mask, mesh, ctx->motion_scratch.get(), ctx->motion_partial.get(), out, per_joint, st);
     HIP_TRY(ctx, hipGetLastError());

@@ -77,32 +77,18 @@ struct rc_ctx {
     SubnetOwner subnet;                  // scratch of rc_subnet_forward (rc_subnet_api.cpp)
     DevBuf<double> optim_partial;        // rc_subnet_optim_step: per-workgroup sums of squares of the gradient norm, sized once for the largest sub-net
     DevBuf<double> loss_partial;         // rc_subnet_loss: RC_LOSS_MAX_PARTIALS per-workgroup sums, allocated by the first call
-    // rc_subnet_eval: per-workgroup sums of all groups (grow-only, its own: not loss_partial) and the group table, staged through a ring
-    // of pinned copies like rc_subnet_batch's sample table (a call waits for the upload made kEvalRing calls earlier)
-    static constexpr int kEvalRing = 4;
+    // rc_subnet_eval: per-workgroup sums of all groups (grow-only, its own: not loss_partial) and the group table
     DevBuf<double> eval_partial;
     size_t eval_partial_n = 0;
-    DevBuf<EvalGroup> eval_tab;
-    size_t eval_tab_n = 0;
-    PinBuf<EvalGroup> eval_tab_h[kEvalRing];
-    size_t eval_tab_hn[kEvalRing] = {};
-    HipEvent eval_ev[kEvalRing];         // the last upload from eval_tab_h[i]
-    int eval_next = 0;
-    // rc_motion_metrics: per-frame scratch, per-block (mean, M2) pairs and the group table (all grow-only), the table staged through a ring
-    // of pinned copies like rc_subnet_eval's
+    StagedTable<EvalGroup, 4> eval_tab;
+    // rc_motion_metrics: per-frame scratch, per-block (mean, M2) pairs (grow-only) and the group table
     DevBuf<float> motion_scratch;
     size_t motion_scratch_n = 0;
     DevBuf<double> motion_partial;
     size_t motion_partial_n = 0;
-    DevBuf<MotionGroup> motion_tab;
-    size_t motion_tab_n = 0;
-    PinBuf<MotionGroup> motion_tab_h[kEvalRing];
-    size_t motion_tab_hn[kEvalRing] = {};
-    HipEvent motion_ev[kEvalRing];       // the last upload from motion_tab_h[i]
-    int motion_next = 0;
+    StagedTable<MotionGroup, 4> motion_tab;
     // rc_set_shape_space / rc_prepare_motions (rc_prepare_api.cpp): the folded shape basis and the 39 picked vertices (one allocation, `prep_sp`
-    // points into it), the per-sequence rest records, the IMU-vertex scratch of a call without vert6_out and the sequence table (grow-only),
-    // the table staged through a ring of pinned copies like rc_motion_metrics'
+    // points into it), the per-sequence rest records, the IMU-vertex scratch of a call without vert6_out (grow-only) and the sequence table
     DevBuf<float> prep_space;
     PrepShapeSpace prep_sp{};
     int prep_V = 0;                      // mesh_V of the rc_set_shape_space call; 0: none yet
@@ -111,12 +97,7 @@ struct rc_ctx {
     size_t prep_rest_n = 0;
     DevBuf<float> prep_vert6;
     size_t prep_vert6_n = 0;
-    DevBuf<PrepSeq> prep_tab;
-    size_t prep_tab_n = 0;
-    PinBuf<PrepSeq> prep_tab_h[kEvalRing];
-    size_t prep_tab_hn[kEvalRing] = {};
-    HipEvent prep_ev[kEvalRing];         // the last upload from prep_tab_h[i]
-    int prep_next = 0;
+    StagedTable<PrepSeq, 4> prep_tab;
 };
 
 #pragma GCC visibility push(hidden)

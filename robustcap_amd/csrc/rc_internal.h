@@ -527,6 +527,43 @@ template <class Cap, class... BufsAndCounts> hipError_t rc_grow(Cap& cap, size_t
     if (e == hipSuccess) cap = (Cap)want;
     return e;
 }
+// A table the host builds per call and sends to the device on the caller's stream: the device table, a ring of `Ring` pinned copies, one
+// event per copy (created with its first use; it says that the last upload from the copy, or whatever the site recorded it behind, is
+// done) and the cursor. A call takes the next copy, so it waits for the call made `Ring` calls earlier and not for the one before it.
+// Everything is grow-only, room for Slack * n entries where n are needed. The owner never synchronises a stream or the device: the
+// device table may only grow behind the site's own synchronisation (kernels of earlier calls may still read the old one), which the
+// site's contract in the header names. A call: stage -> fill -> [holds? -> the site synchronises -> grow] -> upload -> record.
+#pragma GCC visibility push(hidden)
+template <class T, int Ring, int Slack = 2> class StagedTable {
+    static_assert(std::is_trivially_copyable<T>::value && Ring >= 1 && Slack >= 1, "plain entries, at least one pinned copy");
+    DevBuf<T> dev_;
+    size_t dev_n_ = 0;
+    PinBuf<T> pin_[Ring];
+    size_t pin_n_[Ring] = {};
+    HipEvent ev_[Ring];
+    int next_ = 0;
+    int slot() const { return (next_ + Ring - 1) % Ring; }       // the copy the last stage() took
+public:
+    // the next pinned copy, free of its last upload and with room for n entries (the cursor moves before anything can fail)
+    hipError_t stage(size_t n, T** host) {
+        const int s = next_;
+        next_ = (s + 1) % Ring;
+        *host = nullptr;
+        hipError_t e = ev_[s] ? hipEventSynchronize(ev_[s].get()) : hipEventCreateWithFlags(rc_out(ev_[s]), hipEventDisableTiming);
+        if (e == hipSuccess) e = rc_grow(pin_n_[s], n, Slack * n, pin_[s], Slack * n);
+        if (e == hipSuccess) *host = pin_[s].get();
+        return e;
+    }
+    bool holds(size_t n) const { return n <= dev_n_; }
+    hipError_t grow(size_t n) { return rc_grow(dev_n_, n, Slack * n, dev_, Slack * n); }
+    hipError_t upload(size_t n, hipStream_t st) {
+        return hipMemcpyAsync(dev_.get(), pin_[slot()].get(), n * sizeof(T), hipMemcpyHostToDevice, st);
+    }
+    hipError_t record(hipStream_t st) { return hipEventRecord(ev_[slot()].get(), st); }
+    T* get() const { return dev_.get(); }
+    size_t capacity() const { return dev_n_; }                    // entries of the device table
+};
+#pragma GCC visibility pop
 
 // the live session of a context (rc_live_api.cpp; the type is complete there only)
 struct LiveSession;

@@ -88,12 +88,8 @@ int rc_prepare_motions(rc_ctx* ctx, int32_t n_seq, const int64_t* in_frames_host
     hipStream_t st = (hipStream_t)stream;
     // ---- the sequence table: pinned slot -> device, on `stream`
     const size_t G = (size_t)n_seq;
-    const int slot = ctx->prep_next;
-    ctx->prep_next = (slot + 1) % rc_ctx::kEvalRing;
-    if (ctx->prep_ev[slot]) HIP_TRY(ctx, hipEventSynchronize(ctx->prep_ev[slot].get()));   // the upload made kEvalRing calls ago has left the slot
-    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ctx->prep_ev[slot]), hipEventDisableTiming));
-    HIP_TRY(ctx, rc_grow(ctx->prep_tab_hn[slot], G, 2 * G, ctx->prep_tab_h[slot], 2 * G));
-    PrepSeq* th = ctx->prep_tab_h[slot].get();
+    PrepSeq* th = nullptr;
+    HIP_TRY(ctx, ctx->prep_tab.stage(G, &th));
     long long in0 = 0, out0 = 0;
     for (int i = 0; i < n_seq; ++i) {
         const int step = step_host ? step_host[i] : 1;
@@ -105,14 +101,14 @@ int rc_prepare_motions(rc_ctx* ctx, int32_t n_seq, const int64_t* in_frames_host
         out0 += th[i].out_n;
     }
     const size_t need_r = betas ? G : 1, need_v = vert6_out ? 0 : (size_t)frames * 18;
-    if (G > ctx->prep_tab_n || need_r > ctx->prep_rest_n || need_v > ctx->prep_vert6_n) {   // (kernels of earlier calls may still use the old buffers)
+    if (!ctx->prep_tab.holds(G) || need_r > ctx->prep_rest_n || need_v > ctx->prep_vert6_n) {   // (kernels of earlier calls may still use the old buffers)
         HIP_TRY(ctx, hipDeviceSynchronize());                                  // (a call on another stream may still read them)
-        HIP_TRY(ctx, rc_grow(ctx->prep_tab_n, G, 2 * G, ctx->prep_tab, 2 * G));
+        HIP_TRY(ctx, ctx->prep_tab.grow(G));
         HIP_TRY(ctx, rc_grow(ctx->prep_rest_n, need_r, 2 * need_r, ctx->prep_rest, 2 * need_r));
         HIP_TRY(ctx, rc_grow(ctx->prep_vert6_n, need_v, need_v, ctx->prep_vert6, need_v));
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->prep_tab.get(), th, G * sizeof(PrepSeq), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(ctx->prep_ev[slot].get(), st));
+    HIP_TRY(ctx, ctx->prep_tab.upload(G, st));
+    HIP_TRY(ctx, ctx->prep_tab.record(st));
     rc_launch_prepare_motions(ctx->body, ctx->mesh_vt, ctx->prep_sp, ctx->prep_tab.get(), n_seq, frames, pose_aa, pose_joints, tran, betas,
                               world_rot_host, imu_joint_ids_host, smooth_n, ctx->prep_rest.get(), pose_out, tran_out, imu_ori, imu_acc, joint3d,
                               sync_3d_mp, vert6_out ? vert6_out : ctx->prep_vert6.get(), rest_joint_out, st);

@@ -81,14 +81,9 @@ struct SeqEngine {
     DevBuf<int> frame_at_d;              // [cap] host plan: frame every row starts at every tick
     PinBuf<int> frame_at_h;              // pinned
     size_t frame_at_cap = 0;
-    // rc_sequence_rows: the call's per-row lengths, device + pinned (grow-only, released with the context). The pinned copy has two halves
-    // that calls take in turn, each with an event that says its upload has left it: a call only ever waits for the upload of the call
-    // BEFORE the previous one, which has long run.
-    DevBuf<int> row_len_d;
-    PinBuf<int> row_len_h;               // [2][row_len_cap]
-    size_t row_len_cap = 0;
-    HipEvent row_len_ev[2];
-    unsigned row_len_turn = 0;
+    // rc_sequence_rows: the call's per-row lengths [B]. Two pinned copies: a call only ever waits for the upload of the call BEFORE the
+    // previous one, which has long run.
+    StagedTable<int, 2, 1> row_len;
     // resident layer-step kernel of the wavefront engine (run_resident_segment)
     DevBuf<ResidentTick> res_ticks_d;    // [res_cap]
     PinBuf<ResidentTick> res_ticks_h;    // pinned
@@ -780,7 +775,7 @@ int seq_prepare(rc_ctx* ctx) {
 extern "C" {
 
 // rc_sequence (len == nullptr) and rc_sequence_rows: frames [off, off + T) of a call whose per-row lengths are len[B] (HOST; their device
-// copy is ctx->seq->row_len_d), the pointers standing at frame `off`. Row b has frames 0 .. min(len[b] - off, T) - 1 of this piece.
+// copy is ctx->seq->row_len), the pointers standing at frame `off`. Row b has frames 0 .. min(len[b] - off, T) - 1 of this piece.
 static int sequence_impl(rc_ctx* ctx, int32_t T, const int32_t* len, int32_t off, const float* j2dc, int64_t rs_j2d, const float* accc,
                          int64_t rs_acc, const float* oric, int64_t rs_ori, const float* first_tran, uint32_t flags, float* pose_out,
                          int64_t rs_pose, float* tran_out, int64_t rs_tran, void* stream) {
@@ -799,7 +794,7 @@ static int sequence_impl(rc_ctx* ctx, int32_t T, const int32_t* len, int32_t off
         if (same) rows_len.clear();                                         // ... and rows of one length are a uniform call
     }
     const int* L = rows_len.empty() ? nullptr : rows_len.data();
-    const int* len_d = L ? ctx->seq->row_len_d.get() : nullptr;
+    const int* len_d = L ? ctx->seq->row_len.get() : nullptr;
     // Very long calls are planned in pieces: the plan's tables (regime codes, frame_at) grow with batch x frames, and a piece
     // boundary costs one pipeline drain (8 of 4,096 ticks) and one more read-back.
     const int32_t kMaxPlanFrames = std::max(8, tune_env("RC_SEQ_MAX_PLAN_FRAMES", 4096));     // (read per call: tests shrink it)
@@ -934,15 +929,13 @@ int rc_sequence_rows(rc_ctx* ctx, int32_t T, const int32_t* len_host, const floa
     live_forget_last_frame(ctx);
     hipStream_t st = (hipStream_t)stream;
     // the lengths travel once per call: pinned copy -> device copy on `stream`, in front of everything that reads them
-    for (HipEvent& ev : ctx->seq->row_len_ev)                                      // (before the capacity moves: a failure here is retried whole)
-        if (!ev) HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(ev), hipEventDisableTiming));
-    const unsigned turn = ctx->seq->row_len_turn++ & 1u;
-    if (B > ctx->seq->row_len_cap) HIP_TRY(ctx, rc_grow(ctx->seq->row_len_cap, B, B, ctx->seq->row_len_d, B, ctx->seq->row_len_h, 2 * B));
-    else HIP_TRY(ctx, hipEventSynchronize(ctx->seq->row_len_ev[turn].get()));      // this half's last upload (two calls ago) has left it
-    int* len_h = ctx->seq->row_len_h.get() + turn * B;
+    StagedTable<int, 2, 1>& row_len = ctx->seq->row_len;
+    int* len_h = nullptr;
+    HIP_TRY(ctx, row_len.stage(B, &len_h));                                        // (a copy's first call creates its event and has nothing to wait for)
+    if (!row_len.holds(B)) HIP_TRY(ctx, row_len.grow(B));                          // the context's first call: no earlier one reads the table
     std::memcpy(len_h, len_host, B * sizeof(int));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->seq->row_len_d.get(), len_h, B * sizeof(int), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(ctx->seq->row_len_ev[turn].get(), st));
+    HIP_TRY(ctx, row_len.upload(B, st));
+    HIP_TRY(ctx, row_len.record(st));
     return sequence_impl(ctx, T, len_h, 0, j2dc, rs_j2d, accc, rs_acc, oric, rs_ori, first_tran, flags, pose_out, rs_pose, tran_out, rs_tran, stream);
 }
 

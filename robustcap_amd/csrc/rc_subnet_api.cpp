@@ -35,11 +35,7 @@ struct SubnetState {                 // (grow-only buffers; the context's destru
     size_t buf_floats = 0;
     DevBuf<float> st;                // recurrent state of a group: per layer two copies of h [npad, H] and c [npad, H]
     size_t st_floats = 0;
-    DevBuf<int> ibuf;                // rank -> sequence, final copy per rank, row maps of every frame of the call
-    size_t ibuf_ints = 0;
-    PinBuf<int> ihost;               // pinned staging of ibuf
-    size_t ihost_ints = 0;
-    HipEvent ev;                     // the last upload from ihost
+    StagedTable<int, 1, 1> plan;     // rank -> sequence, final copy per rank, row maps of every frame of the call (room for what is needed, no more)
     HipEvent done;                   // the end of the last call's work (a call on another stream waits for it: the scratch is shared)
     long long calls = 0, frames = 0, chunks = 0;
     // backward through time
@@ -52,24 +48,16 @@ struct SubnetState {                 // (grow-only buffers; the context's destru
     DevBuf<double> wg_colsum;        // ... and of a bias sum: [parts][M]
     size_t wg_colsum_doubles = 0;
     int wg_parts = 0;                // rc_set_subnet_wgrad_parts: 0 = from the tile count
-    // training batches (rc_subnet_batch): the sample table, staged through a ring of pinned copies so that a call waits for the upload
-    // made kBatchRing calls earlier, not for the one before it
-    static constexpr int kBatchRing = 4;
-    DevBuf<long long> btab;          // [n] first corpus frame | [n + 1] first output frame of every sample
-    size_t btab_n = 0;
-    PinBuf<long long> btab_h[kBatchRing];
-    size_t btab_hn[kBatchRing] = {};
-    HipEvent btab_ev[kBatchRing];    // the last upload from btab_h[i]
-    int btab_next = 0;
+    // training batches (rc_subnet_batch, rc_subnet_batch_parts)
+    StagedTable<long long, 4> batch_tab;   // [n] first corpus frame | [n + 1] first output frame of every sample (parts: per kind, with ext)
     DevBuf<float> bcam;              // kind world: Rcw | t of every sample [n, 12]
     size_t bcam_floats = 0;
-    // the corpus builders (rc_subnet_corpus): sample table and cameras; a call waits for the one before it (ctab_ev: its last kernel)
-    DevBuf<long long> ctab;          // [n] field frame | [n] keypoint frame | [n + 1] output row of every sample
+    // the corpus builders (rc_subnet_corpus): sample table and cameras; one pinned copy, its event recorded behind the call's kernel: a call
+    // waits for the one before it, and the cameras live under the table's event
+    StagedTable<long long, 1> corpus_tab;  // [n] field frame | [n] keypoint frame | [n + 1] output row of every sample
     DevBuf<float> ccam;              // [n, 22] K^-1 | rows 0 .. 2 of T_cw | occlusion flag
-    PinBuf<long long> ctab_h;
     PinBuf<float> ccam_h;
-    size_t ctab_n = 0, ccam_n = 0;
-    HipEvent ctab_ev;
+    size_t ccam_n = 0;
     int cus = 0;                     // compute units of the device (asked once)
 };
 
@@ -167,13 +155,15 @@ long long plan_rows_max(const SubnetNet& w) {
 
 long long tape_floats(const SubnetNet& w, int n, long long total) { return 2ll * n * w.H + 10ll * total * w.H; }
 
-// the device allocation behind p holds at least `bytes` from p on
-bool dev_holds(const void* p, long long bytes) {
+// the bytes from p to the end of its allocation (-1: not a device allocation)
+long long device_extent(const void* p) {
     void* base = nullptr;
     size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return (long long)((const char*)base + size - (const char*)p) >= bytes;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return (long long)((const char*)base + size - (const char*)p);
 }
+// the device allocation behind p holds at least `bytes` from p on
+bool dev_holds(const void* p, long long bytes) { return device_extent(p) >= bytes; }
 
 // The sub-net entries run the six-product kernels of rc_subnet.hip; gemm mode 2 (two rounded bf16 terms, three products) has no
 // instantiation of them: refused, not run in another arithmetic than the context's.
@@ -198,13 +188,12 @@ int check_args(rc_ctx* ctx, const char* what, const char* net, int32_t n, const 
 // the call's turn at the shared scratch, the plan's upload
 int upload_plan(rc_ctx* ctx, SubnetState* S, const Plan& P, hipStream_t st) {
     const std::vector<int>& ih = P.ih;
-    HIP_TRY(ctx, rc_grow(S->ibuf_ints, ih.size(), ih.size(), S->ibuf, ih.size()));
-    if (S->ev) HIP_TRY(ctx, hipEventSynchronize(S->ev.get()));            // the previous call's upload has left the staging buffer
-    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->ev), hipEventDisableTiming));
-    HIP_TRY(ctx, rc_grow(S->ihost_ints, ih.size(), ih.size(), S->ihost, ih.size()));
-    std::copy(ih.begin(), ih.end(), S->ihost.get());
-    HIP_TRY(ctx, hipMemcpyAsync(S->ibuf.get(), S->ihost.get(), ih.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(S->ev.get(), st));
+    HIP_TRY(ctx, S->plan.grow(ih.size()));                                // (with the scratch: releasing the old table waits for the work that still reads it)
+    int* host = nullptr;
+    HIP_TRY(ctx, S->plan.stage(ih.size(), &host));                        // the previous call's upload has left the pinned copy
+    std::copy(ih.begin(), ih.end(), host);
+    HIP_TRY(ctx, S->plan.upload(ih.size(), st));
+    HIP_TRY(ctx, S->plan.record(st));
     return RC_OK;
 }
 
@@ -253,18 +242,18 @@ int forward_impl(rc_ctx* ctx, const char* what, const char* net, int32_t n, cons
 
     // final_* of the group of ranks [g0, g1): every rank's h from the copy its last step wrote
     auto finish = [&](int g0, int g1) {
-        rc_launch_subnet_state(hst, hl, ps, S->ibuf.get() + n + g0, cst, hl, final_h, final_c, S->ibuf.get() + g0, g1 - g0, n, H, 0, st);
+        rc_launch_subnet_state(hst, hl, ps, S->plan.get() + n + g0, cst, hl, final_h, final_c, S->plan.get() + g0, g1 - g0, n, H, 0, st);
     };
     int g0 = -1, g1 = -1;
     for (const Chunk& c : P.chunks) {
         const long long M = c.off.back();
-        const int* map = S->ibuf.get() + 2 * (size_t)n + c.frame0;
+        const int* map = S->plan.get() + 2 * (size_t)n + c.frame0;
         if (c.g0 != g0) {                    // a new group: its state from init_* (or zeros)
             if (g0 >= 0) finish(g0, g1);
             g0 = c.g0; g1 = c.g1;
-            rc_launch_subnet_state(hst, hl, ps, nullptr, cst, hl, const_cast<float*>(init_h), const_cast<float*>(init_c), S->ibuf.get() + g0,
+            rc_launch_subnet_state(hst, hl, ps, nullptr, cst, hl, const_cast<float*>(init_h), const_cast<float*>(init_c), S->plan.get() + g0,
                                    g1 - g0, n, H, 1, st);
-            if (record) rc_launch_subnet_bstate(nullptr, tape + (long long)g0 * H, (long long)n * H, nullptr, init_c, nullptr, S->ibuf.get() + g0,
+            if (record) rc_launch_subnet_bstate(nullptr, tape + (long long)g0 * H, (long long)n * H, nullptr, init_c, nullptr, S->plan.get() + g0,
                                                 g1 - g0, n, H, 1, st);
         }
         rc_launch_subnet_pack(x, w.in, map, X, Kp1, (int)M, st);
@@ -359,8 +348,8 @@ int backward_impl(rc_ctx* ctx, const char* what, const char* net, int32_t n, con
     for (size_t ci = P.chunks.size(); ci-- > 0;) {
         const Chunk& c = P.chunks[ci];
         const long long M = c.off.back();
-        const int* perm = S->ibuf.get() + c.g0;
-        const int* map = S->ibuf.get() + 2 * (size_t)n + c.frame0;
+        const int* perm = S->plan.get() + c.g0;
+        const int* map = S->plan.get() + 2 * (size_t)n + c.frame0;
         const int nr = c.g1 - c.g0;
         if (c.next_rows == 0)                // the group's last chunk: its state from d_final_* (or zeros)
             rc_launch_subnet_bstate(bst + 2 * cps, bst + 2 * cps + G * H, ls, d_final_h, d_final_c, nullptr, perm, nr, n, H, 1, st);
@@ -521,7 +510,7 @@ int weight_grads_impl(rc_ctx* ctx, const char* net, int32_t n, const int32_t* le
     for (int q = 0; q < 4; ++q) {
         WgradLaunch& l = L[q];
         if (l.nseg) {
-            l.first = S->ibuf.get();
+            l.first = S->plan.get();
             l.partial = S->wg_part.get();
             rc_launch_wgrad(l, split, st);
             if (l.parts > 1) rc_launch_wgrad_reduce(l, st);
@@ -628,37 +617,38 @@ static const struct { int cols; float sigma; } kBatchNoise[6] = {{0, 0.f}, {69, 
 static const BatchCamera kBatchCamera4 = {-180.f, 180.f, -30.f, 30.f, -5.f, 5.f};
 static const BatchCamera kBatchCamera6 = {-90.f, 90.f, -30.f, 30.f, -5.f, 5.f};
 
-// the next pinned slot of the batch-table ring with room for nt entries (*th), the device table grown to hold them (and, for nw world
-// samples, the camera scratch): rc_subnet_batch and rc_subnet_batch_parts fill *th, then upload_batch_table
-static int batch_table_slot(rc_ctx* ctx, SubnetState* S, size_t nt, size_t nw, hipStream_t st, int* slot_out, long long** th) {
-    const int slot = S->btab_next;
-    S->btab_next = (slot + 1) % SubnetState::kBatchRing;
-    if (S->btab_ev[slot]) HIP_TRY(ctx, hipEventSynchronize(S->btab_ev[slot].get()));      // the upload made kBatchRing calls ago has left the slot
-    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->btab_ev[slot]), hipEventDisableTiming));
-    HIP_TRY(ctx, rc_grow(S->btab_hn[slot], nt, 2 * nt, S->btab_h[slot], 2 * nt));
-    if (nt > S->btab_n) {                                                                 // (kernels of earlier calls may still read the old table)
+// One sample of rc_subnet_batch / rc_subnet_batch_parts against the conditions named in `ask`, in the order they stand here: both entries
+// refuse with the same words behind their own prefix f, and each asks in its own order.
+enum { ASK_SPAN = 1, ASK_AUGMENT = 2, ASK_POOL = 4, ASK_DRAW = 8 };
+struct BatchSample { bool world; int augment; const float* conf_pool; int pool_rows; long long off, len; int W, Wl; long long data_bytes, label_bytes; };
+static int check_sample(rc_ctx* ctx, const std::string& f, int ask, const BatchSample& s) {
+    auto refuse = [&](const std::string& why) { return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + why).c_str()); };
+    if ((ask & ASK_SPAN) && (s.len < 1 || s.off < 0)) return refuse("every sample needs an offset >= 0 and at least one frame");
+    if ((ask & ASK_SPAN) && (s.off + s.len > (1ll << 40) || (s.off + s.len) * 4 * s.W > s.data_bytes || (s.off + s.len) * 4 * s.Wl > s.label_bytes))
+        return refuse("a sample ends past the corpus buffers");
+    if ((ask & ASK_AUGMENT) && s.world && !s.augment) return refuse("a world sample has no un-augmented form (the camera is part of it)");
+    if ((ask & ASK_POOL) && s.world && (!s.conf_pool || s.pool_rows < 1)) return refuse("kind world needs a confidence pool");
+    if ((ask & ASK_DRAW) && s.world && s.len > s.pool_rows)
+        return refuse("a sample of " + std::to_string(s.len) + " frames cannot draw distinct rows from a pool of " + std::to_string(s.pool_rows));
+    return RC_OK;
+}
+// ... and the frames of all samples together
+static int check_total(rc_ctx* ctx, const std::string& f, long long F) {
+    return F >= (1ll << 31) ? rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "2^31 frames or more").c_str()) : RC_OK;
+}
+// what both entries do in front of filling their table: the pinned copy for nt entries (*th), then the device table and the camera
+// scratch of nw world samples grown, each behind a synchronisation of `st` (kernels of earlier calls may still read the old ones)
+static int stage_batch_table(rc_ctx* ctx, SubnetState* S, size_t nt, size_t nw, hipStream_t st, long long** th) {
+    HIP_TRY(ctx, S->batch_tab.stage(nt, th));
+    if (!S->batch_tab.holds(nt)) {
         HIP_TRY(ctx, hipStreamSynchronize(st));
-        HIP_TRY(ctx, rc_grow(S->btab_n, nt, 2 * nt, S->btab, 2 * nt));
+        HIP_TRY(ctx, S->batch_tab.grow(nt));
     }
     if (12 * nw > S->bcam_floats) {
         HIP_TRY(ctx, hipStreamSynchronize(st));
         HIP_TRY(ctx, rc_grow(S->bcam_floats, 12 * nw, 24 * nw, S->bcam, 24 * nw));
     }
-    *slot_out = slot;
-    *th = S->btab_h[slot].get();
     return RC_OK;
-}
-static int upload_batch_table(rc_ctx* ctx, SubnetState* S, int slot, size_t nt, hipStream_t st) {
-    HIP_TRY(ctx, hipMemcpyAsync(S->btab.get(), S->btab_h[slot].get(), nt * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(S->btab_ev[slot].get(), st));
-    return RC_OK;
-}
-// the bytes from p to the end of its allocation (-1: not a device allocation)
-static long long device_extent(const void* p) {
-    void* base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) { (void)hipGetLastError(); return -1; }
-    return (long long)((const char*)base + size - (const char*)p);
 }
 
 int rc_subnet_batch(rc_ctx* ctx, const char* net, int32_t kind, const float* data, const float* label, int32_t n,
@@ -674,46 +664,44 @@ int rc_subnet_batch(rc_ctx* ctx, const char* net, int32_t kind, const float* dat
     const bool world = kind == RC_BATCH_WORLD;
     const bool rnn4 = ni == 2, rnn6 = ni == 3;
     if (world && !rnn4 && !rnn6) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "kind world is rnn4's and rnn6's, not " + net + "'s").c_str());
-    if (world && !augment) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a world sample has no un-augmented form (the camera is part of it)").c_str());
-    if (n <= 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "no samples").c_str());
-    if (world && (!conf_pool || pool_rows < 1)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "kind world needs a confidence pool").c_str());
     const int W = world ? 171 : kBatchWidth[ni][0], Wl = world ? 72 : kBatchWidth[ni][1];
     const int Wo = kBatchWidth[ni][0], Wlo = kBatchWidth[ni][1];
+    BatchSample s{world, augment, conf_pool, pool_rows, 0, 0, W, Wl, 0, 0};
+    if (int rc = check_sample(ctx, f, ASK_AUGMENT, s)) return rc;
+    if (n <= 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "no samples").c_str());
+    if (int rc = check_sample(ctx, f, ASK_POOL, s)) return rc;
     // the extents of the caller's allocations, asked once each
     auto extent = device_extent;
-    const long long data_bytes = extent(data), label_bytes = extent(label);
+    s.data_bytes = extent(data);
+    s.label_bytes = extent(label);
     long long F = 0;
     for (int i = 0; i < n; ++i) {
-        const long long off = offsets_host[i], len = lengths_host[i];
-        if (len < 1 || off < 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "every sample needs an offset >= 0 and at least one frame").c_str());
-        if (off + len > (1ll << 40) || (off + len) * 4 * W > data_bytes || (off + len) * 4 * Wl > label_bytes)
-            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sample ends past the corpus buffers").c_str());
-        if (world && len > pool_rows)
-            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sample of " + std::to_string(len) + " frames cannot draw distinct rows from a pool of " +
-                                                     std::to_string(pool_rows)).c_str());
-        F += len;
+        s.off = offsets_host[i];
+        s.len = lengths_host[i];
+        if (int rc = check_sample(ctx, f, ASK_SPAN | ASK_DRAW, s)) return rc;
+        F += s.len;
     }
-    if (F >= (1ll << 31)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "2^31 frames or more").c_str());
+    if (int rc = check_total(ctx, f, F)) return rc;
     if (extent(x_out) < 4 * F * Wo || extent(label_out) < 4 * F * Wlo || (world && extent(conf_pool) < 4ll * pool_rows * 33))
         return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "an output or the pool ends before its extent").c_str());
     hipStream_t st = (hipStream_t)stream;
     SubnetState* S = state(ctx);
     // ---- the table: pinned slot -> device, on `stream`
     const size_t nt = 2 * (size_t)n + 1;
-    int slot = 0;
     long long* th = nullptr;
-    if (int rc = batch_table_slot(ctx, S, nt, world ? (size_t)n : 0, st, &slot, &th)) return rc;
+    if (int rc = stage_batch_table(ctx, S, nt, world ? (size_t)n : 0, st, &th)) return rc;
     long long at = 0;
     for (int i = 0; i < n; ++i) { th[i] = offsets_host[i]; th[n + i] = at; at += lengths_host[i]; }
     th[2 * (size_t)n] = at;
-    if (int rc = upload_batch_table(ctx, S, slot, nt, st)) return rc;
+    HIP_TRY(ctx, S->batch_tab.upload(nt, st));
+    HIP_TRY(ctx, S->batch_tab.record(st));
     const BatchKey key{seed, call};
     if (world) {
-        rc_launch_batch_world(rnn4 ? 1 : 0, data, label, S->btab.get(), n, F, rnn4 ? kBatchCamera4 : kBatchCamera6, S->bcam.get(), conf_pool,
+        rc_launch_batch_world(rnn4 ? 1 : 0, data, label, S->batch_tab.get(), n, F, rnn4 ? kBatchCamera4 : kBatchCamera6, S->bcam.get(), conf_pool,
                               pool_rows, kBatchNoise[ni].sigma, key, x_out, label_out, st);
     } else {
         const int noisy = augment ? kBatchNoise[ni].cols : 0;
-        rc_launch_batch_plain(data, label, S->btab.get(), n, F, W, Wl, W - noisy, kBatchNoise[ni].sigma, key, x_out, label_out, st);
+        rc_launch_batch_plain(data, label, S->batch_tab.get(), n, F, W, Wl, W - noisy, kBatchNoise[ni].sigma, key, x_out, label_out, st);
     }
     HIP_TRY(ctx, hipGetLastError());
     return RC_OK;
@@ -749,20 +737,13 @@ int rc_subnet_batch_parts(rc_ctx* ctx, const char* net, int32_t n_parts, const i
         if (p < 0 || p >= n_parts) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sample of a part that is not there").c_str());
         const bool world = kinds_host[p] == RC_BATCH_WORLD;
         const int W = world ? 171 : Wo, Wl = world ? 72 : Wlo;
-        const long long off = offsets_host[i], len = lengths_host[i];
-        if (len < 1 || off < 0) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "every sample needs an offset >= 0 and at least one frame").c_str());
-        if (off + len > (1ll << 40) || (off + len) * 4 * W > data_bytes[p] || (off + len) * 4 * Wl > label_bytes[p])
-            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sample ends past the corpus buffers").c_str());
-        if (world && !augment)
-            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a world sample has no un-augmented form (the camera is part of it)").c_str());
-        if (world && (!conf_pool || pool_rows < 1)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "kind world needs a confidence pool").c_str());
-        if (world && len > pool_rows)
-            return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a sample of " + std::to_string(len) + " frames cannot draw distinct rows from a pool of " +
-                                                     std::to_string(pool_rows)).c_str());
+        const long long len = lengths_host[i];
+        const BatchSample s{world, augment, conf_pool, pool_rows, offsets_host[i], len, W, Wl, data_bytes[p], label_bytes[p]};
+        if (int rc = check_sample(ctx, f, ASK_SPAN | ASK_AUGMENT | ASK_POOL | ASK_DRAW, s)) return rc;
         nw += world ? 1 : 0;
         F += len;
     }
-    if (F >= (1ll << 31)) return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "2^31 frames or more").c_str());
+    if (int rc = check_total(ctx, f, F)) return rc;
     if (device_extent(x_out) < 4 * F * Wo || device_extent(label_out) < 4 * F * Wlo || (nw && device_extent(conf_pool) < 4ll * pool_rows * 33))
         return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "an output or the pool ends before its extent").c_str());
     hipStream_t st = (hipStream_t)stream;
@@ -770,9 +751,8 @@ int rc_subnet_batch_parts(rc_ctx* ctx, const char* net, int32_t n_parts, const i
     // ---- one table for both launches: per kind [m] corpus frame | [m + 1] the launch's own output frames | ext [4 m] (rc_internal.h)
     const int np = n - nw;
     const size_t nt = 6 * (size_t)n + 2;
-    int slot = 0;
     long long* th = nullptr;
-    if (int rc = batch_table_slot(ctx, S, nt, (size_t)nw, st, &slot, &th)) return rc;
+    if (int rc = stage_batch_table(ctx, S, nt, (size_t)nw, st, &th)) return rc;
     long long* tab_k[2] = {th, th + (6 * (size_t)np + 1)};
     const int m_k[2] = {np, nw};
     int at_k[2] = {0, 0};
@@ -792,8 +772,9 @@ int rc_subnet_batch_parts(rc_ctx* ctx, const char* net, int32_t n_parts, const i
     }
     tab_k[0][2 * (size_t)np] = F_k[0];
     tab_k[1][2 * (size_t)nw] = F_k[1];
-    if (int rc = upload_batch_table(ctx, S, slot, nt, st)) return rc;
-    const long long* dev_k[2] = {S->btab.get(), S->btab.get() + (6 * (size_t)np + 1)};
+    HIP_TRY(ctx, S->batch_tab.upload(nt, st));
+    HIP_TRY(ctx, S->batch_tab.record(st));
+    const long long* dev_k[2] = {S->batch_tab.get(), S->batch_tab.get() + (6 * (size_t)np + 1)};
     const BatchKey key{seed, call};
     if (np) {
         const int noisy = augment ? kBatchNoise[ni].cols : 0;
@@ -872,12 +853,11 @@ int rc_subnet_corpus(rc_ctx* ctx, const char* net, int32_t source, int32_t n_seq
         return rc_ctx_fail(ctx, RC_ERR_INVALID, (f + "a field or an output ends before its extent").c_str());
     hipStream_t st = (hipStream_t)stream;
     SubnetState* S = state(ctx);
-    if (S->ctab_ev) HIP_TRY(ctx, hipEventSynchronize(S->ctab_ev.get()));                   // the call before this one has left the tables
-    else HIP_TRY(ctx, hipEventCreateWithFlags(rc_out(S->ctab_ev), hipEventDisableTiming));
     const size_t nt = 3 * (size_t)n + 1, nc = 22 * (size_t)n;
-    HIP_TRY(ctx, rc_grow(S->ctab_n, nt, 2 * nt, S->ctab, 2 * nt, S->ctab_h, 2 * nt));
+    long long* th = nullptr;
+    HIP_TRY(ctx, S->corpus_tab.stage(nt, &th));                                            // the call before this one has left the tables:
+    if (!S->corpus_tab.holds(nt)) HIP_TRY(ctx, S->corpus_tab.grow(nt));                    // that wait is what the device tables grow behind
     if (mode == 1) HIP_TRY(ctx, rc_grow(S->ccam_n, nc, 2 * nc, S->ccam, 2 * nc, S->ccam_h, 2 * nc));
-    long long* th = S->ctab_h.get();
     long long row = 0, kf = 0;
     for (int s = 0; s < n; ++s) {
         const int q = mode == 1 ? sample_seq_host[s] : s;
@@ -888,7 +868,7 @@ int rc_subnet_corpus(rc_ctx* ctx, const char* net, int32_t source, int32_t n_seq
         kf += seq_frames_host[q];
     }
     th[3 * (size_t)n] = row;
-    HIP_TRY(ctx, hipMemcpyAsync(S->ctab.get(), th, nt * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, S->corpus_tab.upload(nt, st));
     if (mode == 1) {
         float* ch = S->ccam_h.get();
         for (int s = 0; s < n; ++s) {
@@ -901,12 +881,12 @@ int rc_subnet_corpus(rc_ctx* ctx, const char* net, int32_t source, int32_t n_seq
     }
     CorpusArgs a{};
     a.pose = pose; a.acc = imu_acc; a.ori = imu_ori; a.joint = joint3d; a.tran = tran; a.mp = sync_3d_mp; a.kp = kp;
-    a.tab = S->ctab.get(); a.cams = S->ccam.get(); a.body = body;
+    a.tab = S->corpus_tab.get(); a.cams = S->ccam.get(); a.body = body;
     a.n = n; a.net = ni; a.amass = amass ? 1 : 0; a.W = W; a.Wl = Wl; a.R = R;
     a.sx = image_w; a.sy = image_h; a.x = x_out; a.y = label_out;
     rc_launch_subnet_corpus(mode, a, st);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(S->ctab_ev.get(), st));
+    HIP_TRY(ctx, S->corpus_tab.record(st));                                                // behind the kernel: it reads the cameras too
     return RC_OK;
 }
 
@@ -950,7 +930,7 @@ int rc_get_subnet_stats(rc_ctx* ctx, int64_t* calls, int64_t* frames, int64_t* c
     if (calls) *calls = s ? s->calls : 0;
     if (frames) *frames = s ? s->frames : 0;
     if (chunks) *chunks = s ? s->chunks : 0;
-    if (scratch_bytes) *scratch_bytes = s ? (int64_t)(4 * (s->buf_floats + s->st_floats + s->ibuf_ints)) : 0;
+    if (scratch_bytes) *scratch_bytes = s ? (int64_t)(4 * (s->buf_floats + s->st_floats + s->plan.capacity())) : 0;
     return RC_OK;
 }
 
