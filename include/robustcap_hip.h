@@ -691,6 +691,38 @@ int rc_prepare_motions(rc_ctx* ctx, int32_t n_seq, const int64_t* in_frames_host
                        const float* pose_aa, int32_t pose_joints, const float* tran, const float* betas, const float* world_rot_host,
                        const int32_t* imu_joint_ids_host, int32_t smooth_n, float* pose_out, float* tran_out, float* imu_ori,
                        float* imu_acc, float* joint3d, float* sync_3d_mp, float* vert6_out, float* rest_joint_out, void* stream);
+/* Camera-frame motions for ALL sequences in one call: the motion part of preprocess_3dpw / preprocess_3dpwocc (preprocess.py:460-470,
+ * 477-483; :571-582, 589-599: a data set filmed by a MOVING camera, every frame with its own T_cw, the 30 Hz camera poses repeated to
+ * 60 Hz by np.repeat) and, with a static camera and RC_CAM_ROOT_ONLY, the root flip of preprocess_my_totalcapture_pre (:359-360).
+ * Sequence i has in_frames_host[i] pose / translation frames and cam_frames_host[i] camera rows (HOST, summing to in_total / cam_total).
+ * cam_repeat r >= 1: output frame t uses camera row t / r and out_i = min(in_i, r cam_i) -- the `[:len(cam_pose)]` / `cam_pose[:len(posec)]`
+ * pair of :463-465 and :577; preprocess_3dpw itself raises where the pose is the shorter one, this is preprocess_3dpwocc's behaviour. r = 0:
+ * ONE camera row per sequence (static), out_i = in_i. Outputs are concatenated in sequence order over frames = sum out_i; the frames of a
+ * sequence behind out_i are not read. DEVICE float inputs: pose_aa [in_total,24,3] axis-angle, tran [in_total,3], betas [n_seq,10] or NULL.
+ * cam_T_host: HOST [cam_total,4,4] row-major T_cw, row 3 ignored -- on the host because the rows are checked before anything is enqueued;
+ * they travel with the sequence tables (12 floats per row) through rings of four pinned copies.
+ * Per output frame, with C its camera row: local rotations by rc_axis_angle_to_rotmat's arithmetic (joints 1 .. 23 of pose_out carry that
+ * entry's bits); root = C[:3,:3] . R_0 and tran_out = C[:3,:3] . tran + C[:3,3] in float32, every product and sum rounded (an identity
+ * camera leaves both as they are); with RC_CAM_ROOT_ONLY tran_out is a bit copy of tran (TotalCapture rotates the root and takes its
+ * translation from Vicon). pose_out [frames,24,3,3] holds ROTATION MATRICES (the 3DPW dictionary's posec): no R -> axis-angle on this
+ * path. Rest body, joint chain, the global rotations of imu_joint_ids_host, the 33 landmark and 6 IMU vertices and _syn_acc confined to
+ * the sequence: rc_prepare_motions' kernels and expressions, on the camera-frame root and tran_out (:468-470). sync_3d_mp [frames,33,3],
+ * vert6_out and rest_joint_out may be NULL.
+ * Keypoints (kp_in DEVICE [kp_total,33,3] with kp_frames_host and kp_out [frames,33,3], or all three NULL): the 30 Hz detections raised to
+ * 60 Hz as :477-483 does, cut to out_i -- output frame t even: kp[t / 2]; t odd: (kp[t / 2 + 1] + kp[t / 2]) / 2 in all three columns,
+ * the confidence included; t odd behind the last detector frame: that frame again. Bit for bit numpy's float32.
+ * Enqueued on `stream` like rc_prepare_motions (same rings, same shared buffers, same ordering rule for calls of one context): no
+ * read-back, no synchronisation, no atomics, one writer per output element. RC_ERR_INVALID (nothing enqueued, nothing written) on what
+ * rc_prepare_motions refuses and on cam_repeat < 0, a sequence without a camera row, r = 0 with cam_i != 1, a non-finite entry in the first
+ * three rows of a cam_T, tables that do not sum to in_total / cam_total / kp_total, 2 kp_i < out_i, kp_in without kp_out (or the reverse)
+ * and flags other than RC_CAM_ROOT_ONLY; RC_ERR_STATE as rc_prepare_motions. */
+#define RC_CAM_ROOT_ONLY 1u
+int rc_prepare_camera_motions(rc_ctx* ctx, int32_t n_seq, const int64_t* in_frames_host, const int64_t* cam_frames_host, int32_t cam_repeat,
+                              int64_t in_total, int64_t cam_total, const float* pose_aa, const float* tran, const float* betas,
+                              const float* cam_T_host, const float* kp_in, const int64_t* kp_frames_host, int64_t kp_total,
+                              const int32_t* imu_joint_ids_host, int32_t smooth_n, uint32_t flags, float* pose_out, float* tran_out,
+                              float* imu_ori, float* imu_acc, float* joint3d, float* sync_3d_mp, float* vert6_out, float* kp_out,
+                              float* rest_joint_out, void* stream);
 /* reconstruction_error(S1, S2, reduction=None) (utils.py:189-203) on raw point sets: S1, S2 DEVICE [n, n_points, 3]
  * -> err DEVICE [n] = mean point distance after the optimal scale * rotation + translation of S1 onto S2. */
 int rc_procrustes_error(const float* S1, const float* S2, int64_t n, int32_t n_points, float* err, void* stream);

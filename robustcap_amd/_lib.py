@@ -102,6 +102,8 @@ SIGNATURES = {
     "rc_syn_acc": (_I32, [_P, _I64, _I64, _I32, _P, _P]),
     "rc_set_shape_space": (_I32, [_P, _P, _P, _P, _I32, _P, _P]),
     "rc_prepare_motions": (_I32, [_P, _I32, _P, _P, _I64, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rc_prepare_camera_motions": (_I32, [_P, _I32, _P, _P, _I32, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _I32, _U32, _P, _P, _P, _P, _P, _P, _P,
+                                         _P, _P, _P]),
     "rc_procrustes_error": (_I32, [_P, _P, _I64, _I32, _P, _P]),
     "rc_position_error": (_I32, [_P, _P, _I64, _P, C.POINTER(C.c_double), _P]),
     "rc_lstm_step": (_I32, [_P, C.c_char_p, _P, _P, _P, _P]),

@@ -98,6 +98,9 @@ struct rc_ctx {
     DevBuf<float> prep_vert6;
     size_t prep_vert6_n = 0;
     StagedTable<PrepSeq, 4> prep_tab;
+    // rc_prepare_camera_motions: per-sequence camera / detector offsets and the camera rows themselves (checked on the host, then sent)
+    StagedTable<PrepCam, 4> cam_tab;
+    StagedTable<PrepCamRow, 4> cam_rows;
 };
 
 #pragma GCC visibility push(hidden)

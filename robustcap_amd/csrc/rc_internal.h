@@ -392,6 +392,16 @@ void rc_launch_prepare_motions(const BodyConst* body, const float* mesh_vt, cons
                                long long frames, const float* pose_aa, int pose_joints, const float* tran, const float* betas,
                                const float* world_rot, const int* jid, int smooth_n, PrepRest* rest, float* pose_out, float* tran_out,
                                float* ori, float* acc, float* joint, float* sync, float* vert6, float* rest_joint_out, hipStream_t s);
+// rc_prepare_camera_motions: per sequence its first camera row and its detector frames [kp0, kp0 + kp_n) (beside a PrepSeq with step 1);
+// a camera row is the first three rows of a T_cw
+struct PrepCam { long long cam0, kp0; int kp_n, pad; };
+struct PrepCamRow { float m[12]; };
+// tab, cam DEVICE [n_seq]; cam_rows DEVICE; cam_repeat 0: one row per sequence; sync, kp_in / kp_out may be nullptr; the rest as above
+void rc_launch_prepare_camera_motions(const BodyConst* body, const float* mesh_vt, const PrepShapeSpace& sp, const PrepSeq* tab,
+                                      const PrepCam* cam, int n_seq, long long frames, int cam_repeat, bool root_only, const float* pose_aa,
+                                      const float* tran, const float* betas, const PrepCamRow* cam_rows, const float* kp_in, const int* jid,
+                                      int smooth_n, PrepRest* rest, float* pose_out, float* tran_out, float* ori, float* acc, float* joint,
+                                      float* sync, float* vert6, float* kp_out, float* rest_joint_out, hipStream_t s);
 void rc_launch_procrustes(const float* S1, const float* S2, int nk, float* err, long long n, hipStream_t s);
 void rc_launch_point_distance(const float* a, const float* b, float* d, long long n, hipStream_t s);
 // ---- FullMotionEvaluator per group of a concatenated batch (rc_motion.hip; rc_motion_metrics in rc_api.cpp) -----------------------------

@@ -5,6 +5,10 @@
                     [T,72], ``tran`` [T,3], ``imu_ori`` [T,6,3,3], ``imu_acc`` [T,6,3] in the world frame, per camera
                     ``cam_K``, ``cam_T`` (T_cw), ``joint2d_mp`` [n_cam,T,33,3] normalised by the image size.
                     ``robustcap_amd.synth.make_dataset`` generates the same layout (the real data is external).
+                    TotalCapture's ``test.pt`` (preprocess.py:406) has this layout too (8 cameras; ``use_first_tran=False``).
+  camera-frame    : the dictionary of preprocess_3dpw (preprocess.py:454, read by evaluate.py:228-313): ``posec``, ``tranc``,
+                    ``imu_oric``, ``imu_accc`` stored in the frame of a MOVING camera, one ``cam_K`` [3,3] and a ``cam_T`` [T,4,4]
+                    per sequence, ``joint2d_mp`` [T,33,3] in pixels. Every sequence is one row (i, 0) (``is_camera_layout``).
   input prep      : rc_camera_inputs kernel = evaluate.py:38-51,70-73 (K^-1 [u,v,1], R_cw IMU, gravity).
   per-frame loop  : ``Net.forward_sequence`` -- all rows, all frames, one call (evaluate.py:75-83 is a Python loop).
   sharding        : contiguous (sequence, camera) blocks per rank, one final all-gather (robustcap_amd.dist).
@@ -49,14 +53,36 @@ def camera_inputs(kp_norm, imu_acc_w, imu_ori_w, K, Tcw, image_size=(1920, 1080)
     return j2dc, accc, oric, torch.from_numpy(g)
 
 
+def is_camera_layout(dataset):
+    """True for the camera-frame dictionary of preprocess_3dpw (preprocess.py:454: ``posec``, ``tranc``, ``imu_oric``, ``imu_accc``, one
+    ``cam_K`` [3,3] and a ``cam_T`` [T,4,4] per sequence; ``preprocess.prepare_pw3d(...).as_dict()``): every sequence is ONE row (i, 0)
+    whose inputs and labels are stored in its camera's frame already (evaluate.py:236-247)."""
+    return "posec" in dataset
+
+
+def sequence_frames(dataset, i):
+    return len(dataset["posec" if is_camera_layout(dataset) else "pose"][i])
+
+
+def camera_varies(dataset, i):
+    """camera-frame layout: does T_cw of sequence i change over its frames (a moving camera)?"""
+    T = torch.as_tensor(dataset["cam_T"][i], dtype=torch.float32).reshape(-1, 4, 4)
+    return bool((T != T[:1]).any())
+
+
 def rows_of(dataset):
-    """[(sequence index, camera index)] in the reference's order (sequence-major, evaluate.py:32-33)."""
+    """[(sequence index, camera index)] in the reference's order (sequence-major, evaluate.py:32-33); camera-frame layout: (i, 0)."""
+    if is_camera_layout(dataset):
+        return [(i, 0) for i in range(len(dataset["posec"]))]
     return [(i, j) for i in range(len(dataset["pose"])) for j in range(len(dataset["cam_K"][i]))]
 
 
 def labels(dataset, i, j, device="cuda"):
     """camera-frame ground truth of row (i, j): pose [T,24,3,3] with the root rotated by R_cw, tran = T_cw [tran;1]
-    (evaluate.py:46-49)."""
+    (evaluate.py:46-49). Camera-frame layout: ``posec`` / ``tranc`` as they are (evaluate.py:244-245)."""
+    if is_camera_layout(dataset):
+        return (torch.as_tensor(dataset["posec"][i], dtype=torch.float32).reshape(-1, 24, 3, 3).cpu(),
+                torch.as_tensor(dataset["tranc"][i], dtype=torch.float32).reshape(-1, 3).cpu())
     Tcw = torch.as_tensor(dataset["cam_T"][i][j], dtype=torch.float32)
     pose = _body.axis_angle_to_rotation_matrix(torch.as_tensor(dataset["pose"][i]).reshape(-1, 3), device).view(-1, 24, 3, 3).cpu()
     pose[:, 0] = Tcw[:3, :3] @ pose[:, 0]
@@ -70,6 +96,8 @@ def camera_inputs_rows(dataset, rows, Tmax, image_size=(1920, 1080), device="cud
     device -- no per-row launches, copies or synchronisation. Returns device tensors j2dc [n,Tmax,33,3], accc [n,Tmax,6,3],
     oric [n,Tmax,6,3,3] (padding frames: zero keypoints / accelerations, identity orientations) and host gravity [n,3]."""
     dev = torch.device(device)
+    if is_camera_layout(dataset):
+        return _camera_layout_inputs(dataset, rows, Tmax, dev)
     n = len(rows)
     seqs = sorted({i for i, _ in rows})
     slot = {i: k for k, i in enumerate(seqs)}
@@ -105,10 +133,48 @@ def camera_inputs_rows(dataset, rows, Tmax, image_size=(1920, 1080), device="cud
     return j2dc, accc, oric, torch.from_numpy(grav)
 
 
+def _camera_layout_inputs(dataset, rows, Tmax, dev):
+    """``camera_inputs_rows`` for the camera-frame layout (evaluate.py:238-247, 278-285): the keypoints, already in pixels, go through the
+    same launch and K^-1 arithmetic with an image size of (1, 1) -- a multiplication by one --; the IMU rows are in the camera's frame
+    already and are handed over as stored (padding frames as above: zero accelerations, identity orientations), not multiplied by an
+    identity. Gravity of a row = R_cw(frame 0) [0,-1,0]: the engines hold one gravity per row, the reference sets it frame by frame
+    (:284-285) -- which only the flat floor reads, and ``run_dataset`` refuses the flat floor under a moving camera."""
+    n = len(rows)
+    kp = torch.zeros(n, Tmax, 33, 3, device=dev)
+    accc = torch.zeros(n, Tmax, 6, 3, device=dev)
+    oric = torch.eye(3, device=dev).repeat(n, Tmax, 6, 1, 1)
+    K = np.zeros((n, 3, 3), np.float32)
+    Tcw = np.zeros((n, 4, 4), np.float32)
+    lens = np.zeros(n, np.int32)
+    host = lambda a: np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, np.float32)
+    for r, (i, _) in enumerate(rows):
+        T = sequence_frames(dataset, i)
+        kp[r, :T] = torch.as_tensor(dataset["joint2d_mp"][i], dtype=torch.float32).to(dev).reshape(T, 33, 3)
+        accc[r, :T] = torch.as_tensor(dataset["imu_accc"][i], dtype=torch.float32).to(dev).reshape(T, 6, 3)
+        oric[r, :T] = torch.as_tensor(dataset["imu_oric"][i], dtype=torch.float32).to(dev).reshape(T, 6, 3, 3)
+        K[r], Tcw[r], lens[r] = host(dataset["cam_K"][i]).reshape(3, 3), host(dataset["cam_T"][i]).reshape(-1, 4, 4)[0], T
+    sor_d, len_d = torch.arange(n, dtype=torch.int32, device=dev), torch.from_numpy(lens).to(dev)
+    j2dc = torch.empty(n, Tmax, 33, 3, device=dev)
+    unused_a, unused_o = torch.empty_like(accc), torch.empty_like(oric)         # the launch's R_cw . IMU outputs: not used in this layout
+    grav = np.zeros((n, 3), np.float32)
+    scratch = torch.empty(n * 18, device=dev)
+    rc = _lib.load().rc_camera_inputs_rows(_lib.ptr(kp), _lib.ptr(accc), _lib.ptr(oric), _lib.ptr(sor_d), _lib.ptr(len_d),
+                                           K.ctypes.data_as(C.c_void_p), Tcw.ctypes.data_as(C.c_void_p), 1.0, 1.0, n, Tmax, _lib.ptr(j2dc),
+                                           _lib.ptr(unused_a), _lib.ptr(unused_o), grav.ctypes.data_as(C.c_void_p), _lib.ptr(scratch),
+                                           _lib.stream_ptr())
+    _lib.check(None, rc, "rc_camera_inputs_rows")
+    torch.cuda.current_stream().synchronize()
+    return j2dc, accc, oric, torch.from_numpy(grav)
+
+
 def first_translations(dataset, rows):
     """label translation of frame 0 of every row in its camera frame: T_cw [tran; 1] (evaluate.py:46-49,77) -- the same
     float32 expression as ``labels`` (so a row of the batched run equals that row run alone, bit for bit), without the pose."""
     ft = torch.zeros(len(rows), 3)
+    if is_camera_layout(dataset):                                               # evaluate.py:282
+        for r, (i, _) in enumerate(rows):
+            ft[r] = torch.as_tensor(dataset["tranc"][i][0], dtype=torch.float32).cpu()
+        return ft
     for r, (i, j) in enumerate(rows):
         Tcw = torch.as_tensor(dataset["cam_T"][i][j], dtype=torch.float32)
         ft[r] = (torch.as_tensor(dataset["tran"][i], dtype=torch.float32) @ Tcw[:3, :3].T + Tcw[:3, 3])[0]
@@ -134,9 +200,18 @@ def run_dataset(dataset, state_dict, body, use_first_tran=True, use_flat_floor=T
     mode of ``Net.set_gemm_mode``), pinned on every shard; None picks the library's
     default for the TOTAL number of rows of the run, not for this rank's shard, so a row's result does not depend on
     the number of ranks (``Net.default_gemm_mode``). ``ragged=True`` hands every row's own length to ``forward_sequence``: the
-    padding frames behind a short row are neither computed nor read; the frames returned are bitwise those of the padded run."""
+    padding frames behind a short row are neither computed nor read; the frames returned are bitwise those of the padded run.
+
+    Camera-frame layout (``is_camera_layout``, 3DPW): a row per sequence; ``image_size`` is not read (the keypoints are in pixels).
+    ``use_flat_floor=True`` raises ValueError where a sequence's ``cam_T`` varies over its frames: the engines hold one gravity per
+    row, and the reference switches the flat floor off for this data set (evaluate.py:254)."""
     all_rows = rows_of(dataset) if rows is None else list(rows)
-    Tmax = max(len(dataset["pose"][i]) for i, _ in all_rows)
+    if is_camera_layout(dataset) and use_flat_floor:
+        moving = [i for i, _ in all_rows if camera_varies(dataset, i)]
+        if moving:
+            raise ValueError(f"use_flat_floor=True with a moving camera (sequence {moving[0]}): one gravity per row is all the engines hold; "
+                             "the reference evaluates this layout with use_flat_floor=False")
+    Tmax = max(sequence_frames(dataset, i) for i, _ in all_rows)
     split = int(Net.default_gemm_mode(len(all_rows))) if gemm_mode is None else (2 if gemm_mode == 2 else int(bool(gemm_mode)))
 
     def compute(mine):
@@ -156,7 +231,7 @@ def run_dataset(dataset, state_dict, body, use_first_tran=True, use_flat_floor=T
             net.set_gemm_mode(split)
         net.use_flat_floor = use_flat_floor
         net.gravityc = grav
-        lengths = [len(dataset["pose"][i]) for i, _ in mine] if ragged else None
+        lengths = [sequence_frames(dataset, i) for i, _ in mine] if ragged else None
         out_p, out_t = net.forward_sequence(j2d, acc, ori, first_tran=ft if use_first_tran else None, first_frame=not use_first_tran,
                                             lengths=lengths)
         if run_smplify:
@@ -166,7 +241,7 @@ def run_dataset(dataset, state_dict, body, use_first_tran=True, use_flat_floor=T
     rows_out, out_p, out_t = shard_rows(all_rows, Tmax, compute, device=device)
     res = {}
     for r, (i, j) in enumerate(rows_out):
-        T = len(dataset["pose"][i])
+        T = sequence_frames(dataset, i)
         res[(i, j)] = (out_p[r, :T], out_t[r, :T])
     return res
 
@@ -211,12 +286,15 @@ def _refine_rows(dataset, mine, body, gmm, out_p, out_t, ori, image_size, device
             raise ValueError("run_smplify=True needs the GMM pose prior (gmm=)")
         rows = []
         for r, (i, j) in enumerate(mine):
-            T = len(dataset["pose"][i])
-            kp_pix = torch.as_tensor(dataset["joint2d_mp"][i][j], dtype=torch.float32) * scale      # evaluate.py:43-44 -> :87
-            rows.append((out_p[r, :T], out_t[r, :T], kp_pix, ori[r, :T], dataset["cam_K"][i][j]))
+            T = sequence_frames(dataset, i)
+            if is_camera_layout(dataset):                                                           # evaluate.py:297-300: pixels already
+                kp_pix, K = torch.as_tensor(dataset["joint2d_mp"][i], dtype=torch.float32).cpu(), dataset["cam_K"][i]
+            else:
+                kp_pix, K = torch.as_tensor(dataset["joint2d_mp"][i][j], dtype=torch.float32) * scale, dataset["cam_K"][i][j]   # evaluate.py:43-44 -> :87
+            rows.append((out_p[r, :T], out_t[r, :T], kp_pix, ori[r, :T], K))
         res = runner.run_batch(rows, lr=0.001)
         for r, (i, j) in enumerate(mine):
-            T = len(dataset["pose"][i])
+            T = sequence_frames(dataset, i)
             out_p[r, :T], out_t[r, :T] = res[r][0], res[r][1]
             if smplify_info is not None:
                 smplify_info[(i, j)] = dict(runner.last_batch_info[r])
@@ -295,6 +373,12 @@ def dataset_metrics(model, dataset, results, device="cuda"):
         return {}, [float("nan")] * 3
     seq_R, P, G, lens = {}, [], [], []
     for (i, j) in rows:
+        if is_camera_layout(dataset):                                           # the label is stored in the camera's frame (evaluate.py:244)
+            gt = torch.as_tensor(dataset["posec"][i], dtype=torch.float32).reshape(-1, 24, 3, 3).to(dev)
+            pose = results[(i, j)][0].to(dev)
+            n = min(pose.shape[0], gt.shape[0])
+            P.append(pose[:n]), G.append(gt[:n]), lens.append(n)
+            continue
         if i not in seq_R:
             seq_R[i] = _body.axis_angle_to_rotation_matrix(torch.as_tensor(dataset["pose"][i]).reshape(-1, 3), device).view(-1, 24, 3, 3)
         Rcw = torch.as_tensor(dataset["cam_T"][i][j], dtype=torch.float32)[:3, :3].to(dev)
@@ -333,6 +417,32 @@ def motion_metrics(model, dataset, results, fps=60, joint_mask=None, device="cud
                                   joint_mask=_mask_bits(joint_mask), per_joint=False)
     out = out.cpu()
     return {r: out[k] for k, r in enumerate(rows)}, out.mean(dim=0)
+
+
+def root_position_errors(dataset, results, align="none", device="cuda"):
+    """Absolute root position error (``art.PositionErrorEvaluator``: mean Euclidean distance, m) of every row of ``results`` =
+    {(i, j): (pose, tran [T,3])} against the camera-frame label translation. ``align="last"`` first shifts the prediction by
+    ``tran_t[-1] - tran_p[-1]`` so that the LAST frames coincide -- TotalCapture's root metric (evaluate.py:219-225; the sequences start
+    with ``first_frame=True`` there, so the start is not anchored) --; ``"none"`` compares as predicted (evaluate.py:113-117). The
+    distances run through ``rc_position_error``. Returns ({(i, j): error}, their mean over the rows)."""
+    if align not in ("none", "last"):
+        raise ValueError('align is "none" or "last"')
+    out = {}
+    for (i, j), (_, tran) in results.items():
+        tt = labels(dataset, i, j, device)[1] if is_camera_layout(dataset) else _label_translation(dataset, i, j)
+        tp = torch.as_tensor(tran, dtype=torch.float32).cpu()
+        n = min(tp.shape[0], tt.shape[0])
+        tp, tt = tp[:n], tt[:n]
+        if align == "last":
+            tp = tp + (tt[-1] - tp[-1])
+        out[(i, j)] = _body.position_error(tp, tt, device=device)
+    return out, (float(np.mean(list(out.values()))) if out else float("nan"))
+
+
+def _label_translation(dataset, i, j):
+    """``labels(...)[1]`` without the pose: T_cw [tran; 1] in the float32 expression of ``labels``."""
+    Tcw = torch.as_tensor(dataset["cam_T"][i][j], dtype=torch.float32)
+    return torch.as_tensor(dataset["tran"][i], dtype=torch.float32).cpu() @ Tcw[:3, :3].T + Tcw[:3, 3]
 
 
 def evaluate(dataset, state_dict, body, device="cuda", **kw):

@@ -143,12 +143,15 @@ class PreparedMotions:
         return self[key] if key in self else default
 
     def as_dict(self):
-        """The dictionary of preprocess.py:289 (AMASS: ``pose`` [T,24,3]) or :229-237 (AIST++: ``pose`` [T,72]): lists of per-sequence
-        views of the device buffers, plus ``shape`` (AMASS) and whatever ``extra`` holds."""
+        """The dictionary of preprocess.py:289 (AMASS: ``pose`` [T,24,3]), :229-237 (AIST++: ``pose`` [T,72]), :406 (TotalCapture:
+        ``pose`` [T,24,3]) or :454 (3DPW, layout "camera": ``posec`` [T,24,3,3], ``tranc``, ``imu_oric``, ``imu_accc``, ...): lists of
+        per-sequence views of the device buffers, plus ``shape`` (AMASS, 3DPW) and whatever ``extra`` holds."""
         d = {}
-        for k in FIELDS:
+        for k in (CAMERA_FIELDS if self.layout == "camera" else FIELDS):
+            if k not in self.fields:                                       # (camera layout: ``joint2d_mp`` only where keypoints came in)
+                continue
             parts = torch.split(self.fields[k], self.lengths)
-            d[k] = [p.view(-1, 24, 3) for p in parts] if k == "pose" and self.layout == "amass" else list(parts)
+            d[k] = [p.view(-1, 24, 3) for p in parts] if k == "pose" and self.layout in ("amass", "totalcapture") else list(parts)
         if self.shape is not None:
             d["shape"] = list(self.shape)
         d.update(self.extra)
@@ -281,3 +284,154 @@ def prepare_aist(model, smpl_poses, smpl_trans, smpl_scaling, cameras=None, tran
         KT = [aist_cameras(c, s) for c, s in zip(cameras, scales)]
         ex["cam_K"], ex["cam_T"] = [k for k, _ in KT], [t for _, t in KT]
     return prepare_motions(model, smpl_poses, trans, None, None, None, smooth_n, 0, layout="aist", extra=ex)
+
+
+# ---- camera-frame motions: 3DPW / 3DPW-OCC (a T_cw per frame) and TotalCapture (rc_prepare_camera_motions, csrc/rc_prepare.hip) -----------
+CAMERA_FIELDS = ("posec", "tranc", "joint3d", "sync_3d_mp", "imu_accc", "imu_oric", "joint2d_mp")
+TC_IMU_ORDER = (2, 3, 0, 1, 4, 5)                                       # preprocess.py:351-352
+TC_FLIP = ((-1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, -1.0))         # :359
+
+
+def camera_output_lengths(in_frames, cam_frames, cam_repeat=2):
+    """Output frames per sequence: ``min(in, cam_repeat * cam)`` -- the ``[:len(cam_pose)]`` / ``cam_pose[:len(posec)]`` pair of
+    preprocess.py:463-465, :577 -- or ``in`` for ``cam_repeat=0`` (one static camera row per sequence)."""
+    r = int(cam_repeat)
+    if r < 0:
+        raise ValueError("cam_repeat must not be negative")
+    if len(in_frames) != len(cam_frames):
+        raise ValueError(f"{len(cam_frames)} camera tables for {len(in_frames)} sequences")
+    if any(int(c) < 1 for c in cam_frames):
+        raise ValueError("a sequence without a camera row")
+    if r == 0 and any(int(c) != 1 for c in cam_frames):
+        raise ValueError("cam_repeat=0 takes one camera row per sequence")
+    return [int(n) if r == 0 else min(int(n), r * int(c)) for n, c in zip(in_frames, cam_frames)]
+
+
+def prepare_camera_motions(model, poses, trans, cam_T, betas=None, cam_repeat=2, keypoints=None, root_only=False, smooth_n=2, extra=None,
+                           vertex_ids=cfg.vi_mask, joint_ids=cfg.ji_mask, landmark_ids=cfg.mp_mask):
+    """preprocess.py:460-470 (and :571-582) for every sequence at once, in ONE ``rc_prepare_camera_motions`` call: axis-angle poses
+    [T_i,24,3] (or [T_i,72]) and translations [T_i,3] in the world frame, ``cam_T[i]`` [n_i,4,4] the T_cw rows of sequence i (a single
+    [4,4] for ``cam_repeat=0``), output frame t under row ``t // cam_repeat``. ``betas`` [n,10] or None (the model's current body).
+    ``keypoints[i]`` [k_i,33,3]: 30 Hz detections raised to 60 Hz by the midpoint interleave of :477-483, cut to the output length.
+    ``root_only``: the translation is kept as it is (TotalCapture). Returns a ``PreparedMotions`` with ``layout="camera"``: ``posec``
+    [frames,24,3,3] ROTATION MATRICES, ``tranc``, ``imu_oric``, ``imu_accc``, ``joint3d``, ``sync_3d_mp`` and ``joint2d_mp`` on the
+    device; ``as_dict()`` adds ``shape``, ``cam_T`` (the rows actually used, [T,4,4] per sequence, host) and what ``extra`` holds."""
+    dev = model.device
+    pose_all, in_len = _concat(poses, None, 72, "poses")
+    tran_all, t_len = _concat(trans, None, 3, "trans")
+    if t_len != in_len:
+        raise ValueError("poses and trans differ in their frames per sequence")
+    n = len(in_len)
+    cams = [np.asarray(c.detach().cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float32).reshape(-1, 4, 4) for c in cam_T]
+    if len(cams) != n:
+        raise ValueError(f"{len(cams)} camera tables for {n} sequences")
+    cam_len = [int(c.shape[0]) for c in cams]
+    r = int(cam_repeat)
+    out_len = camera_output_lengths(in_len, cam_len, r)
+    F = sum(out_len)
+    beta = None
+    if betas is not None:
+        beta = torch.as_tensor(np.asarray(betas, dtype=np.float32) if not isinstance(betas, torch.Tensor) else betas).detach().to("cpu", torch.float32).reshape(-1, 10)
+        if beta.shape[0] != n:
+            raise ValueError(f"betas: {beta.shape[0]} rows for {n} sequences")
+    kp_d, kp_len = None, None
+    if keypoints is not None:
+        kp_all, kp_len = _concat(keypoints, None, 99, "keypoints")
+        if len(kp_len) != n:
+            raise ValueError(f"{len(kp_len)} keypoint lists for {n} sequences")
+        kp_d = _body._f32c(kp_all, dev)
+    cam_all = np.ascontiguousarray(np.concatenate(cams))
+    pose_d, tran_d = _body._f32c(pose_all, dev), _body._f32c(tran_all, dev)
+    beta_d = None if beta is None else beta.to(dev).contiguous()
+    model._ensure_shape_space(landmark_ids, vertex_ids)
+    f = {"posec": torch.empty(F, 24, 3, 3, device=dev), "tranc": torch.empty(F, 3, device=dev), "joint3d": torch.empty(F, 24, 3, device=dev),
+         "sync_3d_mp": torch.empty(F, 33, 3, device=dev), "imu_accc": torch.empty(F, 6, 3, device=dev),
+         "imu_oric": torch.empty(F, 6, 3, 3, device=dev)}
+    if kp_d is not None:
+        f["joint2d_mp"] = torch.empty(F, 33, 3, device=dev)
+    vert6, rest = torch.empty(F, 6, 3, device=dev), torch.empty(n, 24, 3, device=dev)
+    i64 = lambda v: (C.c_int64 * n)(*[int(x) for x in v])
+    rc = model._lib.rc_prepare_camera_motions(
+        model._ctx, n, i64(in_len), i64(cam_len), r, sum(in_len), sum(cam_len), _lib.ptr(pose_d), _lib.ptr(tran_d), _lib.ptr(beta_d),
+        cam_all.ctypes.data_as(C.c_void_p), _lib.ptr(kp_d), None if kp_len is None else i64(kp_len), 0 if kp_len is None else sum(kp_len),
+        (C.c_int32 * 6)(*[int(j) for j in joint_ids]), int(smooth_n), 1 if root_only else 0, _lib.ptr(f["posec"]), _lib.ptr(f["tranc"]),
+        _lib.ptr(f["imu_oric"]), _lib.ptr(f["imu_accc"]), _lib.ptr(f["joint3d"]), _lib.ptr(f["sync_3d_mp"]), _lib.ptr(vert6),
+        _lib.ptr(f.get("joint2d_mp")), _lib.ptr(rest), _lib.stream_ptr())
+    _lib.check(model._ctx, rc, "rc_prepare_camera_motions")
+    for t in (pose_d, tran_d, beta_d, kp_d):                               # the inputs outlive the asynchronous launch
+        if t is not None:
+            t.record_stream(torch.cuda.current_stream())
+    ex = dict(extra or {})
+    ex["cam_T"] = [torch.from_numpy(c[(np.arange(T) // r) if r else np.zeros(T, np.int64)]) for c, T in zip(cams, out_len)]
+    return PreparedMotions("camera", out_len, f, vert6, rest, beta, list(range(n)), [], ex)
+
+
+def prepare_pw3d(model, poses_60hz, trans_60hz, betas, cam_poses, cam_intrinsics, keypoints30, names=None, generator=None):
+    """The body of ``preprocess_3dpw`` / ``preprocess_3dpwocc`` (preprocess.py:459-494, :570-606) from the arrays of the sequence
+    pickles, one entry per PERSON: ``poses_60hz[i]`` [T_i,72], ``trans_60hz[i]`` [T_i,3], ``betas[i]`` (its first 10 entries),
+    ``cam_poses[i]`` [n_i,4,4] at 30 Hz (repeated twice, :462), ``cam_intrinsics[i]`` [3,3], ``keypoints30[i]`` the detector's list: one
+    [33,3] array per 30 Hz frame, None or empty where it found nothing. Such a frame becomes uniform [0,1) draws with confidence 0
+    (:473-476), taken on the host from ``generator`` before the upload -- THE REFERENCE DRAWS UNSEEDED (``torch.rand``), so its files
+    differ from run to run in exactly these rows; pass a seeded ``torch.Generator`` for a repeatable dictionary. Where the pose is
+    shorter than the repeated cameras the cameras are cut (``preprocess_3dpwocc``; ``preprocess_3dpw`` raises there)."""
+    kps = []
+    for frames in keypoints30:
+        rows = []
+        for k in frames:
+            if k is None or len(k) == 0:
+                k = torch.rand(33, 3, generator=generator)
+                k[:, 2] = 0.0
+            rows.append(torch.as_tensor(np.asarray(k, dtype=np.float32) if not isinstance(k, torch.Tensor) else k).to(torch.float32).reshape(33, 3))
+        kps.append(torch.stack(rows) if rows else torch.zeros(0, 33, 3))
+    b = np.stack([np.asarray(x, dtype=np.float32).reshape(-1)[:10] for x in betas])
+    ex = {"cam_K": [torch.as_tensor(np.asarray(k, dtype=np.float32)).reshape(3, 3) for k in cam_intrinsics]}
+    if names is not None:
+        ex["name"] = list(names)
+    return prepare_camera_motions(model, poses_60hz, trans_60hz, cam_poses, b, 2, kps, False, 2, ex)
+
+
+def prepare_totalcapture(model, gt_aa, imu_ori, imu_acc, vicon_hips_m, cam_K=None, cam_T=None, keypoints=None, names=None, smooth_n=2):
+    """The motion part of ``preprocess_my_totalcapture_pre`` / ``preprocess_my_totalcapture`` (preprocess.py:351-364, 379-385, 429-445)
+    for lists of sequences: ``gt_aa[i]`` [T,72], the real ``imu_ori[i]`` [T,6,3,3] and ``imu_acc[i]`` [T,6,3] in the file's IMU order
+    (re-ordered by ``TC_IMU_ORDER``), ``vicon_hips_m[i]`` [T',3] the Vicon hip position in metres. Pose and IMU rows are clipped to their
+    common length and the translation to it; root, orientations and accelerations are flipped by ``diag(-1,1,-1)`` (the root through
+    a static camera with ``root_only``, the real IMU rows in torch: they are element-wise); ``tran[:,0] -= 0.03`` and
+    ``tran[:,1] += 1 / (10 + tran[:,2])``. Returns a ``PreparedMotions`` in the AIST++ layout (``pose`` [T,24,3] axis-angle through
+    ``body.rotation_matrix_to_axis_angle``, PARITY UNPINNED against OpenCV's ``cv2.Rodrigues`` like that function; real ``imu_ori`` /
+    ``imu_acc``; ``cam_K`` [8,3,3] / ``cam_T`` [8,4,4] and ``joint2d_mp`` as given, cut to the pose). ``.extra["imu_consistency_deg"]``:
+    device tensor [n], per sequence the mean ``angle_between(real, synthetic)`` in degrees -- the reference asserts < 17 (:445), here it is
+    returned. The joint check of :446 needs the HUMBI body's 33 vertices and is not made."""
+    dev = model.device
+    order = list(TC_IMU_ORDER)
+    flip = torch.tensor(TC_FLIP, dtype=torch.float32, device=dev)
+    t32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32) if not isinstance(a, torch.Tensor) else a).detach().to(torch.float32)
+    poses, trans, oris, accs = [], [], [], []
+    for i, (p, o, a, v) in enumerate(zip(gt_aa, imu_ori, imu_acc, vicon_hips_m)):
+        p, o, a, v = t32(p).reshape(-1, 72), t32(o).reshape(-1, 6, 3, 3)[:, order], t32(a).reshape(-1, 6, 3)[:, order], t32(v).reshape(-1, 3).clone()
+        T = min(p.shape[0], a.shape[0])                                    # :354-358
+        if v.shape[0] < T or o.shape[0] < T:
+            raise ValueError(f"sequence {i}: {v.shape[0]} Vicon frames and {o.shape[0]} orientation rows for {T} pose / IMU frames")
+        v = v[:T]                                                          # :379-380
+        v[:, 0] = v[:, 0] - 0.03                                           # :382-383
+        v[:, 1] = v[:, 1] + (1 / (10 + v[:, 2]))
+        poses.append(p[:T]), trans.append(v)
+        oris.append(flip @ o[:T].to(dev)), accs.append((flip @ a[:T].to(dev).unsqueeze(-1)).squeeze(-1))       # :362-364
+    model.set_shape(None)
+    n = len(poses)
+    static = np.eye(4, dtype=np.float32)
+    static[:3, :3] = np.asarray(TC_FLIP, dtype=np.float32)
+    cam = prepare_camera_motions(model, poses, trans, [static] * n, None, 0, None, True, smooth_n)
+    real_ori, real_acc = torch.cat(oris), torch.cat(accs)
+    pose = _body.rotation_matrix_to_axis_angle(cam.posec.view(-1, 3, 3), dev).view(-1, 72)                     # :434
+    ang = torch.rad2deg(_body.angle_between(real_ori.view(-1, 3, 3), cam.imu_oric.view(-1, 3, 3), dev)).view(-1, 6)
+    ex = {"imu_consistency_deg": torch.stack([a.mean() for a in torch.split(ang, cam.lengths)])}              # :445, returned
+    if names is not None:
+        ex["name"] = list(names)
+    if cam_K is not None:
+        ex["cam_K"] = [torch.as_tensor(cam_K, dtype=torch.float32)] * n
+    if cam_T is not None:
+        ex["cam_T"] = [torch.as_tensor(cam_T, dtype=torch.float32)] * n
+    if keypoints is not None:
+        ex["joint2d_mp"] = [torch.stack([t32(k)[:T] for k in per]) for per, T in zip(keypoints, cam.lengths)]   # :426-427, :437
+    f = {"pose": pose, "tran": cam.tranc, "joint3d": cam.joint3d, "sync_3d_mp": cam.sync_3d_mp, "imu_acc": real_acc, "imu_ori": real_ori}
+    return PreparedMotions("totalcapture", cam.lengths, f, cam.vert6, cam.rest_joint, None, cam.kept, [], ex)
