@@ -16,6 +16,10 @@ scale = the size of the numbers the entry is made of, taken from the restatement
 A NaN must sit exactly where the restatement has one.
 
 `mut` names one deliberate mistake each (tests/test_motion_metrics_cpu.py: each moves a named output by more than the bound).
+
+`evaluate_blockwise` forms the same eleven rows the way the device has to: per-block (n, mean, M2) of 32 rows merged in index order by
+Chan's update (`blockwise`), in float64 numpy, sharing no code with the kernel. It equals `evaluate(dtype=F64)` up to the order of the
+sums; BLOCK_MUTATIONS are the mistakes of that path, which need a third block or a one-second window that leaves its block to show.
 """
 import math
 
@@ -92,6 +96,9 @@ def arrays(body, pose_p, pose_t, tran_p=None, tran_t=None, fps=60, align=0, dtyp
     a["jkp"] = ((kp[3:] - 3 * kp[2:-1] + 3 * kp[1:-2] - kp[:-3]) * (fps ** 3)).norm(dim=2)
     a["jkt"] = ((kt[3:] - 3 * kt[2:-1] + 3 * kt[1:-2] - kt[:-3]) * (fps ** 3)).norm(dim=2)
     a["te"] = ((jp[f:, :1] - jp[:-f, :1]) - (jt[f:, :1] - jt[:-f, :1])).norm(dim=2)
+    if mut == "window_wraps_block":                                               # the same N - fps rows, read fps % 32 frames ahead
+        rows, w = max(jp.shape[0] - f, 0), f % 32
+        a["te"] = ((jp[w:w + rows, :1] - jp[:rows, :1]) - (jt[w:w + rows, :1] - jt[:rows, :1])).norm(dim=2)
     mx = lambda z: float(z.double().norm(dim=-1).max())
     pos = mx(jp) + mx(jt) + mx(off)
     ang = lambda z: 180.0 / math.pi * max(1.0, float(z.double().max()) * math.pi / 180.0)
@@ -144,6 +151,70 @@ def evaluate_groups(body, pose_p, pose_t, tran_p, tran_t, sizes, fps=60, align=0
         outs.append(o), pjs.append(pj), scs.append(sc)
         at += N
     return np.stack(outs), np.stack(pjs), np.stack(scs)
+
+
+# ------------------------------------------------------------------------------------------- the same numbers, block by block
+BLOCK_MUTATIONS = {                 # mutation of the block-wise path -> (row, column of out) it must move
+    "count_not_carried": ("je", 1),
+    "no_cross_term": ("je", 1),
+    "unweighted_block_means": ("je", 0),
+    "window_wraps_block": ("te", 0),
+    "jerk_rows_from_frames": ("jkp", 0),
+}
+
+
+def _blockwise_columns(x, fg, mut):
+    """per column (mean, unbiased std) of x [rows, cols]: (n, mean, M2) of every block of fg rows, merged in index order by Chan's update
+      n = na + nb,  mean = mean_a + (mean_b - mean_a) nb / n,  M2 = M2_a + M2_b + (mean_b - mean_a)^2 na nb / n.
+    No rows: (NaN, NaN); one row: (its value, NaN = 0 / 0), as torch's mean and std(dim=0) give them."""
+    x = np.asarray(x, np.float64)
+    rows, cols = x.shape
+    nan = np.full(cols, np.nan)
+    if rows == 0:
+        return nan, nan.copy()
+    na, mean, m2, prev, block_means = 0, None, None, 0, []
+    for lo in range(0, rows, fg):
+        blk = x[lo:lo + fg]
+        nb, mb = blk.shape[0], blk.mean(axis=0)
+        m2b = ((blk - mb) ** 2).sum(axis=0)
+        block_means.append(mb)
+        if na == 0:
+            na, mean, m2 = nb, mb, m2b
+        else:
+            ca = prev if mut == "count_not_carried" else na       # the mistake: the count of the block before, not of all before
+            d = mb - mean
+            mean = mean + d * (nb / (ca + nb))
+            m2 = m2 + m2b + (0.0 if mut == "no_cross_term" else d * d * (ca * nb / (ca + nb)))
+            na += nb
+        prev = nb
+    if mut == "unweighted_block_means":
+        mean = np.mean(block_means, axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        std = np.sqrt(m2 / (rows - 1.0))
+    return mean, std
+
+
+def blockwise(x, fg=32, mut=None):
+    """(x.mean(), x.std(dim=0).mean()) of an [rows, cols] float64 array with equal rows per column, formed from per-block (n, mean, M2)
+    merged in index order: the mean of the column means and the mean of the unbiased column stds"""
+    m, s = _blockwise_columns(x, fg, mut)
+    return [float(m.mean()), float(s.mean())]
+
+
+def evaluate_blockwise(body, pose_p, pose_t, tran_p=None, tran_t=None, fps=60, align=0, mask=None, fg=32, mut=None):
+    """evaluate(dtype=F64) with every (mean, std) pair formed by `blockwise`: (out [11,2], per_joint [4,24], scale [11]). It differs from
+    evaluate by the order of the sums alone; `mut` names one of BLOCK_MUTATIONS."""
+    a, scale = arrays(body, pose_p, pose_t, tran_p, tran_t, fps, align, F64, mut if mut == "window_wraps_block" else None)
+    a = {k: v.numpy() for k, v in a.items()}
+    for src, dst in (("je", "mje"), ("lae", "mlae"), ("gae", "mgae")):
+        a[dst] = a[src][:, list(mask)] if mask is not None else np.zeros((1, 1))
+    if mut == "jerk_rows_from_frames":                                            # N rows in place of N - 3: the last valid row read again
+        for r in ("jkp", "jkt"):
+            if a[r].shape[0] > 0:
+                a[r] = np.concatenate([a[r], np.repeat(a[r][-1:], 3, axis=0)])
+    out = np.array([blockwise(a[r], fg, mut) for r in ROWS], np.float64)
+    pj = np.stack([_blockwise_columns(a[r], fg, mut)[0] for r in ("je", "lae", "gae", "tre")])
+    return out, pj, scale
 
 
 def bound(f32, f64, scale):
@@ -203,3 +274,14 @@ GOLDEN_SETTINGS = {                    # name -> (fps, joint_mask, align_joint) 
     "align5": (60, None, 5),
 }
 GOLDEN_MOTIONS = ("near", "far", "same")
+GOLDEN_LONG = (62, 131)                # motion_pair(seed, frames) of the captured `long` motion: 71 one-second windows at fps 60
+GOLDEN_LONG_SETTINGS = ("fps60", "align5")
+GOLDEN_LONG_INPUTS = ("pose_p", "pose_t", "tran_p", "tran_t")                     # meta.json: sha256 of these arrays' bytes, in this order
+
+
+def golden_long():
+    """the `long` motion of the captured fixture, regenerated from its seed: (pose_p, pose_t, tran_p, tran_t) and {name: sha256 of the
+    array's float32 bytes}, which meta.json records for the arrays the reference was run on"""
+    import hashlib
+    arrs = motion_pair(*GOLDEN_LONG)
+    return arrs, {k: hashlib.sha256(np.ascontiguousarray(a, np.float32).tobytes()).hexdigest() for k, a in zip(GOLDEN_LONG_INPUTS, arrs)}

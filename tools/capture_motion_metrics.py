@@ -6,7 +6,11 @@ which the restatement tests/motion_metrics_f64.py and the device (csrc/rc_motion
   motions   the `near` / `far` / `same` poses of oracle/capture_metrics.py against its `gt` (tests/golden/metrics.npz: pose_near, pose_far,
             pose_gt, 24 frames), with the seeded translations of motion_metrics_f64.golden_translations (`same`: the truth's on both sides)
   settings  motion_metrics_f64.GOLDEN_SETTINGS: fps=60 without a mask | fps=5 with a joint mask | align_joint=5
-  stored    tran_p, tran_t [24,3] float32 and out_<setting>_<motion> [11,2] (the evaluator's float32 result, NaNs included)
+            `long`: motion_metrics_f64.motion_pair(*GOLDEN_LONG), 131 frames, under fps=60 and align_joint=5 only: the one motion long
+            enough for a finite te at the reference's default frame rate (71 one-second windows)
+  stored    tran_p, tran_t [24,3] float32 and out_<setting>_<motion> [11,2] (the evaluator's float32 result, NaNs included);
+            tran_p_long, tran_t_long [131,3] and out_fps60_long, out_align5_long. The long poses are not stored: meta.json holds the sha256 of
+            the four input arrays (pose_p, pose_t, tran_p, tran_t), and the tests regenerate them from the seed and compare.
 
 THE ANGLE ROWS PIN THE WIRING ONLY. OpenCV is not installed here, and capture_reference._install_stubs() gives cv2.Rodrigues a stand-in that
 returns zeros; this tool replaces that stand-in with its own float64 numpy rotation -> axis-angle (the atan2 form, well conditioned at the
@@ -61,6 +65,16 @@ def main():
             out = ev(t(pose), t(gt), tran_p=t(tp), tran_t=t(tran_t))
             assert out.shape == (11, 2) and out.dtype == torch.float32
             g[f"out_{sname}_{mname}"] = out.numpy().astype(np.float64)
+    # the `long` motion: 131 frames, so that te at fps 60 is finite (71 windows). Its poses are not stored: the tests regenerate them from
+    # the seed and compare their sha256 with meta.json.
+    (lpp, lpt, ltp, ltt), long_digests = M.golden_long()
+    g["tran_p_long"], g["tran_t_long"] = ltp, ltt
+    for sname in M.GOLDEN_LONG_SETTINGS:
+        fps, mask, align = M.GOLDEN_SETTINGS[sname]
+        ev = art.FullMotionEvaluator("models/SMPL_male.pkl", align_joint=align, fps=fps, joint_mask=mask)
+        out = ev(t(lpp), t(lpt), tran_p=t(ltp), tran_t=t(ltt))
+        assert out.shape == (11, 2) and out.dtype == torch.float32 and bool(torch.isfinite(out[6]).all())
+        g[f"out_{sname}_long"] = out.numpy().astype(np.float64)
     out_dir = os.path.join(CR.OUT, "motion")
     os.makedirs(out_dir, exist_ok=True)
     path = os.path.join(out_dir, "motion_metrics.npz")
@@ -68,7 +82,7 @@ def main():
     with open(path, "rb") as f:
         digest = hashlib.sha256(f.read()).hexdigest()
     with open(os.path.join(out_dir, "meta.json"), "w") as f:
-        json.dump({"sha256": {"motion_metrics.npz": digest}}, f, indent=1, sort_keys=True)
+        json.dump({"sha256": {"motion_metrics.npz": digest}, "long_inputs_sha256": long_digests}, f, indent=1, sort_keys=True)
     for k in sorted(g):
         if k.startswith("out_"):
             print(k, g[k][:, 0])
