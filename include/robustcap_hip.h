@@ -642,6 +642,46 @@ int rc_mesh_metrics(rc_ctx* ctx, const float* pose, const float* gt_pose, int64_
 int rc_motion_metrics(rc_ctx* ctx, const float* pose_p, const float* tran_p, const float* pose_t, const float* tran_t, int64_t n,
                       int32_t groups, const int64_t* group_frames_host, int32_t fps, int32_t align_joint, uint32_t joint_mask,
                       uint32_t flags, float* out, float* per_joint, void* stream);
+/* art.math.svd_rotate (articulate/math/angular.py:144-184) on point sets, context-free like rc_procrustes_error: src, dst DEVICE [n,m,3],
+ * `what` a combination of RC_ALIGN_R (calc_R), RC_ALIGN_T (calc_t) and RC_ALIGN_S (calc_s); 0 is the identity transform. Per set, exactly
+ * as :159-183: the means are subtracted only with RC_ALIGN_T; s = sqrt(sum |dst - mu_d|^2 / sum |src - mu_s|^2) with RC_ALIGN_S, else 1;
+ * with RC_ALIGN_R, H = (src - mu_s)^T (dst - mu_d) = U S V^T and Q = V U^T, and where det Q < -0.9 ROW 2 of V is negated (:175-177), so
+ * R = diag(1,1,-1) Q -- the reference's rule, not the optimal proper rotation, and not rc_procrustes_error's (whose scale is trace / var
+ * and whose fit runs on 14 keypoints); t = -s R mu_s + mu_d; moved = s src R^T + t. Outputs DEVICE: R [n,3,3], t [n,3], s [n], moved
+ * [n,m,3]; each may be NULL, not all. A wave per set, float64 inside (two passes: means, then centred sums, added by a fixed tree; Q from
+ * a one-sided Jacobi on H, unique for a full-rank H whatever signs LAPACK picks), rounded once.
+ * Rank-deficient H (fewer than three non-coplanar centred points; the reference returns whatever LAPACK returns): singular directions
+ * below 1e-13 of the largest are completed so that U is a proper rotation (H = 0: R = I); R is then finite and proper, and no reflection
+ * is applied. s is the IEEE value of the reference's expression: inf (or NaN for 0 / 0) where sum |src - mu_s|^2 = 0, and t, moved follow.
+ * RC_ERR_INVALID on n < 0 or >= 2^31, m < 1, unknown bits of `what`, a null src / dst or no output; n == 0 is a no-op. */
+#define RC_ALIGN_R 1u
+#define RC_ALIGN_T 2u
+#define RC_ALIGN_S 4u
+int rc_svd_rotate(const float* src, const float* dst, int64_t n, int32_t m, uint32_t what, float* R, float* t, float* s, float* moved,
+                  void* stream);
+/* PerJointErrorEvaluator / MeanPerJointErrorEvaluator (articulate/evaluator.py:195-210) and MeshErrorEvaluator (:298-313) with align_joint
+ * -1 .. -5 for every motion of a concatenated batch in one call: -1 = R|T|S, -2 = R|T, -3 = T|S, -4 = T, -5 = S as `what`. pose_p, pose_t
+ * DEVICE [n,24,3,3] local rotations; translations are zero (:191-194, 294-297); groups / group_frames_host as rc_motion_metrics. Per frame
+ * TWO transforms are fitted by rc_svd_rotate's expressions: one on the 24 joints (its two-pass sums), one on the V vertices of the mesh of
+ * rc_set_mesh (from folded sums, centred in ONE pass: sum p t^T - V mu_p mu_t^T, sum |p|^2 - V |mu_p|^2).
+ * Outputs DEVICE, each may be NULL but not all: joint_err [groups,24] the column means over the group's frames of |joint_p' - joint_t|
+ * (:210; the angle rows of :211-212 are untouched by the alignment and remain rc_motion_metrics'); mesh_err [groups] the mean over
+ * frames and vertices of |mesh_p' - mesh_t| (:313); per_frame [n,2] each frame's mean joint and mean vertex error; xform [n,2,13] = R
+ * [9], t [3], s of the joint fit, then of the mesh fit. flags: RC_MOTION_NO_MESH skips the mesh half (mesh_err, per_frame[:,1] and
+ * xform[:,1] are NaN, every other entry keeps its bits); without it a context with no mesh returns RC_ERR_STATE.
+ * The mesh fit reads no vertex: sum_v p_v t_v^T, sum_v p_v and sum_v |p_v|^2 are bilinear in the 24 joint transforms through constants
+ * folded once per mesh (float64, on the host, by the first call after rc_set_mesh / rc_set_body: that call synchronises the device).
+ * Joint chains, fits and sums in float64; the vertex error is one float32 blend per vertex of 24 aligned difference transforms. The
+ * one-pass centring of the mesh fit leaves 1e-16 V |mu|^2 of rounding in the spreads: a DEGENERATE mesh whose skinned vertices all coincide
+ * gets a rounding-level spread of either sign (s: any value, or NaN from a negative ratio) where rc_svd_rotate's two passes give exactly 0
+ * and the IEEE inf / NaN; a mesh with any extent is unaffected.
+ * Otherwise enqueued on `stream` like rc_motion_metrics: no read-back, no synchronisation, the group table through a ring of four
+ * pinned copies, a wait for the stream where the context-owned scratch grows. No floating-point atomics, every sum in an order fixed by
+ * the frame or the group alone: two calls give the same bits and a group's entries are those of a call with that group alone.
+ * RC_ERR_INVALID (nothing written, nothing enqueued) on a null context, pose or table, no output, what == 0 or unknown bits, an unknown
+ * flag, and the table errors of rc_motion_metrics; n == 0 with groups == 0 is a no-op. */
+int rc_aligned_metrics(rc_ctx* ctx, const float* pose_p, const float* pose_t, int64_t n, int32_t groups, const int64_t* group_frames_host,
+                       uint32_t what, uint32_t flags, float* joint_err, float* mesh_err, float* per_frame, float* xform, void* stream);
 /* IMU synthesis of the dataset preparation (preprocess.py:22-33 `_syn_acc`, :206-214): pose[T,24,3,3] local rotations,
  * tran[T,3] DEVICE; vertex_ids[6] (config.vi_mask) and joint_ids[6] (config.ji_mask) HOST; needs rc_set_mesh.
  * -> imu_ori[T,6,3,3] = global rotations of joint_ids, vert6[T,6,3] = skinned vertices, imu_acc[T,6,3] =

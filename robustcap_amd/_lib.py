@@ -98,6 +98,8 @@ SIGNATURES = {
     "rc_set_regressor": (_I32, [_P, _P, _I32, _I32]),
     "rc_mesh_metrics": (_I32, [_P, _P, _P, _I64, _P, C.POINTER(C.c_double), _P]),
     "rc_motion_metrics": (_I32, [_P, _P, _P, _P, _P, _I64, _I32, C.POINTER(_I64), _I32, _I32, _U32, _U32, _P, _P, _P]),
+    "rc_svd_rotate": (_I32, [_P, _P, _I64, _I32, _U32, _P, _P, _P, _P, _P]),
+    "rc_aligned_metrics": (_I32, [_P, _P, _P, _I64, _I32, C.POINTER(_I64), _U32, _U32, _P, _P, _P, _P, _P]),
     "rc_synth_imu": (_I32, [_P, _P, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P]),
     "rc_syn_acc": (_I32, [_P, _I64, _I64, _I32, _P, _P]),
     "rc_set_shape_space": (_I32, [_P, _P, _P, _P, _I32, _P, _P]),

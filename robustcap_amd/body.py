@@ -285,6 +285,32 @@ class ParametricModel:
         _lib.check(self._ctx, rc, "rc_motion_metrics")
         return out, pj
 
+    def aligned_metrics(self, pose_p, pose_t, group_frames=None, align=-1, mesh=True, per_frame=False):
+        """art.PerJointErrorEvaluator / art.MeshErrorEvaluator with ``align_joint`` -1 .. -5 (articulate/evaluator.py:195-210, 298-313)
+        of every motion of a concatenated batch in one call (rc_aligned_metrics): poses [n,24,3,3] local, ``group_frames`` the lengths
+        of the motions (None: one motion of n frames), ``align`` the reference's mode (-1 R/t/s, -2 R/t, -3 t/s, -4 t, -5 s). Returns
+        device tensors (joint_err [groups,24], mesh_err [groups] or None with ``mesh=False``, and with ``per_frame=True`` also
+        per_frame [n,2] = each frame's mean joint and vertex error and xform [n,2,13] = R, t, s of the joint fit and of the mesh fit);
+        nothing is read back."""
+        what = align_bits(align)
+        pose_p = _f32c(pose_p, self.device).view(-1, 24, 3, 3)
+        pose_t = _f32c(pose_t, self.device).view(-1, 24, 3, 3)
+        if pose_t.shape != pose_p.shape:
+            raise ValueError("pose_p and pose_t must have the same number of frames")
+        n = pose_p.shape[0]
+        sizes = [n] if group_frames is None else [int(f) for f in group_frames]
+        G = len(sizes)
+        if mesh:
+            self._ensure_mesh()
+        je = torch.empty(G, 24, device=self.device)
+        me = torch.empty(G, device=self.device) if mesh else None
+        pf = torch.empty(n, 2, device=self.device) if per_frame else None
+        xf = torch.empty(n, 2, 13, device=self.device) if per_frame else None
+        rc = self._lib.rc_aligned_metrics(self._ctx, _lib.ptr(pose_p), _lib.ptr(pose_t), n, G, (C.c_int64 * G)(*sizes), what,
+                                          0 if mesh else 1, _lib.ptr(je), _lib.ptr(me), _lib.ptr(pf), _lib.ptr(xf), _lib.stream_ptr())
+        _lib.check(self._ctx, rc, "rc_aligned_metrics")
+        return (je, me, pf, xf) if per_frame else (je, me)
+
     def reprojection_residual(self, pose, tran, keypoints_2d, cam_k, sigma=100.0):
         """``TemporalSMPLify.get_fitting_loss`` (temporal_smplify.py:198-220): [T,33] robust reprojection loss."""
         pose = _f32c(pose, self.device).view(-1, 24, 3, 3)
@@ -383,6 +409,33 @@ def position_error(p, t, device="cuda"):
     lib = _lib.load()
     _lib.check(None, lib.rc_position_error(_lib.ptr(a), _lib.ptr(b), a.shape[0], _lib.ptr(d), C.byref(mean), _lib.stream_ptr()), "rc_position_error")
     return mean.value
+
+
+ALIGN_R, ALIGN_T, ALIGN_S = 1, 2, 4
+_ALIGN_MODES = {-1: ALIGN_R | ALIGN_T | ALIGN_S, -2: ALIGN_R | ALIGN_T, -3: ALIGN_T | ALIGN_S, -4: ALIGN_T, -5: ALIGN_S}
+
+
+def align_bits(align_joint):
+    """the reference's negative ``align_joint`` (articulate/evaluator.py:198-209) as RC_ALIGN_* bits; anything else raises its RuntimeError"""
+    if align_joint not in _ALIGN_MODES:
+        raise RuntimeError('Undefined align_joint=%d' % align_joint)
+    return _ALIGN_MODES[align_joint]
+
+
+def svd_rotate(source_points, target_points, calc_R=True, calc_t=False, calc_s=False, device="cuda"):
+    """art.math.svd_rotate (articulate/math/angular.py:144-184) on point sets [n,m,3]: returns device tensors (R [n,3,3], t [n,3], s [n],
+    the transformed source points [n,m,3]). float64 inside, rounded once; where det(V U^T) < -0.9 row 2 of V is negated, as the
+    reference does (not the optimal proper rotation)."""
+    a, b = _f32c(source_points, torch.device(device)), _f32c(target_points, torch.device(device))
+    if a.shape != b.shape or a.dim() != 3 or a.shape[2] != 3:
+        raise ValueError("source_points and target_points must both be [n, m, 3]")
+    n, m = a.shape[0], a.shape[1]
+    R, t, s, moved = (torch.empty(n, 3, 3, device=a.device), torch.empty(n, 3, device=a.device), torch.empty(n, device=a.device),
+                      torch.empty_like(a))
+    what = (ALIGN_R if calc_R else 0) | (ALIGN_T if calc_t else 0) | (ALIGN_S if calc_s else 0)
+    _lib.check(None, _lib.load().rc_svd_rotate(_lib.ptr(a), _lib.ptr(b), n, m, what, _lib.ptr(R), _lib.ptr(t), _lib.ptr(s), _lib.ptr(moved),
+                                               _lib.stream_ptr()), "rc_svd_rotate")
+    return R, t, s, moved
 
 
 def reconstruction_error(S1, S2, device="cuda"):

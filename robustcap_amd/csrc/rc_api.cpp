@@ -287,6 +287,56 @@ int fold_regressor(rc_ctx* ctx) {
     return RC_OK;
 }
 
+// The mesh fit of rc_aligned_metrics needs sum_v p_v t_v^T, sum_v p_v and sum_v |p_v|^2 of two skinned meshes; with p_v = sum_j w[v,j] A_j x~_v
+// (A_j = [G_j | T_j], x~_v = (x_v, 1)) they are bilinear in the 24 transforms, through the pose-independent
+//   C[j,k] = sum_v w[v,j] w[v,k] x~_v x~_v^T (4x4)   and   m_j = sum_v w[v,j] x~_v
+// (float64 here, in vertex order, once per mesh / root). Only pairs j <= k with a non-zero C are kept: C[k,j] = C[j,k], and SMPL's four
+// weights per vertex leave most of the 300 pairs empty. Device layout: 24 x 4 doubles m, then the AlignPair list.
+int fold_align(rc_ctx* ctx) {
+    const int V = ctx->mesh_V;
+    std::vector<double> C((size_t)24 * 24 * 16, 0.0), m((size_t)24 * 4, 0.0);
+    for (int v = 0; v < V; ++v) {
+        const double x[4] = {(double)ctx->mesh_vt_h[3 * (size_t)v] - ctx->jroot_h[0], (double)ctx->mesh_vt_h[3 * (size_t)v + 1] - ctx->jroot_h[1],
+                             (double)ctx->mesh_vt_h[3 * (size_t)v + 2] - ctx->jroot_h[2], 1.0};
+        int nz[24], n_nz = 0;
+        for (int j = 0; j < 24; ++j)
+            if (ctx->mesh_w_h[(size_t)v * 24 + j] != 0.0f) nz[n_nz++] = j;
+        for (int a = 0; a < n_nz; ++a) {
+            const int j = nz[a];
+            const double wj = ctx->mesh_w_h[(size_t)v * 24 + j];
+            for (int c = 0; c < 4; ++c) m[(size_t)j * 4 + c] += wj * x[c];
+            for (int b = a; b < n_nz; ++b) {
+                const int k = nz[b];
+                const double ww = wj * (double)ctx->mesh_w_h[(size_t)v * 24 + k];
+                double* cc = &C[((size_t)j * 24 + k) * 16];
+                for (int r = 0; r < 4; ++r)
+                    for (int c = 0; c < 4; ++c) cc[4 * r + c] += ww * (x[r] * x[c]);
+            }
+        }
+    }
+    std::vector<AlignPair> pairs;
+    for (int j = 0; j < 24; ++j)
+        for (int k = j; k < 24; ++k) {
+            const double* cc = &C[((size_t)j * 24 + k) * 16];
+            bool any = false;
+            for (int i = 0; i < 16; ++i) any = any || cc[i] != 0.0;
+            if (!any) continue;
+            AlignPair p{};
+            p.j = j;
+            p.k = k;
+            for (int i = 0; i < 16; ++i) p.c[i] = cc[i];
+            pairs.push_back(p);
+        }
+    const size_t head = m.size() * sizeof(double), bytes = head + pairs.size() * sizeof(AlignPair);
+    HIP_TRY(ctx, hipDeviceSynchronize());                    // nothing in flight may still read the old fold
+    HIP_TRY(ctx, rc_grow(ctx->align_fold_bytes, bytes, bytes, ctx->align_fold, bytes));
+    HIP_TRY(ctx, hipMemcpy(ctx->align_fold.get(), m.data(), head, hipMemcpyHostToDevice));
+    if (!pairs.empty()) HIP_TRY(ctx, hipMemcpy(ctx->align_fold.get() + head, pairs.data(), pairs.size() * sizeof(AlignPair), hipMemcpyHostToDevice));
+    ctx->align_pairs = (int)pairs.size();
+    ctx->align_dirty = false;
+    return RC_OK;
+}
+
 }  // namespace
 
 int check_ready(rc_ctx* ctx) {
@@ -767,6 +817,7 @@ int rc_set_body(rc_ctx* ctx, const int32_t* parent, const float* J, const float*
     ctx->have_body = true;
     for (int c = 0; c < 3; ++c) ctx->jroot_h[c] = b.jroot[c];
     ctx->fold_dirty = true;
+    ctx->align_dirty = true;
     return RC_OK;
 }
 
@@ -936,6 +987,7 @@ int rc_set_mesh(rc_ctx* ctx, const float* vt, const float* w, int32_t V) {
     ctx->mesh_vt_h.assign(vt, vt + (size_t)V * 3);
     ctx->mesh_w_h.assign(w, w + (size_t)V * 24);
     ctx->fold_dirty = true;
+    ctx->align_dirty = true;
     return RC_OK;
 }
 int rc_body_mesh(rc_ctx* ctx, const float* pose, const float* tran, float* vert, int64_t n, void* stream) {
@@ -1037,6 +1089,71 @@ int rc_motion_metrics(rc_ctx* ctx, const float* pose_p, const float* tran_p, con
     HIP_TRY(ctx, ctx->motion_tab.record(st));
     rc_launch_motion_metrics(ctx->body, ctx->mesh_vt, ctx->mesh_w, ctx->mesh_V, ctx->motion_tab.get(), groups, blocks, pose_p, tran_p, pose_t,
                              tran_t, n, fps, align_joint, joint_mask, mesh, ctx->motion_scratch.get(), ctx->motion_partial.get(), out, per_joint, st);
+    HIP_TRY(ctx, hipGetLastError());
+    return RC_OK;
+}
+// art.math.svd_rotate (angular.py:144-184) on point sets; context-free like rc_procrustes_error
+int rc_svd_rotate(const float* src, const float* dst, int64_t n, int32_t m, uint32_t what, float* R, float* t, float* s, float* moved,
+                  void* stream) {
+    if (n < 0 || n >= (1ll << 31) || m < 1 || (what & ~(uint32_t)(RC_ALIGN_R | RC_ALIGN_T | RC_ALIGN_S))) return RC_ERR_INVALID;
+    if (n == 0) return RC_OK;
+    if (!src || !dst || (!R && !t && !s && !moved)) return RC_ERR_INVALID;
+    rc_launch_svd_rotate(src, dst, n, m, what, R, t, s, moved, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? RC_OK : RC_ERR_HIP;
+}
+// PerJointErrorEvaluator / MeshErrorEvaluator with align_joint -1 .. -5 (articulate/evaluator.py:195-209, 298-312) of every group of a
+// concatenated batch (kernels: rc_align.hip). It touches nothing of the context but its own fold, scratch, partial sums and group table.
+int rc_aligned_metrics(rc_ctx* ctx, const float* pose_p, const float* pose_t, int64_t n, int32_t groups, const int64_t* group_frames_host,
+                       uint32_t what, uint32_t flags, float* joint_err, float* mesh_err, float* per_frame, float* xform, void* stream) {
+    if (!ctx) return RC_ERR_INVALID;
+    const std::string name = "rc_aligned_metrics: ";
+    if (n == 0 && groups == 0) return RC_OK;
+    if (n < 0 || n >= (1ll << 31)) return fail(ctx, RC_ERR_INVALID, name + "n must be in 0 .. 2^31 - 1");
+    if (groups < 1) return fail(ctx, RC_ERR_INVALID, name + "groups must be positive");
+    if (!pose_p || !pose_t || !group_frames_host) return fail(ctx, RC_ERR_INVALID, name + "null argument");
+    if (!joint_err && !mesh_err && !per_frame && !xform) return fail(ctx, RC_ERR_INVALID, name + "no output asked for");
+    if (what == 0 || (what & ~(uint32_t)(RC_ALIGN_R | RC_ALIGN_T | RC_ALIGN_S)))
+        return fail(ctx, RC_ERR_INVALID, name + "what must combine RC_ALIGN_R, RC_ALIGN_T, RC_ALIGN_S");
+    if (flags & ~(uint32_t)RC_MOTION_NO_MESH) return fail(ctx, RC_ERR_INVALID, name + "unknown flag");
+    long long F = 0, blocks = 0;
+    for (int g = 0; g < groups; ++g) {
+        const int64_t f = group_frames_host[g];
+        if (f < 1 || f > n) return fail(ctx, RC_ERR_INVALID, name + "group " + std::to_string(g) + " has " + std::to_string(f) + " frames: 1 .. n expected");
+        F += f;
+        blocks += (f + RC_MOTION_FG - 1) / RC_MOTION_FG;
+    }
+    if (F != n) return fail(ctx, RC_ERR_INVALID, name + "the groups hold " + std::to_string(F) + " frames, n is " + std::to_string(n));
+    const bool mesh = !(flags & RC_MOTION_NO_MESH);
+    if (!ctx->have_body) return fail(ctx, RC_ERR_STATE, name + "rc_set_body first");
+    if (mesh && ctx->mesh_V == 0) return fail(ctx, RC_ERR_STATE, name + "rc_set_mesh first (or pass RC_MOTION_NO_MESH)");
+    hipStream_t st = (hipStream_t)stream;
+    if (mesh && ctx->align_dirty) if (int rc = fold_align(ctx)) return rc;      // once per mesh / body: synchronises the device
+    const size_t G = (size_t)groups;
+    MotionGroup* th = nullptr;
+    HIP_TRY(ctx, ctx->align_tab.stage(G, &th));
+    long long at = 0, blk = 0;
+    for (int g = 0; g < groups; ++g) {
+        th[g].frame0 = at;
+        th[g].frames = group_frames_host[g];
+        th[g].blk0 = (int)blk;
+        th[g].nblk = (int)((th[g].frames + RC_MOTION_FG - 1) / RC_MOTION_FG);
+        at += th[g].frames;
+        blk += th[g].nblk;
+    }
+    const size_t need_s = (size_t)rc_align_scratch_floats(n), need_p = (size_t)rc_align_partial_doubles(ctx->mesh_V, n, mesh);
+    if (!ctx->align_tab.holds(G) || need_s > ctx->align_scratch_n || need_p > ctx->align_partial_n) {   // (kernels of earlier calls may still use the old buffers)
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        HIP_TRY(ctx, ctx->align_tab.grow(G));
+        HIP_TRY(ctx, rc_grow(ctx->align_scratch_n, need_s, need_s, ctx->align_scratch, need_s));
+        HIP_TRY(ctx, rc_grow(ctx->align_partial_n, need_p, need_p, ctx->align_partial, need_p));
+    }
+    HIP_TRY(ctx, ctx->align_tab.upload(G, st));
+    HIP_TRY(ctx, ctx->align_tab.record(st));
+    const double* fold_m = reinterpret_cast<const double*>(ctx->align_fold.get());
+    const AlignPair* pairs = reinterpret_cast<const AlignPair*>(ctx->align_fold.get() + 24 * 4 * sizeof(double));
+    rc_launch_aligned_metrics(ctx->body, ctx->mesh_vt, ctx->mesh_w, ctx->mesh_V, fold_m, pairs, ctx->align_pairs, ctx->align_tab.get(), groups,
+                              blocks, pose_p, pose_t, n, what, mesh, ctx->align_scratch.get(), ctx->align_partial.get(), joint_err, mesh_err,
+                              per_frame, xform, st);
     HIP_TRY(ctx, hipGetLastError());
     return RC_OK;
 }

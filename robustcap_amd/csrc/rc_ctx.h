@@ -87,6 +87,17 @@ struct rc_ctx {
     DevBuf<double> motion_partial;
     size_t motion_partial_n = 0;
     StagedTable<MotionGroup, 4> motion_tab;
+    // rc_aligned_metrics: the mesh fold (24 x 4 doubles m_j, then the listed pairs; rebuilt behind rc_set_mesh / rc_set_body), per-frame
+    // scratch, per-(frame, slab) sums (grow-only) and the group table
+    DevBuf<char> align_fold;
+    size_t align_fold_bytes = 0;
+    int align_pairs = 0;
+    bool align_dirty = true;
+    DevBuf<float> align_scratch;
+    size_t align_scratch_n = 0;
+    DevBuf<double> align_partial;
+    size_t align_partial_n = 0;
+    StagedTable<MotionGroup, 4> align_tab;
     // rc_set_shape_space / rc_prepare_motions (rc_prepare_api.cpp): the folded shape basis and the 39 picked vertices (one allocation, `prep_sp`
     // points into it), the per-sequence rest records, the IMU-vertex scratch of a call without vert6_out (grow-only) and the sequence table
     DevBuf<float> prep_space;

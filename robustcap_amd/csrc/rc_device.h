@@ -1,5 +1,6 @@
 // Device-side helpers shared by rc_frame.hip and rc_smplify.hip (gfx950): wave reductions, 3x3 algebra, 6D -> R,
-// and the wave-per-body FK + 33-landmark skinning of articulate/model.py:229-241.
+// the wave-per-body FK + 33-landmark skinning of articulate/model.py:229-241, and the float64 3x3 one-sided Jacobi of the
+// Procrustes (rc_metrics.hip) and the SVD alignments (rc_align.hip).
 #pragma once
 #include "rc_internal.h"
 
@@ -281,5 +282,43 @@ __device__ __forceinline__ void rotmat_to_aa(const float* Rm, float* aa) {
     } else {
         const double k = theta / (2.0 * s);
         aa[0] = (float)(r[0] * k); aa[1] = (float)(r[1] * k); aa[2] = (float)(r[2] * k);
+    }
+}
+
+// right singular vectors of a 3x3 matrix by a one-sided (Hestenes) Jacobi: W enters as K and leaves as K V with mutually
+// orthogonal columns (w_i = s_i u_i), V (a product of rotations: det V = +1) holds the right singular vectors as columns.
+// Working on K itself keeps a small singular direction to eps * s_1 / s_i; the eigenvectors of K^T K, which this replaces,
+// had eps * (s_1 / s_i)^2 and lost the second direction of a thin point set (s_2 / s_1 ~ 1e-8) altogether.
+// Every index is a compile-time constant (the p, q, k loops are unrolled): the matrices live in registers, no scratch.
+__device__ __forceinline__ void hestenes3(double (&W)[3][3], double (&V)[3][3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 16; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 3; ++q) {
+                const double al = W[0][p] * W[0][p] + W[1][p] * W[1][p] + W[2][p] * W[2][p];
+                const double be = W[0][q] * W[0][q] + W[1][q] * W[1][q] + W[2][q] * W[2][q];
+                const double ga = W[0][p] * W[0][q] + W[1][p] * W[1][q] + W[2][p] * W[2][q];
+                if (ga * ga <= 1e-30 * al * be) continue;           // orthogonal to 1e-15 (or a zero column): nothing to do
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {                       // W <- W J, V <- V J
+                    const double wkp = W[k][p], wkq = W[k][q];
+                    W[k][p] = c * wkp - s * wkq;
+                    W[k][q] = s * wkp + c * wkq;
+                    const double vkp = V[k][p], vkq = V[k][q];
+                    V[k][p] = c * vkp - s * vkq;
+                    V[k][q] = s * vkp + c * vkq;
+                }
+            }
+        if (!rotated) break;
     }
 }

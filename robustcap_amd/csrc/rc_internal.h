@@ -415,6 +415,19 @@ void rc_launch_motion_metrics(const BodyConst* body, const float* vt, const floa
                               long long blocks, const float* pose_p, const float* tran_p, const float* pose_t, const float* tran_t, long long n,
                               int fps, int align, unsigned mask, bool mesh, float* scratch, double* partial, float* out, float* per_joint,
                               hipStream_t s);
+// ---- the evaluators' SVD alignments (rc_align.hip; rc_svd_rotate and rc_aligned_metrics in rc_api.cpp) --------------------------------
+// One listed pair j <= k of the mesh fold: c = C[j,k] = sum_v w[v,j] w[v,k] x~_v x~_v^T, 4x4 row-major (symmetric; C[k,j] is the same matrix)
+struct AlignPair { int j, k; double c[16]; };
+void rc_launch_svd_rotate(const float* src, const float* dst, long long n, int m, unsigned what, float* R, float* t, float* s, float* moved,
+                          hipStream_t st);
+long long rc_align_scratch_floats(long long n);                                           // per-frame joint errors and aligned difference transforms
+long long rc_align_partial_doubles(int V, long long n, bool mesh);                        // per-(frame, slab) sums of the vertex error
+// fold_m DEVICE [24][4] doubles, pairs DEVICE [n_pairs]; tab DEVICE [groups] (rc_motion_metrics' table); any output may be nullptr;
+// mesh == false: no fold, no sweep, the mesh outputs are NaN
+void rc_launch_aligned_metrics(const BodyConst* body, const float* vt, const float* w, int V, const double* fold_m, const AlignPair* pairs,
+                               int n_pairs, const MotionGroup* tab, int groups, long long blocks, const float* pose_p, const float* pose_t,
+                               long long n, unsigned what, bool mesh, float* scratch, double* partial, float* joint_err, float* mesh_err,
+                               float* per_frame, float* xform, hipStream_t st);
 
 // smplify optimiser (rc_smplify.hip): one evaluation = loss terms + analytic gradient of all T frames
 struct SmplifyArgs {

@@ -419,6 +419,28 @@ def motion_metrics(model, dataset, results, fps=60, joint_mask=None, device="cud
     return {r: out[k] for k, r in enumerate(rows)}, out.mean(dim=0)
 
 
+def aligned_metrics(model, dataset, results, align=-1, device="cuda"):
+    """``art.PerJointErrorEvaluator`` / ``art.MeshErrorEvaluator`` with ``align_joint`` = ``align`` in -1 .. -5 (articulate/evaluator.py:
+    195-210, 298-313: the joint and vertex position errors after the frame-wise R/t/s, R/t, t/s, t or s fit) of EVERY (sequence, camera)
+    row of ``results`` = {(i, j): (pose [T,24,3,3], tran)} against the camera-frame label poses, in ONE ``rc_aligned_metrics`` call:
+    every row is one group of the concatenated frames, as ``motion_metrics`` concatenates them. The translations play no part (the
+    reference's evaluators run with zero translation). Returns ({(i, j): joint errors [24]}, {(i, j): mesh error}, the mean over the
+    rows of the joint errors [24], the mean over the rows of the mesh errors), on the CPU."""
+    dev = torch.device(device)
+    rows = list(results)
+    if not rows:
+        return {}, {}, torch.full((24,), float("nan")), float("nan")
+    P, G, lens = [], [], []
+    for (i, j) in rows:
+        pt, _ = labels(dataset, i, j, device)
+        pose = results[(i, j)][0]
+        n = min(pose.shape[0], pt.shape[0])
+        P.append(pose[:n].to(dev)), G.append(pt[:n].to(dev)), lens.append(n)
+    je, me = model.aligned_metrics(torch.cat(P), torch.cat(G), group_frames=lens, align=align)
+    je, me = je.cpu(), me.cpu()
+    return ({r: je[k] for k, r in enumerate(rows)}, {r: float(me[k]) for k, r in enumerate(rows)}, je.mean(dim=0), float(me.mean()))
+
+
 def root_position_errors(dataset, results, align="none", device="cuda"):
     """Absolute root position error (``art.PositionErrorEvaluator``: mean Euclidean distance, m) of every row of ``results`` =
     {(i, j): (pose, tran [T,3])} against the camera-frame label translation. ``align="last"`` first shifts the prediction by

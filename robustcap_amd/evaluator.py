@@ -1,9 +1,12 @@
 """The motion evaluators of ``articulate/evaluator.py:155-394`` on the device: ``FullMotionEvaluator`` and the per-joint, mean-per-joint
-and mesh evaluators, which are column views of the same quantities. One ``rc_motion_metrics`` call each (csrc/rc_motion.hip); this
-file converts the inputs with the ``body.*`` conversions and marshals pointers.
+and mesh evaluators, which are column views of the same quantities. One ``rc_motion_metrics`` call each (csrc/rc_motion.hip); the
+per-joint, mean-per-joint and mesh evaluators also take the SVD alignments ``align_joint`` -1 .. -5 (evaluator.py:198-207, 301-310:
+R/t/s, R/t, t/s, t, s), which are one ``rc_aligned_metrics`` call (csrc/rc_align.hip). This file converts the inputs with the
+``body.*`` conversions and marshals pointers.
 
-Not implemented (``NotImplementedError`` naming the argument): quaternion and Euler-angle inputs, ``use_pose_blendshape=True``, the SVD
-alignments (``align_joint < 0``), and different shapes for prediction and truth (a context holds one body).
+Not implemented (``NotImplementedError`` naming the argument): quaternion and Euler-angle inputs, ``use_pose_blendshape=True``, a
+negative ``align_joint`` in ``FullMotionEvaluator`` (the reference declares it non-negative there), and different shapes for
+prediction and truth (a context holds one body).
 """
 import enum
 
@@ -34,15 +37,15 @@ def _mask_bits(joint_mask):
 
 class _BasePoseEvaluator:
     def __init__(self, official_model_file=None, rep=RotationRepresentation.ROTATION_MATRIX, use_pose_blendshape=False, align_joint=0,
-                 device="cuda", body=None):
+                 device="cuda", body=None, svd_align=False):
         if use_pose_blendshape:
             raise NotImplementedError("use_pose_blendshape=True: pose blendshapes are not implemented")
         rep = RotationRepresentation(rep.value if isinstance(rep, enum.Enum) else rep)
         if rep in (RotationRepresentation.QUATERNION, RotationRepresentation.EULER_ANGLE):
             raise NotImplementedError(f"rep={rep.name}: rotation matrices, axis angles and r6d are implemented")
         align_joint = align_joint if isinstance(align_joint, int) else align_joint.value
-        if align_joint < 0:
-            raise NotImplementedError(f"align_joint={align_joint}: the SVD alignments are not implemented")
+        if align_joint < 0 and not svd_align:
+            raise NotImplementedError(f"align_joint={align_joint}: FullMotionEvaluator takes a joint id (the reference declares it non-negative)")
         if align_joint > 23:
             raise ValueError("align_joint must be a joint id in 0..23")
         self.model = _body.ParametricModel(official_model_file, device=device, body=body)
@@ -68,14 +71,27 @@ class _BasePoseEvaluator:
         return self.model.motion_metrics(self._pose(pose_p), self._pose(pose_t), tran_p, tran_t, fps=fps, align_joint=self.align_joint,
                                          joint_mask=joint_mask, mesh=mesh)
 
+    def _run_aligned(self, pose_p, pose_t, mesh):
+        """align_joint < 0 (evaluator.py:198-209, 301-312) on converted poses: (joint_err [1,24], mesh_err [1] or None); below -5 the
+        reference's RuntimeError"""
+        _body.align_bits(self.align_joint)
+        return self.model.aligned_metrics(pose_p, pose_t, align=self.align_joint, mesh=mesh)
+
 
 class PerJointErrorEvaluator(_BasePoseEvaluator):
-    """articulate/evaluator.py:155-215: [3, 24] = position, local and global rotation error (degrees) of every joint."""
+    """articulate/evaluator.py:155-215: [3, 24] = position, local and global rotation error (degrees) of every joint. ``align_joint``
+    -1 .. -5: the positions after the frame-wise R/t/s, R/t, t/s, t or s fit on the 24 joints; the two angle rows are those of
+    ``align_joint=0``, bit for bit (the alignment does not touch them)."""
 
     def __init__(self, official_model_file=None, align_joint=0, rep=RotationRepresentation.ROTATION_MATRIX, device="cuda", body=None):
-        super().__init__(official_model_file, rep, False, align_joint, device, body)
+        super().__init__(official_model_file, rep, False, align_joint, device, body, svd_align=True)
 
     def __call__(self, pose_p, pose_t):
+        if self.align_joint < 0:
+            pose_p, pose_t = self._pose(pose_p), self._pose(pose_t)
+            je, _ = self._run_aligned(pose_p, pose_t, mesh=False)
+            _, pj = self.model.motion_metrics(pose_p, pose_t, align_joint=0, mesh=False)       # the angle rows: untouched by the alignment
+            return torch.cat((je[:1], pj[0, 1:3])).cpu()
         _, pj = self._run(pose_p, pose_t, mesh=False)
         return pj[0, :3].cpu()
 
@@ -88,14 +104,17 @@ class MeanPerJointErrorEvaluator(PerJointErrorEvaluator):
 
 
 class MeshErrorEvaluator(_BasePoseEvaluator):
-    """articulate/evaluator.py:256-314: the mean vertex position error (align_joint position aligned)."""
+    """articulate/evaluator.py:256-314: the mean vertex position error (align_joint position aligned; -1 .. -5: after the frame-wise
+    R/t/s, R/t, t/s, t or s fit on all vertices)."""
 
     def __init__(self, official_model_file=None, align_joint=0, rep=RotationRepresentation.ROTATION_MATRIX, use_pose_blendshape=False,
                  device="cuda", body=None):
-        super().__init__(official_model_file, rep, use_pose_blendshape, align_joint, device, body)
+        super().__init__(official_model_file, rep, use_pose_blendshape, align_joint, device, body, svd_align=True)
 
     def __call__(self, pose_p, pose_t, shape_p=None, shape_t=None):
         self._shape(shape_p, shape_t)
+        if self.align_joint < 0:
+            return self._run_aligned(self._pose(pose_p), self._pose(pose_t), mesh=True)[1][0].cpu()
         out, _ = self._run(pose_p, pose_t)
         return out[0, 1, 0].cpu()
 
