@@ -14,7 +14,11 @@
  *     rc_shape_body / rc_get_state / rc_get_trace / rc_destroy; rc_sequence synchronises `stream` ONCE per call when its
  *     launch planner is on AND the call has at least min_frames frames (rc_set_sequence_mode; shorter calls and mode 0 are
  *     fully asynchronous), rc_camera_inputs_rows once (constant upload), the
- *     *_host-mean variants of the metric calls and rc_smplify_* as documented with them.
+ *     *_host-mean variants of the metric calls and rc_smplify_* as documented with them. Short of a synchronisation, a call whose table
+ *     travels through pinned copies waits on the HOST for an earlier upload from the copy it takes -- the sub-net forward / backward /
+ *     weight-gradient entries for the previous such call's plan, the entries with a ring of four for the call four calls earlier -- so a
+ *     chain of them on a stream that is held up returns only as those uploads pass; and a call that grows context-owned scratch waits as
+ *     its paragraph says.
  *   - Every function returns 0 on success or a negative rc_status; rc_last_error() gives a message. Nothing
  *     throws across the boundary. A context is not re-entrant; distinct contexts on distinct streams are
  *     independent.

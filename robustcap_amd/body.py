@@ -207,13 +207,20 @@ class ParametricModel:
                    "rc_body_mesh")
         return vert
 
+    def set_mesh(self, v_template, weights):
+        """``rc_set_mesh``: the mesh every vertex sweep of this model runs on -- ``v_template`` [V,3], ``weights`` [V,24] on the model's
+        joints and parents. ``_ensure_mesh`` hands over the body's own; a test hands over a smaller one."""
+        vt = np.ascontiguousarray(v_template, dtype=np.float32)
+        w = np.ascontiguousarray(weights, dtype=np.float32)
+        if vt.ndim != 2 or vt.shape[1] != 3 or w.shape != (vt.shape[0], 24):
+            raise ValueError(f"v_template [V, 3] and weights [V, 24] expected, got {vt.shape} and {w.shape}")
+        _lib.check(self._ctx, self._lib.rc_set_mesh(self._ctx, vt.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p),
+                                                    vt.shape[0]), "rc_set_mesh")
+        self._mesh_set, self._V = True, vt.shape[0]
+
     def _ensure_mesh(self):
         if not self.__dict__.get("_mesh_set"):
-            vt = np.ascontiguousarray(self._body["v_template"], dtype=np.float32)
-            w = np.ascontiguousarray(self._body["weights"], dtype=np.float32)
-            _lib.check(self._ctx, self._lib.rc_set_mesh(self._ctx, vt.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p),
-                                                        vt.shape[0]), "rc_set_mesh")
-            self._mesh_set, self._V = True, vt.shape[0]
+            self.set_mesh(self._body["v_template"], self._body["weights"])
 
     def _ensure_shape_space(self, landmark_ids=cfg.mp_mask, vertex_ids=cfg.vi_mask):
         """``rc_set_shape_space`` once per model and pick: the folded shape basis of the MEAN body (where it has shapedirs and a
