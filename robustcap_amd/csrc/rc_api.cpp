@@ -367,6 +367,7 @@ int rc_ctx_init_net(rc_ctx* ctx, SubnetDense out[3]) {
 int rc_ctx_net_index(const char* name) { return net_index(name); }
 long long rc_ctx_weights_epoch(rc_ctx* ctx) { return ctx->weights_epoch; }
 int rc_ctx_mark_eager(rc_ctx* ctx, hipStream_t st) { return mark_eager(ctx, st); }
+int rc_ctx_flush_pending(rc_ctx* ctx, hipStream_t st) { return flush_pending(ctx, st); }
 SubnetOwner& rc_ctx_subnet(rc_ctx* ctx) { return ctx->subnet; }
 SmplifyOwner& rc_ctx_smplify(rc_ctx* ctx) { return ctx->smplify; }
 unsigned long long rc_ctx_ign_mask(rc_ctx* ctx) { return ctx->ign_mask; }

@@ -1,6 +1,6 @@
 // The context behind the C ABI, for the files that work on all of it: rc_api.cpp (context, weights, frame-stepped plan, op wrappers),
 // rc_gemm_api.cpp (problem builders, gate-GEMM launcher), rc_sequence_api.cpp (the sequence engine), rc_live_api.cpp (the live session)
-// and rc_prepare_api.cpp (the shape space and the motion preparation).
+// rc_prepare_api.cpp (the shape space and the motion preparation) and rc_rowstate_api.cpp (row state: save, load, rc_set_state).
 // (rc_smplify_api.cpp and rc_subnet_api.cpp see it through the rc_ctx_* accessors of rc_internal.h.)
 #pragma once
 #include "../../include/robustcap_hip.h"
@@ -112,6 +112,8 @@ struct rc_ctx {
     // rc_prepare_camera_motions: per-sequence camera / detector offsets and the camera rows themselves (checked on the host, then sent)
     StagedTable<PrepCam, 4> cam_tab;
     StagedTable<PrepCamRow, 4> cam_rows;
+    // rc_save_rows / rc_load_rows (rc_rowstate_api.cpp): the listed rows by 16-row block, sized once for every block of the context
+    StagedTable<RowGroup, 4> row_tab;
 };
 
 #pragma GCC visibility push(hidden)

@@ -341,6 +341,33 @@ void rc_launch_reset(const FrameBuffers& fb, float* const* h, float* const* c, c
                      int B, hipStream_t s);
 
 void rc_launch_flush_flags(const FrameBuffers& fb, int B, hipStream_t s);
+
+// ---- row state (rc_rowstate.hip; rc_save_rows / rc_load_rows / rc_set_state in rc_rowstate_api.cpp) ------------------------------------
+// One record = everything a row carries from frame to frame, as 32-bit words:
+//   per sub-net (kNets order) and layer: h[H] (the copy the row's step counter designates), then c[H]   -- 17,408 words
+//   x4l[256], x6l[256]: the row's part of the context's own updater-input buffers (inputs of a pending step)
+//   the last RC_ROWSTATE_SMALL words: j_temp[99] floor[33] last_pfoot[6] last_tran[3] gravity[3] | has_last n_floor first_reach uv_count
+//   pend | trace[8] | three zero words (the record is a multiple of 16 bytes)
+#define RC_ROWSTATE_SMALL 160
+#define RC_ROWSTATE_SEGS 27   // 12 h + 12 c + x4l + x6l + the small block: grid.y of the two kernels
+enum { RC_RS_PK = 0, RC_RS_ROWS = 1, RC_RS_SMALL = 2 };
+struct RowSeg {
+    float* base;            // RC_RS_PK: [copies][Bp, ld] in rc_pk order; RC_RS_ROWS: [B, ld] row-major; RC_RS_SMALL: unused (the fields come from fb)
+    const int* steps;       // RC_RS_PK: per-row step counter that picks the copy, or nullptr (one copy)
+    long long copy_stride;  // elements between the copies
+    int ld;                 // words of the segment per row (a multiple of 4)
+    int rec_off;            // first word of the segment in a record (a multiple of 4)
+    int kind, pad_;
+};
+struct RowStateArgs { RowSeg seg[RC_ROWSTATE_SEGS]; FrameBuffers fb; long long rec_words; };
+// the listed rows of ONE 16-row block of the context (ascending) and the record each of them owns: built and checked on the host, the only
+// indices the kernels use
+struct RowGroup { int m; int row[16]; int rec[16]; };
+// load == false: context -> blob (gather), true: blob -> context (scatter); groups DEVICE [n_groups], blob DEVICE, 16-byte aligned
+void rc_launch_rowstate(const RowStateArgs& a, const RowGroup* groups, int n_groups, float* blob, bool load, hipStream_t s);
+// rc_set_state: hs / cs DEVICE [2, B, H] row-major or nullptr, mask DEVICE uint8[B] or nullptr; h [2][RC_HBUF][Bp, H] rc_pk, c [2][B, H]
+void rc_launch_set_state(const float* hs, const float* cs, const unsigned char* mask, const int* steps, float* h, float* c, int B,
+                         long long BpH, int H, hipStream_t s);
 void rc_launch_pack_rows(const float* src, int src_ld, int cols, float* dst, int ld, int B, hipStream_t s);
 
 void rc_launch_r6d(const float* r6d, float* R, long long n, hipStream_t s);
@@ -818,6 +845,7 @@ int rc_ctx_init_net(rc_ctx* ctx, SubnetDense out[3]);
 int rc_ctx_net_index(const char* name);
 int rc_ctx_gemm_split(rc_ctx* ctx);                        // 1: the context's products are not fp32 (gemm mode 1 or 2)
 int rc_ctx_gemm_mode(rc_ctx* ctx);                         // rc_get_gemm_mode
+int rc_ctx_flush_pending(rc_ctx* ctx, hipStream_t st);     // every pending updater step runs now, on st (rc_get_state, rc_set_state)
 int rc_ctx_mark_eager(rc_ctx* ctx, hipStream_t st);        // mark_eager (rc_ctx.h): eager work was enqueued on st
 long long rc_ctx_weights_epoch(rc_ctx* ctx);               // counts rc_finalize_weights: what was derived from the packed weights is stale
 void rc_subnet_free(SubnetState* s);                       // delete s

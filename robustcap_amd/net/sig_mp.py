@@ -605,6 +605,64 @@ class Net:
         _lib.check(self._ctx, self._lib.rc_get_state(self._ctx, net.encode(), _lib.ptr(h), _lib.ptr(c), _lib.stream_ptr()), "rc_get_state")
         return h, c
 
+    def set_state(self, net, h, c, rows=None):
+        """The inverse of ``get_state`` (rc_set_state): h, c [2, batch, H] (either may be None: that half stays) written into sub-net
+        ``net``; ``rows``: optional bool/uint8 mask [batch], the other rows keep their state. Synchronises, like ``get_state``."""
+        H = {n: hh for n, _, hh, _ in cfg.NETS}[net]
+        def host(x):
+            return None if x is None else torch.as_tensor(x).detach().to(device="cpu", dtype=torch.float32).reshape(2, self.batch, H).contiguous()
+        h, c = host(h), host(c)
+        m = None if rows is None else torch.as_tensor(rows).detach().cpu().reshape(self.batch).ne(0).to(torch.uint8).contiguous()
+        _lib.check(self._ctx, self._lib.rc_set_state(self._ctx, net.encode(), _lib.ptr(h), _lib.ptr(c), _lib.ptr(m)), "rc_set_state")
+
+    # ----------------------------------------------------------------------------------------------- row state
+    def row_state_info(self):
+        """(bytes per record, format) of this context's row records (rc_row_state_bytes)."""
+        b, f = C.c_int64(), C.c_int32()
+        _lib.check(self._ctx, self._lib.rc_row_state_bytes(self._ctx, C.byref(b), C.byref(f)), "rc_row_state_bytes")
+        return b.value, f.value
+
+    def _row_io(self, rows, n, blob, bytes_per_row):
+        """(descriptor, the host row list it points to): both must live until the call has returned, which consumes the list."""
+        keep = None
+        if rows is not None:
+            keep = np.ascontiguousarray(torch.as_tensor(rows).detach().cpu().numpy().reshape(-1).astype(np.int64))
+            if keep.shape[0] != n:
+                raise ValueError(f"rows: {keep.shape[0]} rows for {n} records")
+            if ((keep < -2 ** 31) | (keep >= 2 ** 31)).any():
+                raise ValueError("rows: not int32")
+            keep = np.ascontiguousarray(keep.astype(np.int32))
+        io = _lib.RcRowIO(None if keep is None else keep.ctypes.data, n, None if blob is None else blob.data_ptr(), bytes_per_row,
+                          torch.cuda.current_stream().cuda_stream)
+        return io, keep
+
+    def save_rows(self, rows=None):
+        """Records of ``rows`` (a sequence of distinct row indices; None: every row, in order) as a ``RowState`` on this device
+        (rc_save_rows). Enqueued on the current stream, no synchronisation: the records are complete in stream order, and the context is
+        left exactly as it was -- a pending updater step stays pending here AND travels in the record."""
+        from ..rowstate import RowState
+        bpr, fmt = self.row_state_info()
+        n = self.batch if rows is None else len(rows)
+        data = torch.empty(n, bpr, dtype=torch.uint8, device=self.device)
+        io, keep = self._row_io(rows, n, data, bpr)
+        _lib.check(self._ctx, self._lib.rc_save_rows(self._ctx, C.byref(io)), "rc_save_rows")
+        return RowState(data, fmt)
+
+    def load_rows(self, state, rows=None):
+        """Record i of ``state`` (a ``RowState``, on any device: a host one is uploaded) into row ``rows[i]`` (None: rows 0 .. n-1) of
+        this context (rc_load_rows), on the current stream. Only the listed rows change; they continue bit for bit where the saved rows
+        stopped, provided this context agrees with the source on parameters, weights, body and gemm mode (none of which a record
+        holds). A record brings its row's gravity: assigning ``net.gravityc`` afterwards overwrites it for every row again.
+        ValueError when the records are of another format or of other hidden sizes than this context's."""
+        bpr, fmt = self.row_state_info()
+        from ..rowstate import HIDDEN
+        state.check(fmt, HIDDEN, bpr, "load_rows")
+        self._sync_gravity()                                                # (an assignment still waiting to be sent would overwrite the records' gravity later)
+        data = state.data.to(self.device).contiguous()
+        io, keep = self._row_io(rows, len(state), data, bpr)
+        _lib.check(self._ctx, self._lib.rc_load_rows(self._ctx, C.byref(io)), "rc_load_rows")
+        self.__dict__["_keep_rows"] = data                                  # the records must outlive the async launch
+
     def get_trace(self):
         """int32 [batch, 8] branch trace of the last frame (see rc_get_trace in the header)."""
         t = torch.empty(self.batch, 8, dtype=torch.int32)
